@@ -15,12 +15,17 @@ which hold a handful of unconverged scans. Every step still begins and ends insi
 the kernel durations behind `roofline` and `kernel_ms_per_step` are HIP-event times of `--extra-steps` further steps of the same workload run
 one alignment at a time right behind it (launches of different batches overlap inside the timed region), the hardware counters come
 from child runs of this script under `rocprofv3 --pmc`, the search loop's lane efficiency from one child run on the library's diagnostic build.
+Everything but the headline is behind `--full`: a plain run sets up, warms up, times `--steps` steps and prints the line (metric, value,
+ms_per_step, the configuration); `--full` adds the instrumented pass, the profiled steps, `roofline` / `roofline_k2`, `kernel_ms_per_step`,
+`icp_iter_ms`, the counter and diagnostic-build child runs (`--traffic`) and the CPU baseline (`--no-cpu-baseline`, `--cpu-seconds`).
+`--dump-outputs DIR` writes what the last timed step returned (poses and per-scan statistics, float64 .npy) for output-by-output comparisons.
 One GPU: BASELINE.json configs[2], every step aligns `--scans-per-gpu` (256) scans. Several GPUs, default (`--scaling strong`):
 configs[3] as written — `--total-scans` (256) scans in all, sharded contiguously over the ranks, per-iteration RCCL all-reduce of
 the per-scan normal equations inside liblocgpu.so (every rank solves every scan and holds all poses). `--scaling weak`: every
 rank aligns its own `--scans-per-gpu` scans, no data-path collective; `value` = scans all ranks completed ÷ max-over-ranks time.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full   # + roofline, kernel times, counters, CPU baseline
     python bench.py --gpus 8 ...          # no WORLD_SIZE in the environment: this process starts the 8 ranks itself (self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 bench.py --gpus 8 ...
 """
@@ -142,7 +147,7 @@ def measure_counters_live(passthrough_args, budget_s=300.0, steps=2, pipeline=1,
     import tempfile
     if not shutil.which("rocprofv3"):
         return {}, "rocprofv3 not on PATH"
-    child = [os.path.realpath(sys.executable), os.path.abspath(__file__)] + list(passthrough_args) + ["--steps", str(steps), "--warmup", "0", "--pipeline", str(pipeline), "--extra-steps", str(extra), "--no-cpu-baseline", "--traffic", "none"]
+    child = [os.path.realpath(sys.executable), os.path.abspath(__file__)] + list(passthrough_args) + ["--steps", str(steps), "--warmup", "0", "--pipeline", str(pipeline), "--extra-steps", str(extra), "--no-cpu-baseline", "--traffic", "none", "--full"]
     agg = collections.defaultdict(lambda: collections.defaultdict(list))
     t_start = time.time()
     notes = []
@@ -176,7 +181,7 @@ def measure_lane_efficiency_live(passthrough_args, budget_s=120.0, steps=1, pipe
     library's diagnostic build (LOCGPU_STAMP=1: the same kernel counting, per lane, the rounds the lane needed and the rounds its
     wave ran; its timing is meaningless and not used). Returns (useful / paid | None, note)."""
     import subprocess
-    child = [os.path.realpath(sys.executable), os.path.abspath(__file__)] + list(passthrough_args) + ["--steps", str(steps), "--warmup", "0", "--pipeline", str(pipeline), "--no-cpu-baseline", "--traffic", "none"] + (["--resident"] if resident and "--resident" not in passthrough_args else [])
+    child = [os.path.realpath(sys.executable), os.path.abspath(__file__)] + list(passthrough_args) + ["--steps", str(steps), "--warmup", "0", "--pipeline", str(pipeline), "--no-cpu-baseline", "--traffic", "none", "--full"] + (["--resident"] if resident and "--resident" not in passthrough_args else [])
     try:
         out = subprocess.run(child, capture_output=True, text=True, timeout=budget_s, env=dict(os.environ, LOCGPU_STAMP="1"), cwd=ROOT)
         for ln in out.stdout.splitlines():
@@ -187,6 +192,17 @@ def measure_lane_efficiency_live(passthrough_args, budget_s=120.0, steps=1, pipe
         return None, "the diagnostic run printed no stamp"
     except Exception as e:
         return None, "diagnostic run failed: %s" % type(e).__name__
+
+
+def dump_outputs(outdir, poses, stats):
+    """--dump-outputs: what the last timed step returned to its caller (locgpu_align_batch_end / locgpu_pool_wait): the poses
+    [scans, 7] and every field of the per-scan AlignStats, one float64 .npy each."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = dict(poses=np.asarray(poses, dtype=np.float64))
+    for f in ("iterations", "converged", "status", "last_effective_num", "last_dx_norm"):
+        arrays[f] = np.array([s[f] for s in stats], dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def launcher_command(n_ranks, port, argv, python=None):
@@ -279,7 +295,7 @@ def main():
                     help="alignments in flight (the library has three compute streams): k = step i+k-1 is begun before step i is ended; "
                          "0 (default) = 3. Kernel launch durations are NOT taken from the timed region (launches of several batches "
                          "overlap there): they come from --extra-steps further steps of the same workload run one at a time behind it")
-    ap.add_argument("--extra-steps", type=int, default=4, help="untimed steps behind the timed region, one alignment at a time with HIP events around every stage")
+    ap.add_argument("--extra-steps", type=int, default=4, help="--full: untimed steps behind the timed region, one alignment at a time with HIP events around every stage")
     ap.add_argument("--total-scans", type=int, default=256)
     ap.add_argument("--pool-slots", type=int, default=-1,
                     help="run the steps through the library's open-scan pool (locgpu_pool: one launch sequence per iteration over the open scans of "
@@ -290,13 +306,20 @@ def main():
                     help="pool: split the slots over this many pools on different streams of the context and deal the steps to them: the launches of "
                          "one fill the tails of the other's (the plain-batch mode's alignments in flight do the same)")
     ap.add_argument("--traffic", choices=["live", "profiles", "none"], default="live",
-                    help="roofline counters: live = rocprofv3 --pmc child runs + one diagnostic-build child run now (1 GPU only), profiles = newest committed traffic collection")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0)
+                    help="--full: roofline counters: live = rocprofv3 --pmc child runs + one diagnostic-build child run now (1 GPU only), profiles = newest committed traffic collection")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: time budget of the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the instrumented pass, the profiled steps (kernel_ms_per_step, icp_iter_ms), roofline / roofline_k2 "
+                         "with their counter child runs (--traffic) and the CPU baseline; a plain run times the steps and prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last step returned (rank 0's poses and per-scan statistics) as DIR/<name>.npy, float64")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be at least 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not launched as a rank of a job: bring the N ranks up from here (before torch or HIP is touched) and relay rank 0's line
         return self_launch(args.gpus, sys.argv[1:])
@@ -450,11 +473,15 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()  # device-wide: covers the library's compute and copy streams
 
-    # ---- visit counts of exactly this workload (separate instrumented pass, untimed) → algorithmic bytes
-    ctx.visit_count_enable(True)
-    out_poses, stats = align_batch(bufs[0])
-    vc = ctx.visit_count_read(reset=True)
-    ctx.visit_count_enable(False)
+    # ---- visit counts of exactly this workload (separate instrumented pass, untimed) → algorithmic bytes. A plain run makes the same
+    # first alignment without the counters, so that its warm-up and timed steps start from the same state as those of --full.
+    if args.full:
+        ctx.visit_count_enable(True)
+        out_poses, stats = align_batch(bufs[0])
+        vc = ctx.visit_count_read(reset=True)
+        ctx.visit_count_enable(False)
+    else:
+        align_batch(bufs[0])
 
     if not args.resident and not use_pool:  # the copy for the first step (every later one is started by the step before it)
         bufs[g_step[0] % len(bufs)].upload_async(scans_c)
@@ -474,20 +501,23 @@ def main():
     stamp = ctx.search_stats_read(reset=True) if stamp_build else None
     for b in bufs:
         b.upload_wait()
-    # ---- kernel durations: `extra` further steps of the same workload, ONE alignment at a time (launches of different batches
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out_poses, stats)
+    # ---- kernel durations (--full): `extra` further steps of the same workload, ONE alignment at a time (launches of different batches
     # overlap in the timed region), HIP events on the library's stream around every stage of every iteration
-    n_extra = max(1, args.extra_steps, -(-4 * pool_slots // max(n_total, 1)) if use_pool else 0)  # pool: four pools' worth, so that most launches profiled are steady-state ones
-    ctx.profile_read(reset=True)
-    ctx.profile_enable(1)
-    if use_pool:
-        run_steps(n_extra, pools[:1])  # ONE lane: with two, an event interval of one lane would contain the other's kernels
-    else:
-        for _ in range(n_extra):
-            align_batch(bufs[0])
-    prof = ctx.profile_read(reset=True)
-    ctx.profile_enable(False)
-    stage_src = ("HIP events around every stage of %d further steps of the same workload through one lane of the pool, right behind the timed region" % n_extra) if use_pool else \
-        "HIP events around every stage of %d further steps of the same workload, one alignment at a time, right behind the timed region" % n_extra
+    if args.full:
+        n_extra = max(1, args.extra_steps, -(-4 * pool_slots // max(n_total, 1)) if use_pool else 0)  # pool: four pools' worth, so that most launches profiled are steady-state ones
+        ctx.profile_read(reset=True)
+        ctx.profile_enable(1)
+        if use_pool:
+            run_steps(n_extra, pools[:1])  # ONE lane: with two, an event interval of one lane would contain the other's kernels
+        else:
+            for _ in range(n_extra):
+                align_batch(bufs[0])
+        prof = ctx.profile_read(reset=True)
+        ctx.profile_enable(False)
+        stage_src = ("HIP events around every stage of %d further steps of the same workload through one lane of the pool, right behind the timed region" % n_extra) if use_pool else \
+            "HIP events around every stage of %d further steps of the same workload, one alignment at a time, right behind the timed region" % n_extra
 
     if dist is not None:
         tt = torch.tensor([dt], dtype=torch.float64, device="cuda")
@@ -500,7 +530,7 @@ def main():
     gn_iters = sum(s["iterations"] for s in stats[own])   # scan-iterations THIS rank computed per step
     err_t = float(np.median(np.linalg.norm(out_poses[:, 4:] - truth[:, 4:], axis=1)))
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # roofline of the dominant kernel over the timed region (all launches, partially idle ones included)
         k = 1 if args.method == "p2p" else 5
         q = vc["queries"] if method >= 0 else gn_iters * pts_per_scan
@@ -608,6 +638,7 @@ def main():
             roofline["note"] = ("valu_issue frac = (32-bit VALU instructions x 2 + FP64 x 4 cycles) / (SIMDs x launch time) at the nominal clock: the kernel is "
                                 "LATENCY-bound (dependent node loads), well below its issue roofline; lane_efficiency = main-loop rounds the "
                                 "lanes need / rounds their waves run (a wave runs until its slowest lane is done)")
+    if rank == 0:
         # which BASELINE.json configuration the arguments amount to
         if strong:
             cfg_name = "BASELINE configs[3] (%d scans in all, sharded over %d GPU(s), RCCL all-reduce)" % (n_total, world)
@@ -632,15 +663,15 @@ def main():
                                 scans_per_gpu=B_local, map_points=args.map_points, scan_h2d_in_timed_region=not args.resident, pipeline_depth=depth,
                                 search_mode=dict(tree="tree_faithful_ann", tree_exact="tree_faithful_exact", grid="grid_exact")[args.search], tree_depth=tinfo["depth"],
                                 tree_bytes=tinfo["bytes"]),
-                    icp_iter_ms=round((t_search + t_accum + t_solve) / max(prof["search_n"] / args.steps, 1), 5),
-                    icp_iter_ms_per_scan=round((t_search + t_accum + t_solve) / max(gn_iters, 1), 6),  # kernel ms of one step ÷ scan-iterations of one step
                     gn_iterations_per_scan=round(gn_iters / max(B_local, 1), 2),
-                    kernel_ms_per_step=dict(search=round(t_search, 4), fit_accumulate=round(t_accum, 4), solve=round(t_solve, 4)),
-                    kernel_ms_source=stage_src,
                     h2d_bytes_per_step=(0 if args.resident else B_local * pts_per_scan * 16),
                     median_translation_error_to_truth_m=round(err_t, 4),
-                    setup_s=dict(map_gen=round(t_map, 2), tree_ingest=round(t_ingest, 2)),
-                    roofline=roofline)
+                    setup_s=dict(map_gen=round(t_map, 2), tree_ingest=round(t_ingest, 2)))
+        if args.full:
+            line.update(icp_iter_ms=round((t_search + t_accum + t_solve) / max(prof["search_n"] / args.steps, 1), 5),
+                        icp_iter_ms_per_scan=round((t_search + t_accum + t_solve) / max(gn_iters, 1), 6),  # kernel ms of one step ÷ scan-iterations of one step
+                        kernel_ms_per_step=dict(search=round(t_search, 4), fit_accumulate=round(t_accum, 4), solve=round(t_solve, 4)),
+                        kernel_ms_source=stage_src, roofline=roofline)
         if use_pool:
             line["pool"] = dict(slots=pool_slots, lanes=lanes, steps_in_flight=depth, chunk=(args.pool_chunk or 4),
                                 iterations=sum(q.info()["iterations"] for q in pools), scan_iterations=sum(q.info()["scan_iterations"] for q in pools))
@@ -650,7 +681,7 @@ def main():
                             ("barrier and max-over-ranks only (torch.distributed nccl)" if dist is not None else "none (one rank, no process group)"))
         if stamp is not None:
             line["stamp"] = dict(lane_rounds=stamp["walked"], paid_rounds=stamp["replayed"])
-        if method >= 0 and t_accum > 0:
+        if args.full and method >= 0 and t_accum > 0:
             # the second kernel (fit + accumulate): algorithmic bytes of SURVEY §8(d) against HBM, its measured HBM traffic, and — what
             # actually bounds it — its VALU and FP64 instruction counts against the issue rate (32-bit wave64 instruction = 2 cycles of its SIMD-32, FP64 = 4)
             a_gbs = (accum_bytes / 1e9) / (t_accum / 1e3)
@@ -667,7 +698,7 @@ def main():
                                        hbm_frac=(round(k2_traffic / (k2_avg / 1e3) / 1e9 / HBM_PEAK_GBS, 5) if k2_traffic and k2_avg > 0 else None),
                                        nominal_bytes_frac=round(a_gbs / HBM_PEAK_GBS, 5),
                                        note="frac at the nominal 2.4 GHz (the chip holds about 1.95 GHz under this load); about two thirds of the instructions are the plane fit; " + stage_src)
-        if world == 1 and not args.no_cpu_baseline and args.search == "tree":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.search == "tree":
             cb, cpu_poses = cpu_baseline(map_xyz, scans, inits, args.cpu_seconds, args.method,
                                          dict(voxel_size=args.ndt_voxel, nearby_type=(1 if args.ndt_nearby == "nearby6" else 0)))
             n = len(cpu_poses)

@@ -1,10 +1,11 @@
-"""Generates tests/golden/filters_small.npz with the CPU oracle (oracle/locref_filters.hpp) in the build container.
+"""Generates tests/golden/filters_small_scan.npz and filters_small_maps.npz with the CPU oracle (oracle/locref_filters.hpp) in the build container.
 
 The reference holds no golden vectors for its filter wrappers and PCL cannot be built here, so these vectors pin the
 ORACLE's behaviour (regression) and let the GPU box check the HIP filters without regenerating anything: a 20 k-pt scan
 with NaN returns and intensities, its removeNaN / VoxelGrid (both summation orders) / CropBox outputs, and the local map
 after each of 5 keyframes with num_kfs = 3 (Lio::AddCloud's keyframe branch), and a 6-ring scan with its LOAM edge / surface
-features (LoamFeatureExtract::Extract).
+features (LoamFeatureExtract::Extract). The scan and its filter outputs go to filters_small_scan.npz, the keyframes, local
+maps and LOAM arrays to filters_small_maps.npz (two files, each under the 1 MiB a committed file may hold).
 
     python tests/golden/make_golden_filters.py
 """
@@ -60,9 +61,13 @@ def main():
     out["loam_edge"], out["loam_surf"] = locref.loam_extract(lo, ring, 16, order=locref.SORT_STABLE)
     e_std, s_std = locref.loam_extract(lo, ring, 16, order=locref.SORT_STD)
     assert np.array_equal(e_std, out["loam_edge"]) and np.array_equal(s_std, out["loam_surf"])  # no equal curvatures in this input
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "filters_small.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", path, os.path.getsize(path), "bytes;", {k: len(v) for k, v in out.items() if k.startswith(("voxel", "crop", "local", "no_nan"))})
+    maps = {k: v for k, v in out.items() if k.startswith(("kf_", "local_map_", "loam_"))}
+    parts = dict(scan={k: v for k, v in out.items() if k not in maps}, maps=maps)
+    for name, arrays in parts.items():
+        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "filters_small_%s.npz" % name)
+        np.savez_compressed(path, **arrays)
+        print("wrote", path, os.path.getsize(path), "bytes")
+    print({k: len(v) for k, v in out.items() if k.startswith(("voxel", "crop", "local", "no_nan"))})
 
 
 if __name__ == "__main__":

@@ -20,7 +20,7 @@ sys.path.insert(0, ROOT)
 
 
 def run_bench(*extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + list(extra)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full"] + list(extra)
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500)
     for ln in reversed(out.stdout.strip().splitlines()):
         if ln.startswith("{"):

@@ -286,10 +286,25 @@ def test_host_tree_build_pool_under_thread_sanitizer(tmp_path):
         pytest.skip("ThreadSanitizer runtime not installed")
     assert r.returncode == 0, r.stderr[-2000:]
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1 second_deadlock_stack=1 die_after_fork=0", LOCGPU_BUILD_THREADS="6")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=env)
+    r = _run_sanitized([exe], capture_output=True, text=True, timeout=900, env=env)
     if r.returncode != 0 and "unexpected memory mapping" in r.stderr:
         pytest.skip("ThreadSanitizer cannot map its shadow memory in this container")
     assert r.returncode == 0 and "tsan harness ok" in r.stdout, r.stdout[-1000:] + r.stderr[-4000:]
+
+
+def _run_sanitized(argv, **kw):
+    """Run a sanitizer binary with address-space randomisation off for that process alone (setarch -R), where the kernel lets a
+    process ask for it. This toolchain's ThreadSanitizer does not yet re-execute itself that way: on kernels with more mmap
+    randomness a PIE binary can land outside its application ranges or on its shadow memory ("unexpected memory mapping", or a
+    silent SIGSEGV at start-up). The checks themselves do not depend on where the binary is loaded."""
+    import platform
+    import shutil
+    import subprocess
+    if shutil.which("setarch"):
+        norand = ["setarch", platform.machine(), "-R"]
+        if subprocess.run(norand + ["true"], capture_output=True).returncode == 0:
+            argv = norand + list(argv)
+    return subprocess.run(argv, **kw)
 
 
 @pytest.mark.parametrize("san", ["address,undefined", "thread"])
@@ -311,7 +326,7 @@ def test_inc_ndt_host_replay_under_sanitizers(tmp_path, san):
     if r.returncode != 0 and ("sanitize" in r.stderr or "tsan" in r.stderr):
         pytest.skip("sanitizer runtime not installed")
     assert r.returncode == 0, r.stderr[-2000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1"))
+    r = _run_sanitized([exe], capture_output=True, text=True, timeout=600, env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1"))
     if r.returncode != 0 and "unexpected memory mapping" in r.stderr:
         pytest.skip("ThreadSanitizer cannot map its shadow memory in this container")
     assert r.returncode == 0 and "inc-ndt host harness ok" in r.stdout, r.stdout[-1000:] + r.stderr[-3000:]
@@ -377,7 +392,9 @@ def test_context_helper_thread_under_tsan(tmp_path):
     if r.returncode != 0 and "sanitize" in r.stderr:
         pytest.skip("sanitizer runtime not installed")
     assert r.returncode == 0, r.stderr[-2000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    r = _run_sanitized([exe], capture_output=True, text=True, timeout=600)
+    if r.returncode != 0 and "unexpected memory mapping" in r.stderr:
+        pytest.skip("ThreadSanitizer cannot map its shadow memory in this container")
     assert r.returncode == 0 and "host_worker: 0 problems" in r.stdout and "ThreadSanitizer" not in r.stderr, r.stdout[-1000:] + r.stderr[-3000:]
 
 

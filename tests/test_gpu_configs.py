@@ -506,7 +506,7 @@ def test_bench_line_contract(mode):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--map-points", "1000000", "--no-cpu-baseline",
-           "--traffic", "none"]
+           "--traffic", "none", "--full"]
     if mode == "strong":
         cmd += ["--scaling", "strong", "--total-scans", "8"]
     else:
@@ -541,6 +541,40 @@ def test_bench_line_contract(mode):
     assert d["roofline_k2"]["bound"].startswith("valu_issue") and "fp64_issue_frac" in d["roofline_k2"]
     assert d["scans_per_rank"] == 8 and d["rccl_ranks"] == 1
     assert "further steps" in d["kernel_ms_source"] and d["kernel_ms_per_step"]["search"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run (no --full) prints the headline line without the --full fields, and --dump-outputs writes what the
+    last timed step returned: float64 arrays, one row per scan, the same whatever the number of steps (same inputs, same results)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    names = ("poses", "iterations", "converged", "status", "last_effective_num", "last_dx_norm")
+    dumps = []
+    for steps in (2, 3):
+        d = str(tmp_path / ("steps%d" % steps))
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--map-points", "1000000",
+               "--scans-per-gpu", "8", "--pool-slots", "0", "--dump-outputs", d]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == steps and line["unit"] == "scans/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+        assert line["metric"].startswith("scans/sec") and line["value"] > 0
+        assert abs(line["value"] - 8 * steps / (line["ms_per_step"] * steps / 1e3)) < 1e-3 * line["value"]
+        assert line["median_translation_error_to_truth_m"] < 0.1
+        for key in ("roofline", "roofline_k2", "kernel_ms_per_step", "icp_iter_ms", "cpu_baseline"):
+            assert key not in line, key
+        arrays = {n: np.load(os.path.join(d, n + ".npy")) for n in names}
+        assert sorted(os.listdir(d)) == sorted(n + ".npy" for n in names)
+        assert all(a.dtype == np.float64 and a.shape[0] == 8 for a in arrays.values())
+        assert arrays["poses"].shape == (8, 7) and (arrays["iterations"] >= 1).all()
+        dumps.append(arrays)
+    for n in names:
+        np.testing.assert_array_equal(dumps[0][n], dumps[1][n])
 
 
 def test_bench_refuses_more_ranks_than_gpus():

@@ -259,7 +259,8 @@ def test_cpp_facade_filters(locref, synth, tmp_path, dense):
 def test_golden_filter_fixture_gpu(gpu_ctx, api):
     """Committed golden vectors (tests/golden/make_golden_filters.py, generated with the oracle in the build container)."""
     import os
-    g = np.load(os.path.join(os.path.dirname(__file__), "golden", "filters_small.npz"))
+    g = dict(np.load(os.path.join(os.path.dirname(__file__), "golden", "filters_small_scan.npz")))
+    g.update(np.load(os.path.join(os.path.dirname(__file__), "golden", "filters_small_maps.npz")))
     scan = g["scan"]
     got, dense = gpu_ctx.remove_nan(scan, False)
     assert dense and np.array_equal(got, g["no_nan"])

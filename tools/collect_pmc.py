@@ -30,7 +30,7 @@ def main():
     ap.add_argument("--method", default="p2plane", help="bench.py --method (ndt: the direct-NDT accumulate kernel)")
     a = ap.parse_args()
     agg = collections.defaultdict(lambda: collections.defaultdict(list))
-    cmd_tail = [os.path.realpath(sys.executable), os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "0", "--resident", "--no-cpu-baseline", "--traffic", "none",
+    cmd_tail = [os.path.realpath(sys.executable), os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "0", "--resident", "--full", "--no-cpu-baseline", "--traffic", "none",
                 "--scans-per-gpu", str(a.scans), "--method", a.method]
     for counters in PASSES:
         d = tempfile.mkdtemp(prefix="locgpu_pmc_", dir="/tmp")

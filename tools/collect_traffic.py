@@ -41,7 +41,7 @@ def main():
     ap.add_argument("--search", default="tree", choices=["tree", "tree_exact", "grid"])
     ap.add_argument("--workdir", default=os.path.join(ROOT, "gpurun_out", "traffic"))
     a = ap.parse_args()
-    bench_args = ["--steps", "2", "--warmup", "0", "--no-cpu-baseline", "--traffic", "none", "--scans-per-gpu", str(a.scans_per_gpu), "--map-points",
+    bench_args = ["--steps", "2", "--warmup", "0", "--full", "--no-cpu-baseline", "--traffic", "none", "--scans-per-gpu", str(a.scans_per_gpu), "--map-points",
                   str(a.map_points), "--method", a.method, "--search", a.search]
     fetch = run_pass("FETCH_SIZE", os.path.join(a.workdir, "fetch"), bench_args)
     write = run_pass("WRITE_SIZE", os.path.join(a.workdir, "write"), bench_args)

@@ -26,7 +26,7 @@ def main():
     d = tempfile.mkdtemp(prefix="locgpu_itrace_", dir="/tmp")
     try:
         cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "t", "--", "python3", os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
-               "--resident", "--pipeline", "1", "--extra-steps", "1", "--no-cpu-baseline", "--traffic", "none", "--scans-per-gpu", str(a.scans), "--search", a.search]
+               "--resident", "--pipeline", "1", "--extra-steps", "1", "--full", "--no-cpu-baseline", "--traffic", "none", "--scans-per-gpu", str(a.scans), "--search", a.search]
         subprocess.run(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, env=dict(os.environ, TMPDIR="/tmp"), cwd="/tmp", timeout=900, check=True)
         f = glob.glob(os.path.join(d, "**", "t_kernel_trace.csv"), recursive=True)[0]
         rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))

@@ -1,4 +1,4 @@
-B="python bench.py --traffic none --no-cpu-baseline"
+B="python bench.py --full --traffic none --no-cpu-baseline"
 for args in "--steps 40" "--steps 40 --pool-slots 768" "--steps 40 --pool-slots 1024" "--scaling strong --total-scans 32 --steps 160" "--scaling strong --total-scans 64 --steps 80"; do
   $B $args > gpurun_out/sw.json 2> gpurun_out/sw.err
   python - <<PY

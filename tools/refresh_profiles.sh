@@ -8,23 +8,23 @@ cd $R
 export TMPDIR=/tmp
 line() { grep '^{' | tail -1; }
 # ---- the bench line as the driver runs it (live counters, CPU baseline), and its variants
-timeout 600 python bench.py --steps 20 --warmup 5 2>/dev/null | line > $O/bench_line.json
-timeout 300 python bench.py --no-cpu-baseline --traffic none 2>/dev/null | line > $O/bench_default_80steps_line.json
-timeout 200 python bench.py --steps 20 --warmup 5 --resident --no-cpu-baseline --traffic none 2>/dev/null | line > $O/bench_resident_line.json
-timeout 200 python bench.py --steps 20 --warmup 5 --pipeline 1 --no-cpu-baseline --traffic none 2>/dev/null | line > $O/bench_pipeline1_line.json
+timeout 600 python bench.py --full --steps 20 --warmup 5 2>/dev/null | line > $O/bench_line.json
+timeout 300 python bench.py --full --no-cpu-baseline --traffic none 2>/dev/null | line > $O/bench_default_80steps_line.json
+timeout 200 python bench.py --full --steps 20 --warmup 5 --resident --no-cpu-baseline --traffic none 2>/dev/null | line > $O/bench_resident_line.json
+timeout 200 python bench.py --full --steps 20 --warmup 5 --pipeline 1 --no-cpu-baseline --traffic none 2>/dev/null | line > $O/bench_pipeline1_line.json
 # ---- configs[3] on ONE rank (RCCL communicator of one rank): the open-scan pool (default for small steps) against plain sharded batches
 for n in 32 64; do
-  timeout 300 python bench.py --scaling strong --total-scans $n --steps $((5120 / n)) --warmup 8 --no-cpu-baseline --traffic none 2>/dev/null | line > $O/bench_strong_1rank_${n}_pool_line.json
-  timeout 300 python bench.py --scaling strong --total-scans $n --steps $((5120 / n)) --warmup 8 --pool-slots 0 --no-cpu-baseline --traffic none 2>/dev/null | line > $O/bench_strong_1rank_${n}_plain_line.json
+  timeout 300 python bench.py --full --scaling strong --total-scans $n --steps $((5120 / n)) --warmup 8 --no-cpu-baseline --traffic none 2>/dev/null | line > $O/bench_strong_1rank_${n}_pool_line.json
+  timeout 300 python bench.py --full --scaling strong --total-scans $n --steps $((5120 / n)) --warmup 8 --pool-slots 0 --no-cpu-baseline --traffic none 2>/dev/null | line > $O/bench_strong_1rank_${n}_plain_line.json
 done
-timeout 300 python bench.py --scaling strong --total-scans 32 --steps 20 --warmup 3 --no-cpu-baseline --traffic none 2>/dev/null | line > $O/bench_strong_1rank_32_pool_20steps_line.json
-timeout 300 python bench.py --scaling strong --total-scans 256 --steps 20 --warmup 5 --no-cpu-baseline --traffic none 2>/dev/null | line > $O/bench_strong_1rank_256_line.json
-timeout 600 python bench.py --scaling strong --total-scans 32 --steps 160 --warmup 8 --no-cpu-baseline 2>/dev/null | line > $O/bench_strong_1rank_32_pool_counters_line.json
+timeout 300 python bench.py --full --scaling strong --total-scans 32 --steps 20 --warmup 3 --no-cpu-baseline --traffic none 2>/dev/null | line > $O/bench_strong_1rank_32_pool_20steps_line.json
+timeout 300 python bench.py --full --scaling strong --total-scans 256 --steps 20 --warmup 5 --no-cpu-baseline --traffic none 2>/dev/null | line > $O/bench_strong_1rank_256_line.json
+timeout 600 python bench.py --full --scaling strong --total-scans 32 --steps 160 --warmup 8 --no-cpu-baseline 2>/dev/null | line > $O/bench_strong_1rank_32_pool_counters_line.json
 # ---- SetEnableANN(false): the exact search through the tree and through the cell grid (K1b, frozen), with live counters
-timeout 600 python bench.py --search tree_exact --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | line > $O/bench_tree_exact_line.json
-timeout 600 python bench.py --search grid --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | line > $O/bench_grid_line.json
+timeout 600 python bench.py --full --search tree_exact --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | line > $O/bench_tree_exact_line.json
+timeout 600 python bench.py --full --search grid --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | line > $O/bench_grid_line.json
 # ---- direct NDT: the line with live counters (row 3b), kernel stats below
-timeout 600 python bench.py --method ndt --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | line > $O/bench_ndt_line.json
+timeout 600 python bench.py --full --method ndt --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | line > $O/bench_ndt_line.json
 timeout 400 python3 tools/collect_pmc.py --out $O/pmc_ndt_kernel.md --scans 64 --method ndt > /dev/null 2>&1
 # ---- the call slam_demo makes (facade ScanMatch: host cloud in, host cloud + pose out), the K1 occupancy point of the shipped shape and of round 5's
 timeout 900 python3 tests/perf/facade_time.py --out $O/facade_time.json > $O/facade_time.md 2>/dev/null
@@ -47,7 +47,7 @@ timeout 120 ./tools/ubench/plane_fit_accuracy > $O/plane_fit_accuracy.txt 2>&1
 cd /tmp
 stats() {  # stats <name> <bench args…>
   name=$1; shift
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python3 $R/bench.py "$@" --no-cpu-baseline --traffic none > /dev/null 2>&1
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python3 $R/bench.py "$@" --full --no-cpu-baseline --traffic none > /dev/null 2>&1
   cp $O/prof/*/bench_kernel_stats.csv $O/${name}_kernel_stats.csv 2>/dev/null || cp $O/prof/bench_kernel_stats.csv $O/${name}_kernel_stats.csv; rm -rf $O/prof
 }
 stats bench --steps 20 --warmup 5
