@@ -205,6 +205,71 @@ LOCGPU_API int locgpu_icp_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const doubl
 LOCGPU_API int locgpu_gn_update(const double hb[44], int method, int min_effective_pts, double eps, double pose[7], double dx[6],
                                 int* applied, int* stop);
 
+/* ---- MatchingInterface::GetFitnessScore (matching_interface.h:53), which the reference leaves a stub that returns 0
+ * (icp_registration.cpp:246-250): how good an alignment is, as pcl::Registration::getFitnessScore defines it. For a source cloud,
+ * a pose T and max_range in metres (+inf allowed):
+ *   q_i   = (float)(T·p_i), the product in FP64 and one cast — the query the alignment itself uses (icp_registration.cpp:169-170);
+ *           points with a non-finite coordinate are skipped and not counted (pcl::isFinite, icp_registration.cpp:64);
+ *   d²_i  = float32 squared distance from q_i to its EXACT nearest target point, dx² + (dy² + dz²) as the tree search evaluates
+ *           it (KdTree::ComputeDisForLeaf, kdtree.cpp:197-212) — never the alpha-pruned search of the matcher's options: a score does not depend on a pruning knob;
+ *   inlier iff d²_i <= (float)(max_range · max_range);
+ *   score = Σ_inliers (double)d²_i / inliers, +infinity when there is no inlier.
+ * The sums are reduced in a fixed order that does not depend on the batch: the same cloud and pose give the same bits alone, among
+ * other poses, in a batch of any size and in a candidate search. */
+typedef struct locgpu_fitness {
+    double score;          /* mean squared distance of the inliers [m²]; +inf without inliers */
+    int64_t inliers;       /* points with d² <= max_range² */
+    int64_t finite_points; /* points that were queries at all */
+} locgpu_fitness;
+/* Score of ONE cloud under n_poses >= 1 poses (n_poses × 7 doubles; out: n_poses entries). The cloud is uploaded once. With more
+ * than one pose the call goes through the context's shared-source batch (see locgpu_icp_init_search for what that retains). */
+LOCGPU_API int locgpu_icp_fitness(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double* poses, int n_poses,
+                                  double max_range, locgpu_fitness* out);
+/* Score of every scan of a batch under its own pose (poses: n_scans × 7; out: n_scans entries). Ordinary and shared-source batches;
+ * a sharded batch is refused with LOCGPU_ERR_INVALID. Equals locgpu_icp_fitness of each scan bit for bit. */
+LOCGPU_API int locgpu_icp_fitness_batch(locgpu_ctx* ctx, locgpu_batch* batch, const double* poses, double max_range, locgpu_fitness* out);
+/* Score of the source cloud that the context's most recent host-pointer single-scan call (locgpu_icp_scan_match, locgpu_icp_align,
+ * locgpu_icp_hb, ...) left in HBM, under `pose`: no second upload. This is what IcpRegistration::GetFitnessScore binds to after
+ * EnableFitnessScore: nothing is added to ScanMatch itself (icp_registration.cpp:216-244). LOCGPU_ERR_INVALID
+ * when no such cloud is resident. */
+LOCGPU_API int locgpu_icp_fitness_resident(locgpu_ctx* ctx, const double pose[7], double max_range, locgpu_fitness* out);
+
+/* ---- A batch whose n_entries entries all read ONE resident cloud (no reference counterpart: the reference's only way to try several
+ * initial poses is to call ScanMatch again, icp_registration.cpp:216-244). The cloud is uploaded once, here; poses, flags, neighbour
+ * lists, sums and stats are per entry as in any batch, and locgpu_icp_align_batch / _begin / locgpu_align_batch_end /
+ * locgpu_icp_hb_batch / locgpu_ndt_align_batch / locgpu_icp_fitness_batch treat it as the batch of n_entries uploaded copies of the
+ * cloud, bit for bit, without the copies (16 B per point and entry). Not shardable and not poolable; locgpu_batch_upload_async into
+ * it is refused with LOCGPU_ERR_INVALID (make a new one for another cloud). */
+LOCGPU_API int locgpu_batch_create_shared(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, int n_entries, locgpu_batch** out);
+
+/* ---- Initial-pose search (no reference counterpart: Loc starts ScanMatch from SetInitPose(SE3()) or a GNSS position with an IMU
+ * heading, lio_matching_flow.cpp:203-205,227-262, metres and degrees off, and IcpRegistration::ScanMatch, icp_registration.cpp:216-244,
+ * only refines a pose that is nearly right). Aligns the cloud from each of m candidate poses (candidates: m × 7) with the caller's ICP
+ * options — any method and search mode; each candidate runs exactly the Gauss–Newton loop locgpu_icp_align_batch runs on a batch of
+ * m copies of the cloud, bit for bit — scores every result (above, sopts->max_range) and reports all m (out_poses m × 7, out_fit m,
+ * stats m or NULL) and the winner: *best = the lowest score among the candidates with inliers >= 1 and inliers / finite_points >=
+ * min_inlier_ratio, ties to the lower index; -1 when none qualifies (the outputs are filled all the same). A candidate whose alignment
+ * ended with too few effective points keeps the pose it had, as in locgpu_icp_align_batch, and is scored there. sopts NULL = defaults.
+ * m is processed in equal chunks of at most 256 candidates, and of at most 1 GiB of per-candidate workspace (28 B per point and
+ * candidate; a single candidate is always allowed). The context keeps that workspace and one copy of the cloud (16 B per point)
+ * for the next call — grow-only within the bound — until locgpu_destroy.
+ * LOCGPU_ERR_NO_TARGET before a set_target; LOCGPU_ERR_INVALID for m < 1, n == 0, a NaN max_range, a negative or NaN min_inlier_ratio. */
+typedef struct locgpu_init_search_opts {
+    double max_range;        /* 1.0 m: the inlier range of the score */
+    double min_inlier_ratio; /* 0.5: a winner needs inliers / finite_points >= this */
+} locgpu_init_search_opts;
+LOCGPU_API void locgpu_init_search_opts_default(locgpu_init_search_opts* o);
+LOCGPU_API int locgpu_icp_init_search(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double* candidates, int m,
+                                      const locgpu_icp_opts* opts, const locgpu_init_search_opts* sopts, double* out_poses,
+                                      locgpu_fitness* out_fit, locgpu_align_stats* stats, int* best);
+/* Host helper (no device, no context): the candidate poses centre ∘ (yaw about the centre's z axis, then x / y offsets in the
+ * centre's frame) for yaw = a · yaw_step, x = i · xy_step, y = j · xy_step with |a| <= floor(yaw_half / yaw_step + 1e-9),
+ * |i|, |j| <= floor(xy_half / xy_step + 1e-9) — the kind of uncertainty a GNSS position with an IMU heading has
+ * (lio_matching_flow.cpp:227-262). Order: yaw-major, then x, then y, each ascending. A half of 0 means that one value (its step is
+ * ignored). Writes min(count, cap) poses to out (7 doubles each) and always the count to *n_out. */
+LOCGPU_API int locgpu_pose_grid(const double centre[7], double xy_half, double xy_step, double yaw_half, double yaw_step, double* out,
+                                size_t cap, size_t* n_out);
+
 /* ---- One node, several GPUs (BASELINE.json configs[3]; no reference counterpart): one process per GPU, one context per process,
  * the ranks joined by an RCCL communicator. A SHARDED batch has n_total scans; this rank holds the points of scans
  * [first_scan, first_scan + n_local) — or, for one large alignment split by points, a slice of the points of every scan

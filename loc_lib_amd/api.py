@@ -42,6 +42,8 @@ ABI_SYMBOLS = [
     "locgpu_pool_opts_default", "locgpu_pool_create", "locgpu_pool_destroy", "locgpu_pool_submit", "locgpu_pool_wait", "locgpu_pool_info",
     "locgpu_pool_profile_read", "locgpu_pool_step", "locgpu_pool_done",
     "locgpu_icp_scan_match", "locgpu_ndt_scan_match",
+    "locgpu_icp_fitness", "locgpu_icp_fitness_batch", "locgpu_icp_fitness_resident", "locgpu_batch_create_shared",
+    "locgpu_init_search_opts_default", "locgpu_icp_init_search", "locgpu_pose_grid",
 ]
 COMM_ID_BYTES = 128
 NO_INTENSITY = ctypes.c_size_t(-1).value
@@ -68,6 +70,14 @@ class NdtOpts(ctypes.Structure):
 class PoolOpts(ctypes.Structure):
     _fields_ = [("slots", ctypes.c_int32), ("prefetch", ctypes.c_int32), ("scans_per_job", ctypes.c_int32), ("chunk", ctypes.c_int32), ("matcher", ctypes.c_int32),
                 ("max_points", ctypes.c_uint64), ("icp", IcpOpts)]
+
+
+class Fitness(ctypes.Structure):
+    _fields_ = [("score", ctypes.c_double), ("inliers", ctypes.c_int64), ("finite_points", ctypes.c_int64)]
+
+
+class InitSearchOpts(ctypes.Structure):
+    _fields_ = [("max_range", ctypes.c_double), ("min_inlier_ratio", ctypes.c_double)]
 
 
 class AlignStats(ctypes.Structure):
@@ -143,6 +153,11 @@ def lib():
             "locgpu_pool_step": (i32, [vp, i32]), "locgpu_pool_done": (i32, [vp, ctypes.c_int64, vp]),
             "locgpu_icp_scan_match": (i32, [vp, vp, sz, sz, vp, vp, vp, vp, vp, sz, vp, vp]),
             "locgpu_ndt_scan_match": (i32, [vp, vp, sz, sz, vp, vp, vp, vp, sz, vp, vp]),
+            "locgpu_icp_fitness": (i32, [vp, vp, sz, sz, vp, i32, dbl, vp]), "locgpu_icp_fitness_batch": (i32, [vp, vp, vp, dbl, vp]),
+            "locgpu_icp_fitness_resident": (i32, [vp, vp, dbl, vp]), "locgpu_batch_create_shared": (i32, [vp, vp, sz, sz, i32, vp]),
+            "locgpu_init_search_opts_default": (None, [vp]),
+            "locgpu_icp_init_search": (i32, [vp, vp, sz, sz, vp, i32, vp, vp, vp, vp, vp, vp]),
+            "locgpu_pose_grid": (i32, [vp, dbl, dbl, dbl, dbl, vp, sz, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -198,6 +213,36 @@ def ndt_opts(**kw):
             raise TypeError("unknown NDT option %r" % k)
         setattr(o, k, v)
     return o
+
+
+def init_search_opts(**kw):
+    o = InitSearchOpts()
+    lib().locgpu_init_search_opts_default(ctypes.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError("unknown initial-pose search option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+def pose_grid(centre, xy_half, xy_step, yaw_half, yaw_step, cap=None):
+    """Candidate poses around `centre` (locgpu_pose_grid; host only, needs no device): yaw-major, then x, then y.
+    Returns (poses [min(count, cap), 7], count)."""
+    c = _pose(centre)
+    n = ctypes.c_size_t(0)
+    rc = lib().locgpu_pose_grid(c.ctypes.data, xy_half, xy_step, yaw_half, yaw_step, None, 0, ctypes.byref(n))
+    if rc != 0:
+        raise LocGpuError(rc, "locgpu_pose_grid: bad arguments")
+    k = n.value if cap is None else min(int(cap), n.value)
+    out = np.zeros((k, 7))
+    rc = lib().locgpu_pose_grid(c.ctypes.data, xy_half, xy_step, yaw_half, yaw_step, out.ctypes.data if k else None, k, ctypes.byref(n))
+    if rc != 0:
+        raise LocGpuError(rc, "locgpu_pose_grid: bad arguments")
+    return out, int(n.value)
+
+
+def _fitness_dict(f):
+    return dict(score=f.score, inliers=int(f.inliers), finite_points=int(f.finite_points))
 
 
 def _stats_dict(s):
@@ -424,6 +469,50 @@ class Context:
         self._check(lib().locgpu_icp_hb_batch(self._h, batch._h, p.ctypes.data, ctypes.byref(opts), hb.ctypes.data))
         return hb
 
+    # ---- MatchingInterface::GetFitnessScore, as pcl::Registration::getFitnessScore defines it (locgpu.h)
+    def icp_fitness(self, src, poses, max_range=1.0, raw=False):
+        """Score of one cloud under one pose ([7] → dict) or several ([n, 7] → list of dicts). raw=True: the ctypes array."""
+        s = _cloud(src)
+        p = _pose(poses)
+        one = p.ndim == 1
+        p = p.reshape(-1, 7)
+        out = (Fitness * p.shape[0])()
+        self._check(lib().locgpu_icp_fitness(self._h, s.ctypes.data, s.shape[0], s.strides[0], p.ctypes.data, p.shape[0], max_range, out))
+        if raw:
+            return out
+        return _fitness_dict(out[0]) if one else [_fitness_dict(f) for f in out]
+
+    def icp_fitness_batch(self, batch, poses, max_range=1.0, raw=False):
+        batch.upload_wait()
+        p = _pose(poses).reshape(batch.n_scans, 7)
+        out = (Fitness * batch.n_scans)()
+        self._check(lib().locgpu_icp_fitness_batch(self._h, batch._h, p.ctypes.data, max_range, out))
+        return out if raw else [_fitness_dict(f) for f in out]
+
+    def icp_fitness_resident(self, pose, max_range=1.0):
+        """Score of the source cloud the last host-pointer single-scan call left in HBM (what the façade's GetFitnessScore uses)."""
+        out = Fitness()
+        self._check(lib().locgpu_icp_fitness_resident(self._h, _pose(pose).ctypes.data, max_range, ctypes.byref(out)))
+        return _fitness_dict(out)
+
+    def batch_shared(self, scan, n_entries):
+        """A batch whose n_entries entries all read one resident copy of `scan` (locgpu_batch_create_shared)."""
+        return Batch(self, None, n_scans=n_entries, shared=scan)
+
+    # ---- initial-pose search: align from every candidate, score every result, pick the winner
+    def icp_init_search(self, src, candidates, opts, sopts=None, raw=False):
+        """Returns (poses [m, 7], fitness (list of dicts; raw=True: the ctypes array), stats, best index or -1)."""
+        s = _cloud(src)
+        c = _pose(candidates).reshape(-1, 7)
+        m = c.shape[0]
+        out = np.zeros((m, 7))
+        fit = (Fitness * max(m, 1))()
+        st = (AlignStats * max(m, 1))()
+        best = ctypes.c_int(-2)
+        self._check(lib().locgpu_icp_init_search(self._h, s.ctypes.data, s.shape[0], s.strides[0], c.ctypes.data, m, ctypes.byref(opts),
+                                                 ctypes.byref(sopts) if sopts is not None else None, out.ctypes.data, fit, st, ctypes.byref(best)))
+        return out, (fit if raw else [_fitness_dict(f) for f in fit]), [_stats_dict(x) for x in st], int(best.value)
+
     # ---- NdtRegistration
     def ndt_set_target(self, cloud, opts=None):
         c = _cloud(cloud)
@@ -632,10 +721,16 @@ class MarshalledScans:
 class Batch:
     """A batch of scans resident in HBM (locgpu_batch). ``n_scans`` = the scans poses are kept for (all n_total of a sharded batch)."""
 
-    def __init__(self, ctx, scans, first=None, n_total=None, n_scans=None, max_points=None):
+    def __init__(self, ctx, scans, first=None, n_total=None, n_scans=None, max_points=None, shared=None):
         self.ctx = ctx
         self._h = ctypes.c_void_p()
         self._keep = None
+        if shared is not None:  # n_scans entries that all read one resident copy of `shared`
+            c = _cloud(shared)
+            self.n_local = self.n_scans = int(n_scans)
+            self.max_points = c.shape[0]
+            ctx._check(lib().locgpu_batch_create_shared(ctx._h, c.ctypes.data, c.shape[0], c.strides[0], self.n_scans, ctypes.byref(self._h)))
+            return
         if scans is None:  # capacity only; fill with upload_async
             self.n_local = self.n_scans = int(n_scans)
             self.max_points = int(max_points)

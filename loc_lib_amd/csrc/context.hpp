@@ -65,6 +65,9 @@ struct locgpu_ctx {
     // reusable one-scan batch for the single-scan entry points
     locgpu_batch* single = nullptr;
     size_t single_cap = 0;
+    // the shared-source batch of locgpu_icp_fitness (several poses) and locgpu_icp_init_search: kept between calls, grow-only, at most
+    // kSearchEntries entries and kSearchBytes of per-entry workspace (locgpu.h says what that retains)
+    locgpu_batch* search = nullptr;
     locgpu::HostWorker* worker = nullptr;  // locgpu_*_scan_match: host copy of the output cloud's fields beside the alignment
 
     // multi-GPU (locgpu_comm_init): RCCL communicator of the ranks that share sharded batches
@@ -99,6 +102,14 @@ struct locgpu_batch {
     int* d_counts = nullptr;
     locgpu::PoseState* d_state = nullptr;
     uint32_t* d_nn = nullptr;      // [5][pitch]
+    // Shared-source batch (locgpu_batch_create_shared): ONE region of points in d_src, read by every entry — d_src_of holds a zero per
+    // entry and travels as SearchArgs / AccumArgs::src_of. The buffers are sized for cap_scans entries of cap_points points; n_scans
+    // and max_n are what the current call uses of them (reshape_shared, locgpu_api.hip). split_scans > 0: the accumulate kernels
+    // split their sums as a plain batch of that many scans would (AccumArgs::split_scans) — a candidate search in chunks.
+    bool shared_src = false;
+    int* d_src_of = nullptr;
+    int cap_scans = 0, split_scans = 0;
+    size_t cap_points = 0;
     const float4* d_src_ext = nullptr;           // one-scan batches: the points stay where the caller's cloud holds them (no copy into d_src); nullptr = d_src
     bool counters_clean = false;                 // the search stage's work-list counters are known to be zero (the last alignment ran to its end)
     int last_iterations = -1;                    // one-scan batches: iterations of the previous alignment run on this batch (-1: none yet) — sizes the next first chunk
@@ -160,7 +171,7 @@ bool hip_ok(locgpu_ctx* ctx, hipError_t e, const char* what);
 // locgpu_api.hip
 void ndt_free(locgpu_ctx* ctx);
 // Device buffers + pinned result staging for n_scans scans of at most max_n points each; no points yet. n_total >= 0: a sharded batch.
-int alloc_batch(locgpu_ctx* ctx, int n_scans, size_t max_n, locgpu_batch** out, int first = 0, int n_total = -1);
+int alloc_batch(locgpu_ctx* ctx, int n_scans, size_t max_n, locgpu_batch** out, int first = 0, int n_total = -1, bool shared_src = false);
 void free_batch(locgpu_batch* b);
 // Validate the matcher's options against the context's target; fill the Gauss–Newton parameters of an alignment.
 int check_icp(locgpu_ctx* ctx, const locgpu_icp_opts* o, GnParams& prm, int& k, float& alpha_eff);

@@ -1,0 +1,96 @@
+// loc_lib_amd/csrc/fitness.hip — the fitness score of an alignment (MatchingInterface::GetFitnessScore, matching_interface.h:53; the
+// quantity pcl::Registration::getFitnessScore reports): mean squared distance from the transformed source points to their EXACT
+// nearest target points, over the points within max_range.
+//
+// Shape: the existing search stage (launch_icp_search, k = 1, alpha_eff = 1: the exact walk of search_walk.hpp, with its deep pass and
+// its tie redo — no new instantiation of the walk) leaves one leaf slot per point in the batch's neighbour list; the accumulate kernel
+// below re-forms the float32 query and the float32 squared distance exactly as the walk evaluates it, and reduces {Σd², inliers,
+// finite points} in FP64 per block; a last small kernel adds the block rows of a scan in a fixed order. Same skeleton and same
+// determinism rule as icp_point_accum_kernel + gn_solve_kernel: no atomics on the sums, two runs give the same bits. A fused
+// walk + reduce kernel was not built: the walk retires lanes to the deep pass and the redo kernel, so a fused reduction would have
+// to live in three kernels; the separate pass costs one 4-byte load per point.
+//
+// The split of the sums is FIXED (kFitPts points per thread, rows added in the order of fitness_sum_kernel) and does not depend on
+// the batch: a scan scores the same bits alone, in a batch of any size and in any chunk of a candidate search.
+#include "icp_kernels.hpp"
+#include "launch.hpp"
+
+namespace locgpu {
+
+constexpr int kFitPts = 4;  // points per thread of the accumulate kernel: a block covers 1024 consecutive points of its scan
+
+__global__ __launch_bounds__(kBlock) void icp_fitness_accum_kernel(const uint2* __restrict__ tree, const float4* __restrict__ src,
+                                                                   const int* __restrict__ counts, const PoseState* __restrict__ st,
+                                                                   const uint32_t* __restrict__ nn, int max_n, float gate2,
+                                                                   double* __restrict__ partials, const int* __restrict__ src_of) {
+    __shared__ double s_part[kBlock / 64][kFitW];
+    const int scan = blockIdx.y;
+    const int n = counts[scan];
+    const size_t region = (size_t)(src_of ? src_of[scan] : scan) * max_n;
+    double sum = 0.0, inl = 0.0, fin = 0.0;
+#pragma unroll
+    for (int pp = 0; pp < kFitPts; ++pp) {
+        const int i = (blockIdx.x * kFitPts + pp) * kBlock + threadIdx.x;
+        if (i < n) {
+            const float4 p = src[region + i];
+            const uint32_t s0 = __builtin_nontemporal_load(&nn[(size_t)scan * max_n + i]);
+            // a point with a non-finite coordinate is not a query (the search left it the empty list) and is not counted
+            if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z) && s0 != kInvalidSlot) {
+                const D3 qs = se3_apply(st[scan].q, st[scan].t, D3{(double)p.x, (double)p.y, (double)p.z});
+                const float qx = (float)qs.x, qy = (float)qs.y, qz = (float)qs.z;  // the query of the alignment (icp_registration.cpp:169-170)
+                uint4 w;
+                __builtin_memcpy(&w, tree + s0, 16);
+                const float dx = qx - as_f32(w.x), dy = qy - as_f32(w.z), dz = qz - as_f32(w.w);
+                const float d2 = dx * dx + (dy * dy + dz * dz);  // as the walk evaluates it (search_walk.hpp; no contraction: -ffp-contract=off)
+                fin += 1.0;
+                if (d2 <= gate2) { sum += (double)d2; inl += 1.0; }
+            }
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    sum = wave_sum(sum); inl = wave_sum(inl); fin = wave_sum(fin);
+    if (lane == 0) { s_part[wave][0] = sum; s_part[wave][1] = inl; s_part[wave][2] = fin; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        double t = s_part[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < kBlock / 64; ++w) t += s_part[w][threadIdx.x];
+        partials[((size_t)scan * gridDim.x + blockIdx.x) * kFitW + threadIdx.x] = t;
+    }
+}
+
+// One wave per scan: lane l adds rows l, l + 64, … in order, then lane 0 adds the 64 lane sums in order. Rows that do not exist count
+// as zeros, so the result does not depend on how many rows the batch's longest scan needs. out[scan] = {Σd², inliers, finite points, 0}.
+// list_counts: the search stage's work-list counters, consumed by now — zeroed for the next search (as gn_solve_kernel does).
+__global__ __launch_bounds__(64) void icp_fitness_sum_kernel(const double* __restrict__ partials, int rows, double* __restrict__ out,
+                                                             unsigned int* __restrict__ list_counts) {
+    __shared__ double s_lane[3][64];
+    const int scan = blockIdx.x, lane = threadIdx.x;
+    if (list_counts && blockIdx.x == 0 && lane < 4) list_counts[lane] = 0u;
+    const double* p = partials + (size_t)scan * rows * kFitW;
+    double a = 0.0, b = 0.0, c = 0.0;
+    for (int r = lane; r < rows; r += 64) {
+        a += p[(size_t)r * kFitW + 0];
+        b += p[(size_t)r * kFitW + 1];
+        c += p[(size_t)r * kFitW + 2];
+    }
+    s_lane[0][lane] = a; s_lane[1][lane] = b; s_lane[2][lane] = c;
+    __syncthreads();
+    if (lane < 3) {
+        double t = s_lane[lane][0];
+        for (int l = 1; l < 64; ++l) t += s_lane[lane][l];
+        out[(size_t)scan * kFitW + lane] = t;
+    }
+    if (lane == 3) out[(size_t)scan * kFitW + 3] = 0.0;
+}
+
+int icp_fitness_rows(int max_n) { return (max_n + kFitPts * kBlock - 1) / (kFitPts * kBlock); }
+
+void launch_icp_fitness(const FitnessArgs& a, hipStream_t s) {
+    const int rows = icp_fitness_rows(a.max_n);
+    hipLaunchKernelGGL(icp_fitness_accum_kernel, dim3(rows, a.n_scans), dim3(kBlock), 0, s, a.tree, a.src, a.counts, a.st, a.nn, a.max_n, a.gate2, a.partials,
+                       a.src_of);
+    hipLaunchKernelGGL(icp_fitness_sum_kernel, dim3(a.n_scans), dim3(64), 0, s, a.partials, rows, a.out, a.list_counts);
+}
+
+}  // namespace locgpu

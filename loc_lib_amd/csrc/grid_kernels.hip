@@ -253,7 +253,7 @@ __global__ __launch_bounds__(kBlock) void grid_bin_count_kernel(GridDev g, const
                                                                 const PoseState* __restrict__ st, uint32_t* __restrict__ nn, size_t nn_pitch, int max_n,
                                                                 int skip_nonfinite, uint32_t* __restrict__ qkey, uint32_t* __restrict__ tile_count,
                                                                 uint32_t* __restrict__ walk_list, unsigned int* __restrict__ walk_count,
-                                                                unsigned long long* __restrict__ search_stats) {
+                                                                unsigned long long* __restrict__ search_stats, const int* __restrict__ src_of) {
     __shared__ uint32_t s_key[kBinSlots], s_cnt[kBinSlots];
     const int scan = blockIdx.y;
     if (st[scan].done) return;  // uniform per block
@@ -262,7 +262,7 @@ __global__ __launch_bounds__(kBlock) void grid_bin_count_kernel(GridDev g, const
     bool has = false, to_tree = false, counted = false;
     uint32_t key = kEmptyCell;
     if (i < counts[scan]) {
-        const float4 p = src[gi];
+        const float4 p = src[src_of ? (size_t)src_of[scan] * max_n + i : gi];  // shared-source batches: the region a scan reads (SearchArgs::src_of)
         if (skip_nonfinite && !(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) {  // pcl::isFinite, icp cpp:64 (P2P only)
 #pragma unroll
             for (int j = 0; j < K; ++j) nn[(size_t)j * nn_pitch + gi] = kInvalidSlot;
@@ -321,7 +321,8 @@ template <int K>
 __global__ __launch_bounds__(64) void grid_tile_search_kernel(GridDev g, const uint2* __restrict__ sorted, const uint32_t* __restrict__ n_binned_ptr,
                                                               const float4* __restrict__ src, const PoseState* __restrict__ st,
                                                               uint32_t* __restrict__ nn, size_t nn_pitch, int max_n,
-                                                              uint32_t* __restrict__ tree_list, unsigned int* __restrict__ tree_count, int exp_flags) {
+                                                              uint32_t* __restrict__ tree_list, unsigned int* __restrict__ tree_count, int exp_flags,
+                                                              const int* __restrict__ src_of) {
     __shared__ float4 s_pts[kStageCap];
     __shared__ uint16_t s_lstart[kStageCells + 8];
     __shared__ uint32_t s_keys[kRangeQ];
@@ -404,7 +405,7 @@ __global__ __launch_bounds__(64) void grid_tile_search_kernel(GridDev g, const u
                 }
                 if (j < end && fits && !(exp_flags & 1)) {
                     const int scan = (int)(gi / (uint32_t)max_n);
-                    const float4 p = src[gi];
+                    const float4 p = src[src_of ? (size_t)src_of[scan] * max_n + (gi - (uint32_t)scan * (uint32_t)max_n) : gi];
                     const D3 qs = se3_apply(st[scan].q, st[scan].t, D3{(double)p.x, (double)p.y, (double)p.z});
                     const float qx = (float)qs.x, qy = (float)qs.y, qz = (float)qs.z;
                     const int cx = cell_coord(qx, g.ox, g.inv_cell), cy = cell_coord(qy, g.oy, g.inv_cell), cz = cell_coord(qz, g.oz, g.inv_cell);
@@ -492,7 +493,7 @@ static bool search_grid_k(const GridView& grid, const GridDev& g, const SearchAr
     (void)hipMemsetAsync(a.redo_count2, 0, sizeof(unsigned int), s);
     (void)hipMemsetAsync(sc.tile_count, 0, ((size_t)grid.n_tocc + 1) * sizeof(uint32_t), s);
     hipLaunchKernelGGL((grid_bin_count_kernel<K>), blocks, dim3(kBlock), 0, s, g, a.src, a.counts, a.st, a.nn, a.nn_pitch, a.max_n, a.skip_nonfinite, sc.qkey,
-                       sc.tile_count, a.redo_list2, a.redo_count2, a.search_stats);
+                       sc.tile_count, a.redo_list2, a.redo_count2, a.search_stats, a.src_of);
     size_t tb = grid.scan_temp_bytes;
     if (prim::exclusive_sum(sc.scan_temp, tb, sc.tile_count, sc.tile_count, (int)(grid.n_tocc + 1), s) != hipSuccess) return false;
     hipLaunchKernelGGL(grid_bin_scatter_kernel, blocks, dim3(kBlock), 0, s, a.counts, a.st, a.max_n, sc.qkey, sc.tile_count, sc.sorted);
@@ -501,7 +502,7 @@ static bool search_grid_k(const GridView& grid, const GridDev& g, const SearchAr
     const unsigned waves = (unsigned)std::min<size_t>((total_q + kRangeQ - 1) / kRangeQ, 256u * 8u);
     static const int exp_flags = [] { const char* e = getenv("LOCGPU_GRID_EXP"); return e ? atoi(e) : 0; }();  // timing experiments only (results wrong)
     hipLaunchKernelGGL((grid_tile_search_kernel<K>), dim3(waves), dim3(64), 0, s, g, sc.sorted, sc.tile_count + grid.n_tocc, a.src, a.st, a.nn, a.nn_pitch,
-                       a.max_n, a.redo_list2, a.redo_count2, exp_flags);
+                       a.max_n, a.redo_list2, a.redo_count2, exp_flags, a.src_of);
     return launch_icp_search_list(a, a.redo_list2, a.redo_count2, s);  // a.alpha_eff = 1: exact pruning
 }
 

@@ -79,6 +79,24 @@ int icp_accum_split(int method, int max_n, int n_scans);  // points per thread o
 // owned (optional, scan pools): per global scan, whether this rank holds its points (then first = 0, n_local = n_total)
 void launch_sum_partials(const double* partials, int blocks_per_scan, const PoseState* st_all, int first, int n_local, int n_total, double* acc,
                          hipStream_t s, const unsigned char* owned = nullptr);
+// Fitness score (fitness.hip): after a k = 1 exact search stage has filled `nn`, per scan {Σd² over the inliers, inliers, finite
+// points, 0} → out[scan][kFitW]. partials: room for n_scans × icp_fitness_rows(max_n) × kFitW doubles. gate2 = (float)max_range².
+constexpr int kFitW = 4;
+struct FitnessArgs {
+    const uint2* tree;
+    const float4* src;
+    const int* counts;
+    const PoseState* st;
+    const uint32_t* nn;
+    int max_n, n_scans;
+    float gate2;
+    double* partials;
+    double* out;
+    unsigned int* list_counts;    // the search stage's work-list counters, zeroed behind it (may be null)
+    const int* src_of = nullptr;  // see SearchArgs
+};
+int icp_fitness_rows(int max_n);
+void launch_icp_fitness(const FitnessArgs& a, hipStream_t s);
 struct M12f { float v[12]; };  // rows of pose.matrix().cast<float>() (icp_registration.cpp:241), a kernel argument
 void launch_transform_cloud(const float4* src, size_t n, const M12f& m12, float* dst_xyz, hipStream_t s);
 // Code-object self-test (once per process): no walk kernel owns static LDS, so every traversal stack starts at LDS address 0 —

@@ -137,6 +137,7 @@ void locgpu::free_batch(locgpu_batch* b) {
     if (b->ev_ready) (void)hipEventDestroy(b->ev_ready);
     if (b->ev_reduced) (void)hipEventDestroy(b->ev_reduced);
     if (b->d_src) (void)hipFree(b->d_src);
+    if (b->d_src_of) (void)hipFree(b->d_src_of);
     if (b->d_counts) (void)hipFree(b->d_counts);
     if (b->d_state) (void)hipFree(b->d_state);
     if (b->d_nn) (void)hipFree(b->d_nn);
@@ -247,6 +248,7 @@ void locgpu_destroy(locgpu_ctx* ctx) {
     if (ctx->comm_stream) (void)hipStreamSynchronize(ctx->comm_stream);
     delete ctx->worker;  // joins the helper thread (no job outlives the call that started it)
     free_batch(ctx->single);
+    free_batch(ctx->search);
     upload_free_ctx(ctx);
     if (ctx->comm) { (void)rccl().CommDestroy((ncclComm_t)ctx->comm); ctx->comm = nullptr; }
     if (ctx->comm_stream) (void)hipStreamDestroy(ctx->comm_stream);
@@ -556,11 +558,12 @@ int locgpu_knn(locgpu_ctx* ctx, const float* queries, size_t nq, int k, int appr
 }  // extern "C"
 
 // Device buffers + pinned result staging for n_scans scans of at most max_n points each; no points yet.
-int locgpu::alloc_batch(locgpu_ctx* ctx, int n_scans, size_t max_n, locgpu_batch** out, int first, int n_total) {
+int locgpu::alloc_batch(locgpu_ctx* ctx, int n_scans, size_t max_n, locgpu_batch** out, int first, int n_total, bool shared_src) {
     if (!ctx || !out) return LOCGPU_ERR_INVALID;
     *out = nullptr;
     const bool sharded = n_total >= 0;
     if (!sharded) n_total = n_scans;
+    if (shared_src && (sharded || n_scans < 1)) return fail(ctx, LOCGPU_ERR_INVALID, "batch_create: a shared-source batch cannot be sharded or empty");
     // a sharded batch may hold NO scan on this rank (more ranks than scans): it then only contributes zeros to the exchange
     if (n_scans < 0 || (n_scans == 0 && !sharded) || first < 0 || first + n_scans > n_total) return fail(ctx, LOCGPU_ERR_INVALID, "batch_create: bad arguments");
     if (n_total > 65535) return fail(ctx, LOCGPU_ERR_INVALID, "batch_create: at most 65535 scans per batch");
@@ -582,7 +585,13 @@ int locgpu::alloc_batch(locgpu_ctx* ctx, int n_scans, size_t max_n, locgpu_batch
     b->blocks_per_scan = (int)((max_n + kBlock - 1) / kBlock);
     b->pitch = (size_t)n_scans * max_n;
     b->counts.assign(n_scans, 0);
-    bool ok = hip_ok(ctx, hipMalloc((void**)&b->d_src, std::max<size_t>(b->pitch, 1) * sizeof(float4)), "hipMalloc src") &&
+    b->shared_src = shared_src;
+    b->cap_scans = n_scans;
+    b->cap_points = max_n;
+    // a shared-source batch holds ONE region of points, whatever its number of entries, and a zero per entry that says so
+    bool ok = hip_ok(ctx, hipMalloc((void**)&b->d_src, std::max<size_t>(shared_src ? max_n : b->pitch, 1) * sizeof(float4)), "hipMalloc src") &&
+              (!shared_src || (hip_ok(ctx, hipMalloc((void**)&b->d_src_of, (size_t)n_scans * sizeof(int)), "hipMalloc src_of") &&
+                               fill_now(ctx, b->d_src_of, (size_t)n_scans * sizeof(int), "hipMemset src_of"))) &&
               hip_ok(ctx, hipMalloc((void**)&b->d_counts, std::max(n_scans, 1) * sizeof(int)), "hipMalloc counts") &&
               hip_ok(ctx, hipMalloc((void**)&b->d_state, n_total * sizeof(PoseState)), "hipMalloc state") &&
               (!sharded || hip_ok(ctx, hipMalloc((void**)&b->d_acc, (size_t)kFirstChunk * n_total * kAccW * sizeof(double)), "hipMalloc acc")) &&  // one slot per iteration of a chunk
@@ -642,6 +651,7 @@ int locgpu_batch_create_empty(locgpu_ctx* ctx, int n_scans, size_t max_points_pe
 
 int locgpu_batch_upload_async(locgpu_batch* b, const void* const* srcs, const size_t* counts, size_t stride_bytes) {
     if (!b) return LOCGPU_ERR_INVALID;
+    if (b->shared_src) return fail(b->ctx, LOCGPU_ERR_INVALID, "batch upload: a shared-source batch takes its cloud when it is created");
     LOCGPU_HIP(b->ctx, hipSetDevice(b->ctx->device));
     return upload_start(b, srcs, counts, stride_bytes);
 }
@@ -790,6 +800,7 @@ bool IterLauncher::launch(int do_update) {
         if (grid_mode && !b->d_grid_qkey) { fail(ctx, LOCGPU_ERR_INVALID, "grid search: work list missing (ensure_grid_lists was not called)"); return false; }
         sa.redo_list2 = b->d_redo_list2;
         sa.active = active; sa.n_active = n_active;
+        sa.src_of = b->d_src_of;  // shared-source batches: every entry reads region 0 (nullptr otherwise)
         if (sa.visit_totals && !capturing) {  // instrumented pass: which tree slots does this launch read at all? (bench.py: compulsory bytes)
             const size_t words = (ctx->tree_slots + 2 + 31) / 32;
             if (words > ctx->touched_words) {
@@ -808,6 +819,8 @@ bool IterLauncher::launch(int do_update) {
         const double gate = prm.method == LOCGPU_P2PLANE ? prm.max_plane_distance : (prm.method == LOCGPU_P2LINE ? prm.max_line_distance : prm.max_nn_distance);
         AccumArgs aa{ctx->d_tree, batch_src(b), b->d_counts, st_local, b->d_nn, b->pitch, b->max_n, b->n_scans, gate, b->d_partials};
         aa.active = active; aa.n_active = n_active;
+        aa.src_of = b->d_src_of;
+        if (b->split_scans > 0) aa.split_scans = b->split_scans;  // a candidate search in chunks: the sums of a plain batch of all candidates
         // a rank of a scan-sharded batch splits the partial sums as the WHOLE batch would (points per thread follow the batch's size):
         // the order of a scan's additions — hence its bits — must not depend on how many ranks share the batch (found by the eight-rank
         // loopback run of round 6: 32 of 256 scans per rank summed one point per thread where the plain batch sums four)
@@ -817,9 +830,9 @@ bool IterLauncher::launch(int do_update) {
         mark(true);  // NDT has no separate search kernel: search slot stays empty
         if (prm.method == 4)
             launch_inc_accum(ctx->inc, ctx->ndt_opts.res_outlier_th, ctx->ndt_opts.nearby_type == 0 ? 1 : 7, batch_src(b), b->d_counts, st_local,
-                             b->max_n, b->n_scans, b->d_partials, s);
+                             b->max_n, b->n_scans, b->d_partials, s, nullptr, 0, b->d_src_of);
         else
-            n_partial_blocks = launch_ndt_accum(ctx->ndt, batch_src(b), b->d_counts, st_local, b->max_n, b->n_scans, b->d_partials, s, nullptr, 0, b->sharded ? b->n_total : 0);
+            n_partial_blocks = launch_ndt_accum(ctx->ndt, batch_src(b), b->d_counts, st_local, b->max_n, b->n_scans, b->d_partials, s, nullptr, 0, b->sharded ? b->n_total : 0, b->d_src_of);
     }
     mark();
     if (b->sharded) {
@@ -1536,6 +1549,254 @@ int locgpu_transform_cloud(locgpu_ctx* ctx, const double pose[7], const void* sr
     const int rc = single_batch(ctx, src, n, src_stride_bytes, &b);
     if (rc != LOCGPU_OK) return rc;
     return write_output_cloud(ctx, b, b->d_src, n, pose, out, out_stride_bytes);
+}
+
+// --------------------------------------------------------------------------------------------- fitness score, shared-source batches, initial-pose search
+}  // extern "C"
+
+namespace {
+// The context's own shared-source batch (locgpu_icp_fitness with several poses, locgpu_icp_init_search) is bounded: at most
+// kSearchEntries entries per chunk and kSearchBytes of per-entry workspace (neighbour lists 20 B + two work lists 8 B per point and entry).
+constexpr int kSearchEntries = 256;
+constexpr size_t kSearchBytes = (size_t)1 << 30;
+constexpr size_t kSearchBytesPerPoint = 28;
+
+void drop_graphs(locgpu_batch* b) {
+    if (b->graph_exec) { (void)hipGraphExecDestroy(b->graph_exec); b->graph_exec = nullptr; }
+    if (b->graph_exec_next) { (void)hipGraphExecDestroy(b->graph_exec_next); b->graph_exec_next = nullptr; }
+}
+
+// What the next call uses of a shared-source batch's buffers: n_scans entries (<= cap_scans) of n points (<= cap_points), every entry
+// n points long; split_scans as in locgpu_batch. Everything the kernels index goes through n_scans / max_n / pitch, so a smaller
+// shape is the same batch as one created at that size.
+int reshape_shared(locgpu_ctx* ctx, locgpu_batch* b, int n_scans, size_t n, int split_scans) {
+    if (n_scans < 1 || n_scans > b->cap_scans || n == 0 || n > b->cap_points) return fail(ctx, LOCGPU_ERR_INVALID, "shared-source batch: shape exceeds its capacity");
+    if (b->n_scans != n_scans || (size_t)b->max_n != n || b->split_scans != split_scans) {
+        LOCGPU_HIP(ctx, hipStreamSynchronize(b->stream));
+        drop_graphs(b);  // captured launches carry the old shape
+        if ((size_t)n_scans * n > b->pitch) {  // the grid search's lists were sized by the old pitch (ensure_grid_lists)
+            if (b->d_grid_qkey) { (void)hipFree(b->d_grid_qkey); b->d_grid_qkey = nullptr; }
+            if (b->d_grid_sorted) { (void)hipFree(b->d_grid_sorted); b->d_grid_sorted = nullptr; }
+        }
+        b->n_scans = b->n_total = n_scans;
+        b->max_n = (int)n;
+        b->blocks_per_scan = (int)((n + kBlock - 1) / kBlock);
+        b->pitch = (size_t)n_scans * n;
+        b->split_scans = split_scans;
+        b->last_iterations = -1;
+    }
+    b->counts.assign(n_scans, (int)n);
+    LOCGPU_HIP(ctx, hipMemcpyAsync(b->d_counts, b->counts.data(), (size_t)n_scans * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    return LOCGPU_OK;
+}
+
+// The one upload of a shared-source batch: the deep copy of the source (SetSource, icp_registration.cpp:252-265), 16 B per point once.
+int upload_shared(locgpu_ctx* ctx, locgpu_batch* b, const void* src, size_t n, size_t stride_bytes) {
+    if (!b->h_src) LOCGPU_HIP(ctx, hipHostMalloc((void**)&b->h_src, b->cap_points * sizeof(float4)));
+    pack_points((const char*)src, stride_bytes, n, b->h_src);
+    LOCGPU_HIP(ctx, hipMemcpyAsync(b->d_src, b->h_src, n * sizeof(float4), hipMemcpyHostToDevice, b->stream));
+    return LOCGPU_OK;
+}
+
+// The context's shared-source batch with the cloud resident, for m entries in all: *chunk = entries per chunk (equal chunks, the
+// last one may be shorter).
+int search_batch(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, int m, int* chunk, locgpu_batch** out) {
+    const size_t fit = kSearchBytes / (kSearchBytesPerPoint * n);
+    const int chunk_max = (int)std::min<size_t>(kSearchEntries, std::max<size_t>(fit, 1));
+    const int n_chunks = (m + chunk_max - 1) / chunk_max;
+    *chunk = (m + n_chunks - 1) / n_chunks;
+    locgpu_batch* b = ctx->search;
+    if (!b || b->cap_scans < *chunk || b->cap_points < n) {
+        // grow-only while the bound holds; else exactly what this call needs
+        int cs = std::max(*chunk, b ? b->cap_scans : 0);
+        size_t cp = std::max(n, b ? b->cap_points : (size_t)0);
+        if ((size_t)cs * cp * kSearchBytesPerPoint > kSearchBytes) { cs = *chunk; cp = n; }
+        if (b) { (void)hipStreamSynchronize(b->stream); free_batch(b); ctx->search = nullptr; }
+        const int slot = ctx->next_slot;
+        const int rc = alloc_batch(ctx, cs, cp, &ctx->search, 0, -1, true);
+        ctx->next_slot = slot;  // the context's own batch does not take part in the rotation of the caller's batches over the streams
+        if (rc != LOCGPU_OK) return rc;
+        b = ctx->search;
+        b->slot = 0;
+        b->stream = ctx->stream;
+    }
+    const int rc = upload_shared(ctx, b, src, n, stride_bytes);
+    if (rc != LOCGPU_OK) return rc;
+    *out = b;
+    return LOCGPU_OK;
+}
+
+// Score of every entry of `b` under its pose: k = 1 exact search stage, then the reduction of fitness.hip.
+int fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, double max_range, locgpu_fitness* out) {
+    if (b->sharded) return fail(ctx, LOCGPU_ERR_INVALID, "icp_fitness: sharded batches are not scored");
+    if (b->pending.active) return fail(ctx, LOCGPU_ERR_INVALID, "icp_fitness: an alignment of this batch has been begun and not finished");
+    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+    { const int urc = batch_ready(ctx, b); if (urc != LOCGPU_OK) return urc; }
+    init_states(b, poses);
+    hipStream_t s = b->stream;
+    if (!b->counters_clean) LOCGPU_HIP(ctx, hipMemsetAsync(b->d_redo_count, 0, 4 * sizeof(unsigned int), s));
+    b->counters_clean = false;
+    LOCGPU_HIP(ctx, hipMemcpyAsync(b->d_state, b->h_state, b->n_total * sizeof(PoseState), hipMemcpyHostToDevice, s));
+    // the exact walk whatever the matcher's options say: a score must not depend on a pruning knob (alpha_eff = 1), and it skips the
+    // points pcl::isFinite rejects
+    SearchArgs sa{ctx->d_tree, ctx->tree_slots * sizeof(uint64_t), ctx->depth, batch_src(b), b->d_counts, b->d_state, b->d_nn, b->pitch, b->max_n, b->n_scans, 1, 1.0f,
+                  1, nullptr, b->d_redo_list, b->d_redo_count, b->d_redo_list2, b->d_redo_count + 1, ctx->d_search_stats};
+    if (!ctx->tree_bounded) sa.redo_list = nullptr;  // huge / non-finite map coordinates: exact tree kernel only
+    sa.src_of = b->d_src_of;
+    if (!launch_icp_search(sa, s)) return fail(ctx, LOCGPU_ERR_DEPTH, "icp_fitness: unsupported tree depth");
+    FitnessArgs fa{ctx->d_tree, batch_src(b), b->d_counts, b->d_state, b->d_nn, b->max_n, b->n_scans, (float)(max_range * max_range), b->d_partials, b->d_hb, b->d_redo_count};
+    fa.src_of = b->d_src_of;
+    launch_icp_fitness(fa, s);
+    LOCGPU_HIP(ctx, hipGetLastError());
+    LOCGPU_HIP(ctx, hipMemcpyAsync(b->h_hb, b->d_hb, (size_t)b->n_scans * kFitW * sizeof(double), hipMemcpyDeviceToHost, s));
+    LOCGPU_HIP(ctx, hipStreamSynchronize(s));
+    b->counters_clean = true;  // the sum kernel zeroed them behind the search
+    for (int i = 0; i < b->n_scans; ++i) {
+        const double* r = b->h_hb + (size_t)i * kFitW;
+        out[i].inliers = (int64_t)r[1];
+        out[i].finite_points = (int64_t)r[2];
+        out[i].score = out[i].inliers > 0 ? r[0] / (double)out[i].inliers : HUGE_VAL;
+    }
+    return LOCGPU_OK;
+}
+
+int fitness_target(locgpu_ctx* ctx) {
+    { const int jrc = target_join(ctx); if (jrc != LOCGPU_OK) return jrc; }
+    if (!ctx->d_tree) return fail(ctx, LOCGPU_ERR_NO_TARGET, "icp_fitness: SetInputTarget has not been called");
+    return LOCGPU_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int locgpu_batch_create_shared(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, int n_entries, locgpu_batch** out) {
+    if (!ctx || !out) return LOCGPU_ERR_INVALID;
+    *out = nullptr;
+    if (!src || n == 0 || stride_bytes < 12 || n_entries < 1) return fail(ctx, LOCGPU_ERR_INVALID, "batch_create_shared: bad arguments");
+    locgpu_batch* b = nullptr;
+    int rc = alloc_batch(ctx, n_entries, n, &b, 0, -1, true);
+    if (rc != LOCGPU_OK) return rc;
+    rc = upload_shared(ctx, b, src, n, stride_bytes);
+    if (rc == LOCGPU_OK) rc = reshape_shared(ctx, b, n_entries, n, 0);
+    if (rc == LOCGPU_OK && !hip_ok(ctx, hipStreamSynchronize(b->stream), "batch_create_shared: H2D")) rc = LOCGPU_ERR_NO_DEVICE;
+    if (rc != LOCGPU_OK) { free_batch(b); return rc; }
+    *out = b;
+    return LOCGPU_OK;
+}
+
+int locgpu_icp_fitness_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, double max_range, locgpu_fitness* out) {
+    if (!ctx) return LOCGPU_ERR_INVALID;
+    const int rc = fitness_target(ctx);
+    if (rc != LOCGPU_OK) return rc;
+    if (!b || b->ctx != ctx || !poses || !out || std::isnan(max_range)) return fail(ctx, LOCGPU_ERR_INVALID, "icp_fitness_batch: bad arguments");
+    if (b->n_scans < 1) return fail(ctx, LOCGPU_ERR_INVALID, "icp_fitness_batch: the batch holds no scan");
+    return fitness_on_batch(ctx, b, poses, max_range, out);
+}
+
+int locgpu_icp_fitness(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double* poses, int n_poses, double max_range,
+                       locgpu_fitness* out) {
+    if (!ctx) return LOCGPU_ERR_INVALID;
+    int rc = fitness_target(ctx);
+    if (rc != LOCGPU_OK) return rc;
+    if (!src || n == 0 || stride_bytes < 12 || !poses || n_poses < 1 || !out || std::isnan(max_range)) return fail(ctx, LOCGPU_ERR_INVALID, "icp_fitness: bad arguments");
+    if (n > 0x7FFFFF00u) return fail(ctx, LOCGPU_ERR_INVALID, "icp_fitness: too many points");
+    locgpu_batch* b = nullptr;
+    if (n_poses == 1) {
+        rc = single_batch(ctx, src, n, stride_bytes, &b);
+        return rc != LOCGPU_OK ? rc : fitness_on_batch(ctx, b, poses, max_range, out);
+    }
+    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+    int chunk = 0;
+    rc = search_batch(ctx, src, n, stride_bytes, n_poses, &chunk, &b);
+    for (int off = 0; rc == LOCGPU_OK && off < n_poses; off += chunk) {
+        const int cnt = std::min(chunk, n_poses - off);
+        rc = reshape_shared(ctx, b, cnt, n, 0);
+        if (rc == LOCGPU_OK) rc = fitness_on_batch(ctx, b, poses + 7 * (size_t)off, max_range, out + off);
+    }
+    return rc;
+}
+
+int locgpu_icp_fitness_resident(locgpu_ctx* ctx, const double pose[7], double max_range, locgpu_fitness* out) {
+    if (!ctx) return LOCGPU_ERR_INVALID;
+    const int rc = fitness_target(ctx);
+    if (rc != LOCGPU_OK) return rc;
+    if (!pose || !out || std::isnan(max_range)) return fail(ctx, LOCGPU_ERR_INVALID, "icp_fitness_resident: bad arguments");
+    locgpu_batch* b = ctx->single;
+    if (!b || b->d_src_ext || b->counts[0] <= 0) return fail(ctx, LOCGPU_ERR_INVALID, "icp_fitness_resident: no source cloud of a single-scan call is resident");
+    return fitness_on_batch(ctx, b, pose, max_range, out);
+}
+
+void locgpu_init_search_opts_default(locgpu_init_search_opts* o) {
+    if (!o) return;
+    o->max_range = 1.0;
+    o->min_inlier_ratio = 0.5;
+}
+
+int locgpu_icp_init_search(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double* candidates, int m, const locgpu_icp_opts* opts,
+                           const locgpu_init_search_opts* sopts, double* out_poses, locgpu_fitness* out_fit, locgpu_align_stats* stats, int* best) {
+    GnParams prm{};
+    int k;
+    float alpha_eff;
+    int rc = check_icp(ctx, opts, prm, k, alpha_eff);
+    if (rc != LOCGPU_OK) return rc;
+    locgpu_init_search_opts so;
+    if (sopts) so = *sopts; else locgpu_init_search_opts_default(&so);
+    if (!src || n == 0 || stride_bytes < 12 || !candidates || m < 1 || !out_poses || !out_fit || !best || std::isnan(so.max_range) ||
+        !(so.min_inlier_ratio >= 0.0))
+        return fail(ctx, LOCGPU_ERR_INVALID, "icp_init_search: bad arguments");
+    if (n > 0x7FFFFF00u) return fail(ctx, LOCGPU_ERR_INVALID, "icp_init_search: too many points");
+    *best = -1;
+    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+    locgpu_batch* b = nullptr;
+    int chunk = 0;
+    rc = search_batch(ctx, src, n, stride_bytes, m, &chunk, &b);
+    for (int off = 0; rc == LOCGPU_OK && off < m; off += chunk) {
+        const int cnt = std::min(chunk, m - off);
+        // every chunk sums as the plain batch of all m candidates would: chunking never shows in a pose
+        rc = reshape_shared(ctx, b, cnt, n, m);
+        if (rc == LOCGPU_OK) rc = run_align(ctx, b, candidates + 7 * (size_t)off, prm, k, alpha_eff, false, out_poses + 7 * (size_t)off, stats ? stats + off : nullptr);
+        if (rc == LOCGPU_OK) rc = fitness_on_batch(ctx, b, out_poses + 7 * (size_t)off, so.max_range, out_fit + off);
+    }
+    if (rc != LOCGPU_OK) return rc;
+    for (int i = 0; i < m; ++i) {
+        const locgpu_fitness& f = out_fit[i];
+        if (f.inliers <= 0 || !((double)f.inliers >= so.min_inlier_ratio * (double)f.finite_points)) continue;
+        if (*best < 0 || f.score < out_fit[*best].score) *best = i;  // ties stay with the lower index
+    }
+    return LOCGPU_OK;
+}
+
+int locgpu_pose_grid(const double centre[7], double xy_half, double xy_step, double yaw_half, double yaw_step, double* out, size_t cap, size_t* n_out) {
+    if (!centre || !n_out || (cap && !out)) return LOCGPU_ERR_INVALID;
+    auto steps = [](double half, double step, long* k) {
+        if (!(half >= 0.0) || !std::isfinite(half)) return false;
+        if (half == 0.0) { *k = 0; return true; }
+        if (!(step > 0.0)) return false;
+        const double r = std::floor(half / step + 1e-9);  // 0.15 / 0.05 is 2.9999999999999996 in binary64: the steps that divide the half reach it
+        if (r > 1e6) return false;
+        *k = (long)r;
+        return true;
+    };
+    long kxy = 0, kyaw = 0;
+    if (!steps(xy_half, xy_step, &kxy) || !steps(yaw_half, yaw_step, &kyaw)) return LOCGPU_ERR_INVALID;
+    const size_t nxy = (size_t)(2 * kxy + 1), nyaw = (size_t)(2 * kyaw + 1);
+    *n_out = nyaw * nxy * nxy;
+    double R[9];
+    quat_to_R(centre, R);
+    size_t w = 0;
+    for (long a = -kyaw; a <= kyaw && w < cap; ++a) {
+        const double yaw = (double)a * yaw_step, sz = std::sin(0.5 * yaw), cz = std::cos(0.5 * yaw);
+        // centre ⊗ (0, 0, sz, cz), Hamilton product in (x, y, z, w) order
+        const double q[4] = {centre[0] * cz + centre[1] * sz, centre[1] * cz - centre[0] * sz, centre[2] * cz + centre[3] * sz, centre[3] * cz - centre[2] * sz};
+        for (long ix = -kxy; ix <= kxy && w < cap; ++ix)
+            for (long iy = -kxy; iy <= kxy && w < cap; ++iy) {
+                const double x = (double)ix * xy_step, y = (double)iy * xy_step;
+                double* o = out + 7 * w++;
+                for (int j = 0; j < 4; ++j) o[j] = q[j];
+                for (int r = 0; r < 3; ++r) o[4 + r] = centre[4 + r] + (R[3 * r] * x + R[3 * r + 1] * y);
+            }
+    }
+    return LOCGPU_OK;
 }
 
 // --------------------------------------------------------------------------------------------- measurement

@@ -5,6 +5,7 @@
 // accelerated path: constructing with it is accepted, matching calls report failure through the bool.
 #pragma once
 #include <memory>
+#include <vector>
 
 #include "LocUtils/model/matching/3d/matching_interface.h"
 
@@ -42,6 +43,19 @@ public:
     bool ScanMatch(const CloudPtr& input_source, const SE3& predict_pose, CloudPtr& result_cloud_ptr, SE3& result_pose) override;
     float GetFitnessScore() override;
 
+    // Not in the reference, where GetFitnessScore is a stub that returns 0 (icp_registration.cpp:246-250). After
+    // EnableFitnessScore(max_range [m]) GetFitnessScore() returns the score of the last ScanMatch as pcl::Registration::getFitnessScore
+    // defines it (locgpu.h, locgpu_icp_fitness): it is computed on that call, from the source copy ScanMatch left in HBM and the
+    // result pose — ScanMatch itself does nothing more than before. +inf when no point lies within max_range; 0 before the first
+    // ScanMatch or when the library fails (LastError). WITHOUT the opt-in GetFitnessScore() keeps returning the reference's 0.0f.
+    // NdtRegistration and LoamRegistration keep the stub: an NDT context has no nearest-neighbour structure to score against.
+    void EnableFitnessScore(double max_range);
+    // Not in the reference: aligns `source` from every candidate pose with this matcher's options in one batched call on the GPU
+    // (locgpu_icp_init_search: the cloud is uploaded once), scores every result (EnableFitnessScore's range, 1 m by default) and hands
+    // back the best: the lowest score among the results with at least half of their points within range. false — and best_pose /
+    // best_score untouched — when no candidate qualifies, there is no target, or the library fails (LastError).
+    bool InitialPoseSearch(const CloudPtr& source, const std::vector<SE3>& candidates, SE3& best_pose, float& best_score);
+
     // Which GPU the matcher lives on (default 0). Not in the reference; must be called before SetInputTarget.
     void SetDevice(int device_id);
     // Text of the last liblocgpu error (the reference only logs through glog) — or, when the options name a branch of the reference
@@ -57,6 +71,9 @@ private:
     locgpu_ctx* ctx_ = nullptr;
     int device_id_ = 0;
     bool has_target_ = false;
+    bool fitness_enabled_ = false, have_last_pose_ = false;  // have_last_pose_: the last ScanMatch left its source in HBM
+    double fitness_range_ = 1.0;
+    SE3 last_pose_;
 };
 
 }  // namespace LocUtils

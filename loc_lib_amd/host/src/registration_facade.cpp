@@ -84,6 +84,7 @@ bool IcpRegistration::CaculateMatrixHAndB(const CloudPtr& input_source, const SE
     const locgpu_icp_opts o = to_c(options_);
     double h[36], b[6];
     int ok = 0;
+    have_last_pose_ = false;  // the evaluation replaces the source copy ScanMatch left in HBM: GetFitnessScore has nothing to score
     if (locgpu_icp_hb(ctx_, input_source->points.data(), input_source->points.size(), sizeof(PointType), predict_pose.data(), &o, h, b, nullptr,
                       &ok) != LOCGPU_OK)
         return false;
@@ -97,6 +98,7 @@ bool IcpRegistration::ScanMatch(const CloudPtr& input_source, const SE3& predict
     if (Unsupported()) return false;  // a refusal, loudly (LastError): neither result_pose nor the output cloud is touched
     if (!input_source) return true;
     SE3 pose = predict_pose;
+    have_last_pose_ = false;
     if (has_target_ && !input_source->points.empty()) {
         // alignment + output cloud in ONE call: the source crosses PCIe once, the transform runs on the copy the alignment left in HBM
         const locgpu_icp_opts o = to_c(options_);
@@ -106,6 +108,8 @@ bool IcpRegistration::ScanMatch(const CloudPtr& input_source, const SE3& predict
                                   nullptr, nullptr, sizeof(PointType) | LOCGPU_OUT_FIELDS_DONE, size_output_cloud, &oc) == LOCGPU_OK) {
             std::memcpy(pose.data(), out, sizeof(out));
             result_pose = pose;
+            last_pose_ = pose;  // what a later GetFitnessScore scores (the source stays in HBM until the next call)
+            have_last_pose_ = true;
             return true;  // icp_registration.cpp:243
         }
     }
@@ -114,7 +118,36 @@ bool IcpRegistration::ScanMatch(const CloudPtr& input_source, const SE3& predict
     return true;  // icp_registration.cpp:243
 }
 
-float IcpRegistration::GetFitnessScore() { return 0.0f; }  // icp_registration.cpp:246-250
+void IcpRegistration::EnableFitnessScore(double max_range) {
+    fitness_enabled_ = true;
+    fitness_range_ = max_range;
+}
+
+float IcpRegistration::GetFitnessScore() {
+    if (!fitness_enabled_ || !have_last_pose_) return 0.0f;  // icp_registration.cpp:246-250: the reference's stub
+    locgpu_fitness f;
+    if (locgpu_icp_fitness_resident(ctx_, last_pose_.data(), fitness_range_, &f) != LOCGPU_OK) return 0.0f;
+    return (float)f.score;
+}
+
+bool IcpRegistration::InitialPoseSearch(const CloudPtr& source, const std::vector<SE3>& candidates, SE3& best_pose, float& best_score) {
+    if (Unsupported() || !has_target_ || !source || source->points.empty() || candidates.empty()) return false;
+    const locgpu_icp_opts o = to_c(options_);
+    locgpu_init_search_opts so;
+    locgpu_init_search_opts_default(&so);
+    so.max_range = fitness_range_;
+    const size_t m = candidates.size();
+    std::vector<double> in(7 * m), out(7 * m);
+    for (size_t i = 0; i < m; ++i) std::memcpy(&in[7 * i], candidates[i].data(), 7 * sizeof(double));
+    std::vector<locgpu_fitness> fit(m);
+    int best = -1;
+    if (locgpu_icp_init_search(ctx_, source->points.data(), source->points.size(), sizeof(PointType), in.data(), (int)m, &o, &so, out.data(), fit.data(),
+                               nullptr, &best) != LOCGPU_OK || best < 0)
+        return false;
+    std::memcpy(best_pose.data(), &out[7 * (size_t)best], 7 * sizeof(double));
+    best_score = (float)fit[best].score;
+    return true;
+}
 
 // ------------------------------------------------------------------------------------------------ NDT
 NdtRegistration::NdtRegistration() { options_.inv_voxel_size_ = 1.0 / options_.voxel_size_; }
