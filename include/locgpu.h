@@ -45,7 +45,16 @@ typedef enum locgpu_status {
 } locgpu_status;
 
 /* IcpMethod, LocUtils/include/LocUtils/model/matching/3d/icp/icp_registration.hpp:15-20 (PCLICP is not on the path). */
-typedef enum locgpu_icp_method { LOCGPU_P2P = 0, LOCGPU_P2LINE = 1, LOCGPU_P2PLANE = 2 } locgpu_icp_method;
+typedef enum locgpu_icp_method {
+    LOCGPU_P2P = 0,
+    LOCGPU_P2LINE = 1,
+    LOCGPU_P2PLANE = 2,
+    /* A labelled FAST MODE with no reference counterpart, never the source of a parity claim (see locgpu_icp_build_map_planes):
+     * point-to-plane against the plane fitted ONCE per map point at ingest, looked up at the 1-nearest leaf, instead of the
+     * reference's math::FitPlane per query and iteration (math_utils.h:112-136, icp_registration.cpp:161-213). Not the default.
+     * (3 and 4 are taken inside the library by the NDT variants of the Gauss-Newton solve.) */
+    LOCGPU_P2PLANE_MAP = 5
+} locgpu_icp_method;
 
 /* How correspondences are searched.
  * TREE_FAITHFUL replays the reference's mean-split KD-tree and its DFS visit order bit for bit
@@ -110,6 +119,33 @@ LOCGPU_API int locgpu_icp_set_target(locgpu_ctx* ctx, const void* pts, size_t n,
 LOCGPU_API int locgpu_icp_set_target_async(locgpu_ctx* ctx, const void* pts, size_t n, size_t stride_bytes);
 /* out[0]=leaves (KdTree::size_), out[1]=tree nodes, out[2]=depth, out[3]=bytes of the packed tree in HBM */
 LOCGPU_API int locgpu_icp_target_info(const locgpu_ctx* ctx, int64_t out[4]);
+
+/* ---- Map planes: the per-map-point plane table behind LOCGPU_P2PLANE_MAP (no reference counterpart). It stands in
+ * for the math::FitPlane call (math_utils.h:112-136) that IcpRegistration::CaculateMatrixHAndBP2Plane (icp_registration.cpp:161-213)
+ * makes per source point and iteration. For every leaf of the target's KD-tree: its five EXACT nearest leaves (itself included; the
+ * walk of KdTree::GetClosestPoint with approximate_ = false) in FP64 -> FitPlane -> the FP64 4-vector n4 (the normal is not unit, as in
+ * the reference), valid iff all five (n3·p + d)² <= 1e-2; a tree of fewer than five leaves has no valid plane. One evaluation of
+ * H, B with the method: for every finite source point q, qs = pose·q in FP64, the 1-nearest leaf of (float)qs under the caller's
+ * approximate / ann_alpha / search_mode; no neighbour or no valid plane there: skipped; otherwise effective_num++, dis = n3·qs + n4[3],
+ * skipped if |dis| > max_plane_distance, else J = [-n3ᵀ·R·hat(q), n3ᵀ], H += JᵀJ, B += -Jᵀ·dis; update, `ok` and stop rule are
+ * AlignP2Plane's (icp_registration.cpp:345-381). The method is accepted by locgpu_icp_hb / _align / _scan_match / _align_cloud,
+ * locgpu_icp_align_batch / _begin / _end, locgpu_icp_hb_batch, shared-source batches and locgpu_icp_init_search, eager and hipGraph,
+ * tree and grid search; locgpu_gn_update takes it as P2PLANE. Scan pools (locgpu_pool_create) and sharded batches
+ * (locgpu_batch_create_sharded) return LOCGPU_ERR_INVALID for it.
+ * build: estimates the table for the current ICP target on the device (completing an asynchronous ingest first); idempotent; any
+ * locgpu_icp_set_target* drops the table, and the first use of the method without one builds it. 32 B per row, about 1.5 rows per
+ * map point; the table and a workspace for chunks of 2^20 leaves stay with the context, grow-only. */
+LOCGPU_API int locgpu_icp_build_map_planes(locgpu_ctx* ctx);
+/* math::FitPlane results held for the target (math_utils.h:112-136; icp_registration.cpp:161-213 reads them through the method above):
+ * out[0] = leaves with a plane row, out[1] = valid planes, out[2] = bytes of the table in HBM. All zero when no table is built.
+ * Like locgpu_icp_target_info it completes a pending asynchronous ingest (the context is const in name only). */
+LOCGPU_API int locgpu_icp_map_planes_info(const locgpu_ctx* ctx, int64_t out[3]);
+/* Debug / test read-back (like locgpu_ndt_dump) of the math::FitPlane rows (math_utils.h:112-136) the method reads in place of
+ * icp_registration.cpp:161-213's own fit: rows indexed by ORIGINAL point index, n4: cap × 4 doubles, valid: cap bytes; a point that is
+ * no leaf of the tree (dropped by the degenerate-split rule) is reported invalid with a zero row. Builds the table if there is none.
+ * *n_out = number of target points; LOCGPU_ERR_INVALID when cap is smaller. n4 = valid = NULL with cap = 0 is a size query: it
+ * only sets *n_out and returns LOCGPU_OK. */
+LOCGPU_API int locgpu_icp_map_planes_dump(locgpu_ctx* ctx, double* n4, uint8_t* valid, size_t cap, size_t* n_out);
 
 /* ---- SearchPointInterface::FindNearstPoints (search_point_interface.h:13; kdtree.cpp:272-283), many queries at once.
  * queries: nq × 3 packed float32 (host). out_idx: nq × k int32 original point indices, ascending distance (host).

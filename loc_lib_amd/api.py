@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("LOCGPU_LIB") or os.path.join(_HERE, "liblocgpu.so")  
 CSRC = os.path.join(_HERE, "csrc")
 
 P2P, P2LINE, P2PLANE = 0, 1, 2
+P2PLANE_MAP = 5  # labelled fast mode: planes fitted once per map point at ingest; never a parity source
 SEARCH_TREE_FAITHFUL, SEARCH_GRID_EXACT = 0, 1
 CENTER, NEARBY6 = 0, 1
 DIRECT_NDT, INCREMENTAL_NDT = 1, 2
@@ -44,6 +45,7 @@ ABI_SYMBOLS = [
     "locgpu_icp_scan_match", "locgpu_ndt_scan_match",
     "locgpu_icp_fitness", "locgpu_icp_fitness_batch", "locgpu_icp_fitness_resident", "locgpu_batch_create_shared",
     "locgpu_init_search_opts_default", "locgpu_icp_init_search", "locgpu_pose_grid",
+    "locgpu_icp_build_map_planes", "locgpu_icp_map_planes_info", "locgpu_icp_map_planes_dump",
 ]
 COMM_ID_BYTES = 128
 NO_INTENSITY = ctypes.c_size_t(-1).value
@@ -158,6 +160,8 @@ def lib():
             "locgpu_init_search_opts_default": (None, [vp]),
             "locgpu_icp_init_search": (i32, [vp, vp, sz, sz, vp, i32, vp, vp, vp, vp, vp, vp]),
             "locgpu_pose_grid": (i32, [vp, dbl, dbl, dbl, dbl, vp, sz, vp]),
+            "locgpu_icp_build_map_planes": (i32, [vp]), "locgpu_icp_map_planes_info": (i32, [vp, vp]),
+            "locgpu_icp_map_planes_dump": (i32, [vp, vp, vp, sz, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -283,6 +287,24 @@ class Context:
         out = np.zeros(4, dtype=np.int64)
         self._check(lib().locgpu_icp_target_info(self._h, out.ctypes.data))
         return dict(num_leaves=int(out[0]), num_nodes=int(out[1]), depth=int(out[2]), bytes=int(out[3]))
+
+    # ---- the plane table of P2PLANE_MAP (one math::FitPlane per map point at ingest)
+    def icp_build_map_planes(self):
+        self._check(lib().locgpu_icp_build_map_planes(self._h))
+
+    def icp_map_planes_info(self):
+        out = np.zeros(3, dtype=np.int64)
+        self._check(lib().locgpu_icp_map_planes_info(self._h, out.ctypes.data))
+        return dict(rows=int(out[0]), valid=int(out[1]), bytes=int(out[2]))
+
+    def icp_map_planes_dump(self):
+        """(n4 [n_points, 4] float64, valid [n_points] bool), rows by original point index of the target cloud."""
+        n = ctypes.c_size_t(0)
+        self._check(lib().locgpu_icp_map_planes_dump(self._h, None, None, 0, ctypes.byref(n)))  # size query
+        n4 = np.zeros((max(n.value, 1), 4))
+        valid = np.zeros(max(n.value, 1), dtype=np.uint8)
+        self._check(lib().locgpu_icp_map_planes_dump(self._h, n4.ctypes.data, valid.ctypes.data, n4.shape[0], ctypes.byref(n)))
+        return n4[:n.value], valid[:n.value].astype(bool)
 
     # ---- SearchPointInterface::FindNearstPoints, many queries
     def knn(self, queries, k=5, approximate=True, alpha=0.1, search_mode=SEARCH_TREE_FAITHFUL, with_visits=False):

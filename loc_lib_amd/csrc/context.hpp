@@ -46,6 +46,15 @@ struct locgpu_ctx {
 
     uint32_t* d_leaf_slots = nullptr;  // slot of every leaf, preorder (what the exact-search grid is built from)
 
+    // LOCGPU_P2PLANE_MAP: one plane per leaf, row slot >> 1 = four doubles, NaNs = none (map_planes.hip). Built on first use or by
+    // locgpu_icp_build_map_planes, dropped (planes_ready) by every set_target; the buffers are grow-only.
+    double* d_planes = nullptr;
+    size_t planes_cap_rows = 0, planes_rows = 0;
+    bool planes_ready = false;
+    long long planes_valid = 0;
+    unsigned long long* d_planes_count = nullptr;
+    locgpu_batch* planes_ws = nullptr;  // one-scan search batch of the ingest's chunks
+
     // exact-search grid over the tree's leaves (built on the device on first use of LOCGPU_SEARCH_GRID_EXACT)
     locgpu::GridView grid;
     locgpu::GridBuffers grid_buf;

@@ -2,6 +2,7 @@
 #include "icp_kernels.hpp"
 #include "launch.hpp"
 #include "search_walk.hpp"
+#include "../../include/locgpu.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -500,6 +501,56 @@ __global__ __launch_bounds__(kBlock) void icp_point_accum_kernel(const uint2* __
     block_reduce_store<28>(acc, partials + ((size_t)scan * gridDim.x + blockIdx.x) * kAccW);
 }
 
+// K2'', LOCGPU_P2PLANE_MAP: CaculateMatrixHAndBP2Plane (icp_registration.cpp:161-213) with the per-query math::FitPlane
+// (math_utils.h:112-136) replaced by a look-up of the plane fitted at ingest for the NEAREST leaf (map_planes.hip). Per point: the
+// source point, one slot word, one 32-byte row planes[slot >> 1] (four NaNs = no valid plane) — no leaf load, no SVD. J and dis in the
+// plane kernel's coefficient order; sums per thread and one wave reduction per block like the point kernel.
+__global__ __launch_bounds__(kBlock) void icp_mapplane_accum_kernel(const double4* __restrict__ planes, const float4* __restrict__ src,
+                                                                    const int* __restrict__ counts, const PoseState* __restrict__ st,
+                                                                    const uint32_t* __restrict__ nn, int max_n, double max_plane_distance,
+                                                                    double* __restrict__ partials, int pts, const int* __restrict__ active,
+                                                                    const int* __restrict__ src_of) {
+    const int scan = active ? active[blockIdx.y] : (int)blockIdx.y;
+    if (st[scan].done) return;
+    double acc[28];
+#pragma unroll
+    for (int v = 0; v < 28; ++v) acc[v] = 0.0;
+    const int n = counts[scan];
+    const size_t region = (size_t)(src_of ? src_of[scan] : scan) * max_n;
+#pragma unroll 1
+    for (int pp = 0; pp < pts; ++pp) {
+        const int i = (blockIdx.x * pts + pp) * kBlock + threadIdx.x;
+        if (i < n) {
+            const uint32_t s0 = __builtin_nontemporal_load(&nn[(size_t)scan * max_n + i]);
+            const float4 p = src[region + i];
+            if (s0 != kInvalidSlot) {  // a non-finite source point is no query (the search left it the empty list)
+                const double4 n4 = planes[s0 >> 1];
+                if (n4.x == n4.x) {
+                    acc[27] += 1.0;  // effective_num++ before the residual gate (icp cpp:184)
+                    const D3 n3{n4.x, n4.y, n4.z};
+                    const D3 q{(double)p.x, (double)p.y, (double)p.z};
+                    const D3 qs = se3_apply(st[scan].q, st[scan].t, q);
+                    const double dis = dot3(n3, qs) + n4.w;
+                    if (!(fabs(dis) > max_plane_distance)) {
+                        const double* R = st[scan].R;
+                        double nR[3];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) nR[c] = -n3.x * R[c] + (-n3.y * R[3 + c] + -n3.z * R[6 + c]);  // as icp_plane_accum_kernel
+                        double J[1][6];
+                        J[0][0] = nR[1] * q.z - nR[2] * q.y;
+                        J[0][1] = nR[2] * q.x - nR[0] * q.z;
+                        J[0][2] = nR[0] * q.y - nR[1] * q.x;
+                        J[0][3] = n3.x; J[0][4] = n3.y; J[0][5] = n3.z;
+                        const double e[1] = {dis};
+                        add_rows<1>(acc, J, e);
+                    }
+                }
+            }
+        }
+    }
+    block_reduce_store<28>(acc, partials + ((size_t)scan * gridDim.x + blockIdx.x) * kAccW);
+}
+
 // K2', P2Line: CaculateMatrixHAndBP2Line (icp_registration.cpp:105-159) + math::FitLine (math_utils.h:138-163).
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5, 5))) void icp_line_accum_kernel(const uint2* __restrict__ tree, const float4* __restrict__ src,
                                                                 const int* __restrict__ counts, const PoseState* __restrict__ st,
@@ -993,7 +1044,9 @@ int launch_icp_accum(int method, const AccumArgs& a, hipStream_t s) {
             hipLaunchKernelGGL(icp_plane_accum_kernel<1>, grid, dim3(kBlock), 0, s, a.tree, a.src, a.counts, a.st, a.nn, a.nn_pitch, a.max_n, a.gate, a.partials, pts, a.active, a.src_of);
         else
             hipLaunchKernelGGL(icp_plane_accum_kernel<0>, grid, dim3(kBlock), 0, s, a.tree, a.src, a.counts, a.st, a.nn, a.nn_pitch, a.max_n, a.gate, a.partials, pts, a.active, a.src_of);
-    } else if (method == 1)
+    } else if (method == LOCGPU_P2PLANE_MAP)
+        hipLaunchKernelGGL(icp_mapplane_accum_kernel, grid, dim3(kBlock), 0, s, reinterpret_cast<const double4*>(a.planes), a.src, a.counts, a.st, a.nn, a.max_n, a.gate, a.partials, pts, a.active, a.src_of);
+    else if (method == 1)
         hipLaunchKernelGGL(icp_line_accum_kernel, grid, dim3(kBlock), 0, s, a.tree, a.src, a.counts, a.st, a.nn, a.nn_pitch, a.max_n, a.gate, a.partials, pts, a.active, a.src_of);
     else
         hipLaunchKernelGGL(icp_point_accum_kernel, grid, dim3(kBlock), 0, s, a.tree, a.src, a.counts, a.st, a.nn, a.nn_pitch, a.max_n, a.gate, a.partials, pts, a.active, a.src_of);

@@ -56,6 +56,8 @@ struct AccumArgs {
     // > 0: split the sums as a plain batch of this many scans would (a scan pool of many slots serving jobs of that size), so that
     // a pooled scan's partial sums — hence its pose — are the plain batch's bit for bit. 0: by n_scans.
     int split_scans = 0;
+    // LOCGPU_P2PLANE_MAP: the plane table of the target (map_planes.hip), one 32-byte row of four doubles per slot >> 1
+    const double* planes = nullptr;
 };
 
 bool launch_icp_search(const SearchArgs& a, hipStream_t s);
@@ -99,6 +101,14 @@ int icp_fitness_rows(int max_n);
 void launch_icp_fitness(const FitnessArgs& a, hipStream_t s);
 struct M12f { float v[12]; };  // rows of pose.matrix().cast<float>() (icp_registration.cpp:241), a kernel argument
 void launch_transform_cloud(const float4* src, size_t n, const M12f& m12, float* dst_xyz, hipStream_t s);
+// Plane table of LOCGPU_P2PLANE_MAP (map_planes.hip). queries: the coordinates of leaves [first, first + n) as the source points of a
+// one-scan search batch (counts[0] = n). fit: the chunk's k = 5 lists → rows planes[slot >> 1], *n_valid += valid planes.
+// dump: rows by original point index into zeroed out_n4 [n_points][4] / out_valid [n_points].
+void launch_map_plane_queries(const uint2* tree, const uint32_t* leaf_slots, size_t first, int n, float4* src, int* counts, hipStream_t s);
+void launch_map_plane_fit(const uint2* tree, const uint32_t* leaf_slots, size_t first, int n, const uint32_t* nn, size_t nn_pitch, double* planes,
+                          unsigned long long* n_valid, hipStream_t s);
+void launch_map_plane_dump(const uint2* tree, const uint32_t* leaf_slots, size_t n_leaves, const double* planes, size_t n_points, double* out_n4,
+                           unsigned char* out_valid, hipStream_t s);
 // Code-object self-test (once per process): no walk kernel owns static LDS, so every traversal stack starts at LDS address 0 —
 // the precondition of search_walk.hpp's out-of-range rows (tests/test_gpu_lds_semantics.py pins the hardware side).
 bool search_kernels_lds_ok();

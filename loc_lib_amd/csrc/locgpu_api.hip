@@ -249,6 +249,9 @@ void locgpu_destroy(locgpu_ctx* ctx) {
     delete ctx->worker;  // joins the helper thread (no job outlives the call that started it)
     free_batch(ctx->single);
     free_batch(ctx->search);
+    free_batch(ctx->planes_ws);
+    if (ctx->d_planes) (void)hipFree(ctx->d_planes);
+    if (ctx->d_planes_count) (void)hipFree(ctx->d_planes_count);
     upload_free_ctx(ctx);
     if (ctx->comm) { (void)rccl().CommDestroy((ncclComm_t)ctx->comm); ctx->comm = nullptr; }
     if (ctx->comm_stream) (void)hipStreamDestroy(ctx->comm_stream);
@@ -344,6 +347,9 @@ static int install_tree_meta(locgpu_ctx* ctx, const long long meta[6]) {
     ctx->depth = (int)meta[4];
     ctx->tree_bounded = meta[5] != 0;
     ctx->target_epoch++;
+    ctx->planes_ready = false;  // the plane table belongs to the previous target (rebuilt on the next use of LOCGPU_P2PLANE_MAP)
+    ctx->planes_rows = 0;
+    ctx->planes_valid = 0;
     return LOCGPU_OK;
 }
 
@@ -792,7 +798,7 @@ bool IterLauncher::launch(int do_update) {
         mark(true);  // nothing local: this rank only takes part in the exchange below
     } else if (!ndt) {
         SearchArgs sa{ctx->d_tree, ctx->tree_slots * sizeof(uint64_t), ctx->depth, batch_src(b), b->d_counts, st_local, b->d_nn, b->pitch, b->max_n, b->n_scans, k, alpha_eff,
-                      prm.method == LOCGPU_P2P ? 1 : 0, ctx->count_visits ? ctx->d_visits : nullptr, b->d_redo_list, b->d_redo_count,
+                      (prm.method == LOCGPU_P2P || prm.method == LOCGPU_P2PLANE_MAP) ? 1 : 0, ctx->count_visits ? ctx->d_visits : nullptr, b->d_redo_list, b->d_redo_count,
                       b->d_redo_list2, b->d_redo_count + 1, ctx->d_search_stats};
         const bool grid_mode = alpha_eff < 0.f && ctx->tree_bounded;
         if (alpha_eff < 0.f) sa.alpha_eff = 1.0f;                       // grid mode is exact by construction (`approximate` is ignored)
@@ -816,8 +822,9 @@ bool IterLauncher::launch(int do_update) {
         if (!ok_search) { fail(ctx, LOCGPU_ERR_DEPTH, "search: unsupported k/depth"); return false; }
         if (sa.touched) launch_count_touched(sa.touched, (ctx->tree_slots + 2 + 31) / 32, sa.visit_totals, s);
         mark(true);
-        const double gate = prm.method == LOCGPU_P2PLANE ? prm.max_plane_distance : (prm.method == LOCGPU_P2LINE ? prm.max_line_distance : prm.max_nn_distance);
+        const double gate = (prm.method == LOCGPU_P2PLANE || prm.method == LOCGPU_P2PLANE_MAP) ? prm.max_plane_distance : (prm.method == LOCGPU_P2LINE ? prm.max_line_distance : prm.max_nn_distance);
         AccumArgs aa{ctx->d_tree, batch_src(b), b->d_counts, st_local, b->d_nn, b->pitch, b->max_n, b->n_scans, gate, b->d_partials};
+        aa.planes = ctx->d_planes;
         aa.active = active; aa.n_active = n_active;
         aa.src_of = b->d_src_of;
         if (b->split_scans > 0) aa.split_scans = b->split_scans;  // a candidate search in chunks: the sums of a plain batch of all candidates
@@ -1219,12 +1226,78 @@ static void write_results(locgpu_batch* b, const double* init_poses, double* out
     }
 }
 
+// The plane table of LOCGPU_P2PLANE_MAP for the current target (map_planes.hip), on the context's stream; no-op when it is there.
+// Leaves go through the existing search stage in chunks of at most kPlaneChunk, as the points of a one-scan batch under the
+// identity pose (k = 5, exact). The table and the chunk workspace are kept: nothing is allocated after the first call unless the map grew.
+// The workspace is a whole one-scan batch (alloc_batch also makes partials, H/B and pinned state the ingest never touches: a few KB
+// beside the 44 MB of points, lists and work lists at 2^20 leaves); like ctx->search it stays resident until locgpu_destroy, even
+// if the table is never built again.
+constexpr size_t kPlaneChunk = (size_t)1 << 20;
+static int ensure_map_planes(locgpu_ctx* ctx) {
+    if (ctx->planes_ready) return LOCGPU_OK;
+    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t rows = ctx->tree_slots / 2 + 2;  // slot >> 1 of every slot, the sentinel leaf behind the tree included
+    if (rows > ctx->planes_cap_rows) {
+        if (ctx->d_planes) { LOCGPU_HIP(ctx, hipFree(ctx->d_planes)); ctx->d_planes = nullptr; ctx->planes_cap_rows = 0; }
+        const size_t cap = rows + rows / 4 + 1024;
+        if (!hip_ok(ctx, hipMalloc((void**)&ctx->d_planes, cap * 4 * sizeof(double)), "hipMalloc map planes")) return LOCGPU_ERR_OOM;
+        ctx->planes_cap_rows = cap;
+    }
+    if (!ctx->d_planes_count && !hip_ok(ctx, hipMalloc((void**)&ctx->d_planes_count, sizeof(unsigned long long)), "hipMalloc map planes")) return LOCGPU_ERR_OOM;
+    LOCGPU_HIP(ctx, hipMemsetAsync(ctx->d_planes, 0xFF, rows * 4 * sizeof(double), s));  // all-ones doubles are NaNs: no plane
+    LOCGPU_HIP(ctx, hipMemsetAsync(ctx->d_planes_count, 0, sizeof(unsigned long long), s));
+    unsigned long long n_valid = 0;
+    if (ctx->num_leaves >= 5) {  // k > size_: GetClosestPoint returns nothing (kdtree.cpp:149-153) ⇒ no plane at all
+        const size_t chunk = std::min(ctx->num_leaves, kPlaneChunk);
+        locgpu_batch* w = ctx->planes_ws;
+        if (!w || (size_t)w->max_n < chunk) {
+            if (w) { free_batch(w); ctx->planes_ws = nullptr; }
+            const int next_slot = ctx->next_slot;  // the workspace must not shift the streams the caller's batches are dealt
+            const int rc = alloc_batch(ctx, 1, chunk, &ctx->planes_ws);
+            ctx->next_slot = next_slot;
+            if (rc != LOCGPU_OK) return rc;
+            w = ctx->planes_ws;
+            w->slot = 0;
+            w->stream = s;
+        }
+        const double identity[7] = {0, 0, 0, 1, 0, 0, 0};
+        init_states(w, identity);
+        LOCGPU_HIP(ctx, hipMemsetAsync(w->d_redo_count, 0, 4 * sizeof(unsigned int), s));
+        LOCGPU_HIP(ctx, hipMemcpyAsync(w->d_state, w->h_state, sizeof(PoseState), hipMemcpyHostToDevice, s));
+        for (size_t first = 0; first < ctx->num_leaves; first += chunk) {
+            const int cnt = (int)std::min(chunk, ctx->num_leaves - first);
+            launch_map_plane_queries(ctx->d_tree, ctx->d_leaf_slots, first, cnt, w->d_src, w->d_counts, s);
+            SearchArgs sa{ctx->d_tree, ctx->tree_slots * sizeof(uint64_t), ctx->depth, w->d_src, w->d_counts, w->d_state, w->d_nn, w->pitch, w->max_n, 1, 5, 1.0f,
+                          0, nullptr, w->d_redo_list, w->d_redo_count, w->d_redo_list2, w->d_redo_count + 1, nullptr};
+            if (!ctx->tree_bounded) sa.redo_list = nullptr;  // huge / non-finite map coordinates: exact tree kernel only
+            if (!launch_icp_search(sa, s)) return fail(ctx, LOCGPU_ERR_DEPTH, "icp_build_map_planes: unsupported tree depth");
+            LOCGPU_HIP(ctx, hipMemsetAsync(w->d_redo_count, 0, 4 * sizeof(unsigned int), s));  // the work lists are consumed
+            launch_map_plane_fit(ctx->d_tree, ctx->d_leaf_slots, first, cnt, w->d_nn, w->pitch, ctx->d_planes, ctx->d_planes_count, s);
+        }
+        LOCGPU_HIP(ctx, hipGetLastError());
+        LOCGPU_HIP(ctx, hipMemcpyAsync(&n_valid, ctx->d_planes_count, sizeof(n_valid), hipMemcpyDeviceToHost, s));
+    }
+    LOCGPU_HIP(ctx, hipStreamSynchronize(s));  // batches run on other streams: the table is complete before anyone reads it
+    ctx->planes_rows = ctx->num_leaves;
+    ctx->planes_valid = (long long)n_valid;
+    ctx->planes_ready = true;
+    return LOCGPU_OK;
+}
+
+// Scan pools and sharded batches do not take the map-plane method (locgpu.h).
+static int refuse_map_planes_sharded(locgpu_ctx* ctx, const locgpu_batch* b, const GnParams& prm) {
+    if (b && b->sharded && prm.method == LOCGPU_P2PLANE_MAP)
+        return fail(ctx, LOCGPU_ERR_INVALID, "icp: LOCGPU_P2PLANE_MAP is not available on a sharded batch");
+    return LOCGPU_OK;
+}
+
 int check_icp(locgpu_ctx* ctx, const locgpu_icp_opts* o, GnParams& prm, int& k, float& alpha_eff) {
     if (!ctx) return LOCGPU_ERR_INVALID;
     if (!o) return fail(ctx, LOCGPU_ERR_INVALID, "icp: opts is NULL");
     { const int jrc = target_join(ctx); if (jrc != LOCGPU_OK) return jrc; }  // an asynchronous SetInputTarget ends here at the latest
     if (!ctx->d_tree) return fail(ctx, LOCGPU_ERR_NO_TARGET, "icp: SetInputTarget has not been called");
-    if (o->method < LOCGPU_P2P || o->method > LOCGPU_P2PLANE) return fail(ctx, LOCGPU_ERR_INVALID, "icp: unknown method");
+    if ((o->method < LOCGPU_P2P || o->method > LOCGPU_P2PLANE) && o->method != LOCGPU_P2PLANE_MAP) return fail(ctx, LOCGPU_ERR_INVALID, "icp: unknown method");
     if (o->search_mode != LOCGPU_SEARCH_TREE_FAITHFUL && o->search_mode != LOCGPU_SEARCH_GRID_EXACT)
         return fail(ctx, LOCGPU_ERR_INVALID, "icp: unknown search mode");
     if (o->search_mode == LOCGPU_SEARCH_GRID_EXACT) {
@@ -1238,7 +1311,11 @@ int check_icp(locgpu_ctx* ctx, const locgpu_icp_opts* o, GnParams& prm, int& k, 
     prm.max_nn_distance = o->max_nn_distance;
     prm.max_plane_distance = o->max_plane_distance;
     prm.max_line_distance = o->max_line_distance;
-    k = o->method == LOCGPU_P2P ? 1 : 5;
+    if (o->method == LOCGPU_P2PLANE_MAP) {  // the first use without a table builds it
+        const int rc = ensure_map_planes(ctx);
+        if (rc != LOCGPU_OK) return rc;
+    }
+    k = (o->method == LOCGPU_P2P || o->method == LOCGPU_P2PLANE_MAP) ? 1 : 5;
     alpha_eff = o->approximate ? o->ann_alpha : 1.0f;
     if (o->search_mode == LOCGPU_SEARCH_GRID_EXACT) alpha_eff = -1.0f;  // marker: grid search (exact by construction; `approximate` is ignored)
     // k > size_: GetClosestPoint logs an error and returns nothing (kdtree.cpp:149-153) ⇒ no correspondences at all.
@@ -1309,6 +1386,7 @@ int locgpu_icp_align_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* init_
     const int rc = check_icp(ctx, opts, prm, k, alpha_eff);
     if (rc != LOCGPU_OK) return rc;
     if (!b || b->ctx != ctx || !init_poses || !out_poses) return fail(ctx, LOCGPU_ERR_INVALID, "icp_align_batch: bad arguments");
+    { const int src = refuse_map_planes_sharded(ctx, b, prm); if (src != LOCGPU_OK) return src; }
     return run_align(ctx, b, init_poses, prm, k, alpha_eff, false, out_poses, stats);
 }
 
@@ -1319,6 +1397,7 @@ int locgpu_icp_align_batch_begin(locgpu_ctx* ctx, locgpu_batch* b, const double*
     const int rc = check_icp(ctx, opts, prm, k, alpha_eff);
     if (rc != LOCGPU_OK) return rc;
     if (!b || b->ctx != ctx || !init_poses) return fail(ctx, LOCGPU_ERR_INVALID, "icp_align_batch_begin: bad arguments");
+    { const int src = refuse_map_planes_sharded(ctx, b, prm); if (src != LOCGPU_OK) return src; }
     return align_begin(ctx, b, init_poses, prm, k, alpha_eff, false);
 }
 
@@ -1349,6 +1428,7 @@ int locgpu_icp_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, c
     const int rc = check_icp(ctx, opts, prm, k, alpha_eff);
     if (rc != LOCGPU_OK) return rc;
     if (!b || b->ctx != ctx || !poses || !hb) return fail(ctx, LOCGPU_ERR_INVALID, "icp_hb_batch: bad arguments");
+    { const int src = refuse_map_planes_sharded(ctx, b, prm); if (src != LOCGPU_OK) return src; }
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
     { const int grc = ensure_grid_lists(ctx, b, alpha_eff); if (grc != LOCGPU_OK) return grc; }
     { const int urc = batch_ready(ctx, b); if (urc != LOCGPU_OK) return urc; }
@@ -1402,6 +1482,49 @@ int locgpu_icp_hb(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_byte
     if (effective_num) *effective_num = (int64_t)hb[42];
     if (ok) *ok = hb[43] != 0.0;
     return LOCGPU_OK;
+}
+
+int locgpu_icp_build_map_planes(locgpu_ctx* ctx) {
+    if (!ctx) return LOCGPU_ERR_INVALID;
+    { const int jrc = target_join(ctx); if (jrc != LOCGPU_OK) return jrc; }
+    if (!ctx->d_tree) return fail(ctx, LOCGPU_ERR_NO_TARGET, "icp_build_map_planes: SetInputTarget has not been called");
+    return ensure_map_planes(ctx);
+}
+
+int locgpu_icp_map_planes_info(const locgpu_ctx* ctx, int64_t out[3]) {
+    if (!ctx || !out) return LOCGPU_ERR_INVALID;
+    { const int jrc = target_join(const_cast<locgpu_ctx*>(ctx)); if (jrc != LOCGPU_OK) return jrc; }
+    out[0] = out[1] = out[2] = 0;
+    if (!ctx->d_tree) return LOCGPU_ERR_NO_TARGET;
+    if (!ctx->planes_ready) return LOCGPU_OK;
+    out[0] = (int64_t)ctx->planes_rows;
+    out[1] = (int64_t)ctx->planes_valid;
+    out[2] = (int64_t)((ctx->tree_slots / 2 + 2) * 4 * sizeof(double));
+    return LOCGPU_OK;
+}
+
+int locgpu_icp_map_planes_dump(locgpu_ctx* ctx, double* n4, uint8_t* valid, size_t cap, size_t* n_out) {
+    if (!ctx) return LOCGPU_ERR_INVALID;
+    int rc = locgpu_icp_build_map_planes(ctx);
+    if (rc != LOCGPU_OK) return rc;
+    const size_t n = ctx->num_points;
+    if (n_out) *n_out = n;
+    if (!n4 && !valid && cap == 0 && n_out) return LOCGPU_OK;  // size query
+    if (!n4 || !valid || cap < n) return fail(ctx, LOCGPU_ERR_INVALID, "icp_map_planes_dump: NULL output or capacity below the number of target points");
+    double* d_n4 = nullptr;
+    unsigned char* d_valid = nullptr;
+    hipStream_t s = ctx->stream;
+    bool ok = hip_ok(ctx, hipMalloc((void**)&d_n4, std::max<size_t>(n, 1) * 4 * sizeof(double)), "hipMalloc") &&
+              hip_ok(ctx, hipMalloc((void**)&d_valid, std::max<size_t>(n, 1)), "hipMalloc");
+    if (!ok) rc = LOCGPU_ERR_OOM;
+    ok = ok && hip_ok(ctx, hipMemsetAsync(d_n4, 0, n * 4 * sizeof(double), s), "hipMemset") && hip_ok(ctx, hipMemsetAsync(d_valid, 0, n, s), "hipMemset");
+    if (ok && ctx->num_leaves > 0) launch_map_plane_dump(ctx->d_tree, ctx->d_leaf_slots, ctx->num_leaves, ctx->d_planes, n, d_n4, d_valid, s);
+    ok = ok && hip_ok(ctx, hipGetLastError(), "map_planes_dump launch") && hip_ok(ctx, hipMemcpyAsync(n4, d_n4, n * 4 * sizeof(double), hipMemcpyDeviceToHost, s), "D2H") &&
+         hip_ok(ctx, hipMemcpyAsync(valid, d_valid, n, hipMemcpyDeviceToHost, s), "D2H");
+    if (!hip_ok(ctx, hipStreamSynchronize(s), "sync")) ok = false;
+    if (d_n4) (void)hipFree(d_n4);
+    if (d_valid) (void)hipFree(d_valid);
+    return ok ? LOCGPU_OK : (rc != LOCGPU_OK ? rc : LOCGPU_ERR_NO_DEVICE);
 }
 
 int locgpu_gn_update(const double hb[44], int method, int min_effective_pts, double eps, double pose[7], double dx[6], int* applied, int* stop) {

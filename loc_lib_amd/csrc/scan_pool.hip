@@ -363,6 +363,8 @@ int locgpu_pool_create(locgpu_ctx* ctx, const locgpu_pool_opts* o, locgpu_pool**
     *out = nullptr;
     if (o->slots < 1 || o->slots > 65535 || o->prefetch < -1 || o->prefetch > 1000000 || o->max_points == 0 || o->chunk < 0 || o->chunk > kAccRing || o->scans_per_job < 0 || (o->matcher != 0 && o->matcher != 1))
         return fail(ctx, LOCGPU_ERR_INVALID, "pool_create: bad options (1 <= slots <= 65535, chunk <= 8, matcher 0 | 1)");
+    if (o->matcher == 0 && o->icp.method == LOCGPU_P2PLANE_MAP)
+        return fail(ctx, LOCGPU_ERR_INVALID, "pool_create: LOCGPU_P2PLANE_MAP is not available in a scan pool");
     auto* P = new locgpu_pool();
     P->ctx = ctx;
     P->slots = o->slots;

@@ -50,6 +50,13 @@ public:
     // ScanMatch or when the library fails (LastError). WITHOUT the opt-in GetFitnessScore() keeps returning the reference's 0.0f.
     // NdtRegistration and LoamRegistration keep the stub: an NDT context has no nearest-neighbour structure to score against.
     void EnableFitnessScore(double max_range);
+    // Not in the reference: a labelled FAST MODE, never the source of a parity claim. With it on and method_ == P2PLANE the matcher
+    // fits ONE plane per map point when the target is set (SetInputTarget builds the table; locgpu_icp_build_map_planes) and every
+    // iteration is plain point-to-plane against the plane of the nearest map point (LOCGPU_P2PLANE_MAP) instead of the reference's
+    // math::FitPlane per source point and iteration (math_utils.h:112-136, icp_registration.cpp:161-213). ScanMatch,
+    // CaculateMatrixHAndB and InitialPoseSearch follow the switch; GetFitnessScore scores whatever ScanMatch ran. Other methods and
+    // the switch left off: nothing changes. Call it before SetInputTarget (later is allowed: the first matching call builds the table).
+    void EnableMapPlanes(bool on);
     // Not in the reference: aligns `source` from every candidate pose with this matcher's options in one batched call on the GPU
     // (locgpu_icp_init_search: the cloud is uploaded once), scores every result (EnableFitnessScore's range, 1 m by default) and hands
     // back the best: the lowest score among the results with at least half of their points within range. false — and best_pose /
@@ -72,6 +79,7 @@ private:
     int device_id_ = 0;
     bool has_target_ = false;
     bool fitness_enabled_ = false, have_last_pose_ = false;  // have_last_pose_: the last ScanMatch left its source in HBM
+    bool map_planes_ = false;
     double fitness_range_ = 1.0;
     SE3 last_pose_;
 };

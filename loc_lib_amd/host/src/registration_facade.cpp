@@ -20,10 +20,12 @@
 namespace LocUtils {
 
 namespace {
-locgpu_icp_opts to_c(const IcpOptions& o) {
+// map_planes: IcpRegistration::EnableMapPlanes — P2PLANE then runs as the labelled fast mode LOCGPU_P2PLANE_MAP
+locgpu_icp_opts to_c(const IcpOptions& o, bool map_planes = false) {
     locgpu_icp_opts c;
     locgpu_icp_opts_default(&c);
     c.method = o.method_ == IcpMethod::P2P ? LOCGPU_P2P : (o.method_ == IcpMethod::P2LINE ? LOCGPU_P2LINE : LOCGPU_P2PLANE);
+    if (map_planes && o.method_ == IcpMethod::P2PLANE) c.method = LOCGPU_P2PLANE_MAP;
     c.max_iteration = o.max_iteration_;
     c.max_nn_distance = o.max_nn_distance_;
     c.max_plane_distance = o.max_plane_distance_;
@@ -76,12 +78,14 @@ bool IcpRegistration::EnsureContext() { return ctx_ || locgpu_create(device_id_,
 bool IcpRegistration::SetInputTarget(const CloudPtr& input_target) {
     if (Unsupported() || !input_target || !EnsureContext()) return false;
     has_target_ = locgpu_icp_set_target(ctx_, input_target->points.data(), input_target->points.size(), sizeof(PointType)) == LOCGPU_OK;
+    // the fast mode's plane table is part of the ingest, not of the first ScanMatch (a failure stays in LastError; the matching calls report it)
+    if (has_target_ && map_planes_ && options_.method_ == IcpMethod::P2PLANE) (void)locgpu_icp_build_map_planes(ctx_);
     return true;  // the reference returns true whatever happened (icp_registration.cpp:28)
 }
 
 bool IcpRegistration::CaculateMatrixHAndB(const CloudPtr& input_source, const SE3& predict_pose, Mat6d& H, Vec6d& B) {
     if (Unsupported() || !has_target_ || !input_source) return false;
-    const locgpu_icp_opts o = to_c(options_);
+    const locgpu_icp_opts o = to_c(options_, map_planes_);
     double h[36], b[6];
     int ok = 0;
     have_last_pose_ = false;  // the evaluation replaces the source copy ScanMatch left in HBM: GetFitnessScore has nothing to score
@@ -101,7 +105,7 @@ bool IcpRegistration::ScanMatch(const CloudPtr& input_source, const SE3& predict
     have_last_pose_ = false;
     if (has_target_ && !input_source->points.empty()) {
         // alignment + output cloud in ONE call: the source crosses PCIe once, the transform runs on the copy the alignment left in HBM
-        const locgpu_icp_opts o = to_c(options_);
+        const locgpu_icp_opts o = to_c(options_, map_planes_);
         double out[7];
         OutputCloud oc{input_source.get(), result_cloud_ptr.get()};
         if (locgpu_icp_scan_match(ctx_, input_source->points.data(), input_source->points.size(), sizeof(PointType), predict_pose.data(), &o, out,
@@ -123,6 +127,8 @@ void IcpRegistration::EnableFitnessScore(double max_range) {
     fitness_range_ = max_range;
 }
 
+void IcpRegistration::EnableMapPlanes(bool on) { map_planes_ = on; }
+
 float IcpRegistration::GetFitnessScore() {
     if (!fitness_enabled_ || !have_last_pose_) return 0.0f;  // icp_registration.cpp:246-250: the reference's stub
     locgpu_fitness f;
@@ -132,7 +138,7 @@ float IcpRegistration::GetFitnessScore() {
 
 bool IcpRegistration::InitialPoseSearch(const CloudPtr& source, const std::vector<SE3>& candidates, SE3& best_pose, float& best_score) {
     if (Unsupported() || !has_target_ || !source || source->points.empty() || candidates.empty()) return false;
-    const locgpu_icp_opts o = to_c(options_);
+    const locgpu_icp_opts o = to_c(options_, map_planes_);
     locgpu_init_search_opts so;
     locgpu_init_search_opts_default(&so);
     so.max_range = fitness_range_;
