@@ -16,7 +16,18 @@
 struct NdtTable;  // ndt_kernels.hpp
 namespace locgpu { struct IncNdtState; struct FilterScratch; }  // ndt_inc.hpp, cloud_filters.hpp
 
-namespace locgpu { struct PendingTarget; }
+namespace locgpu {
+struct PendingTarget;
+// Stage marks of locgpu_profile_enable (gn_driver.hip): HIP events around the stages of every Gauss–Newton iteration enqueued on one
+// stream since the last collect().
+struct StageEvents {
+    std::vector<hipEvent_t> ev;
+    size_t used = 0;
+    int mode = 0;  // 0: record nothing (also under stream capture); 1: search | fit + accumulate | solve; 2: the search stage's edges only
+    void mark(hipStream_t s, bool search_edge = false);
+    void collect(locgpu_ctx* ctx, bool ndt);  // the stream is idle: adds the elapsed times to ctx->prof_ms / prof_n
+};
+}  // namespace locgpu
 
 struct locgpu_ctx {
     int device = 0;
@@ -32,8 +43,8 @@ struct locgpu_ctx {
     hipEvent_t foreign_ev = nullptr;    // ordering behind another context's stream when one of ITS clouds is an input here (cloud_input_ready)
     hipStream_t comm_stream = nullptr;  // every collective of the context, in host order (one communicator, one stream: no two at once)
     locgpu::Uploader* up = nullptr;     // host → HBM staging shared by the context's batches (batch_upload.hpp)
-    locgpu::PendingTarget* target_scratch = nullptr;  // the previous ingest's host buffers, kept for the next one (locgpu_api.hip)
-    locgpu::PendingTarget* pending_target = nullptr;  // locgpu_icp_set_target_cloud_async: a host tree build still running (locgpu_api.hip)
+    locgpu::PendingTarget* target_scratch = nullptr;  // the previous ingest's host buffers, kept for the next one (icp_target.hip)
+    locgpu::PendingTarget* pending_target = nullptr;  // locgpu_icp_set_target_cloud_async: a host tree build still running (icp_target.hip)
     std::string err;
 
     // ICP target: packed KD-tree in HBM (kdtree_build.cpp layout)
@@ -144,7 +155,7 @@ struct locgpu_batch {
     float4* h_src = nullptr;               // pinned staging of the packed source (single-scan path only; reused across calls)
     hipEvent_t xyz_ev[8] = {};             // one-scan batch: the output cloud's pieces on their way back (write_output_cloud)
     locgpu::PoseState* h_state = nullptr;  // pinned
-    // one-scan alignments paced from the host (locgpu_api.hip, align_finish): the solve kernel posts the state here after every
+    // one-scan alignments paced from the host (gn_driver.hip, align_finish): the solve kernel posts the state here after every
     // iteration — pinned COHERENT memory: [0] a finished scan's GnPostRecord, [kPostWord] call << 32 | iterations << 1 | done, [+1] checksum
     unsigned long long* h_post = nullptr;
     static constexpr int kPostWord = 16;  // in 8-byte words: behind the record, 16-byte aligned
@@ -156,7 +167,7 @@ struct locgpu_batch {
     int* d_active = nullptr;               // its device copy (see SearchArgs::active)
     std::vector<int> counts;
     locgpu::BatchUploadState upl;          // event + pinned counts of locgpu_batch_upload_async (batch_upload.hpp)
-    std::vector<hipEvent_t> events;        // profiling events of the batch's alignments (locgpu_profile_enable)
+    locgpu::StageEvents stage_ev;          // profiling events of the batch's (or the pool's) iterations (locgpu_profile_enable)
     hipEvent_t ev_ready = nullptr, ev_reduced = nullptr;  // sharded batches: compute stream ⇄ comm stream hand-over
     // an alignment begun with *_align_batch_begin and not yet finished
     struct Pending {
@@ -167,7 +178,6 @@ struct locgpu_batch {
         bool ndt = false, graph = false;
         bool paced = false;  // one scan, eager: iterations are launched as the solve kernel posts its progress
         int launched = 0;
-        size_t ev_used = 0;
         std::vector<double> init_poses;
     } pending;
 };
@@ -185,7 +195,16 @@ void free_batch(locgpu_batch* b);
 // Validate the matcher's options against the context's target; fill the Gauss–Newton parameters of an alignment.
 int check_icp(locgpu_ctx* ctx, const locgpu_icp_opts* o, GnParams& prm, int& k, float& alpha_eff);
 int check_ndt(locgpu_ctx* ctx, GnParams& prm);
+// icp_target.hip
+int target_join(locgpu_ctx* ctx, bool install = true);  // finishes a pending locgpu_icp_set_target_cloud_async (no-op without one)
+void free_target_scratch(locgpu_ctx* ctx);              // the ingest buffers the context keeps between SetInputTarget calls
+int ensure_grid(locgpu_ctx* ctx);                       // the exact-search grid of the current target (built on first use)
+void free_grid(locgpu_ctx* ctx);
+// comm.hip: collectives over the context's communicator, in place, on stream `s`
 bool comm_all_reduce_f64(locgpu_ctx* ctx, double* buf, size_t count, hipStream_t s);
+bool comm_broadcast(locgpu_ctx* ctx, void* buf, size_t bytes, int root, hipStream_t s);
+bool comm_all_reduce_min_int(locgpu_ctx* ctx, int* buf, hipStream_t s);
+void comm_destroy(locgpu_ctx* ctx);
 
 }  // namespace locgpu
 

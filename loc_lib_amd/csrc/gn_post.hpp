@@ -1,4 +1,4 @@
-// loc_lib_amd/csrc/gn_post.hpp — the finished-scan post of a one-scan alignment paced from the host (locgpu_api.hip, paced_wait;
+// loc_lib_amd/csrc/gn_post.hpp — the finished-scan post of a one-scan alignment paced from the host (gn_driver.hip, paced_wait;
 // icp_kernels.hip, gn_solve_kernel). Plain C++, no HIP in it: the CPU suite drives the host side against injected torn reads
 // (tests/cpp/gn_post_sanitize.cpp).
 //

@@ -1,95 +1,29 @@
-// loc_lib_amd/csrc/locgpu_api.hip — C ABI of include/locgpu.h: context, ICP target ingest, search, H/B, align, batch.
+// loc_lib_amd/csrc/locgpu_api.hip — C ABI of include/locgpu.h: context, batches, k-NN and the matchers' entry points.
 //
-// Host control flow mirrors the reference's matcher (IcpRegistration, icp_registration.cpp): SetInputTarget
-// builds the search structure once per map; ScanMatch runs the Gauss–Newton loop. Here the loop body is three
-// kernel launches per iteration on one HIP stream and the convergence test lives on the device, so the host only
-// reads back the small per-scan state every `kChunk` iterations.
+// An entry point checks its arguments and calls into the Gauss–Newton driver (gn_driver.hip), the target ingest (icp_target.hip) or the
+// communicator (comm.hip). Host control flow mirrors the reference's matcher (IcpRegistration, icp_registration.cpp): SetInputTarget
+// builds the search structure once per map; ScanMatch runs the Gauss–Newton loop.
 #include <algorithm>
 #include <atomic>
-#include <chrono>
-#include <thread>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "batch_upload.hpp"
-#include "context.hpp"
 #include "cloud_filters.hpp"
-#include "kdtree_build.hpp"
+#include "context.hpp"
+#include "gn_driver.hpp"
 #include "launch.hpp"
-
-#include <dlfcn.h>
-#include <rccl/rccl.h>
+#include "ndt_inc.hpp"
+#include "ndt_kernels.hpp"
 
 using namespace locgpu;
 
-// RCCL is bound at the first locgpu_comm_* call (dlopen), not at load time: a single-GPU process — the slam_demo front-end, the
-// tests — never maps librccl and its dependencies (rocm_smi, roctx, rocprofiler-register). The entry points used:
-namespace {
-struct Rccl {
-    ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*Broadcast)(const void*, void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-    const char* (*GetErrorString)(ncclResult_t) = nullptr;
-    bool ok = false;
-    std::string err;
-};
-Rccl& rccl() {
-    static Rccl r = [] {
-        Rccl x;
-        // LOCGPU_RCCL_LIB names another library with the same six entry points: a site's own RCCL build, or the loopback double the
-        // tests use to run two ranks as two threads on one GPU (tests/cpp/loopback_rccl.hip).
-        const char* named = getenv("LOCGPU_RCCL_LIB");
-        void* h = (named && *named) ? dlopen(named, RTLD_NOW | RTLD_LOCAL)
-                                    : dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);  // a copy already mapped by the host process (e.g. PyTorch's) is reused
-        if (!h && !(named && *named)) h = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
-        if (!h) { x.err = std::string("cannot load librccl: ") + dlerror(); return x; }
-        x.GetUniqueId = (decltype(x.GetUniqueId))dlsym(h, "ncclGetUniqueId");
-        x.CommInitRank = (decltype(x.CommInitRank))dlsym(h, "ncclCommInitRank");
-        x.CommDestroy = (decltype(x.CommDestroy))dlsym(h, "ncclCommDestroy");
-        x.AllReduce = (decltype(x.AllReduce))dlsym(h, "ncclAllReduce");
-        x.Broadcast = (decltype(x.Broadcast))dlsym(h, "ncclBroadcast");
-        x.GetErrorString = (decltype(x.GetErrorString))dlsym(h, "ncclGetErrorString");
-        x.ok = x.GetUniqueId && x.CommInitRank && x.CommDestroy && x.AllReduce && x.Broadcast && x.GetErrorString;
-        if (!x.ok) x.err = "librccl lacks an expected entry point";
-        return x;
-    }();
-    return r;
-}
-}  // namespace
-
-// Sum of `count` doubles over the context's communicator, in place, on stream `s` (scan_pool.hip's exchange step).
-bool locgpu::comm_all_reduce_f64(locgpu_ctx* ctx, double* buf, size_t count, hipStream_t s) {
-    const ncclResult_t nr = rccl().AllReduce(buf, buf, count, ncclDouble, ncclSum, (ncclComm_t)ctx->comm, s);
-    if (nr == ncclSuccess) return true;
-    fail(ctx, LOCGPU_ERR_NO_DEVICE, std::string("ncclAllReduce: ") + rccl().GetErrorString(nr));
-    return false;
-}
-
 namespace {
 std::string g_create_err;
-// GN iterations enqueued between two host reads of the convergence flags. Kernels of a finished scan return at once (device-side
-// `done` flag), so running ahead costs ≈2 µs per empty launch while a host round trip costs tens of µs: the first chunk covers the
-// typical alignment (7-8 iterations with the reference's eps), later ones are shorter.
-constexpr int kFirstChunk = 8, kNextChunk = 4, kLongFirstChunk = 12;
-// A one-scan alignment follows its first chunk with chunks of two: there a chunk boundary (read-back, host, relaunch ≈ 35 µs) costs
-// about what two idle iterations do (3 dispatches of ≈4.6 µs each), and nine iterations — the common case beyond eight — then pay
-// 35 + 15 µs instead of 35 + 45 (tools/single_scan_trace.py).
-inline int next_chunk(const locgpu_batch* b) { return b->n_total == 1 ? 2 : kNextChunk; }
-inline const float4* batch_src(const locgpu_batch* b) { return b->d_src_ext ? b->d_src_ext : b->d_src; }
-// ... and sizes its FIRST chunk by the alignment it ran before: a front-end that matches every scan from a good prediction
-// (Lio::AddCloud: 4-5 iterations per scan) used to pay three or four idle iterations, ≈15 µs each, in every call — a sixth of the
-// match stage of the streaming loop (tools/stream_trace.py). One more than last time, between 3 and kFirstChunk; chunking never
-// changes a result (the same kernels run on the same data in the same order), only where the host looks at the flags.
-inline int first_chunk_len(const locgpu_batch* b) {
-    if (b->n_total != 1 || b->sharded || b->last_iterations < 0) return kFirstChunk;
-    // ... up to kLongFirstChunk when the last call needed more than eight: a chunk boundary there cost 33 µs + two idle iterations (round 5)
-    return std::min(kLongFirstChunk, std::max(3, b->last_iterations + 1));
-}
 }  // namespace
 
 namespace locgpu {
@@ -105,25 +39,6 @@ bool hip_ok(locgpu_ctx* ctx, hipError_t e, const char* what) {
 }
 }  // namespace locgpu
 
-static void free_grid(locgpu_ctx* ctx) {
-    locgpu::grid_free(ctx->grid_buf);
-    ctx->grid = locgpu::GridView();
-}
-
-// Build the exact-search grid from the packed tree already in HBM (first use of LOCGPU_SEARCH_GRID_EXACT after a set_target).
-static int ensure_grid(locgpu_ctx* ctx) {
-    if (ctx->grid.pts) return LOCGPU_OK;
-    std::string msg;
-    const hipError_t e = locgpu::grid_build_device(ctx->d_tree, ctx->d_leaf_slots, ctx->num_leaves, ctx->stream, ctx->grid_buf, ctx->grid, msg);
-    if (e != hipSuccess) {
-        free_grid(ctx);
-        if (!msg.empty()) return locgpu::fail(ctx, LOCGPU_ERR_INVALID, "grid search: " + msg);
-        locgpu::hip_ok(ctx, e, "grid build");
-        return LOCGPU_ERR_NO_DEVICE;
-    }
-    return LOCGPU_OK;
-}
-
 // Zero-fill of device memory that is COMPLETE when the call returns (see alloc_batch: a plain hipMemset is not, and is not ordered
 // with the context's non-blocking streams either).
 static bool fill_now(locgpu_ctx* ctx, void* p, size_t bytes, const char* what) {
@@ -133,7 +48,7 @@ static bool fill_now(locgpu_ctx* ctx, void* p, size_t bytes, const char* what) {
 void locgpu::free_batch(locgpu_batch* b) {
     if (!b) return;
     upload_free_batch(b);
-    for (hipEvent_t ev : b->events) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : b->stage_ev.ev) (void)hipEventDestroy(ev);
     if (b->ev_ready) (void)hipEventDestroy(b->ev_ready);
     if (b->ev_reduced) (void)hipEventDestroy(b->ev_reduced);
     if (b->d_src) (void)hipFree(b->d_src);
@@ -164,9 +79,6 @@ void locgpu::free_batch(locgpu_batch* b) {
     if (b->d_active) (void)hipFree(b->d_active);
     delete b;
 }
-
-static int target_join(locgpu_ctx* ctx, bool install = true);  // finishes a pending locgpu_icp_set_target_cloud_async (defined with it, below)
-static void free_target_scratch(locgpu_ctx* ctx);  // the ingest buffers the context keeps between SetInputTarget calls (defined with PendingTarget, below)
 
 extern "C" {
 
@@ -253,7 +165,7 @@ void locgpu_destroy(locgpu_ctx* ctx) {
     if (ctx->d_planes) (void)hipFree(ctx->d_planes);
     if (ctx->d_planes_count) (void)hipFree(ctx->d_planes_count);
     upload_free_ctx(ctx);
-    if (ctx->comm) { (void)rccl().CommDestroy((ncclComm_t)ctx->comm); ctx->comm = nullptr; }
+    comm_destroy(ctx);
     if (ctx->comm_stream) (void)hipStreamDestroy(ctx->comm_stream);
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
     if (ctx->foreign_ev) (void)hipEventDestroy(ctx->foreign_ev);
@@ -272,229 +184,6 @@ void locgpu_destroy(locgpu_ctx* ctx) {
 }
 
 const char* locgpu_last_error(const locgpu_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
-
-// --------------------------------------------------------------------------------------------- target
-// One target ingest's host side: the deep copy of the points, the packed tree, and — for the asynchronous entry points — the
-// worker thread that builds it. The context keeps ONE of these between ingests (target_scratch): a keyframe front-end re-ingests
-// its ≈35 k-point local map every few scans, and the vectors' capacity (≈1.4 MB: fresh mmaps and page faults per ingest) is
-// worth keeping.
-namespace locgpu {
-struct PendingTarget {
-    std::thread worker;
-    std::vector<float> xyz;
-    PackedKdTree tree;
-    std::string err;
-    bool ok = false;
-};
-}  // namespace locgpu
-
-static locgpu::PendingTarget* take_target_scratch(locgpu_ctx* ctx) {
-    locgpu::PendingTarget* p = ctx->target_scratch;
-    ctx->target_scratch = nullptr;
-    if (!p) p = new locgpu::PendingTarget();
-    p->err.clear();
-    p->ok = false;
-    return p;
-}
-
-static void free_target_scratch(locgpu_ctx* ctx) {
-    delete ctx->target_scratch;  // never holds a running worker (keep_target_scratch joins first)
-    ctx->target_scratch = nullptr;
-}
-
-static void keep_target_scratch(locgpu_ctx* ctx, locgpu::PendingTarget* p) {
-    if (p->worker.joinable()) p->worker.join();
-    // a 10 M-point map's buffers (≈360 MB) go back to the allocator; a local map's stay
-    if (ctx->target_scratch || p->xyz.capacity() > (size_t)3 << 21) delete p;
-    else ctx->target_scratch = p;
-}
-
-// The reference's tree for `pts`, built on the host (kdtree_build.cpp).
-static int build_host_tree(locgpu_ctx* ctx, const void* pts, size_t n, size_t stride_bytes, std::vector<float>& xyz, PackedKdTree& t) {
-    if (!pts || n == 0 || stride_bytes < 12) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target: empty cloud or stride < 12");
-    // deep copy (icp_registration.cpp:16 + kdtree.cpp:267 copy too): pack xyz
-    xyz.resize(3 * n);
-    const char* base = (const char*)pts;
-    for (size_t i = 0; i < n; ++i) std::memcpy(&xyz[3 * i], base + i * stride_bytes, 12);
-    std::string err;
-    if (!build_packed_kdtree(xyz.data(), n, t, err)) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target: " + err);
-    if (t.depth > 64) return fail(ctx, LOCGPU_ERR_DEPTH, "icp_set_target: KD-tree depth " + std::to_string(t.depth) + " exceeds the 64-entry traversal stack");
-    return LOCGPU_OK;
-}
-
-// meta = {slots, leaves, nodes, points, depth, bounded}. The device buffers only ever grow: a streaming front-end re-ingests its
-// local map every keyframe (lio.cpp:296-305) and must not pay a hipMalloc/hipFree pair (≈100 µs each) per ingest.
-static int install_tree_meta(locgpu_ctx* ctx, const long long meta[6]) {
-    for (hipStream_t st : ctx->slot_stream) LOCGPU_HIP(ctx, hipStreamSynchronize(st));  // nobody reads the old tree any more (a begun alignment must be finished first)
-    free_grid(ctx);
-    const size_t slots = (size_t)meta[0], leaves = (size_t)meta[1];
-    if (slots + 2 > ctx->tree_cap_slots) {  // + the sentinel leaf behind the tree (search_walk.hpp)
-        if (ctx->d_tree) { LOCGPU_HIP(ctx, hipFree(ctx->d_tree)); ctx->d_tree = nullptr; ctx->tree_cap_slots = 0; }
-        const size_t cap = slots + slots / 4 + 1024;
-        LOCGPU_HIP(ctx, hipMalloc((void**)&ctx->d_tree, cap * sizeof(uint64_t)));
-        ctx->tree_cap_slots = cap;
-    }
-    if (leaves > ctx->leaf_cap) {
-        if (ctx->d_leaf_slots) { LOCGPU_HIP(ctx, hipFree(ctx->d_leaf_slots)); ctx->d_leaf_slots = nullptr; ctx->leaf_cap = 0; }
-        const size_t cap = leaves + leaves / 4 + 1024;
-        LOCGPU_HIP(ctx, hipMalloc((void**)&ctx->d_leaf_slots, cap * sizeof(uint32_t)));
-        ctx->leaf_cap = cap;
-    }
-    ctx->tree_slots = slots;
-    ctx->num_leaves = leaves;
-    ctx->num_nodes = (size_t)meta[2];
-    ctx->num_points = (size_t)meta[3];
-    ctx->depth = (int)meta[4];
-    ctx->tree_bounded = meta[5] != 0;
-    ctx->target_epoch++;
-    ctx->planes_ready = false;  // the plane table belongs to the previous target (rebuilt on the next use of LOCGPU_P2PLANE_MAP)
-    ctx->planes_rows = 0;
-    ctx->planes_valid = 0;
-    return LOCGPU_OK;
-}
-
-// The sentinel leaf behind the packed tree (two slots at index tree_slots): what a lane of the search kernel "visits" when it has
-// no node to visit. Its coordinates are so large that the squared distance overflows to +inf for every sane query.
-static hipError_t write_sentinel_leaf(locgpu_ctx* ctx) {
-    static const uint32_t leaf[4] = {0x7F61B1E6u /* 3.0e38f */, 0xC0000000u, 0x7F61B1E6u, 0x7F61B1E6u};
-    return hipMemcpyAsync(ctx->d_tree + ctx->tree_slots, leaf, sizeof(leaf), hipMemcpyHostToDevice, ctx->stream);
-}
-
-// ---- SetInputTarget with the host build off the caller's thread (locgpu_icp_set_target_cloud_async) ----
-// The mean-split tree is built on the host (its float32 sums are sequential by definition), 0.5–0.7 ms for a 35 k-pt local map. A
-// streaming front-end that re-ingests its local map every keyframe (lio.cpp:296-305) has work to do in the meantime — upload and
-// filter the next scan — so the build may run on a worker thread. Only the BUILD does: the worker touches its own copy of the points,
-// its own PackedKdTree and the process-wide build pool, nothing of HIP and nothing of the context; every HIP call of the ingest
-// (buffers, H2D, sentinel) is made by the caller's thread in target_join(), which every entry point that reads the target calls first.
-
-static int install_built_tree(locgpu_ctx* ctx, const PackedKdTree& t) {
-    const long long meta[6] = {(long long)t.slots.size(), (long long)t.num_leaves, (long long)t.num_nodes, (long long)t.num_points, t.depth, t.bounded ? 1 : 0};
-    const int rc = install_tree_meta(ctx, meta);
-    if (rc != LOCGPU_OK) return rc;
-    LOCGPU_HIP(ctx, hipMemcpyAsync(ctx->d_tree, t.slots.data(), t.slots.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    LOCGPU_HIP(ctx, hipMemcpyAsync(ctx->d_leaf_slots, t.leaf_slots.data(), t.leaf_slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    LOCGPU_HIP(ctx, write_sentinel_leaf(ctx));
-    LOCGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LOCGPU_OK;
-}
-
-// Finishes a pending asynchronous ingest (no-op without one). install = false: only wait for the worker (context teardown, or a new
-// target that supersedes the pending one).
-static int target_join(locgpu_ctx* ctx, bool install) {
-    if (!ctx || !ctx->pending_target) return LOCGPU_OK;
-    locgpu::PendingTarget* p = ctx->pending_target;
-    ctx->pending_target = nullptr;
-    if (p->worker.joinable()) p->worker.join();
-    int rc = LOCGPU_OK;
-    if (install) {
-        if (!p->ok) rc = fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target: " + p->err);
-        else if (p->tree.depth > 64) rc = fail(ctx, LOCGPU_ERR_DEPTH, "icp_set_target: KD-tree depth " + std::to_string(p->tree.depth) + " exceeds the 64-entry traversal stack");
-        else if (hipSetDevice(ctx->device) != hipSuccess) rc = LOCGPU_ERR_NO_DEVICE;
-        else rc = install_built_tree(ctx, p->tree);
-    }
-    keep_target_scratch(ctx, p);
-    return rc;
-}
-
-int locgpu_icp_set_target(locgpu_ctx* ctx, const void* pts, size_t n, size_t stride_bytes) {
-    if (!ctx) return LOCGPU_ERR_INVALID;
-    (void)target_join(ctx, false);  // a pending asynchronous ingest is superseded
-    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
-    static const bool times = getenv("LOCGPU_INGEST_TIMES") != nullptr;  // diagnostic: phase times on stderr
-    auto t0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!times) return;
-        const auto t1 = std::chrono::steady_clock::now();
-        fprintf(stderr, "[locgpu ingest] %s %.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-        t0 = t1;
-    };
-    locgpu::PendingTarget* p = take_target_scratch(ctx);
-    int rc = build_host_tree(ctx, pts, n, stride_bytes, p->xyz, p->tree);
-    lap("host build");
-    if (rc == LOCGPU_OK) {
-        rc = install_built_tree(ctx, p->tree);
-        lap("device buffers + H2D");
-    }
-    keep_target_scratch(ctx, p);
-    return rc;
-}
-
-// The same with the host build on a worker thread (see PendingTarget): returns once the points have been copied.
-int locgpu_icp_set_target_async(locgpu_ctx* ctx, const void* pts, size_t n, size_t stride_bytes) {
-    if (!ctx) return LOCGPU_ERR_INVALID;
-    if (!pts || n == 0 || stride_bytes < 12) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target: empty cloud or stride < 12");
-    (void)target_join(ctx, false);  // an earlier pending ingest is superseded
-    locgpu::PendingTarget* p = take_target_scratch(ctx);
-    p->xyz.resize(3 * n);  // the deep copy of SetInputTarget (icp_registration.cpp:16)
-    const char* base = (const char*)pts;
-    for (size_t i = 0; i < n; ++i) std::memcpy(&p->xyz[3 * i], base + i * stride_bytes, 12);
-    p->worker = std::thread([p, n] { p->ok = build_packed_kdtree(p->xyz.data(), n, p->tree, p->err); });
-    ctx->pending_target = p;
-    return LOCGPU_OK;
-}
-
-// Collective over the context's communicator: rank `root` builds the tree from its `pts` (the other ranks' pts/n are ignored)
-// and broadcasts the packed tree over xGMI — one host build per node instead of one per GPU.
-int locgpu_icp_set_target_bcast(locgpu_ctx* ctx, const void* pts, size_t n, size_t stride_bytes, int root) {
-    if (!ctx) return LOCGPU_ERR_INVALID;
-    if (!ctx->comm) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target_bcast: locgpu_comm_init has not been called");
-    if (root < 0 || root >= ctx->comm_world) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target_bcast: bad root");
-    (void)target_join(ctx, false);  // a pending asynchronous ingest is superseded
-    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
-    ncclComm_t comm = (ncclComm_t)ctx->comm;
-    hipStream_t s = ctx->stream;
-    PackedKdTree t;
-    std::vector<float> xyz;
-    long long meta[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // [6] = the root's status
-    int rc = LOCGPU_OK;
-    if (ctx->comm_rank == root) {
-        rc = build_host_tree(ctx, pts, n, stride_bytes, xyz, t);
-        if (rc == LOCGPU_OK) { meta[0] = (long long)t.slots.size(); meta[1] = (long long)t.num_leaves; meta[2] = (long long)t.num_nodes; meta[3] = (long long)t.num_points; meta[4] = t.depth; meta[5] = t.bounded ? 1 : 0; }
-        meta[6] = rc;
-    }
-    long long* d_meta = nullptr;
-    LOCGPU_HIP(ctx, hipMalloc((void**)&d_meta, sizeof(meta)));
-    bool ok = hip_ok(ctx, hipMemcpyAsync(d_meta, meta, sizeof(meta), hipMemcpyHostToDevice, s), "bcast meta H2D");
-    ok = ok && rccl().Broadcast(d_meta, d_meta, sizeof(meta), ncclChar, root, comm, s) == ncclSuccess;
-    ok = ok && hip_ok(ctx, hipMemcpyAsync(meta, d_meta, sizeof(meta), hipMemcpyDeviceToHost, s), "bcast meta D2H") && hip_ok(ctx, hipStreamSynchronize(s), "sync");
-    (void)hipFree(d_meta);
-    if (!ok) return fail(ctx, LOCGPU_ERR_NO_DEVICE, "icp_set_target_bcast: broadcast of the tree header failed");
-    if (meta[6] != LOCGPU_OK) return ctx->comm_rank == root ? (int)meta[6] : fail(ctx, (int)meta[6], "icp_set_target_bcast: the root rank could not build the tree");
-    rc = install_tree_meta(ctx, meta);
-    {
-        // collective error exit: a rank that could not make room for the tree must not leave the others waiting in the broadcast
-        int* d_rc = nullptr;
-        int all_rc = rc;
-        bool okc = hip_ok(ctx, hipMalloc((void**)&d_rc, sizeof(int)), "bcast status") &&
-                   hip_ok(ctx, hipMemcpyAsync(d_rc, &rc, sizeof(int), hipMemcpyHostToDevice, s), "bcast status H2D");
-        okc = okc && rccl().AllReduce(d_rc, d_rc, 1, ncclInt, ncclMin, comm, s) == ncclSuccess;  // status codes are <= 0
-        okc = okc && hip_ok(ctx, hipMemcpyAsync(&all_rc, d_rc, sizeof(int), hipMemcpyDeviceToHost, s), "bcast status D2H") && hip_ok(ctx, hipStreamSynchronize(s), "sync");
-        if (d_rc) (void)hipFree(d_rc);
-        if (!okc) return fail(ctx, LOCGPU_ERR_NO_DEVICE, "icp_set_target_bcast: status exchange failed");
-        if (rc != LOCGPU_OK) return rc;
-        if (all_rc != LOCGPU_OK) return fail(ctx, all_rc, "icp_set_target_bcast: another rank could not allocate the tree buffers");
-    }
-    if (ctx->comm_rank == root) {
-        LOCGPU_HIP(ctx, hipMemcpyAsync(ctx->d_tree, t.slots.data(), t.slots.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-        LOCGPU_HIP(ctx, hipMemcpyAsync(ctx->d_leaf_slots, t.leaf_slots.data(), t.leaf_slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    }
-    if (rccl().Broadcast(ctx->d_tree, ctx->d_tree, ctx->tree_slots * sizeof(uint64_t), ncclChar, root, comm, s) != ncclSuccess ||
-        rccl().Broadcast(ctx->d_leaf_slots, ctx->d_leaf_slots, ctx->num_leaves * sizeof(uint32_t), ncclChar, root, comm, s) != ncclSuccess)
-        return fail(ctx, LOCGPU_ERR_NO_DEVICE, "icp_set_target_bcast: broadcast of the tree failed");
-    LOCGPU_HIP(ctx, write_sentinel_leaf(ctx));
-    LOCGPU_HIP(ctx, hipStreamSynchronize(s));
-    return LOCGPU_OK;
-}
-
-int locgpu_icp_target_info(const locgpu_ctx* ctx, int64_t out[4]) {
-    if (!ctx || !out) return LOCGPU_ERR_INVALID;
-    { const int jrc = target_join(const_cast<locgpu_ctx*>(ctx)); if (jrc != LOCGPU_OK) return jrc; }
-    out[0] = (int64_t)ctx->num_leaves;
-    out[1] = (int64_t)ctx->num_nodes;
-    out[2] = ctx->depth;
-    out[3] = (int64_t)(ctx->tree_slots * sizeof(uint64_t));
-    return ctx->d_tree ? LOCGPU_OK : LOCGPU_ERR_NO_TARGET;
-}
 
 // --------------------------------------------------------------------------------------------- k-NN
 int locgpu_knn(locgpu_ctx* ctx, const float* queries, size_t nq, int k, int approximate, float alpha, int search_mode, int32_t* out_idx,
@@ -686,44 +375,6 @@ int locgpu_batch_create_sharded(locgpu_ctx* ctx, const void* const* srcs, const 
     return LOCGPU_OK;
 }
 
-int locgpu_comm_unique_id(void* id_out) {
-    if (!id_out) return LOCGPU_ERR_INVALID;
-    static_assert(LOCGPU_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "locgpu.h and rccl.h disagree on the id size");
-    ncclUniqueId id;
-    if (!rccl().ok || rccl().GetUniqueId(&id) != ncclSuccess) return LOCGPU_ERR_NO_DEVICE;
-    std::memcpy(id_out, &id, sizeof(id));
-    return LOCGPU_OK;
-}
-
-int locgpu_comm_init(locgpu_ctx* ctx, int rank, int world, const void* id) {
-    if (!ctx) return LOCGPU_ERR_INVALID;
-    if (!id || world < 1 || rank < 0 || rank >= world) return fail(ctx, LOCGPU_ERR_INVALID, "comm_init: bad arguments");
-    if (ctx->comm) return fail(ctx, LOCGPU_ERR_INVALID, "comm_init: this context already has a communicator");
-    if (!rccl().ok) return fail(ctx, LOCGPU_ERR_NO_DEVICE, "comm_init: " + rccl().err);
-    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
-    ncclUniqueId uid;
-    std::memcpy(&uid, id, sizeof(uid));
-    ncclComm_t comm = nullptr;
-    // RCCL may narrow the calling thread's CPU affinity while it initialises, and threads created afterwards (the uploader's
-    // packers, the tree-build pool) inherit what it leaves behind: put the caller's mask back.
-    cpu_set_t saved_affinity;
-    const bool have_affinity = sched_getaffinity(0, sizeof(saved_affinity), &saved_affinity) == 0;
-    const ncclResult_t nr = rccl().CommInitRank(&comm, world, uid, rank);
-    if (have_affinity) (void)sched_setaffinity(0, sizeof(saved_affinity), &saved_affinity);
-    if (nr != ncclSuccess) return fail(ctx, LOCGPU_ERR_NO_DEVICE, std::string("ncclCommInitRank: ") + rccl().GetErrorString(nr));
-    ctx->comm = comm;
-    ctx->comm_rank = rank;
-    ctx->comm_world = world;
-    return LOCGPU_OK;
-}
-
-int locgpu_comm_info(const locgpu_ctx* ctx, int* rank, int* world) {
-    if (!ctx) return LOCGPU_ERR_INVALID;
-    if (rank) *rank = ctx->comm_rank;
-    if (world) *world = ctx->comm ? ctx->comm_world : 1;
-    return LOCGPU_OK;
-}
-
 void locgpu_batch_destroy(locgpu_batch* b) {
     if (!b) return;
     (void)hipSetDevice(b->ctx->device);
@@ -734,556 +385,7 @@ void locgpu_batch_destroy(locgpu_batch* b) {
 
 }  // extern "C"
 
-// --------------------------------------------------------------------------------------------- GN driver
 namespace locgpu {
-
-static void init_states(locgpu_batch* b, const double* poses) {
-    for (int s = 0; s < b->n_total; ++s) {  // an empty scan still runs the loop: effective_num < min ⇒ no-op iterations
-        PoseState& ps = b->h_state[s];
-        std::memset(&ps, 0, sizeof(ps));
-        for (int i = 0; i < 4; ++i) ps.q[i] = poses[7 * s + i];
-        for (int i = 0; i < 3; ++i) ps.t[i] = poses[7 * s + 4 + i];
-        quat_to_R(ps.q, ps.R);
-    }
-}
-
-static hipEvent_t get_event(locgpu_batch* b, size_t i) {
-    while (b->events.size() <= i) {
-        hipEvent_t ev;
-        if (hipEventCreate(&ev) != hipSuccess) return nullptr;
-        b->events.push_back(ev);
-    }
-    return b->events[i];
-}
-
-struct IterLauncher {
-    locgpu_ctx* ctx;
-    locgpu_batch* b;
-    GnParams prm{};
-    int k;
-    float alpha_eff;
-    size_t ev_used = 0;
-
-    // One GN iteration = search + accumulate + solve. Returns false on a launch error.
-    bool ndt = false;
-    bool capturing = false;  // inside hipStreamBeginCapture: no event records
-    int slot = 0;            // sharded batches: which of the chunk's exchange buffers this iteration uses
-    bool replicated_on_comm_stream = false;  // the chunk's read-back must wait for the communication stream as well
-    const int* active = nullptr;  // later chunks: the local scans still open (SearchArgs::active); nullptr = all
-    int n_active = 0;
-    const GnPost* post = nullptr;  // paced one-scan alignment: the solve kernel posts the state to the host
-    bool launch(int do_update);
-    void collect_profile();
-};
-
-}  // namespace locgpu
-
-#include "ndt_inc.hpp"
-#include "ndt_kernels.hpp"
-
-namespace locgpu {
-
-bool IterLauncher::launch(int do_update) {
-    hipStream_t s = b->stream;
-    const int prof = capturing ? 0 : ctx->profile;
-    auto mark = [&](bool search_edge = false) {
-        if (!prof || (prof == 2 && !search_edge)) return;
-        hipEvent_t ev = get_event(b, ev_used);
-        if (ev) { (void)hipEventRecord(ev, s); ev_used++; }
-    };
-    mark(true);
-    int n_partial_blocks = b->blocks_per_scan;
-    PoseState* st_local = b->d_state + b->first;  // kernels index the scans this rank holds: 0..n_scans-1
-    if (b->n_scans == 0) {
-        mark(true);  // nothing local: this rank only takes part in the exchange below
-    } else if (!ndt) {
-        SearchArgs sa{ctx->d_tree, ctx->tree_slots * sizeof(uint64_t), ctx->depth, batch_src(b), b->d_counts, st_local, b->d_nn, b->pitch, b->max_n, b->n_scans, k, alpha_eff,
-                      (prm.method == LOCGPU_P2P || prm.method == LOCGPU_P2PLANE_MAP) ? 1 : 0, ctx->count_visits ? ctx->d_visits : nullptr, b->d_redo_list, b->d_redo_count,
-                      b->d_redo_list2, b->d_redo_count + 1, ctx->d_search_stats};
-        const bool grid_mode = alpha_eff < 0.f && ctx->tree_bounded;
-        if (alpha_eff < 0.f) sa.alpha_eff = 1.0f;                       // grid mode is exact by construction (`approximate` is ignored)
-        if (!ctx->tree_bounded) sa.redo_list = nullptr;                 // huge / non-finite map coordinates: exact tree kernel only
-        if (grid_mode && !b->d_grid_qkey) { fail(ctx, LOCGPU_ERR_INVALID, "grid search: work list missing (ensure_grid_lists was not called)"); return false; }
-        sa.redo_list2 = b->d_redo_list2;
-        sa.active = active; sa.n_active = n_active;
-        sa.src_of = b->d_src_of;  // shared-source batches: every entry reads region 0 (nullptr otherwise)
-        if (sa.visit_totals && !capturing) {  // instrumented pass: which tree slots does this launch read at all? (bench.py: compulsory bytes)
-            const size_t words = (ctx->tree_slots + 2 + 31) / 32;
-            if (words > ctx->touched_words) {
-                if (ctx->d_touched) (void)hipFree(ctx->d_touched);
-                ctx->d_touched = nullptr; ctx->touched_words = 0;
-                if (hipMalloc((void**)&ctx->d_touched, words * sizeof(uint32_t)) == hipSuccess && hipMemsetAsync(ctx->d_touched, 0, words * sizeof(uint32_t), s) == hipSuccess)
-                    ctx->touched_words = words;
-            }
-            sa.touched = ctx->touched_words ? ctx->d_touched : nullptr;
-        }
-        const GridSearchScratch gsc{b->d_grid_qkey, b->d_grid_sorted, b->d_grid_tile_count, b->d_grid_scan_temp};
-        const bool ok_search = (grid_mode && !sa.visit_totals) ? launch_icp_search_grid(ctx->grid, sa, gsc, s) : launch_icp_search(sa, s);
-        if (!ok_search) { fail(ctx, LOCGPU_ERR_DEPTH, "search: unsupported k/depth"); return false; }
-        if (sa.touched) launch_count_touched(sa.touched, (ctx->tree_slots + 2 + 31) / 32, sa.visit_totals, s);
-        mark(true);
-        const double gate = (prm.method == LOCGPU_P2PLANE || prm.method == LOCGPU_P2PLANE_MAP) ? prm.max_plane_distance : (prm.method == LOCGPU_P2LINE ? prm.max_line_distance : prm.max_nn_distance);
-        AccumArgs aa{ctx->d_tree, batch_src(b), b->d_counts, st_local, b->d_nn, b->pitch, b->max_n, b->n_scans, gate, b->d_partials};
-        aa.planes = ctx->d_planes;
-        aa.active = active; aa.n_active = n_active;
-        aa.src_of = b->d_src_of;
-        if (b->split_scans > 0) aa.split_scans = b->split_scans;  // a candidate search in chunks: the sums of a plain batch of all candidates
-        // a rank of a scan-sharded batch splits the partial sums as the WHOLE batch would (points per thread follow the batch's size):
-        // the order of a scan's additions — hence its bits — must not depend on how many ranks share the batch (found by the eight-rank
-        // loopback run of round 6: 32 of 256 scans per rank summed one point per thread where the plain batch sums four)
-        if (b->sharded) aa.split_scans = b->n_total;
-        n_partial_blocks = launch_icp_accum(prm.method, aa, s);
-    } else {
-        mark(true);  // NDT has no separate search kernel: search slot stays empty
-        if (prm.method == 4)
-            launch_inc_accum(ctx->inc, ctx->ndt_opts.res_outlier_th, ctx->ndt_opts.nearby_type == 0 ? 1 : 7, batch_src(b), b->d_counts, st_local,
-                             b->max_n, b->n_scans, b->d_partials, s, nullptr, 0, b->d_src_of);
-        else
-            n_partial_blocks = launch_ndt_accum(ctx->ndt, batch_src(b), b->d_counts, st_local, b->max_n, b->n_scans, b->d_partials, s, nullptr, 0, b->sharded ? b->n_total : 0, b->d_src_of);
-    }
-    mark();
-    if (b->sharded) {
-        // The exchange step of the sharded mode: per scan 28 sums (21 H + 6 B + effective_num), zeros from the
-        // ranks that do not hold the scan, summed over xGMI on this stream; then every rank solves every scan, so all ranks see the
-        // same convergence flags and stay in lock-step.
-        double* acc = b->d_acc + (size_t)(slot % kFirstChunk) * b->n_total * kAccW;
-        slot++;
-        launch_sum_partials(b->d_partials, n_partial_blocks, b->d_state, b->first, b->n_scans, b->n_total, acc, s);
-        // Scan-sharded over several ranks: a scan's sums are complete on the rank that holds it (everybody else adds zeros), so the
-        // OWNER solves its scans at once and goes on to the next search, while the all-reduce — on the context's communication
-        // stream — only replicates: behind it every rank solves the scans it does not hold, from the reduced sums, and ends up with
-        // the same poses and flags as their owners. The network is off the Gauss–Newton loop's critical path; the host looks at the
-        // flags of ALL scans only between chunks (both streams joined), which keeps the ranks' collective counts in lock-step.
-        // Point-sharded batches (every rank holds a slice of every scan) and H/B evaluations need the sum itself: they wait.
-        static const int decouple_env = [] { const char* e = getenv("LOCGPU_SHARD_DECOUPLED"); return e ? atoi(e) : -1; }();
-        const bool scan_sharded = b->n_scans != b->n_total;
-        const bool decoupled = ctx->comm && do_update && scan_sharded && (decouple_env >= 0 ? decouple_env != 0 : ctx->comm_world > 1);
-        if (decoupled) {
-            hipStream_t cs = ctx->comm_stream;
-            if (b->n_scans > 0)
-                launch_gn_solve(acc + (size_t)b->first * kAccW, 1, b->d_state + b->first, b->n_scans, prm, do_update, b->d_hb + (size_t)b->first * 44,
-                                ndt ? nullptr : b->d_redo_count, s);
-            if (!hip_ok(ctx, hipEventRecord(b->ev_ready, s), "sharded: hipEventRecord") || !hip_ok(ctx, hipStreamWaitEvent(cs, b->ev_ready, 0), "sharded: hipStreamWaitEvent")) return false;
-            const ncclResult_t nr = rccl().AllReduce(acc, acc, (size_t)b->n_total * kAccW, ncclDouble, ncclSum, (ncclComm_t)ctx->comm, cs);
-            if (nr != ncclSuccess) { fail(ctx, LOCGPU_ERR_NO_DEVICE, std::string("ncclAllReduce: ") + rccl().GetErrorString(nr)); return false; }
-            const int after = b->first + b->n_scans;
-            if (b->first > 0) launch_gn_solve(acc, 1, b->d_state, b->first, prm, do_update, b->d_hb, nullptr, cs);
-            if (after < b->n_total)
-                launch_gn_solve(acc + (size_t)after * kAccW, 1, b->d_state + after, b->n_total - after, prm, do_update, b->d_hb + (size_t)after * 44, nullptr, cs);
-            replicated_on_comm_stream = true;
-            mark();
-            return hip_ok(ctx, hipGetLastError(), "kernel launch");
-        }
-        if (ctx->comm) {
-            // Every collective of the context goes through ONE stream in host order — the order is the same on every rank because
-            // every rank sees the same convergence flags — so two batches in flight never have two collectives of the one
-            // communicator racing each other.
-            // (A one-rank communicator has nobody to disagree with about the order: its collective stays on the batch's own stream —
-            // 32 scans per step, two in flight: 8500 scans/s against 5700 through the comm stream, whose in-order queue makes the
-            // second batch's first exchange wait for the first batch's whole chunk. LOCGPU_COMM_DIRECT=0/1 forces either way.)
-            static const int force = [] { const char* e = getenv("LOCGPU_COMM_DIRECT"); return e ? atoi(e) : -1; }();
-            const bool direct = force >= 0 ? force != 0 : ctx->comm_world == 1;
-            hipStream_t cs = direct ? s : ctx->comm_stream;
-            if (!direct && (!hip_ok(ctx, hipEventRecord(b->ev_ready, s), "sharded: hipEventRecord") || !hip_ok(ctx, hipStreamWaitEvent(cs, b->ev_ready, 0), "sharded: hipStreamWaitEvent"))) return false;
-            const ncclResult_t nr = rccl().AllReduce(acc, acc, (size_t)b->n_total * kAccW, ncclDouble, ncclSum, (ncclComm_t)ctx->comm, cs);
-            if (nr != ncclSuccess) { fail(ctx, LOCGPU_ERR_NO_DEVICE, std::string("ncclAllReduce: ") + rccl().GetErrorString(nr)); return false; }
-            if (!direct && (!hip_ok(ctx, hipEventRecord(b->ev_reduced, cs), "sharded: hipEventRecord") || !hip_ok(ctx, hipStreamWaitEvent(s, b->ev_reduced, 0), "sharded: hipStreamWaitEvent"))) return false;
-        }
-        launch_gn_solve(acc, 1, b->d_state, b->n_total, prm, do_update, b->d_hb, ndt ? nullptr : b->d_redo_count, s);
-    } else {
-        launch_gn_solve(b->d_partials, n_partial_blocks, b->d_state, b->n_scans, prm, do_update, b->d_hb, ndt ? nullptr : b->d_redo_count, s, nullptr, post);
-    }
-    mark();
-    return hip_ok(ctx, hipGetLastError(), "kernel launch");
-}
-
-void IterLauncher::collect_profile() {
-    // launch() records four events per iteration: [0,1] search, [1,2] fit+accumulate, [2,3] solve — or, in the light mode, two: [0,1] search.
-    if (ctx->profile == 2) {
-        for (size_t i = 0; i + 1 < ev_used; i += 2) {
-            float ms = 0.f;
-            if (!ndt && hipEventElapsedTime(&ms, b->events[i], b->events[i + 1]) == hipSuccess) {
-                ctx->prof_ms[0] += ms;
-                ctx->prof_n[0] += 1;
-            }
-        }
-    } else if (ctx->profile) {
-        for (size_t i = 0; i + 3 < ev_used; i += 4)
-            for (int j = 0; j < 3; ++j) {
-                if (ndt && j == 0) continue;  // NDT has no search kernel
-                float ms = 0.f;
-                if (hipEventElapsedTime(&ms, b->events[i + j], b->events[i + j + 1]) == hipSuccess) {
-                    ctx->prof_ms[j] += ms;
-                    ctx->prof_n[j] += 1;
-                }
-            }
-    }
-    ev_used = 0;
-}
-
-static void write_results(locgpu_batch* b, const double* init_poses, double* out_poses, locgpu_align_stats* stats);
-
-// The grid search hands its leftovers through a second work list. It is allocated here, by every entry point that may run the
-// grid search on `b`, BEFORE any launch: launch() can run under hipStreamBeginCapture, where hipMalloc is not allowed.
-// A pending locgpu_batch_upload_async of `b`: wait until the host side is through, then order the compute stream behind the copies.
-static int batch_ready(locgpu_ctx* ctx, locgpu_batch* b) {
-    const int rc = upload_join_batch(b);
-    if (rc != LOCGPU_OK) return rc;
-    LOCGPU_HIP(ctx, upload_order_after(b, b->stream));
-    return LOCGPU_OK;
-}
-
-static int ensure_grid_lists(locgpu_ctx* ctx, locgpu_batch* b, float alpha_eff) {
-    if (alpha_eff >= 0.f) return LOCGPU_OK;
-    if (!b->d_grid_qkey) {
-        LOCGPU_HIP(ctx, hipMalloc((void**)&b->d_grid_qkey, b->pitch * sizeof(uint32_t)));
-        LOCGPU_HIP(ctx, hipMalloc((void**)&b->d_grid_sorted, b->pitch * sizeof(uint2)));
-    }
-    // the binning's per-tile counts and scan workspace are the batch's own as well (several alignments run at once); sized by the
-    // current target's grid — a new target may have more occupied tiles
-    const size_t tocc = ctx->grid.n_tocc, scan = std::max<size_t>(ctx->grid.scan_temp_bytes, 1);
-    if (!b->d_grid_tile_count || b->grid_tocc_cap < tocc) {
-        LOCGPU_HIP(ctx, hipStreamSynchronize(b->stream));
-        if (b->d_grid_tile_count) (void)hipFree(b->d_grid_tile_count);
-        b->d_grid_tile_count = nullptr;
-        LOCGPU_HIP(ctx, hipMalloc((void**)&b->d_grid_tile_count, (tocc + 1) * sizeof(uint32_t)));
-        b->grid_tocc_cap = tocc;
-    }
-    if (!b->d_grid_scan_temp || b->grid_scan_cap < scan) {
-        LOCGPU_HIP(ctx, hipStreamSynchronize(b->stream));
-        if (b->d_grid_scan_temp) (void)hipFree(b->d_grid_scan_temp);
-        b->d_grid_scan_temp = nullptr;
-        LOCGPU_HIP(ctx, hipMalloc(&b->d_grid_scan_temp, scan));
-        b->grid_scan_cap = scan;
-    }
-    return LOCGPU_OK;
-}
-
-// hipGraph path (BASELINE config 5): the Gauss–Newton iterations are captured once — the kernels early-out per scan on the
-// device-side `done` flag, so a fixed node sequence gives the same result as the data-dependent eager loop — and replayed per call.
-// Two graphs mirror the eager loop's chunks: graph 0 = {H2D state, kFirstChunk iterations, D2H state} covers the typical alignment
-// with one launch and one host synchronisation; graph 1 = {kNextChunk iterations, D2H state} is replayed while scans are still
-// open (capturing all max_iteration iterations in one graph made every call pay a dozen empty iterations).
-static int capture_chunk(locgpu_ctx* ctx, locgpu_batch* b, const GnParams& prm, int k, float alpha_eff, bool ndt, int iters, bool with_h2d,
-                         hipGraphExec_t* out) {
-    hipStream_t s = b->stream;
-    hipGraph_t graph = nullptr;
-    LOCGPU_HIP(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    bool ok = !with_h2d || hip_ok(ctx, hipMemcpyAsync(b->d_state, b->h_state, b->n_total * sizeof(PoseState), hipMemcpyHostToDevice, s), "capture H2D");
-    IterLauncher it{ctx, b, prm, k, alpha_eff};
-    it.ndt = ndt;
-    it.capturing = true;
-    for (int i = 0; ok && i < iters; ++i) ok = it.launch(1);
-    ok = ok && hip_ok(ctx, hipMemcpyAsync(b->h_state, b->d_state, b->n_total * sizeof(PoseState), hipMemcpyDeviceToHost, s), "capture D2H");
-    const hipError_t e = hipStreamEndCapture(s, &graph);
-    if (!ok || !hip_ok(ctx, e, "hipStreamEndCapture")) { if (graph) (void)hipGraphDestroy(graph); return LOCGPU_ERR_NO_DEVICE; }
-    const bool inst = hip_ok(ctx, hipGraphInstantiate(out, graph, nullptr, nullptr, 0), "hipGraphInstantiate");
-    (void)hipGraphDestroy(graph);
-    if (!inst) { *out = nullptr; return LOCGPU_ERR_NO_DEVICE; }
-    return LOCGPU_OK;
-}
-
-// An alignment in two halves, so that a caller can have two batches in flight (their streams differ): align_begin enqueues the
-// first chunk of iterations and returns; align_finish waits for it, enqueues further chunks while scans are still open, and
-// writes the results. The blocking entry points are begin + finish back to back.
-static int ensure_graphs(locgpu_ctx* ctx, locgpu_batch* b, const GnParams& prm, int k, float alpha_eff, bool ndt) {
-    const void* target = !ndt ? (const void*)ctx->d_tree : (prm.method == 4 ? inc_ndt_table_ptr(ctx->inc) : (const void*)ctx->ndt->d_rec);
-    const bool same = b->graph_exec && b->graph_k == k && b->graph_alpha == alpha_eff && b->graph_ndt == ndt && b->graph_target == target &&
-                      b->graph_epoch == ctx->target_epoch &&
-                      b->graph_prm == prm;
-    if (same) return LOCGPU_OK;
-    const int first = std::min(kFirstChunk, prm.max_iteration);
-    if (b->graph_exec) { (void)hipGraphExecDestroy(b->graph_exec); b->graph_exec = nullptr; }
-    if (b->graph_exec_next) { (void)hipGraphExecDestroy(b->graph_exec_next); b->graph_exec_next = nullptr; }
-    int rc = capture_chunk(ctx, b, prm, k, alpha_eff, ndt, first, true, &b->graph_exec);
-    if (rc == LOCGPU_OK && prm.max_iteration > first) rc = capture_chunk(ctx, b, prm, k, alpha_eff, ndt, next_chunk(b), false, &b->graph_exec_next);
-    if (rc != LOCGPU_OK) return rc;
-    b->graph_prm = prm; b->graph_k = k; b->graph_alpha = alpha_eff; b->graph_ndt = ndt; b->graph_target = target;
-    b->graph_epoch = ctx->target_epoch;
-    return LOCGPU_OK;
-}
-
-// One chunk of iterations + the read-back of the per-scan states behind it, on the batch's stream.
-static int enqueue_chunk(locgpu_ctx* ctx, locgpu_batch* b, bool first_chunk) {
-    locgpu_batch::Pending& P = b->pending;
-    hipStream_t s = b->stream;
-    if (P.graph) {
-        // kernels of a finished scan return at once and the solve kernel stops at max_iteration, so a whole chunk is always safe
-        LOCGPU_HIP(ctx, hipGraphLaunch(first_chunk ? b->graph_exec : b->graph_exec_next, s));
-        P.launched += first_chunk ? std::min(kFirstChunk, P.prm.max_iteration) : next_chunk(b);
-        return LOCGPU_OK;
-    }
-    if (first_chunk) LOCGPU_HIP(ctx, hipMemcpyAsync(b->d_state, b->h_state, b->n_total * sizeof(PoseState), hipMemcpyHostToDevice, s));
-    IterLauncher it{ctx, b, P.prm, P.k, P.alpha_eff};
-    it.ndt = P.ndt;
-    it.ev_used = P.ev_used;
-    if (!first_chunk && !P.ndt && b->n_scans > 1) {
-        // The host has just read every scan's flags (align_finish): launch the search and accumulate kernels of this chunk over the
-        // local scans still open only. A 256-scan step's second and third chunk hold ≈60 and ≈5 scans; the rest used to be 1800
-        // early-exit workgroups per scan and kernel (≈96 µs per search launch for nothing). Results are the same bits: a scan's
-        // blocks do the same work wherever blockIdx.y finds it, and the accumulate kernels' split does not depend on the list.
-        int na = 0;
-        for (int i = 0; i < b->n_scans; ++i)
-            if (!b->h_state[b->first + i].done) b->h_active[na++] = i;
-        if (na > 0 && na < b->n_scans) {
-            LOCGPU_HIP(ctx, hipMemcpyAsync(b->d_active, b->h_active, (size_t)na * sizeof(int), hipMemcpyHostToDevice, s));
-            it.active = b->d_active;
-            it.n_active = na;
-        }
-    }
-    const int todo = std::min(first_chunk ? first_chunk_len(b) : next_chunk(b), P.prm.max_iteration - P.launched);
-    for (int c = 0; c < todo; ++c)
-        if (!it.launch(1)) return LOCGPU_ERR_NO_DEVICE;
-    P.ev_used = it.ev_used;
-    P.launched += todo;
-    if (it.replicated_on_comm_stream) {  // the states of the scans other ranks hold are written on the communication stream
-        LOCGPU_HIP(ctx, hipEventRecord(b->ev_reduced, ctx->comm_stream));
-        LOCGPU_HIP(ctx, hipStreamWaitEvent(s, b->ev_reduced, 0));
-    }
-    LOCGPU_HIP(ctx, hipMemcpyAsync(b->h_state, b->d_state, b->n_total * sizeof(PoseState), hipMemcpyDeviceToHost, s));
-    return LOCGPU_OK;
-}
-
-// A ONE-SCAN alignment is paced from the host instead of chunked: the solve kernel posts the scan's state and an iteration word to
-// pinned host memory (GnPost, icp_kernels.hip); the host keeps `ahead` iterations queued behind the one that is running and launches
-// the next when a post arrives. Against chunks (first_chunk_len / next_chunk above, still what graphs and batches use) a call no
-// longer pays the idle iterations of a chunk that was sized by the previous call (≈14 µs each: three dispatches that find `done`),
-// nor a chunk boundary (read-back + host + relaunch ≈ 33 µs) when the guess was short, nor the copy and the stream synchronisation
-// at the end: the result is in host memory when the done bit arrives. At most `ahead` idle iterations stay queued behind a finished
-// call; they return on the `done` flag before they read anything (an upload or the next call's state copy may follow at once).
-// Same kernels on the same data in the same order: results are the chunked path's bits. LOCGPU_PACE_AHEAD=0 switches it off.
-inline int pace_ahead() {
-    static const int v = [] { const char* e = getenv("LOCGPU_PACE_AHEAD"); return e ? std::max(0, std::min(8, atoi(e))) : 1; }();
-    return v;
-}
-
-static int paced_launch(locgpu_ctx* ctx, locgpu_batch* b, int upto) {
-    locgpu_batch::Pending& P = b->pending;
-    IterLauncher it{ctx, b, P.prm, P.k, P.alpha_eff};
-    it.ndt = P.ndt;
-    const GnPost post{reinterpret_cast<GnPostRecord*>(b->h_post), b->h_post + locgpu_batch::kPostWord, b->post_call};
-    it.post = &post;
-    while (P.launched < upto) {
-        if (!it.launch(1)) return LOCGPU_ERR_NO_DEVICE;
-        P.launched++;
-    }
-    return LOCGPU_OK;
-}
-
-// Wait for a post of this call that is newer than iteration `seen`; returns the word. A post with the done bit is taken only when the
-// state behind it is complete (its checksum matches what this thread reads: the kernel's stores carry no fence).
-constexpr int kPacedTimeoutS = 30;  // an iteration of the largest alignment this path takes (one scan) lasts well under a millisecond
-static int paced_wait(locgpu_ctx* ctx, locgpu_batch* b, int seen, unsigned long long* out) {
-    auto fresh = [&](unsigned long long* w_out) {
-        unsigned long long w;
-        GnPostRecord r;
-        if (!gn_post_take(b->h_post, locgpu_batch::kPostWord, b->post_call, seen, &w, &r)) return false;
-        if (w & 1ull) {
-            PoseState& ps = b->h_state[0];
-            for (int i = 0; i < 4; ++i) std::memcpy(&ps.q[i], &r.w[i], 8);
-            for (int i = 0; i < 3; ++i) std::memcpy(&ps.t[i], &r.w[4 + i], 8);
-            quat_to_R(ps.q, ps.R);
-            std::memcpy(&ps.last_dx_norm, &r.w[7], 8);
-            ps.last_eff = (long long)r.w[8];
-            ps.iterations = (int)((w & 0xffffffffull) >> 1);
-            ps.converged = (int)(r.w[9] >> 32);
-            ps.status = (int)(r.w[9] & 0xffffffffull);
-            ps.done = 1;
-        }
-        *w_out = w;
-        return true;
-    };
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned long spins = 1;; ++spins) {
-        if (fresh(out)) return LOCGPU_OK;
-#if defined(__x86_64__)
-        __builtin_ia32_pause();  // a polite spin: the sibling hyper-thread (the uploader, the helper thread) gets the core's issue slots
-#endif
-        if ((spins & 0xffff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) {
-            // nothing for a long time: is the stream still working? An idle stream with no post means a kernel died or the posts do
-            // not reach the host. (Not earlier: a stream query is a runtime call on the latency path.)
-            const hipError_t q = hipStreamQuery(b->stream);
-            if (q == hipErrorNotReady) {
-                // a stream that stays busy without ever posting (a hung kernel) must not spin a core for ever: give up after kPacedTimeoutS
-                if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(kPacedTimeoutS))
-                    return fail(ctx, LOCGPU_ERR_NO_DEVICE, "paced alignment: no post from the solve kernel within the time-out (the stream is still busy)");
-                std::this_thread::yield();
-                continue;
-            }
-            if (q != hipSuccess) { hip_ok(ctx, q, "paced alignment"); return LOCGPU_ERR_NO_DEVICE; }
-            if (fresh(out)) return LOCGPU_OK;
-            return fail(ctx, LOCGPU_ERR_NO_DEVICE, "paced alignment: the stream is idle and the solve kernel's post has not arrived");
-        }
-    }
-}
-
-static int align_begin(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const GnParams& prm, int k, float alpha_eff, bool ndt,
-                       bool blocking = false) {
-    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
-    locgpu_batch::Pending& P = b->pending;
-    if (P.active) return fail(ctx, LOCGPU_ERR_INVALID, "align: an alignment of this batch has been begun and not finished");
-    if (!ndt) { const int grc = ensure_grid_lists(ctx, b, alpha_eff); if (grc != LOCGPU_OK) return grc; }
-    { const int urc = batch_ready(ctx, b); if (urc != LOCGPU_OK) return urc; }
-    P.prm = prm; P.k = k; P.alpha_eff = alpha_eff; P.ndt = ndt;
-    P.graph = ctx->use_graph && !ctx->count_visits && !b->sharded && prm.max_iteration > 0;
-    P.launched = 0;
-    P.ev_used = 0;
-    P.init_poses.assign(init_poses, init_poses + 7 * (size_t)b->n_total);
-    init_states(b, init_poses);
-    // the search stage's work-list counters: zero once per alignment, whatever an earlier call that failed between a search and
-    // its solve kernel left behind (the solve kernel re-zeroes them after every search)
-    if (!ndt && !b->counters_clean) LOCGPU_HIP(ctx, hipMemsetAsync(b->d_redo_count, 0, 4 * sizeof(unsigned int), b->stream));
-    b->counters_clean = false;  // until this alignment has run to its end
-    if (P.graph) { const int rc = ensure_graphs(ctx, b, prm, k, alpha_eff, ndt); if (rc != LOCGPU_OK) return rc; }
-    // (a blocking call only: between a begin and its end the host is elsewhere, and a chunk keeps the GPU busy meanwhile)
-    P.paced = blocking && !P.graph && b->n_total == 1 && !b->sharded && !ctx->profile && !ctx->count_visits && prm.max_iteration > 0 && pace_ahead() > 0 && (ndt || alpha_eff >= 0.f);
-    if (P.paced) {
-        if (!b->h_post) {
-            LOCGPU_HIP(ctx, hipHostMalloc((void**)&b->h_post, 256, hipHostMallocCoherent));
-            std::memset(b->h_post, 0, 256);
-        }
-        b->post_call++;  // posts carry the call's number: a word left by the previous call is not this call's
-        LOCGPU_HIP(ctx, hipMemcpyAsync(b->d_state, b->h_state, sizeof(PoseState), hipMemcpyHostToDevice, b->stream));
-        const int rc = paced_launch(ctx, b, std::min(prm.max_iteration, 1 + pace_ahead()));
-        if (rc != LOCGPU_OK) { (void)hipStreamSynchronize(b->stream); return rc; }
-    } else if (prm.max_iteration > 0) {
-        const int rc = enqueue_chunk(ctx, b, true);
-        if (rc != LOCGPU_OK) return rc;
-    }
-    P.active = true;
-    return LOCGPU_OK;
-}
-
-static int align_finish(locgpu_ctx* ctx, locgpu_batch* b, double* out_poses, locgpu_align_stats* stats) {
-    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
-    locgpu_batch::Pending& P = b->pending;
-    if (!P.active) return fail(ctx, LOCGPU_ERR_INVALID, "align: no alignment of this batch has been begun");
-    P.active = false;
-    if (P.paced) {
-        int seen = 0;
-        for (;;) {
-            unsigned long long w = 0;
-            int rc = paced_wait(ctx, b, seen, &w);
-            if (rc == LOCGPU_OK) {
-                seen = (int)((w & 0xffffffffull) >> 1);
-                if ((w & 1ull) || seen >= P.prm.max_iteration) break;
-                rc = paced_launch(ctx, b, std::min(P.prm.max_iteration, seen + 1 + pace_ahead()));
-            }
-            if (rc != LOCGPU_OK) { (void)hipStreamSynchronize(b->stream); return rc; }
-        }
-        b->paced_tail = true;
-    }
-    while (!P.paced && P.prm.max_iteration > 0) {
-        LOCGPU_HIP(ctx, hipStreamSynchronize(b->stream));
-        if (!P.graph) {
-            IterLauncher it{ctx, b, P.prm, P.k, P.alpha_eff};
-            it.ndt = P.ndt;
-            it.ev_used = P.ev_used;
-            it.collect_profile();
-            P.ev_used = 0;
-        }
-        bool all_done = true;
-        for (int i = 0; i < b->n_total; ++i)
-            if (!b->h_state[i].done) { all_done = false; break; }
-        if (all_done || P.launched >= P.prm.max_iteration) break;
-        const int rc = enqueue_chunk(ctx, b, false);
-        if (rc != LOCGPU_OK) {
-            // whatever of the chunk was enqueued must not run on under the batch's next upload (which relies on an ended alignment
-            // leaving its stream idle, batch_upload.hip)
-            (void)hipStreamSynchronize(b->stream);
-            return rc;
-        }
-    }
-    write_results(b, P.init_poses.data(), out_poses, stats);
-    b->counters_clean = !P.ndt && !ctx->count_visits && P.alpha_eff >= 0.f && !b->sharded;  // every search was followed by its solve kernel, which zeroes them (a one-scan front-end saves a fill launch per call)
-    if (b->n_total == 1 && P.prm.max_iteration > 0) b->last_iterations = b->h_state[0].iterations;
-    return LOCGPU_OK;
-}
-
-static int run_align(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const GnParams& prm, int k, float alpha_eff, bool ndt,
-                     double* out_poses, locgpu_align_stats* stats) {
-    const int rc = align_begin(ctx, b, init_poses, prm, k, alpha_eff, ndt, /*blocking*/ true);
-    return rc != LOCGPU_OK ? rc : align_finish(ctx, b, out_poses, stats);
-}
-
-static void write_results(locgpu_batch* b, const double* init_poses, double* out_poses, locgpu_align_stats* stats) {
-    for (int i = 0; i < b->n_total; ++i) {
-        const PoseState& ps = b->h_state[i];
-        if (ps.status == 1) {  // direct NDT aborted: reference leaves result_pose unassigned; hand back init_pose
-            for (int j = 0; j < 7; ++j) out_poses[7 * i + j] = init_poses[7 * i + j];
-        } else {
-            for (int j = 0; j < 4; ++j) out_poses[7 * i + j] = ps.q[j];
-            for (int j = 0; j < 3; ++j) out_poses[7 * i + 4 + j] = ps.t[j];
-        }
-        if (stats) {
-            stats[i].iterations = ps.iterations;
-            stats[i].converged = ps.converged;
-            stats[i].status = ps.status;
-            stats[i].reserved = 0;
-            stats[i].last_effective_num = ps.last_eff;
-            stats[i].last_dx_norm = ps.last_dx_norm;
-        }
-    }
-}
-
-// The plane table of LOCGPU_P2PLANE_MAP for the current target (map_planes.hip), on the context's stream; no-op when it is there.
-// Leaves go through the existing search stage in chunks of at most kPlaneChunk, as the points of a one-scan batch under the
-// identity pose (k = 5, exact). The table and the chunk workspace are kept: nothing is allocated after the first call unless the map grew.
-// The workspace is a whole one-scan batch (alloc_batch also makes partials, H/B and pinned state the ingest never touches: a few KB
-// beside the 44 MB of points, lists and work lists at 2^20 leaves); like ctx->search it stays resident until locgpu_destroy, even
-// if the table is never built again.
-constexpr size_t kPlaneChunk = (size_t)1 << 20;
-static int ensure_map_planes(locgpu_ctx* ctx) {
-    if (ctx->planes_ready) return LOCGPU_OK;
-    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const size_t rows = ctx->tree_slots / 2 + 2;  // slot >> 1 of every slot, the sentinel leaf behind the tree included
-    if (rows > ctx->planes_cap_rows) {
-        if (ctx->d_planes) { LOCGPU_HIP(ctx, hipFree(ctx->d_planes)); ctx->d_planes = nullptr; ctx->planes_cap_rows = 0; }
-        const size_t cap = rows + rows / 4 + 1024;
-        if (!hip_ok(ctx, hipMalloc((void**)&ctx->d_planes, cap * 4 * sizeof(double)), "hipMalloc map planes")) return LOCGPU_ERR_OOM;
-        ctx->planes_cap_rows = cap;
-    }
-    if (!ctx->d_planes_count && !hip_ok(ctx, hipMalloc((void**)&ctx->d_planes_count, sizeof(unsigned long long)), "hipMalloc map planes")) return LOCGPU_ERR_OOM;
-    LOCGPU_HIP(ctx, hipMemsetAsync(ctx->d_planes, 0xFF, rows * 4 * sizeof(double), s));  // all-ones doubles are NaNs: no plane
-    LOCGPU_HIP(ctx, hipMemsetAsync(ctx->d_planes_count, 0, sizeof(unsigned long long), s));
-    unsigned long long n_valid = 0;
-    if (ctx->num_leaves >= 5) {  // k > size_: GetClosestPoint returns nothing (kdtree.cpp:149-153) ⇒ no plane at all
-        const size_t chunk = std::min(ctx->num_leaves, kPlaneChunk);
-        locgpu_batch* w = ctx->planes_ws;
-        if (!w || (size_t)w->max_n < chunk) {
-            if (w) { free_batch(w); ctx->planes_ws = nullptr; }
-            const int next_slot = ctx->next_slot;  // the workspace must not shift the streams the caller's batches are dealt
-            const int rc = alloc_batch(ctx, 1, chunk, &ctx->planes_ws);
-            ctx->next_slot = next_slot;
-            if (rc != LOCGPU_OK) return rc;
-            w = ctx->planes_ws;
-            w->slot = 0;
-            w->stream = s;
-        }
-        const double identity[7] = {0, 0, 0, 1, 0, 0, 0};
-        init_states(w, identity);
-        LOCGPU_HIP(ctx, hipMemsetAsync(w->d_redo_count, 0, 4 * sizeof(unsigned int), s));
-        LOCGPU_HIP(ctx, hipMemcpyAsync(w->d_state, w->h_state, sizeof(PoseState), hipMemcpyHostToDevice, s));
-        for (size_t first = 0; first < ctx->num_leaves; first += chunk) {
-            const int cnt = (int)std::min(chunk, ctx->num_leaves - first);
-            launch_map_plane_queries(ctx->d_tree, ctx->d_leaf_slots, first, cnt, w->d_src, w->d_counts, s);
-            SearchArgs sa{ctx->d_tree, ctx->tree_slots * sizeof(uint64_t), ctx->depth, w->d_src, w->d_counts, w->d_state, w->d_nn, w->pitch, w->max_n, 1, 5, 1.0f,
-                          0, nullptr, w->d_redo_list, w->d_redo_count, w->d_redo_list2, w->d_redo_count + 1, nullptr};
-            if (!ctx->tree_bounded) sa.redo_list = nullptr;  // huge / non-finite map coordinates: exact tree kernel only
-            if (!launch_icp_search(sa, s)) return fail(ctx, LOCGPU_ERR_DEPTH, "icp_build_map_planes: unsupported tree depth");
-            LOCGPU_HIP(ctx, hipMemsetAsync(w->d_redo_count, 0, 4 * sizeof(unsigned int), s));  // the work lists are consumed
-            launch_map_plane_fit(ctx->d_tree, ctx->d_leaf_slots, first, cnt, w->d_nn, w->pitch, ctx->d_planes, ctx->d_planes_count, s);
-        }
-        LOCGPU_HIP(ctx, hipGetLastError());
-        LOCGPU_HIP(ctx, hipMemcpyAsync(&n_valid, ctx->d_planes_count, sizeof(n_valid), hipMemcpyDeviceToHost, s));
-    }
-    LOCGPU_HIP(ctx, hipStreamSynchronize(s));  // batches run on other streams: the table is complete before anyone reads it
-    ctx->planes_rows = ctx->num_leaves;
-    ctx->planes_valid = (long long)n_valid;
-    ctx->planes_ready = true;
-    return LOCGPU_OK;
-}
 
 // Scan pools and sharded batches do not take the map-plane method (locgpu.h).
 static int refuse_map_planes_sharded(locgpu_ctx* ctx, const locgpu_batch* b, const GnParams& prm) {
@@ -1429,21 +531,7 @@ int locgpu_icp_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, c
     if (rc != LOCGPU_OK) return rc;
     if (!b || b->ctx != ctx || !poses || !hb) return fail(ctx, LOCGPU_ERR_INVALID, "icp_hb_batch: bad arguments");
     { const int src = refuse_map_planes_sharded(ctx, b, prm); if (src != LOCGPU_OK) return src; }
-    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
-    { const int grc = ensure_grid_lists(ctx, b, alpha_eff); if (grc != LOCGPU_OK) return grc; }
-    { const int urc = batch_ready(ctx, b); if (urc != LOCGPU_OK) return urc; }
-    if (b->pending.active) return fail(ctx, LOCGPU_ERR_INVALID, "icp_hb_batch: an alignment of this batch has been begun and not finished");
-    init_states(b, poses);
-    b->counters_clean = false;
-    LOCGPU_HIP(ctx, hipMemsetAsync(b->d_redo_count, 0, 4 * sizeof(unsigned int), b->stream));
-    LOCGPU_HIP(ctx, hipMemcpyAsync(b->d_state, b->h_state, b->n_total * sizeof(PoseState), hipMemcpyHostToDevice, b->stream));
-    IterLauncher it{ctx, b, prm, k, alpha_eff};
-    if (!it.launch(0)) return LOCGPU_ERR_NO_DEVICE;
-    LOCGPU_HIP(ctx, hipMemcpyAsync(b->h_hb, b->d_hb, (size_t)b->n_total * 44 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    LOCGPU_HIP(ctx, hipStreamSynchronize(b->stream));
-    it.collect_profile();
-    std::memcpy(hb, b->h_hb, (size_t)b->n_total * 44 * sizeof(double));
-    return LOCGPU_OK;
+    return eval_hb_batch(ctx, b, poses, prm, k, alpha_eff, hb);
 }
 
 int locgpu_debug_batch_nn(locgpu_ctx* ctx, locgpu_batch* b, int k, int32_t* out) {
@@ -1746,40 +834,6 @@ int search_batch(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes
     const int rc = upload_shared(ctx, b, src, n, stride_bytes);
     if (rc != LOCGPU_OK) return rc;
     *out = b;
-    return LOCGPU_OK;
-}
-
-// Score of every entry of `b` under its pose: k = 1 exact search stage, then the reduction of fitness.hip.
-int fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, double max_range, locgpu_fitness* out) {
-    if (b->sharded) return fail(ctx, LOCGPU_ERR_INVALID, "icp_fitness: sharded batches are not scored");
-    if (b->pending.active) return fail(ctx, LOCGPU_ERR_INVALID, "icp_fitness: an alignment of this batch has been begun and not finished");
-    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
-    { const int urc = batch_ready(ctx, b); if (urc != LOCGPU_OK) return urc; }
-    init_states(b, poses);
-    hipStream_t s = b->stream;
-    if (!b->counters_clean) LOCGPU_HIP(ctx, hipMemsetAsync(b->d_redo_count, 0, 4 * sizeof(unsigned int), s));
-    b->counters_clean = false;
-    LOCGPU_HIP(ctx, hipMemcpyAsync(b->d_state, b->h_state, b->n_total * sizeof(PoseState), hipMemcpyHostToDevice, s));
-    // the exact walk whatever the matcher's options say: a score must not depend on a pruning knob (alpha_eff = 1), and it skips the
-    // points pcl::isFinite rejects
-    SearchArgs sa{ctx->d_tree, ctx->tree_slots * sizeof(uint64_t), ctx->depth, batch_src(b), b->d_counts, b->d_state, b->d_nn, b->pitch, b->max_n, b->n_scans, 1, 1.0f,
-                  1, nullptr, b->d_redo_list, b->d_redo_count, b->d_redo_list2, b->d_redo_count + 1, ctx->d_search_stats};
-    if (!ctx->tree_bounded) sa.redo_list = nullptr;  // huge / non-finite map coordinates: exact tree kernel only
-    sa.src_of = b->d_src_of;
-    if (!launch_icp_search(sa, s)) return fail(ctx, LOCGPU_ERR_DEPTH, "icp_fitness: unsupported tree depth");
-    FitnessArgs fa{ctx->d_tree, batch_src(b), b->d_counts, b->d_state, b->d_nn, b->max_n, b->n_scans, (float)(max_range * max_range), b->d_partials, b->d_hb, b->d_redo_count};
-    fa.src_of = b->d_src_of;
-    launch_icp_fitness(fa, s);
-    LOCGPU_HIP(ctx, hipGetLastError());
-    LOCGPU_HIP(ctx, hipMemcpyAsync(b->h_hb, b->d_hb, (size_t)b->n_scans * kFitW * sizeof(double), hipMemcpyDeviceToHost, s));
-    LOCGPU_HIP(ctx, hipStreamSynchronize(s));
-    b->counters_clean = true;  // the sum kernel zeroed them behind the search
-    for (int i = 0; i < b->n_scans; ++i) {
-        const double* r = b->h_hb + (size_t)i * kFitW;
-        out[i].inliers = (int64_t)r[1];
-        out[i].finite_points = (int64_t)r[2];
-        out[i].score = out[i].inliers > 0 ? r[0] / (double)out[i].inliers : HUGE_VAL;
-    }
     return LOCGPU_OK;
 }
 
@@ -2158,40 +1212,6 @@ int locgpu_ndt_align(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_b
 }
 
 // ---- matcher entry points on clouds resident in HBM (cloud_filters.hpp) ----
-int locgpu_icp_set_target_cloud(locgpu_ctx* ctx, const locgpu_cloud* target) {
-    if (!ctx) return LOCGPU_ERR_INVALID;
-    if (!target || target->ctx != ctx) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target_cloud: bad cloud");
-    if (target->n == 0) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target: empty cloud or stride < 12");
-    (void)target_join(ctx, false);  // a pending asynchronous ingest is superseded
-    // The mean-split tree is built on the host (its float32 sums are sequential by definition, kdtree.cpp:94-123), so the
-    // cloud crosses PCIe once in each direction: 16 B/point down, the packed tree (≈24 B/point) up.
-    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
-    float4* stage = nullptr;
-    if (!hip_ok(ctx, cloud_stage(ctx, target->n, &stage), "pinned staging")) return LOCGPU_ERR_OOM;
-    LOCGPU_HIP(ctx, hipMemcpyAsync(stage, target->d, target->n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    LOCGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return locgpu_icp_set_target(ctx, stage, target->n, sizeof(float4));
-}
-
-int locgpu_icp_set_target_cloud_async(locgpu_ctx* ctx, const locgpu_cloud* target) {
-    if (!ctx) return LOCGPU_ERR_INVALID;
-    if (!target || target->ctx != ctx) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target_cloud: bad cloud");
-    if (target->n == 0) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target: empty cloud or stride < 12");
-    (void)target_join(ctx, false);  // an earlier pending ingest is superseded
-    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
-    float4* stage = nullptr;
-    if (!hip_ok(ctx, cloud_stage(ctx, target->n, &stage), "pinned staging")) return LOCGPU_ERR_OOM;
-    LOCGPU_HIP(ctx, hipMemcpyAsync(stage, target->d, target->n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    LOCGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    locgpu::PendingTarget* p = take_target_scratch(ctx);
-    p->xyz.resize(3 * target->n);  // the deep copy of SetInputTarget (icp_registration.cpp:16): the staging block is free again after it
-    for (size_t i = 0; i < target->n; ++i) std::memcpy(&p->xyz[3 * i], &stage[i], 12);
-    const size_t n = target->n;
-    p->worker = std::thread([p, n] { p->ok = build_packed_kdtree(p->xyz.data(), n, p->tree, p->err); });
-    ctx->pending_target = p;
-    return LOCGPU_OK;
-}
-
 int locgpu_ndt_set_target_cloud(locgpu_ctx* ctx, const locgpu_cloud* target, const locgpu_ndt_opts* opts) {
     if (!ctx) return LOCGPU_ERR_INVALID;
     if (!target || target->ctx != ctx) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_set_target_cloud: bad cloud");
@@ -2230,4 +1250,3 @@ int locgpu_ndt_align_cloud(locgpu_ctx* ctx, const locgpu_cloud* src, const doubl
 }
 
 }  // extern "C"
-

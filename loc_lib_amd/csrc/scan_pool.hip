@@ -36,10 +36,7 @@
 #include <vector>
 
 #include "batch_upload.hpp"
-#include "context.hpp"
-#include "launch.hpp"
-#include "ndt_inc.hpp"
-#include "ndt_kernels.hpp"
+#include "gn_driver.hpp"
 #include "pool_sched.hpp"
 
 using namespace locgpu;
@@ -106,8 +103,6 @@ struct locgpu_pool {
     bool timed = false;
     double chunk_ms = 0.0;
     long long chunks = 0;
-    std::vector<hipEvent_t> stage_ev;     // profile mode 1: four per iteration of the chunk — search | fit+accumulate | solve (+ exchange)
-    size_t stage_used = 0;
     int deferred_rc = 0;                  // a pump failure behind an accepted submit: reported by the next step / wait
     std::string deferred_msg;
 };
@@ -125,30 +120,14 @@ void job_free(PoolJob* j) {
     delete j;
 }
 
-void init_state(PoseState& ps, const double* pose) {
-    std::memset(&ps, 0, sizeof(ps));
-    for (int i = 0; i < 4; ++i) ps.q[i] = pose[i];
-    for (int i = 0; i < 3; ++i) ps.t[i] = pose[4 + i];
-    quat_to_R(ps.q, ps.R);
-}
-
 // The chunk in flight has run (the caller synchronised the stream): finished scans hand their results to their jobs and leave.
 void pool_collect(locgpu_pool* P) {
     locgpu_batch* b = P->b;
     for (int s = 0; s < P->slots; ++s) {
         PoolJob* j = static_cast<PoolJob*>(P->sched->job_of(s));
         if (!j || !b->h_state[s].done) continue;
-        const PoseState& ps = b->h_state[s];
-        const int i = P->sched->idx_of(s);
-        if (ps.status == 1) {  // direct NDT aborted: the reference leaves result_pose unassigned; hand back init_pose (locgpu_api.hip write_results)
-            for (int c = 0; c < 7; ++c) j->out[7 * i + c] = j->init[7 * i + c];
-        } else {
-            for (int c = 0; c < 4; ++c) j->out[7 * i + c] = ps.q[c];
-            for (int c = 0; c < 3; ++c) j->out[7 * i + 4 + c] = ps.t[c];
-        }
-        locgpu_align_stats& st = j->stats[i];
-        st.iterations = ps.iterations; st.converged = ps.converged; st.status = ps.status; st.reserved = 0;
-        st.last_effective_num = ps.last_eff; st.last_dx_norm = ps.last_dx_norm;
+        const size_t i = (size_t)P->sched->idx_of(s);
+        write_scan_result(b->h_state[s], &j->init[7 * i], &j->out[7 * i], &j->stats[i]);
         P->sched->finish(s);
     }
     if (P->timed) {
@@ -156,14 +135,7 @@ void pool_collect(locgpu_pool* P) {
         if (hipEventElapsedTime(&ms, P->ev_t0, P->ev_t1) == hipSuccess) { P->chunk_ms += ms; P->chunks++; }
         P->timed = false;
     }
-    // per-stage times go where a batch alignment's go (locgpu_profile_read): [0] search, [1] fit + accumulate, [2] solve (and exchange)
-    for (size_t i = 0; i + 3 < P->stage_used; i += 4)
-        for (int st = 0; st < 3; ++st) {
-            if (P->ndt && st == 0) continue;  // NDT has no search kernel
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, P->stage_ev[i + st], P->stage_ev[i + st + 1]) == hipSuccess) { P->ctx->prof_ms[st] += ms; P->ctx->prof_n[st] += 1; }
-        }
-    P->stage_used = 0;
+    b->stage_ev.collect(P->ctx, P->ndt);  // per-stage times go where a batch alignment's go (locgpu_profile_read)
     P->in_flight = false;
 }
 
@@ -174,46 +146,18 @@ bool pool_launch_iteration(locgpu_pool* P) {
     hipStream_t s = b->stream;
     const int* mine = P->d_list;
     const int* theirs = P->d_list + P->slots;
-    int n_partial_blocks = b->blocks_per_scan;
-    auto mark = [&]() {
-        if (ctx->profile != 1) return;
-        while (P->stage_ev.size() <= P->stage_used) {
-            hipEvent_t ev;
-            if (hipEventCreate(&ev) != hipSuccess) return;
-            P->stage_ev.push_back(ev);
-        }
-        (void)hipEventRecord(P->stage_ev[P->stage_used++], s);
-    };
-    mark();
-    if (P->n_mine > 0) {
-        if (!P->ndt) {
-            SearchArgs sa{ctx->d_tree, ctx->tree_slots * sizeof(uint64_t), ctx->depth, P->d_arena, b->d_counts, b->d_state, b->d_nn, b->pitch, b->max_n, b->n_scans, P->k,
-                          P->alpha_eff, P->prm.method == LOCGPU_P2P ? 1 : 0, nullptr, b->d_redo_list, b->d_redo_count, b->d_redo_list2, b->d_redo_count + 1,
-                          ctx->d_search_stats};
-            sa.active = mine; sa.n_active = P->n_mine; sa.src_of = P->d_src_of;
-            if (!ctx->tree_bounded) sa.redo_list = nullptr;  // huge / non-finite map coordinates: exact tree kernel only
-            if (!launch_icp_search(sa, s)) { fail(ctx, LOCGPU_ERR_DEPTH, "pool: unsupported k/depth"); return false; }
-            mark();
-            const double gate = P->prm.method == LOCGPU_P2PLANE ? P->prm.max_plane_distance : (P->prm.method == LOCGPU_P2LINE ? P->prm.max_line_distance : P->prm.max_nn_distance);
-            AccumArgs aa{ctx->d_tree, P->d_arena, b->d_counts, b->d_state, b->d_nn, b->pitch, b->max_n, b->n_scans, gate, b->d_partials};
-            aa.active = mine; aa.n_active = P->n_mine; aa.split_scans = P->split_scans; aa.src_of = P->d_src_of;
-            n_partial_blocks = launch_icp_accum(P->prm.method, aa, s);
-        } else if (P->prm.method == 4) {
-            mark();
-            launch_inc_accum(ctx->inc, ctx->ndt_opts.res_outlier_th, ctx->ndt_opts.nearby_type == 0 ? 1 : 7, P->d_arena, b->d_counts, b->d_state, b->max_n, b->n_scans, b->d_partials, s,
-                             mine, P->n_mine, P->d_src_of);
-        } else {
-            mark();
-            n_partial_blocks = launch_ndt_accum(ctx->ndt, P->d_arena, b->d_counts, b->d_state, b->max_n, b->n_scans, b->d_partials, s, mine, P->n_mine, P->split_scans, P->d_src_of);
-        }
-    } else {
-        mark();  // nothing local: this rank only takes part in the exchange below
-    }
-    mark();
+    StageEvents& ev = b->stage_ev;  // profile mode 1 only: four marks per iteration — search | fit + accumulate | solve (+ exchange)
+    ev.mode = ctx->profile == 1 ? 1 : 0;
+    // the slots index the arena through d_src_of, and the sums split as a plain batch of scans_per_job scans would
+    const LocalStage w{P->d_arena, b->d_state, mine, P->n_mine, P->d_src_of, P->split_scans, P->prm, P->k, P->alpha_eff, P->ndt, nullptr, nullptr, false, "pool"};
+    const int n_partial_blocks = launch_local_stage(ctx, b, w, s);
+    if (n_partial_blocks < 0) return false;
+    // The exchange-and-solve tail. Against a sharded batch's (gn_driver.hip): two slot lists instead of contiguous ranges, no
+    // LOCGPU_COMM_DIRECT, a ring of kAccRing exchange buffers.
     unsigned int* list_counts = P->ndt ? nullptr : b->d_redo_count;
     if (!P->with_comm) {
         launch_gn_solve(b->d_partials, n_partial_blocks, b->d_state, P->n_mine, P->prm, 1, nullptr, list_counts, s, mine);
-        mark();
+        ev.mark(s);
         return hip_ok(ctx, hipGetLastError(), "pool: kernel launch");
     }
     // The exchange step: per slot 28 sums, zeros from the ranks that do not hold it, in exactly the order
@@ -223,7 +167,7 @@ bool pool_launch_iteration(locgpu_pool* P) {
     launch_sum_partials(b->d_partials, n_partial_blocks, b->d_state, 0, P->slots, P->slots, acc, s, P->d_owned);
     if (P->decoupled) {
         // A slot's sums are complete on the rank that holds it: the owner solves at once and goes on to the next search, the
-        // all-reduce and the replicas' solve follow on the communication stream (locgpu_api.hip, sharded batches).
+        // all-reduce and the replicas' solve follow on the communication stream (gn_driver.hip, sharded batches).
         hipStream_t cs = ctx->comm_stream;
         if (P->n_mine > 0) launch_gn_solve(acc, 1, b->d_state, P->n_mine, P->prm, 1, nullptr, list_counts, s, mine);
         if (!hip_ok(ctx, hipEventRecord(P->ev_ready, s), "pool: hipEventRecord") || !hip_ok(ctx, hipStreamWaitEvent(cs, P->ev_ready, 0), "pool: hipStreamWaitEvent")) return false;
@@ -235,7 +179,7 @@ bool pool_launch_iteration(locgpu_pool* P) {
         if (P->n_mine > 0) launch_gn_solve(acc, 1, b->d_state, P->n_mine, P->prm, 1, nullptr, list_counts, s, mine);
         if (P->n_theirs > 0) launch_gn_solve(acc, 1, b->d_state, P->n_theirs, P->prm, 1, nullptr, nullptr, s, theirs);
     }
-    mark();
+    ev.mark(s);
     return hip_ok(ctx, hipGetLastError(), "pool: kernel launch");
 }
 
@@ -378,9 +322,7 @@ int locgpu_pool_create(locgpu_ctx* ctx, const locgpu_pool_opts* o, locgpu_pool**
     if (rc != LOCGPU_OK) { delete P; return rc; }
     P->with_comm = ctx->comm != nullptr;
     P->multi_rank = P->with_comm && ctx->comm_world > 1;
-    // LOCGPU_SHARD_DECOUPLED=0|1 (tests; the switch of the sharded batches): force the exchange onto the pool's stream / behind the owner's solve
-    static const int decouple_env = [] { const char* e = getenv("LOCGPU_SHARD_DECOUPLED"); return e ? atoi(e) : -1; }();
-    P->decoupled = P->with_comm && (decouple_env >= 0 ? decouple_env != 0 : P->multi_rank);
+    P->decoupled = shard_decoupled(ctx, true);  // the switch of the sharded batches
     rc = alloc_batch(ctx, o->slots, (size_t)o->max_points, &P->b);
     if (rc != LOCGPU_OK) { delete P; return rc; }
     const size_t S = (size_t)P->slots;
@@ -428,7 +370,6 @@ void locgpu_pool_destroy(locgpu_pool* P) {
     if (P->d_arena) (void)hipFree(P->d_arena);
     if (P->d_owned) (void)hipFree(P->d_owned);
     if (P->d_acc) (void)hipFree(P->d_acc);
-    for (hipEvent_t ev : P->stage_ev) (void)hipEventDestroy(ev);
     if (P->ev_t0) (void)hipEventDestroy(P->ev_t0);
     if (P->ev_t1) (void)hipEventDestroy(P->ev_t1);
     if (P->ev_ready) (void)hipEventDestroy(P->ev_ready);

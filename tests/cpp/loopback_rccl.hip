@@ -1,4 +1,4 @@
-// tests/cpp/loopback_rccl.hip — TEST DOUBLE of the six RCCL entry points liblocgpu.so binds (csrc/locgpu_api.hip: rccl()), for ranks
+// tests/cpp/loopback_rccl.hip — TEST DOUBLE of the six RCCL entry points liblocgpu.so binds (csrc/comm.hip: rccl()), for ranks
 // that are THREADS of one process sharing one GPU. RCCL itself refuses two ranks on one device ("Duplicate GPU detected") and
 // the boxes this suite runs on have one GPU, so this is the only way to drive the library's world-size-2 control flow — scan
 // shards, the owner solving ahead of the exchange, the ring of exchange buffers, collectives of two batches in flight on the

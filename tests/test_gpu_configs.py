@@ -854,7 +854,7 @@ def test_secular_plane_fit_agrees_with_the_four_column_fit(tmp_path):
 
 
 def test_paced_one_scan_alignment_equals_the_chunked_one(tmp_path):
-    """A one-scan eager alignment is paced from the host (locgpu_api.hip: the solve kernel posts an iteration word — and the finished
+    """A one-scan eager alignment is paced from the host (gn_driver.hip: the solve kernel posts an iteration word — and the finished
     scan's result under a checksum — to pinned host memory; the host keeps one iteration queued ahead) instead of running in chunks
     sized by the call before (LOCGPU_PACE_AHEAD=0). Same kernels, same data, same order: poses, iteration counts and stats are equal
     bit for bit — P2Plane / P2P / P2Line / direct NDT, a start that converges at once, far starts, runs cut short by max_iteration, a

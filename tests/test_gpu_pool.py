@@ -76,6 +76,57 @@ def test_pool_with_direct_ndt(gpu_ctx, api, small_world):
     pool.close()
 
 
+def test_pool_p2p_skips_non_finite_points_like_the_plain_batch(gpu_ctx, api, small_world):
+    """P2P is the method whose search stage skips the points pcl::isFinite rejects: jobs whose scans carry a few NaN and ±inf
+    coordinates come out of a pool of six slots with the plain batches' poses, iteration counts and stats, bit for bit."""
+    gpu_ctx.icp_set_target(small_world["map"])
+    opts = api.icp_opts(method=api.P2P)
+    bad = np.array([np.nan, np.inf, -np.inf], np.float32)
+    jobs = []
+    for j, (scans, inits) in enumerate(_jobs(small_world, 5, 3)):
+        scans = [sc.copy() for sc in scans]  # a job's scan may be a view of the shared world
+        for i, sc in enumerate(scans):
+            rows = np.arange(7 + i, len(sc), 397 + 31 * j)  # 3 to 16 points of every scan
+            sc[rows, (rows + i) % 3] = bad[(rows + j) % 3]
+            assert 3 <= len(rows) <= 16 and not np.isfinite(sc[rows]).all(axis=1).any()
+        jobs.append((scans, inits))
+    want = []
+    for scans, inits in jobs:
+        b = gpu_ctx.batch(scans)
+        want.append(gpu_ctx.icp_align_batch(b, inits, opts))
+        b.close()
+    pool = api.Pool(gpu_ctx, slots=6, max_points=6000, scans_per_job=3, chunk=2, opts=opts, prefetch=3)
+    tickets = [pool.submit(scans, inits) for scans, inits in jobs]
+    for t, w in zip(tickets, want):
+        got, st = pool.wait(t)
+        assert np.array_equal(got, w[0])
+        assert st == w[1]
+    pool.close()
+
+
+def test_pool_with_incremental_ndt(api, small_world):
+    """A pool over an incremental-NDT target (a context of its own: the voxel set outlives SetInputTarget calls): the jobs' poses,
+    iteration counts and stats are those of locgpu_ndt_align_batch on a plain batch of each job, bit for bit."""
+    ctx = api.Context(0)
+    try:
+        ctx.ndt_set_target(small_world["map"], api.ndt_opts(method=api.INCREMENTAL_NDT))
+        jobs = _jobs(small_world, 5, 3)
+        want = []
+        for scans, inits in jobs:
+            b = ctx.batch(scans)
+            want.append(ctx.ndt_align_batch(b, inits))
+            b.close()
+        pool = api.Pool(ctx, slots=7, max_points=6000, scans_per_job=3, chunk=2, ndt=True)
+        tickets = [pool.submit(scans, inits) for scans, inits in jobs]
+        for t, w in zip(tickets, want):
+            got, st = pool.wait(t)
+            assert np.array_equal(got, w[0])
+            assert st == w[1]
+        pool.close()
+    finally:
+        ctx.close()
+
+
 def test_pool_refusals(gpu_ctx, api, small_world):
     gpu_ctx.icp_set_target(small_world["map"])
     opts = api.icp_opts(method=api.P2PLANE)
