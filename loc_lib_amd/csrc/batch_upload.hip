@@ -12,6 +12,7 @@
 #endif
 
 #include "context.hpp"
+#include "env.hpp"
 
 namespace locgpu {
 
@@ -77,7 +78,7 @@ bool ensure_slots(Uploader& u, size_t want_slots, std::string& err) {
 void run_upload(locgpu_ctx* ctx, Uploader& u, UploadRequest& rq) {
     locgpu_batch* b = rq.b;
     BatchUploadState& bst = *rq.st;
-    static const bool dbg = getenv("LOCGPU_UPLOAD_DEBUG") != nullptr;
+    static const bool dbg = env_flag("LOCGPU_UPLOAD_DEBUG");
     const auto t_entry = std::chrono::steady_clock::now();
     int rc = LOCGPU_OK;
     std::string err;
@@ -89,7 +90,7 @@ void run_upload(locgpu_ctx* ctx, Uploader& u, UploadRequest& rq) {
         for (size_t o = 0; o < rq.counts[s]; o += Uploader::kSlotPoints) units.push_back({s, o, std::min(Uploader::kSlotPoints, rq.counts[s] - o)});
     if (!ensure_slots(u, units.size(), err)) rc = LOCGPU_ERR_OOM;
     {   // test hook (tests/test_gpu_pool.py): LOCGPU_TEST_FAIL_UPLOAD=n makes the n-th copy into a pool's regions of this process fail
-        static const int fail_at = [] { const char* e = getenv("LOCGPU_TEST_FAIL_UPLOAD"); return e ? atoi(e) : 0; }();
+        static const int fail_at = env_int("LOCGPU_TEST_FAIL_UPLOAD", 0);
         static std::atomic<int> seen{0};
         if (fail_at > 0 && to_slots && ++seen == fail_at) { rc = LOCGPU_ERR_NO_DEVICE; err = "batch upload: injected failure (LOCGPU_TEST_FAIL_UPLOAD)"; }
     }

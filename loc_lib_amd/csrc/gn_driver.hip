@@ -12,6 +12,7 @@
 #include <thread>
 
 #include "batch_upload.hpp"
+#include "env.hpp"
 #include "gn_driver.hpp"
 #include "ndt_inc.hpp"
 #include "ndt_kernels.hpp"
@@ -67,7 +68,7 @@ void write_scan_result(const PoseState& ps, const double* init, double* out_pose
 }
 
 bool shard_decoupled(const locgpu_ctx* ctx, bool scan_sharded) {
-    static const int env = [] { const char* e = getenv("LOCGPU_SHARD_DECOUPLED"); return e ? atoi(e) : -1; }();
+    static const int env = env_int("LOCGPU_SHARD_DECOUPLED", -1);
     return ctx->comm && scan_sharded && (env >= 0 ? env != 0 : ctx->comm_world > 1);
 }
 
@@ -206,7 +207,7 @@ bool IterLauncher::launch(int do_update) {
             // (A one-rank communicator has nobody to disagree with about the order: its collective stays on the batch's own stream —
             // 32 scans per step, two in flight: 8500 scans/s against 5700 through the comm stream, whose in-order queue makes the
             // second batch's first exchange wait for the first batch's whole chunk. LOCGPU_COMM_DIRECT=0/1 forces either way.)
-            static const int force = [] { const char* e = getenv("LOCGPU_COMM_DIRECT"); return e ? atoi(e) : -1; }();
+            static const int force = env_int("LOCGPU_COMM_DIRECT", -1);
             const bool direct = force >= 0 ? force != 0 : ctx->comm_world == 1;
             hipStream_t cs = direct ? s : ctx->comm_stream;
             if (!direct && (!hip_ok(ctx, hipEventRecord(b->ev_ready, s), "sharded: hipEventRecord") || !hip_ok(ctx, hipStreamWaitEvent(cs, b->ev_ready, 0), "sharded: hipStreamWaitEvent"))) return false;
@@ -338,7 +339,7 @@ static int enqueue_chunk(locgpu_ctx* ctx, locgpu_batch* b, bool first_chunk) {
 }
 
 // A ONE-SCAN alignment is paced from the host instead of chunked: the solve kernel posts the scan's state and an iteration word to
-// pinned host memory (GnPost, icp_kernels.hip); the host keeps `ahead` iterations queued behind the one that is running and launches
+// pinned host memory (GnPost, icp_fit.hip); the host keeps `ahead` iterations queued behind the one that is running and launches
 // the next when a post arrives. Against chunks (first_chunk_len / next_chunk above, still what graphs and batches use) a call no
 // longer pays the idle iterations of a chunk that was sized by the previous call (≈14 µs each: three dispatches that find `done`),
 // nor a chunk boundary (read-back + host + relaunch ≈ 33 µs) when the guess was short, nor the copy and the stream synchronisation
@@ -346,7 +347,7 @@ static int enqueue_chunk(locgpu_ctx* ctx, locgpu_batch* b, bool first_chunk) {
 // call; they return on the `done` flag before they read anything (an upload or the next call's state copy may follow at once).
 // Same kernels on the same data in the same order: results are the chunked path's bits. LOCGPU_PACE_AHEAD=0 switches it off.
 inline int pace_ahead() {
-    static const int v = [] { const char* e = getenv("LOCGPU_PACE_AHEAD"); return e ? std::max(0, std::min(8, atoi(e))) : 1; }();
+    static const int v = std::max(0, std::min(8, env_int("LOCGPU_PACE_AHEAD", 1)));
     return v;
 }
 

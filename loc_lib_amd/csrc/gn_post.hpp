@@ -1,5 +1,5 @@
 // loc_lib_amd/csrc/gn_post.hpp — the finished-scan post of a one-scan alignment paced from the host (gn_driver.hip, paced_wait;
-// icp_kernels.hip, gn_solve_kernel). Plain C++, no HIP in it: the CPU suite drives the host side against injected torn reads
+// icp_fit.hip, gn_solve_kernel). Plain C++, no HIP in it: the CPU suite drives the host side against injected torn reads
 // (tests/cpp/gn_post_sanitize.cpp).
 //
 // The solve kernel writes, to pinned coherent host memory and WITHOUT a fence (a system-scope release writes the whole L2 back: ≈ 12 µs

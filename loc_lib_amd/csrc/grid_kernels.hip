@@ -21,6 +21,7 @@
 //              in a block larger than the LDS stage, and every tie: the fast tree traversal with alpha = 1 over the compacted list
 //              (icp_search_fast_list_kernel), then icp_search_redo_kernel for the few it hands on.
 // locgpu_knn's grid mode (plain queries, no poses) walks rings through the tile records, one thread per query.
+#include "env.hpp"
 #include "grid_kernels.hpp"
 #include "icp_kernels.hpp"
 
@@ -480,7 +481,7 @@ __global__ __launch_bounds__(kBlock) void knn_grid_query_kernel(GridDev g, const
 }
 
 static GridDev to_dev(const GridView& v) {
-    static const int max_ring2 = [] { const char* e = getenv("LOCGPU_GRID_RINGS2"); const int r = e ? atoi(e) : 6; return r < 1 ? 1 : (r > 32 ? 32 : r); }();
+    static const int max_ring2 = [] { const int r = env_int("LOCGPU_GRID_RINGS2", 6); return r < 1 ? 1 : (r > 32 ? 32 : r); }();
     return GridDev{v.tile_hash, v.tile_mask, v.tiles, v.pts, v.dims[0], v.dims[1], v.dims[2], v.tdims[0], v.tdims[1], v.tdims[2],
                    v.origin[0], v.origin[1], v.origin[2], v.cell, v.inv_cell, v.slack, max_ring2};
 }
@@ -500,7 +501,7 @@ static bool search_grid_k(const GridView& grid, const GridDev& g, const SearchAr
     // after the scatter tile_count[t] = end of tile t's queries; the last entry (never incremented) still holds the total
     const size_t total_q = (size_t)a.max_n * a.n_scans;
     const unsigned waves = (unsigned)std::min<size_t>((total_q + kRangeQ - 1) / kRangeQ, 256u * 8u);
-    static const int exp_flags = [] { const char* e = getenv("LOCGPU_GRID_EXP"); return e ? atoi(e) : 0; }();  // timing experiments only (results wrong)
+    static const int exp_flags = env_int("LOCGPU_GRID_EXP", 0);  // timing experiments only (results wrong)
     hipLaunchKernelGGL((grid_tile_search_kernel<K>), dim3(waves), dim3(64), 0, s, g, sc.sorted, sc.tile_count + grid.n_tocc, a.src, a.st, a.nn, a.nn_pitch,
                        a.max_n, a.redo_list2, a.redo_count2, exp_flags, a.src_of);
     return launch_icp_search_list(a, a.redo_list2, a.redo_count2, s);  // a.alpha_eff = 1: exact pruning

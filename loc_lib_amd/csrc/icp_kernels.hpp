@@ -39,6 +39,12 @@ struct GnParams {
 
 __device__ __forceinline__ float as_f32(uint32_t u) { return __uint_as_float(u); }
 
+// Index into `src` of point i of scan slot `scan`. A scan pool keeps the points in an arena of max_n-point source regions and says
+// which one a slot reads (src_of, scan_pool.hip); without one the slot is its own region.
+__device__ __forceinline__ size_t src_index(const int* __restrict__ src_of, int scan, int max_n, int i) {
+    return (size_t)(src_of ? src_of[scan] : scan) * max_n + i;
+}
+
 // list[(*count)++] = value for every lane with `pred`, one atomic per wave (same-address atomics cost ≈10 ns each on gfx950: a
 // per-lane append from millions of queries serialises for milliseconds). Every active lane of the wave must reach the call.
 __device__ __forceinline__ void wave_append(uint32_t* __restrict__ list, unsigned int* __restrict__ count, bool pred, uint32_t value) {

@@ -9,6 +9,7 @@
 
 #include "cloud_filters.hpp"
 #include "context.hpp"
+#include "env.hpp"
 #include "kdtree_build.hpp"
 
 using namespace locgpu;
@@ -161,7 +162,7 @@ int locgpu_icp_set_target(locgpu_ctx* ctx, const void* pts, size_t n, size_t str
     if (!ctx) return LOCGPU_ERR_INVALID;
     (void)target_join(ctx, false);  // a pending asynchronous ingest is superseded
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
-    static const bool times = getenv("LOCGPU_INGEST_TIMES") != nullptr;  // diagnostic: phase times on stderr
+    static const bool times = env_flag("LOCGPU_INGEST_TIMES");  // diagnostic: phase times on stderr
     auto t0 = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
         if (!times) return;

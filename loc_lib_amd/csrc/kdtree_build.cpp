@@ -14,6 +14,7 @@
 //   internal node  : 1 slot  { float thresh ; u32 (axis<<30) | right_child_slot }   left child = slot+1
 //   leaf           : 2 slots { float x ; u32 (3<<30) | point_index } { float y ; float z }
 // A 16-byte load at a leaf's slot therefore returns the whole point.
+#include "env.hpp"
 #include "kdtree_build.hpp"
 
 #include <unistd.h>
@@ -189,7 +190,7 @@ inline unsigned pool_thread_budget() {
     if (!lw) lw = std::getenv("WORLD_SIZE");
     const int ranks = lw ? std::atoi(lw) : 1;
     if (ranks > 1) nt = std::max(2u, nt / (unsigned)ranks);
-    if (const char* e = std::getenv("LOCGPU_BUILD_THREADS")) { const int v = std::atoi(e); if (v >= 1) nt = (unsigned)std::min(v, 256); }
+    if (const int v = env_int("LOCGPU_BUILD_THREADS", 0); v >= 1) nt = (unsigned)std::min(v, 256);
     return nt;
 }
 
@@ -411,7 +412,7 @@ bool build_packed_kdtree(const float* xyz, size_t n, PackedKdTree& out, std::str
     if (n == 0) { err = "empty target cloud"; return false; }
     // 3n-1 slots of 8 bytes must stay below 4 GiB: the search kernel addresses the tree through a 32-bit buffer offset
     if (n >= (1ull << 29) / 3) { err = "target cloud too large (the packed tree must stay below 4 GiB)"; return false; }
-    static const bool times = std::getenv("LOCGPU_BUILD_TIMES") != nullptr;  // diagnostic: phase times of every build on stderr
+    static const bool times = env_flag("LOCGPU_BUILD_TIMES");  // diagnostic: phase times of every build on stderr
     auto t_prev = std::chrono::steady_clock::now();
     double t_phase[5] = {0, 0, 0, 0, 0};  // records, root split, further top levels, tasks, lay-out + top slots
     auto lap = [&](int ph) {
@@ -429,11 +430,11 @@ bool build_packed_kdtree(const float* xyz, size_t n, PackedKdTree& out, std::str
     lap(0);
 
     Pool& pool = Pool::get();
-    static const size_t grain = [] { const char* e = std::getenv("LOCGPU_BUILD_GRAIN"); const long v = e ? std::atol(e) : 0; return v >= 256 ? (size_t)v : (size_t)2048; }();
+    static const size_t grain = [] { const int v = env_int("LOCGPU_BUILD_GRAIN", 0); return v >= 256 ? (size_t)v : (size_t)2048; }();
     const unsigned nt = (unsigned)std::min<size_t>(pool.size(), std::max<size_t>(1, n / grain));  // threads worth waking for this map
     {
         bool all_bounded = true;
-        static const size_t min_task = [] { const char* e = std::getenv("LOCGPU_BUILD_TASK"); const long v = e ? std::atol(e) : 0; return v >= 16 ? (size_t)v : (size_t)1024; }();
+        static const size_t min_task = [] { const int v = env_int("LOCGPU_BUILD_TASK", 0); return v >= 16 ? (size_t)v : (size_t)1024; }();
         if (build_direct(b, idx.data(), tmp.data(), n, pool, nt, std::max<size_t>(n / (8 * (size_t)nt), min_task), out, all_bounded)) {
             lap(3);
             if (times) std::fprintf(stderr, "[locgpu build] %zu points, %u threads: records %.0f us | direct build %.0f us\n", n, nt, t_phase[0], t_phase[3]);

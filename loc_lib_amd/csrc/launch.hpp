@@ -1,4 +1,4 @@
-// loc_lib_amd/csrc/launch.hpp — host-callable launchers of the kernels in icp_kernels.hip / ndt_kernels.hip.
+// loc_lib_amd/csrc/launch.hpp — host-callable launchers of the kernels in icp_search.hip / icp_fit.hip / ndt_kernels.hip.
 #pragma once
 #include "gn_post.hpp"
 #include <hip/hip_runtime.h>
@@ -112,6 +112,9 @@ void launch_map_plane_dump(const uint2* tree, const uint32_t* leaf_slots, size_t
 // Code-object self-test (once per process): no walk kernel owns static LDS, so every traversal stack starts at LDS address 0 —
 // the precondition of search_walk.hpp's out-of-range rows (tests/test_gpu_lds_semantics.py pins the hardware side).
 bool search_kernels_lds_ok();
+// LOCGPU_STAMP is set and non-zero (read once): the diagnostic build of the walk kernel — per-query round counts behind the redo list
+// (twice its size), other meanings of locgpu_search_stats_read's out[2..3], locgpu_debug_stamp_trips
+bool stamp_build();
 // instrumented pass: totals[3] += number of set bits of touched[0..n_words), then touched := 0
 void launch_count_touched(uint32_t* touched, size_t n_words, unsigned long long* totals, hipStream_t s);
 // test hook: slot lists [k][pitch] → original point indices out[query * k + j] (-1 = none)

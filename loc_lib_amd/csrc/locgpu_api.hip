@@ -293,7 +293,7 @@ int locgpu::alloc_batch(locgpu_ctx* ctx, int n_scans, size_t max_n, locgpu_batch
               hip_ok(ctx, hipMalloc((void**)&b->d_nn, 5 * std::max<size_t>(b->pitch, 1) * sizeof(uint32_t)), "hipMalloc nn") &&
               hip_ok(ctx, hipMalloc((void**)&b->d_partials, (size_t)std::max(n_scans, 1) * b->blocks_per_scan * kAccW * sizeof(double)), "hipMalloc partials") &&
               hip_ok(ctx, hipMalloc((void**)&b->d_hb, (size_t)n_total * 44 * sizeof(double)), "hipMalloc hb") &&
-              hip_ok(ctx, hipMalloc((void**)&b->d_redo_list, (getenv("LOCGPU_STAMP") ? 2 : 1) * std::max<size_t>(b->pitch, 1) * sizeof(uint32_t)), "hipMalloc redo") &&  // diagnostic build: + per-query trip counts
+              hip_ok(ctx, hipMalloc((void**)&b->d_redo_list, (stamp_build() ? 2 : 1) * std::max<size_t>(b->pitch, 1) * sizeof(uint32_t)), "hipMalloc redo") &&  // diagnostic build: + per-query trip counts
               hip_ok(ctx, hipMalloc((void**)&b->d_redo_list2, std::max<size_t>(b->pitch, 1) * sizeof(uint32_t)), "hipMalloc redo2") &&  // deep pass / grid search: second work list
               hip_ok(ctx, hipMalloc((void**)&b->d_redo_count, 4 * sizeof(unsigned int)), "hipMalloc redo") &&  // [0] redo list, [1] deep list, [2..3] spare
               hip_ok(ctx, hipHostMalloc((void**)&b->h_state, n_total * sizeof(PoseState)), "hipHostMalloc state") &&
@@ -1010,7 +1010,7 @@ int locgpu_search_stats_read(locgpu_ctx* ctx, uint64_t out[4], int reset) {
     for (hipStream_t st : ctx->slot_stream) LOCGPU_HIP(ctx, hipStreamSynchronize(st));
     unsigned long long h[kSearchStatSlots];
     LOCGPU_HIP(ctx, hipMemcpy(h, ctx->d_search_stats, sizeof(h), hipMemcpyDeviceToHost));
-    static const bool stamp = getenv("LOCGPU_STAMP") != nullptr;
+    const bool stamp = stamp_build();
     // diagnostic build (LOCGPU_STAMP=1): out[2] = Σ over queries of the main-loop rounds the query needed, out[3] = Σ over queries of
     // the rounds its wave ran (what the wave paid for that lane) — lane efficiency of the search kernel = out[2] / out[3]
     out[0] = h[0]; out[1] = h[1]; out[2] = stamp ? h[4] : h[2]; out[3] = stamp ? h[13] : 0;
@@ -1050,7 +1050,7 @@ int locgpu_visit_count_read(locgpu_ctx* ctx, uint64_t out[4], int reset) {
 // Diagnostic build only (LOCGPU_STAMP=1 when the batch was created): per query the main-loop rounds it needed in the batch's most
 // recent search stage, out[n_scans * max_n].
 extern "C" __attribute__((visibility("default"))) int locgpu_debug_stamp_trips(locgpu_ctx* ctx, locgpu_batch* b, uint32_t* out) {
-    if (!ctx || !b || !out || !getenv("LOCGPU_STAMP")) return LOCGPU_ERR_INVALID;
+    if (!ctx || !b || !out || !stamp_build()) return LOCGPU_ERR_INVALID;
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
     LOCGPU_HIP(ctx, hipStreamSynchronize(b->stream));
     LOCGPU_HIP(ctx, hipMemcpy(out, b->d_redo_list + b->pitch, b->pitch * sizeof(uint32_t), hipMemcpyDeviceToHost));

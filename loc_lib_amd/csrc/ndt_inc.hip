@@ -32,6 +32,7 @@
 // effective_num counts accepted (point, voxel) pairs (:343), too few ⇒ `return false` with result = current pose (:349-353), and
 // there is no det(H) test.
 #include "device_prims.hpp"
+#include "env.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -236,7 +237,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
 #pragma unroll
     for (int v = 0; v < 28; ++v) acc[v] = 0.0;
     if (i < counts[scan]) {
-        const float4 p = src[(size_t)(src_of ? src_of[scan] : scan) * max_n + i];
+        const float4 p = src[src_index(src_of, scan, max_n, i)];
         const D3 q{(double)p.x, (double)p.y, (double)p.z};
         const D3 qs = se3_apply(st[scan].q, st[scan].t, q);
         const int kx = (int)(qs.x * inv_voxel), ky = (int)(qs.y * inv_voxel), kz = (int)(qs.z * inv_voxel);
@@ -586,7 +587,7 @@ hipError_t inc_ndt_ingest(IncNdtState& st, const float4* host_pts, const float4*
     const long long M = (long long)st.capacity - 1;            // voxels the reference's list holds after every point (ndt cpp:161-165)
     if (m == 0) return hipSuccess;                             // every point skipped: nothing changes
     const int n_evict = (long long)m > M ? -1 : (int)std::max<long long>(0, (long long)st.n_live + m_new - M);
-    static const bool dbg = getenv("LOCGPU_INC_DEBUG") != nullptr;  // which path a call took (the determinism harness asserts it has seen all three)
+    static const bool dbg = env_flag("LOCGPU_INC_DEBUG");  // which path a call took (the determinism harness asserts it has seen all three)
     if (dbg) fprintf(stderr, "[locgpu inc-ndt] call %u: %zu points, %d voxels touched (%d new), %d alive, capacity %zu: %s\n", st.epoch, n, m, m_new, st.n_live, st.capacity,
                      n_evict < 0 ? "replayed on the host" : (n_evict > 0 ? "device path with evictions" : "device path, no eviction"));
     if (n_evict < 0) return ingest_replayed(st, host_pts, d_pts, n, s);

@@ -255,7 +255,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LOCGPU_N
     for (int pp = 0; pp < pts; ++pp) {  // several points per thread before the 28-value block reduction (≈ as costly as a point)
     const int i = (blockIdx.x * pts + pp) * kBlock + threadIdx.x;
     if (i < counts[scan]) {
-        const float4 p = src[(size_t)(src_of ? src_of[scan] : scan) * max_n + i];
+        const float4 p = src[src_index(src_of, scan, max_n, i)];
         const D3 q{(double)p.x, (double)p.y, (double)p.z};
         const D3 qs = se3_apply(st[scan].q, st[scan].t, q);
         int kx, ky, kz;

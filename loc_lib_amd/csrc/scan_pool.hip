@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "batch_upload.hpp"
+#include "env.hpp"
 #include "gn_driver.hpp"
 #include "pool_sched.hpp"
 
@@ -233,7 +234,7 @@ int pool_launch(locgpu_pool* P) {
     }
     P->n_mine = n_mine; P->n_theirs = n_theirs;
     P->n_open = n_mine + n_theirs;
-    static const bool dbg = getenv("LOCGPU_POOL_DEBUG") != nullptr;  // diagnostic: one line per chunk
+    static const bool dbg = env_flag("LOCGPU_POOL_DEBUG");  // diagnostic: one line per chunk
     if (dbg) {
         static const auto t0 = std::chrono::steady_clock::now();
         fprintf(stderr, "[pool] t=%.3f ms open=%d (mine %d) waiting=%zu free slots=%zu regions=%zu jobs=%zu\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(),

@@ -596,8 +596,8 @@ def test_bench_refuses_more_ranks_than_gpus():
 @pytest.mark.parametrize("rows", ["12", "15", "24"])
 def test_search_parity_at_other_stack_depths(rows):
     """The fast traversal stores `LOCGPU_FAST_STACK` stack rows in LDS and keeps the levels above them as candidates (direct
-    expansion, replay) — with 12 rows the replay and overflow paths run ~100× more often than at the default 15, with 24 hardly
-    ever. The index-list / H,B / alignment parity tests must pass unchanged either way (the setting is read once per process)."""
+    expansion, replay). The default is the 10-row sliding window; with 12 plain rows the replay and overflow paths run ~100× more
+    often than with 15, with 24 hardly ever. The index-list / H,B / alignment parity tests must pass unchanged either way (the setting is read once per process)."""
     import os
     import subprocess
     import sys

@@ -738,6 +738,97 @@ def test_bench_config_parity_10m(gpu_ctx, api, locref, synth):
     b.close()
 
 
+# ----------------------------------------------------------------------------------------------- deep trees: every rung of the depth dispatch
+# The kernels are compiled for 32, 40 and 64 stack rows and picked by the tree's depth; ordinary maps stay at or below 32. A chain of
+# points in geometric progression along each axis makes the reference's mean split peel one point per level, so depth = points.
+_CHAINS = {32: (10, 45.0, 1e-3), 40: (13, 45.0, 1e-3), 64: (18, 60.0, 1e-15)}  # rung: (points per axis, ratio, first point) → depth 30, 39, 54
+_CHAIN_SCANS, _CHAIN_PTS = 64, 2112  # 64 x 33 waves of 64 lanes = 2 112 > 2 048: the 64-lane walk, deep-pass and redo kernels; one scan: the 16-lane kernel
+
+
+def _chain_target(rung):
+    m, r, lo = _CHAINS[rung]
+    pts = np.zeros((3 * m, 3), dtype=np.float32)
+    for a in range(3):
+        pts[a * m:(a + 1) * m, a] = (lo * r ** np.arange(m, dtype=np.float64)).astype(np.float32)
+    return pts
+
+
+_chain_cache = {}
+
+
+def _chain_case(locref, rung):
+    """Target, oracle tree and the fixed queries of one rung: a random axis and sign, a log-uniform magnitude over the chain's own
+    range, a little off-axis jitter, and in every scan twelve queries far from everything (< 1e18, so the walk kernels take them):
+    their float32 distances tie, eight in a row (more than a wave answers itself → redo list) and four apart (answered in the wave)."""
+    if rung not in _chain_cache:
+        m, r, lo = _CHAINS[rung]
+        rng = np.random.default_rng(1000 + rung)
+        n = _CHAIN_SCANS * _CHAIN_PTS
+        mag = lo * r ** rng.uniform(-1.0, m - 0.5, n)  # from below the first point to beyond the last
+        q = mag[:, None] * rng.normal(0.0, 1e-3, (n, 3))
+        q[np.arange(n), rng.integers(0, 3, n)] = mag * rng.choice([-1.0, 1.0], n)
+        q = q.reshape(_CHAIN_SCANS, _CHAIN_PTS, 3)
+        far = (100, 101, 102, 103, 104, 105, 106, 107, 500, 900, 1300, 1999)
+        q[:, far, :] = rng.uniform(1e17, 9e17, (_CHAIN_SCANS, len(far), 3)) * rng.choice([-1.0, 1.0], (_CHAIN_SCANS, len(far), 3))
+        q = q.astype(np.float32)
+        assert np.all(np.isfinite(q)) and np.abs(q).max() < 1e18
+        pts = _chain_target(rung)
+        _chain_cache[rung] = (pts, locref.KdTree(pts), q, {})
+    return _chain_cache[rung]
+
+
+def _chain_oracle(case, k, approximate):
+    _, tree, q, memo = case
+    if (k, approximate) not in memo:
+        memo[(k, approximate)] = tree.knn(q.reshape(-1, 3), k, approximate=approximate, alpha=0.1).reshape(_CHAIN_SCANS, _CHAIN_PTS, k)
+    return memo[(k, approximate)]
+
+
+def _set_chain_target(gpu_ctx, case, rung):
+    pts, tree = case[0], case[1]
+    gpu_ctx.icp_set_target(pts)
+    info = gpu_ctx.icp_target_info()
+    assert (info["num_leaves"], info["num_nodes"], info["depth"]) == (tree.num_leaves, tree.num_nodes, tree.depth)
+    assert tree.depth == len(pts) and {32: 0, 40: 32, 64: 40}[rung] < tree.depth <= rung  # the fixture sits on the rung it is named for
+
+
+@pytest.mark.parametrize("k", [1, 5])
+@pytest.mark.parametrize("rung", [32, 40, 64])
+def test_search_lists_knn_on_deep_trees(gpu_ctx, api, locref, rung, k):
+    """The search stage's neighbour lists (locgpu_debug_batch_nn) on trees of depth 30, 39 and 54 — the D = 32, 40 and 64
+    instantiations — equal the oracle's k-NN index for index: one scan (16-lane kernel) and a 64-scan batch (64-lane walk kernel,
+    deep-pass list kernel, redo kernel), k = 1 and 5, ANN (alpha = 0.1) and exact. Every query is compared."""
+    case = _chain_case(locref, rung)
+    _set_chain_target(gpu_ctx, case, rung)
+    q = case[2]
+    ident = np.array([0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0])
+    opts = api.icp_opts(method=api.P2P if k == 1 else api.P2PLANE)
+    for scans in ([q[0, :2000]], list(q)):
+        b = gpu_ctx.batch(scans)
+        for approximate in (True, False):
+            opts.approximate = 1 if approximate else 0
+            gpu_ctx.icp_hb_batch(b, np.stack([ident] * len(scans)), opts)
+            got = gpu_ctx.debug_batch_nn(b, k)
+            want = _chain_oracle(case, k, approximate)
+            for i, s in enumerate(scans):
+                bad = int(np.sum(np.any(got[i, :len(s)] != want[i, :len(s)], axis=1)))
+                print("rung %d k %d %s scans %d scan %d: %d of %d lists differ" % (rung, k, "ann" if approximate else "exact", len(scans), i, bad, len(s))) if bad or i == 0 else None
+                assert np.array_equal(got[i, :len(s)], want[i, :len(s)]), (rung, k, approximate, len(scans), i, bad)
+        b.close()
+
+
+@pytest.mark.parametrize("rung", [32, 40, 64])
+def test_knn_on_deep_trees(gpu_ctx, locref, rung):
+    """locgpu_knn (knn_query_kernel<1|5|8, 32|40|64>) on the same trees and queries."""
+    case = _chain_case(locref, rung)
+    _set_chain_target(gpu_ctx, case, rung)
+    q = case[2].reshape(-1, 3)
+    for k in (1, 5, 8):
+        for approximate in (True, False):
+            np.testing.assert_array_equal(gpu_ctx.knn(q, k=k, approximate=approximate, alpha=0.1),
+                                          _chain_oracle(case, k, approximate).reshape(-1, k), err_msg="rung %d k %d approximate %s" % (rung, k, approximate))
+
+
 # ----------------------------------------------------------------------------------------------- properties at full size
 def test_full_size_properties(gpu_ctx, api, synth):
     """BASELINE config 2 size (115 200-pt scan vs 1 M-pt map): size-independent properties, no oracle needed.

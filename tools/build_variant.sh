@@ -1,9 +1,9 @@
 #!/bin/bash
-# A/B builds of the library:  bash tools/build_variant.sh <name> "<extra hipcc flags>" [objects to rebuild with them, default icp_kernels.o]
+# A/B builds of the library:  bash tools/build_variant.sh <name> "<extra hipcc flags>" [objects to rebuild with them, default icp_search.o]
 #   ->  build_variants/<name>/loc_lib_amd/liblocgpu.so     (run with LOCGPU_LIB=<that path>; build_variants/ travels to the GPU box, not into git)
 set -e
 name=$1; flags=$2; shift; shift
-objs=${*:-icp_kernels.o}
+objs=${*:-icp_search.o}
 root=$(cd "$(dirname "$0")/.." && pwd)
 dir=$root/build_variants/$name
 rm -rf $dir && mkdir -p $dir/loc_lib_amd $dir/include
