@@ -18,6 +18,20 @@ namespace locgpu { struct IncNdtState; struct FilterScratch; }  // ndt_inc.hpp, 
 
 namespace locgpu {
 struct PendingTarget;
+// A validated alignment request: what check_icp / check_ndt (locgpu_api.hip), its only producers, make of the caller's options, and
+// the one value the Gauss–Newton driver, a batch's pending alignment, its graph-cache key and a scan pool are told it by.
+struct AlignSpec {
+    GnParams prm{};
+    float alpha = 1.0f;  // pruning factor of the tree walk; 1.0f = exact. Always 1.0f for grid and NDT.
+    bool grid = false;   // LOCGPU_SEARCH_GRID_EXACT was asked for
+    bool ndt() const { return method_is_ndt(prm.method); }
+    int k() const { return method_k(prm.method); }
+    bool operator==(const AlignSpec& o) const { return prm == o.prm && alpha == o.alpha && grid == o.grid; }
+};
+// locgpu_ndt_opts::method and ::nearby_type (NdtMethod, NdtNearbyType of the reference), and the voxels a nearby type probes per point.
+constexpr int kNdtOptDirect = 1, kNdtOptIncremental = 2;
+constexpr int kNearbyCenter = 0, kNearby6 = 1;
+constexpr int ndt_n_nearby(int nearby_type) { return nearby_type == kNearbyCenter ? 1 : 7; }
 // Stage marks of locgpu_profile_enable (gn_driver.hip): HIP events around the stages of every Gauss–Newton iteration enqueued on one
 // stream since the last collect().
 struct StageEvents {
@@ -146,10 +160,7 @@ struct locgpu_batch {
     // hipGraph of {H2D state, max_iteration × (search, fit+accumulate, solve), D2H state}, keyed by the launch parameters
     hipGraphExec_t graph_exec = nullptr;       // {H2D state, first chunk of iterations, D2H state}
     hipGraphExec_t graph_exec_next = nullptr;  // {further chunk, D2H state}
-    locgpu::GnParams graph_prm{};
-    int graph_k = -1;
-    float graph_alpha = 0.f;
-    bool graph_ndt = false;
+    locgpu::AlignSpec graph_spec;
     const void* graph_target = nullptr;  // tree / NDT table the capture was made against
     unsigned long long graph_epoch = 0;
     float4* h_src = nullptr;               // pinned staging of the packed source (single-scan path only; reused across calls)
@@ -172,10 +183,8 @@ struct locgpu_batch {
     // an alignment begun with *_align_batch_begin and not yet finished
     struct Pending {
         bool active = false;
-        locgpu::GnParams prm{};
-        int k = 0;
-        float alpha_eff = 0.f;
-        bool ndt = false, graph = false;
+        locgpu::AlignSpec spec;
+        bool graph = false;
         bool paced = false;  // one scan, eager: iterations are launched as the solve kernel posts its progress
         int launched = 0;
         std::vector<double> init_poses;
@@ -192,9 +201,9 @@ void ndt_free(locgpu_ctx* ctx);
 // Device buffers + pinned result staging for n_scans scans of at most max_n points each; no points yet. n_total >= 0: a sharded batch.
 int alloc_batch(locgpu_ctx* ctx, int n_scans, size_t max_n, locgpu_batch** out, int first = 0, int n_total = -1, bool shared_src = false);
 void free_batch(locgpu_batch* b);
-// Validate the matcher's options against the context's target; fill the Gauss–Newton parameters of an alignment.
-int check_icp(locgpu_ctx* ctx, const locgpu_icp_opts* o, GnParams& prm, int& k, float& alpha_eff);
-int check_ndt(locgpu_ctx* ctx, GnParams& prm);
+// Validate the matcher's options against the context's target; fill the request of an alignment.
+int check_icp(locgpu_ctx* ctx, const locgpu_icp_opts* o, AlignSpec& spec);
+int check_ndt(locgpu_ctx* ctx, AlignSpec& spec);
 // icp_target.hip
 int target_join(locgpu_ctx* ctx, bool install = true);  // finishes a pending locgpu_icp_set_target_cloud_async (no-op without one)
 void free_target_scratch(locgpu_ctx* ctx);              // the ingest buffers the context keeps between SetInputTarget calls

@@ -100,10 +100,10 @@ int launch_local_stage(locgpu_ctx* ctx, locgpu_batch* b, const LocalStage& w, hi
     ev.mark(s, true);
     if (b->n_scans == 0 || (w.active && w.n_active == 0)) {
         ev.mark(s, true);  // nothing local: this rank only takes part in the exchange that follows
-    } else if (!w.ndt) {
-        SearchArgs sa = make_search_args(ctx, b, w.src, w.state, w.k, w.alpha_eff, skips_nonfinite(w.prm.method));
-        const bool grid_mode = w.alpha_eff < 0.f && ctx->tree_bounded;
-        if (w.alpha_eff < 0.f) sa.alpha_eff = 1.0f;  // grid mode is exact by construction (`approximate` is ignored)
+    } else if (!w.spec.ndt()) {
+        const GnParams& prm = w.spec.prm;
+        SearchArgs sa = make_search_args(ctx, b, w.src, w.state, w.spec.k(), w.spec.alpha, skips_nonfinite(prm.method));
+        const bool grid_mode = w.spec.grid && ctx->tree_bounded;
         if (grid_mode && !w.grid) { fail(ctx, LOCGPU_ERR_INVALID, "grid search: work list missing (ensure_grid_lists was not called)"); return -1; }
         sa.visit_totals = w.visits;
         sa.active = w.active; sa.n_active = w.n_active;
@@ -122,16 +122,16 @@ int launch_local_stage(locgpu_ctx* ctx, locgpu_batch* b, const LocalStage& w, hi
         if (!ok_search) { fail(ctx, LOCGPU_ERR_DEPTH, std::string(w.who) + ": unsupported k/depth"); return -1; }
         if (sa.touched) launch_count_touched(sa.touched, (ctx->tree_slots + 2 + 31) / 32, sa.visit_totals, s);
         ev.mark(s, true);
-        AccumArgs aa{ctx->d_tree, w.src, b->d_counts, w.state, b->d_nn, b->pitch, b->max_n, b->n_scans, icp_gate(w.prm), b->d_partials};
+        AccumArgs aa{ctx->d_tree, w.src, b->d_counts, w.state, b->d_nn, b->pitch, b->max_n, b->n_scans, icp_gate(prm), b->d_partials};
         aa.planes = ctx->d_planes;
         aa.active = w.active; aa.n_active = w.n_active;
         aa.src_of = w.src_of;
         aa.split_scans = w.split_scans;
-        n_partial_blocks = launch_icp_accum(w.prm.method, aa, s);
+        n_partial_blocks = launch_icp_accum(prm.method, aa, s);
     } else {
         ev.mark(s, true);  // NDT has no separate search kernel: the search slot stays empty
-        if (w.prm.method == 4)
-            launch_inc_accum(ctx->inc, ctx->ndt_opts.res_outlier_th, ctx->ndt_opts.nearby_type == 0 ? 1 : 7, w.src, b->d_counts, w.state, b->max_n, b->n_scans, b->d_partials, s,
+        if (w.spec.prm.method == kMethodNdtInc)
+            launch_inc_accum(ctx->inc, ctx->ndt_opts.res_outlier_th, ndt_n_nearby(ctx->ndt_opts.nearby_type), w.src, b->d_counts, w.state, b->max_n, b->n_scans, b->d_partials, s,
                              w.active, w.n_active, w.src_of);
         else
             n_partial_blocks = launch_ndt_accum(ctx->ndt, w.src, b->d_counts, w.state, b->max_n, b->n_scans, b->d_partials, s, w.active, w.n_active, w.split_scans, w.src_of);
@@ -143,10 +143,7 @@ int launch_local_stage(locgpu_ctx* ctx, locgpu_batch* b, const LocalStage& w, hi
 struct IterLauncher {
     locgpu_ctx* ctx;
     locgpu_batch* b;
-    GnParams prm{};
-    int k;
-    float alpha_eff;
-    bool ndt = false;
+    const AlignSpec& spec;
     bool capturing = false;  // inside hipStreamBeginCapture: no event records
     int slot = 0;            // sharded batches: which of the chunk's exchange buffers this iteration uses
     bool replicated_on_comm_stream = false;  // the chunk's read-back must wait for the communication stream as well
@@ -159,6 +156,8 @@ struct IterLauncher {
 
 bool IterLauncher::launch(int do_update) {
     hipStream_t s = b->stream;
+    const GnParams& prm = spec.prm;
+    const bool ndt = spec.ndt();
     StageEvents& ev = b->stage_ev;
     ev.mode = capturing ? 0 : ctx->profile;
     const GridSearchScratch gsc{b->d_grid_qkey, b->d_grid_sorted, b->d_grid_tile_count, b->d_grid_scan_temp};
@@ -166,7 +165,7 @@ bool IterLauncher::launch(int do_update) {
     // and a rank of a scan-sharded batch splits the partial sums as the WHOLE batch would (points per thread follow the batch's size):
     // the order of a scan's additions — hence its bits — must not depend on how many ranks share the batch (found by the eight-rank
     // loopback run of round 6: 32 of 256 scans per rank summed one point per thread where the plain batch sums four)
-    const LocalStage w{batch_src(b), b->d_state + b->first, active, n_active, b->d_src_of, b->sharded ? b->n_total : b->split_scans, prm, k, alpha_eff, ndt,
+    const LocalStage w{batch_src(b), b->d_state + b->first, active, n_active, b->d_src_of, b->sharded ? b->n_total : b->split_scans, spec,
                        ctx->count_visits ? ctx->d_visits : nullptr, b->d_grid_qkey ? &gsc : nullptr, capturing, "search"};
     const int n_partial_blocks = launch_local_stage(ctx, b, w, s);
     if (n_partial_blocks < 0) return false;
@@ -232,8 +231,8 @@ static int batch_ready(locgpu_ctx* ctx, locgpu_batch* b) {
 
 // The grid search hands its leftovers through a second work list. It is allocated here, by every entry point that may run the
 // grid search on `b`, BEFORE any launch: launch() can run under hipStreamBeginCapture, where hipMalloc is not allowed.
-static int ensure_grid_lists(locgpu_ctx* ctx, locgpu_batch* b, float alpha_eff) {
-    if (alpha_eff >= 0.f) return LOCGPU_OK;
+static int ensure_grid_lists(locgpu_ctx* ctx, locgpu_batch* b, const AlignSpec& spec) {
+    if (!spec.grid) return LOCGPU_OK;
     if (!b->d_grid_qkey) {
         LOCGPU_HIP(ctx, hipMalloc((void**)&b->d_grid_qkey, b->pitch * sizeof(uint32_t)));
         LOCGPU_HIP(ctx, hipMalloc((void**)&b->d_grid_sorted, b->pitch * sizeof(uint2)));
@@ -263,14 +262,12 @@ static int ensure_grid_lists(locgpu_ctx* ctx, locgpu_batch* b, float alpha_eff) 
 // Two graphs mirror the eager loop's chunks: graph 0 = {H2D state, kFirstChunk iterations, D2H state} covers the typical alignment
 // with one launch and one host synchronisation; graph 1 = {kNextChunk iterations, D2H state} is replayed while scans are still
 // open (capturing all max_iteration iterations in one graph made every call pay a dozen empty iterations).
-static int capture_chunk(locgpu_ctx* ctx, locgpu_batch* b, const GnParams& prm, int k, float alpha_eff, bool ndt, int iters, bool with_h2d,
-                         hipGraphExec_t* out) {
+static int capture_chunk(locgpu_ctx* ctx, locgpu_batch* b, const AlignSpec& spec, int iters, bool with_h2d, hipGraphExec_t* out) {
     hipStream_t s = b->stream;
     hipGraph_t graph = nullptr;
     LOCGPU_HIP(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     bool ok = !with_h2d || hip_ok(ctx, hipMemcpyAsync(b->d_state, b->h_state, b->n_total * sizeof(PoseState), hipMemcpyHostToDevice, s), "capture H2D");
-    IterLauncher it{ctx, b, prm, k, alpha_eff};
-    it.ndt = ndt;
+    IterLauncher it{ctx, b, spec};
     it.capturing = true;
     for (int i = 0; ok && i < iters; ++i) ok = it.launch(1);
     ok = ok && hip_ok(ctx, hipMemcpyAsync(b->h_state, b->d_state, b->n_total * sizeof(PoseState), hipMemcpyDeviceToHost, s), "capture D2H");
@@ -282,19 +279,16 @@ static int capture_chunk(locgpu_ctx* ctx, locgpu_batch* b, const GnParams& prm, 
     return LOCGPU_OK;
 }
 
-static int ensure_graphs(locgpu_ctx* ctx, locgpu_batch* b, const GnParams& prm, int k, float alpha_eff, bool ndt) {
-    const void* target = !ndt ? (const void*)ctx->d_tree : (prm.method == 4 ? inc_ndt_table_ptr(ctx->inc) : (const void*)ctx->ndt->d_rec);
-    const bool same = b->graph_exec && b->graph_k == k && b->graph_alpha == alpha_eff && b->graph_ndt == ndt && b->graph_target == target &&
-                      b->graph_epoch == ctx->target_epoch &&
-                      b->graph_prm == prm;
-    if (same) return LOCGPU_OK;
-    const int first = std::min(kFirstChunk, prm.max_iteration);
+static int ensure_graphs(locgpu_ctx* ctx, locgpu_batch* b, const AlignSpec& spec) {
+    const void* target = !spec.ndt() ? (const void*)ctx->d_tree : (spec.prm.method == kMethodNdtInc ? inc_ndt_table_ptr(ctx->inc) : (const void*)ctx->ndt->d_rec);
+    if (b->graph_exec && b->graph_spec == spec && b->graph_target == target && b->graph_epoch == ctx->target_epoch) return LOCGPU_OK;
+    const int first = std::min(kFirstChunk, spec.prm.max_iteration);
     if (b->graph_exec) { (void)hipGraphExecDestroy(b->graph_exec); b->graph_exec = nullptr; }
     if (b->graph_exec_next) { (void)hipGraphExecDestroy(b->graph_exec_next); b->graph_exec_next = nullptr; }
-    int rc = capture_chunk(ctx, b, prm, k, alpha_eff, ndt, first, true, &b->graph_exec);
-    if (rc == LOCGPU_OK && prm.max_iteration > first) rc = capture_chunk(ctx, b, prm, k, alpha_eff, ndt, next_chunk(b), false, &b->graph_exec_next);
+    int rc = capture_chunk(ctx, b, spec, first, true, &b->graph_exec);
+    if (rc == LOCGPU_OK && spec.prm.max_iteration > first) rc = capture_chunk(ctx, b, spec, next_chunk(b), false, &b->graph_exec_next);
     if (rc != LOCGPU_OK) return rc;
-    b->graph_prm = prm; b->graph_k = k; b->graph_alpha = alpha_eff; b->graph_ndt = ndt; b->graph_target = target;
+    b->graph_spec = spec; b->graph_target = target;
     b->graph_epoch = ctx->target_epoch;
     return LOCGPU_OK;
 }
@@ -302,17 +296,17 @@ static int ensure_graphs(locgpu_ctx* ctx, locgpu_batch* b, const GnParams& prm, 
 // One chunk of iterations + the read-back of the per-scan states behind it, on the batch's stream.
 static int enqueue_chunk(locgpu_ctx* ctx, locgpu_batch* b, bool first_chunk) {
     locgpu_batch::Pending& P = b->pending;
+    const GnParams& prm = P.spec.prm;
     hipStream_t s = b->stream;
     if (P.graph) {
         // kernels of a finished scan return at once and the solve kernel stops at max_iteration, so a whole chunk is always safe
         LOCGPU_HIP(ctx, hipGraphLaunch(first_chunk ? b->graph_exec : b->graph_exec_next, s));
-        P.launched += first_chunk ? std::min(kFirstChunk, P.prm.max_iteration) : next_chunk(b);
+        P.launched += first_chunk ? std::min(kFirstChunk, prm.max_iteration) : next_chunk(b);
         return LOCGPU_OK;
     }
     if (first_chunk) LOCGPU_HIP(ctx, hipMemcpyAsync(b->d_state, b->h_state, b->n_total * sizeof(PoseState), hipMemcpyHostToDevice, s));
-    IterLauncher it{ctx, b, P.prm, P.k, P.alpha_eff};
-    it.ndt = P.ndt;
-    if (!first_chunk && !P.ndt && b->n_scans > 1) {
+    IterLauncher it{ctx, b, P.spec};
+    if (!first_chunk && !P.spec.ndt() && b->n_scans > 1) {
         // The host has just read every scan's flags (align_finish): launch the search and accumulate kernels of this chunk over the
         // local scans still open only. A 256-scan step's second and third chunk hold ≈60 and ≈5 scans; the rest used to be 1800
         // early-exit workgroups per scan and kernel (≈96 µs per search launch for nothing). Results are the same bits: a scan's
@@ -326,7 +320,7 @@ static int enqueue_chunk(locgpu_ctx* ctx, locgpu_batch* b, bool first_chunk) {
             it.n_active = na;
         }
     }
-    const int todo = std::min(first_chunk ? first_chunk_len(b) : next_chunk(b), P.prm.max_iteration - P.launched);
+    const int todo = std::min(first_chunk ? first_chunk_len(b) : next_chunk(b), prm.max_iteration - P.launched);
     for (int c = 0; c < todo; ++c)
         if (!it.launch(1)) return LOCGPU_ERR_NO_DEVICE;
     P.launched += todo;
@@ -353,8 +347,7 @@ inline int pace_ahead() {
 
 static int paced_launch(locgpu_ctx* ctx, locgpu_batch* b, int upto) {
     locgpu_batch::Pending& P = b->pending;
-    IterLauncher it{ctx, b, P.prm, P.k, P.alpha_eff};
-    it.ndt = P.ndt;
+    IterLauncher it{ctx, b, P.spec};
     const GnPost post{reinterpret_cast<GnPostRecord*>(b->h_post), b->h_post + locgpu_batch::kPostWord, b->post_call};
     it.post = &post;
     while (P.launched < upto) {
@@ -411,13 +404,15 @@ static int paced_wait(locgpu_ctx* ctx, locgpu_batch* b, int seen, unsigned long 
     }
 }
 
-int align_begin(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const GnParams& prm, int k, float alpha_eff, bool ndt, bool blocking) {
+int align_begin(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const AlignSpec& spec, bool blocking) {
+    const GnParams& prm = spec.prm;
+    const bool ndt = spec.ndt();
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
     locgpu_batch::Pending& P = b->pending;
     if (P.active) return fail(ctx, LOCGPU_ERR_INVALID, "align: an alignment of this batch has been begun and not finished");
-    if (!ndt) { const int grc = ensure_grid_lists(ctx, b, alpha_eff); if (grc != LOCGPU_OK) return grc; }
+    if (!ndt) { const int grc = ensure_grid_lists(ctx, b, spec); if (grc != LOCGPU_OK) return grc; }
     { const int urc = batch_ready(ctx, b); if (urc != LOCGPU_OK) return urc; }
-    P.prm = prm; P.k = k; P.alpha_eff = alpha_eff; P.ndt = ndt;
+    P.spec = spec;
     P.graph = ctx->use_graph && !ctx->count_visits && !b->sharded && prm.max_iteration > 0;
     P.launched = 0;
     b->stage_ev.used = 0;
@@ -427,9 +422,9 @@ int align_begin(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, cons
     // its solve kernel left behind (the solve kernel re-zeroes them after every search)
     if (!ndt && !b->counters_clean) LOCGPU_HIP(ctx, hipMemsetAsync(b->d_redo_count, 0, 4 * sizeof(unsigned int), b->stream));
     b->counters_clean = false;  // until this alignment has run to its end
-    if (P.graph) { const int rc = ensure_graphs(ctx, b, prm, k, alpha_eff, ndt); if (rc != LOCGPU_OK) return rc; }
+    if (P.graph) { const int rc = ensure_graphs(ctx, b, spec); if (rc != LOCGPU_OK) return rc; }
     // (a blocking call only: between a begin and its end the host is elsewhere, and a chunk keeps the GPU busy meanwhile)
-    P.paced = blocking && !P.graph && b->n_total == 1 && !b->sharded && !ctx->profile && !ctx->count_visits && prm.max_iteration > 0 && pace_ahead() > 0 && (ndt || alpha_eff >= 0.f);
+    P.paced = blocking && !P.graph && b->n_total == 1 && !b->sharded && !ctx->profile && !ctx->count_visits && prm.max_iteration > 0 && pace_ahead() > 0 && !spec.grid;
     if (P.paced) {
         if (!b->h_post) {
             LOCGPU_HIP(ctx, hipHostMalloc((void**)&b->h_post, 256, hipHostMallocCoherent));
@@ -451,6 +446,7 @@ int align_finish(locgpu_ctx* ctx, locgpu_batch* b, double* out_poses, locgpu_ali
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
     locgpu_batch::Pending& P = b->pending;
     if (!P.active) return fail(ctx, LOCGPU_ERR_INVALID, "align: no alignment of this batch has been begun");
+    const int max_iteration = P.spec.prm.max_iteration;
     P.active = false;
     if (P.paced) {
         int seen = 0;
@@ -459,20 +455,20 @@ int align_finish(locgpu_ctx* ctx, locgpu_batch* b, double* out_poses, locgpu_ali
             int rc = paced_wait(ctx, b, seen, &w);
             if (rc == LOCGPU_OK) {
                 seen = (int)((w & 0xffffffffull) >> 1);
-                if ((w & 1ull) || seen >= P.prm.max_iteration) break;
-                rc = paced_launch(ctx, b, std::min(P.prm.max_iteration, seen + 1 + pace_ahead()));
+                if ((w & 1ull) || seen >= max_iteration) break;
+                rc = paced_launch(ctx, b, std::min(max_iteration, seen + 1 + pace_ahead()));
             }
             if (rc != LOCGPU_OK) { (void)hipStreamSynchronize(b->stream); return rc; }
         }
         b->paced_tail = true;
     }
-    while (!P.paced && P.prm.max_iteration > 0) {
+    while (!P.paced && max_iteration > 0) {
         LOCGPU_HIP(ctx, hipStreamSynchronize(b->stream));
-        b->stage_ev.collect(ctx, P.ndt);
+        b->stage_ev.collect(ctx, P.spec.ndt());
         bool all_done = true;
         for (int i = 0; i < b->n_total; ++i)
             if (!b->h_state[i].done) { all_done = false; break; }
-        if (all_done || P.launched >= P.prm.max_iteration) break;
+        if (all_done || P.launched >= max_iteration) break;
         const int rc = enqueue_chunk(ctx, b, false);
         if (rc != LOCGPU_OK) {
             // whatever of the chunk was enqueued must not run on under the batch's next upload (which relies on an ended alignment
@@ -482,14 +478,13 @@ int align_finish(locgpu_ctx* ctx, locgpu_batch* b, double* out_poses, locgpu_ali
         }
     }
     for (int i = 0; i < b->n_total; ++i) write_scan_result(b->h_state[i], P.init_poses.data() + 7 * (size_t)i, out_poses + 7 * (size_t)i, stats ? stats + i : nullptr);
-    b->counters_clean = !P.ndt && !ctx->count_visits && P.alpha_eff >= 0.f && !b->sharded;  // every search was followed by its solve kernel, which zeroes them (a one-scan front-end saves a fill launch per call)
-    if (b->n_total == 1 && P.prm.max_iteration > 0) b->last_iterations = b->h_state[0].iterations;
+    b->counters_clean = !P.spec.ndt() && !ctx->count_visits && !P.spec.grid && !b->sharded;  // every search was followed by its solve kernel, which zeroes them (a one-scan front-end saves a fill launch per call)
+    if (b->n_total == 1 && max_iteration > 0) b->last_iterations = b->h_state[0].iterations;
     return LOCGPU_OK;
 }
 
-int run_align(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const GnParams& prm, int k, float alpha_eff, bool ndt,
-                     double* out_poses, locgpu_align_stats* stats) {
-    const int rc = align_begin(ctx, b, init_poses, prm, k, alpha_eff, ndt, /*blocking*/ true);
+int run_align(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const AlignSpec& spec, double* out_poses, locgpu_align_stats* stats) {
+    const int rc = align_begin(ctx, b, init_poses, spec, /*blocking*/ true);
     return rc != LOCGPU_OK ? rc : align_finish(ctx, b, out_poses, stats);
 }
 
@@ -583,9 +578,9 @@ int fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, doub
     return LOCGPU_OK;
 }
 
-int eval_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, const GnParams& prm, int k, float alpha_eff, double* hb) {
+int eval_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, const AlignSpec& spec, double* hb) {
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
-    { const int grc = ensure_grid_lists(ctx, b, alpha_eff); if (grc != LOCGPU_OK) return grc; }
+    { const int grc = ensure_grid_lists(ctx, b, spec); if (grc != LOCGPU_OK) return grc; }
     { const int urc = batch_ready(ctx, b); if (urc != LOCGPU_OK) return urc; }
     if (b->pending.active) return fail(ctx, LOCGPU_ERR_INVALID, "icp_hb_batch: an alignment of this batch has been begun and not finished");
     init_states(b, poses);
@@ -593,7 +588,7 @@ int eval_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, const G
     LOCGPU_HIP(ctx, hipMemsetAsync(b->d_redo_count, 0, 4 * sizeof(unsigned int), b->stream));
     LOCGPU_HIP(ctx, hipMemcpyAsync(b->d_state, b->h_state, b->n_total * sizeof(PoseState), hipMemcpyHostToDevice, b->stream));
     b->stage_ev.used = 0;
-    IterLauncher it{ctx, b, prm, k, alpha_eff};
+    IterLauncher it{ctx, b, spec};
     if (!it.launch(0)) return LOCGPU_ERR_NO_DEVICE;
     LOCGPU_HIP(ctx, hipMemcpyAsync(b->h_hb, b->d_hb, (size_t)b->n_total * 44 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     LOCGPU_HIP(ctx, hipStreamSynchronize(b->stream));

@@ -28,10 +28,7 @@ struct LocalStage {
     int n_active;
     const int* src_of;            // SearchArgs::src_of
     int split_scans;              // AccumArgs::split_scans: the batch whose split of the partial sums is reproduced (0: b's own)
-    const GnParams& prm;
-    int k;
-    float alpha_eff;              // < 0: grid search
-    bool ndt;
+    const AlignSpec& spec;
     unsigned long long* visits;   // SearchArgs::visit_totals (instrumented pass), or nullptr
     const GridSearchScratch* grid;  // the grid search's work lists when the batch has them
     bool capturing;               // inside hipStreamBeginCapture: nothing may be allocated
@@ -52,12 +49,11 @@ void write_scan_result(const PoseState& ps, const double* init, double* out_pose
 // An alignment in two halves, so that a caller can have two batches in flight (their streams differ): align_begin enqueues the
 // first chunk of iterations and returns; align_finish waits for it, enqueues further chunks while scans are still open, and
 // writes the results. run_align is begin + finish back to back.
-int align_begin(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const GnParams& prm, int k, float alpha_eff, bool ndt, bool blocking = false);
+int align_begin(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const AlignSpec& spec, bool blocking = false);
 int align_finish(locgpu_ctx* ctx, locgpu_batch* b, double* out_poses, locgpu_align_stats* stats);
-int run_align(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const GnParams& prm, int k, float alpha_eff, bool ndt, double* out_poses,
-              locgpu_align_stats* stats);
+int run_align(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const AlignSpec& spec, double* out_poses, locgpu_align_stats* stats);
 // H, B, effective_num and ok of every scan of `b` at `poses` (one iteration without the update) → hb[n_total][44].
-int eval_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, const GnParams& prm, int k, float alpha_eff, double* hb);
+int eval_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, const AlignSpec& spec, double* hb);
 // Score of every entry of `b` under its pose: k = 1 exact search stage, then the reduction of fitness.hip.
 int fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, double max_range, locgpu_fitness* out);
 // The plane table of LOCGPU_P2PLANE_MAP for the current target (map_planes.hip); no-op when it is there.

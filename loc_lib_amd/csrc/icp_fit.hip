@@ -1,7 +1,6 @@
 // loc_lib_amd/csrc/icp_fit.hip — K2/K3, the fit and solve stage of the ICP hot path: kernels + launchers (see icp_kernels.hpp).
 #include "icp_kernels.hpp"
 #include "launch.hpp"
-#include "../../include/locgpu.h"
 
 #include <cstdlib>
 
@@ -418,7 +417,7 @@ __device__ __forceinline__ void gn_update(const double* tot, PoseState& ps, cons
         hb[42] = (double)eff;
         hb[43] = okv;
     };
-    if (prm.method == 3) {
+    if (prm.method == kMethodNdtDirect) {
         // direct NDT: det(H)==0 is tested FIRST and aborts the whole alignment (ndt cpp:435-436)
         if (det == 0.0) {
             ps.status = 1; ps.done = 1; ps.iterations += 1; ps.last_eff = eff;
@@ -426,7 +425,7 @@ __device__ __forceinline__ void gn_update(const double* tot, PoseState& ps, cons
             return;
         }
         ok = eff >= prm.min_effective_pts;
-    } else if (prm.method == 4) {
+    } else if (prm.method == kMethodNdtInc) {
         // incremental NDT: too few accepted residuals ⇒ `result_pose = pose; return false` (ndt cpp:349-353); no det(H) test
         ok = eff >= prm.min_effective_pts;
         if (!ok) {
@@ -442,7 +441,7 @@ __device__ __forceinline__ void gn_update(const double* tot, PoseState& ps, cons
     if (!do_update) return;
     ps.iterations += 1;
     if (ok) {
-        if (prm.method == 0)
+        if (prm.method == LOCGPU_P2P)
             for (int i = 0; i < 6; ++i) dx[i] = dx[i] / 16;  // dx = H.inverse()/16 * err (icp cpp:287)
         se3_apply_update(ps.q, ps.t, dx);
         quat_to_R(ps.q, ps.R);
@@ -532,7 +531,7 @@ int plane_fit_mode() {
 // there): 4 is as good as 8 and leaves a finer tail; the line and point kernels still pay a 28-value wave reduction per block.
 int icp_accum_split(int method, int max_n, int n_scans) {
     const long total_blocks = (long)((max_n + kBlock - 1) / kBlock) * n_scans;
-    return total_blocks >= 8192 ? (method == 2 ? 4 : 8) : (total_blocks >= 4096 ? 4 : (total_blocks >= 2048 ? 2 : 1));
+    return total_blocks >= 8192 ? (method == LOCGPU_P2PLANE ? 4 : 8) : (total_blocks >= 4096 ? 4 : (total_blocks >= 2048 ? 2 : 1));
 }
 
 int launch_icp_accum(int method, const AccumArgs& a, hipStream_t s) {
@@ -540,14 +539,14 @@ int launch_icp_accum(int method, const AccumArgs& a, hipStream_t s) {
     int pts = icp_accum_split(method, a.max_n, a.n_scans);  // ALL scans of the batch, open or not: the split — hence the order of the sums — must not depend on a.active
     if (a.split_scans > 0) pts = icp_accum_split(method, a.max_n, a.split_scans);
     const dim3 grid((blocks + pts - 1) / pts, a.active ? a.n_active : a.n_scans);
-    if (method == 2) {
+    if (method == LOCGPU_P2PLANE) {
         if (plane_fit_mode() == 1)
             hipLaunchKernelGGL(icp_plane_accum_kernel<1>, grid, dim3(kBlock), 0, s, a.tree, a.src, a.counts, a.st, a.nn, a.nn_pitch, a.max_n, a.gate, a.partials, pts, a.active, a.src_of);
         else
             hipLaunchKernelGGL(icp_plane_accum_kernel<0>, grid, dim3(kBlock), 0, s, a.tree, a.src, a.counts, a.st, a.nn, a.nn_pitch, a.max_n, a.gate, a.partials, pts, a.active, a.src_of);
     } else if (method == LOCGPU_P2PLANE_MAP)
         hipLaunchKernelGGL(icp_mapplane_accum_kernel, grid, dim3(kBlock), 0, s, reinterpret_cast<const double4*>(a.planes), a.src, a.counts, a.st, a.nn, a.max_n, a.gate, a.partials, pts, a.active, a.src_of);
-    else if (method == 1)
+    else if (method == LOCGPU_P2LINE)
         hipLaunchKernelGGL(icp_line_accum_kernel, grid, dim3(kBlock), 0, s, a.tree, a.src, a.counts, a.st, a.nn, a.nn_pitch, a.max_n, a.gate, a.partials, pts, a.active, a.src_of);
     else
         hipLaunchKernelGGL(icp_point_accum_kernel, grid, dim3(kBlock), 0, s, a.tree, a.src, a.counts, a.st, a.nn, a.nn_pitch, a.max_n, a.gate, a.partials, pts, a.active, a.src_of);

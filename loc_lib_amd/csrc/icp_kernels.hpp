@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/locgpu.h"
 #include "device_math.hpp"
 
 namespace locgpu {
@@ -26,7 +27,7 @@ constexpr uint32_t kInvalidSlot = 0xFFFFFFFFu;
 constexpr int kSearchStatSlots = 16 + 2 * 64;  // [0..15] counters, then two 64-bin histograms of the LOCGPU_STAMP diagnostic build
 
 struct GnParams {
-    int method;              // locgpu_icp_method, 3 = direct NDT, 4 = incremental NDT
+    int method;              // locgpu_icp_method, kMethodNdtDirect or kMethodNdtInc
     int max_iteration;
     int min_effective_pts;
     double eps;
@@ -36,6 +37,13 @@ struct GnParams {
                max_nn_distance == o.max_nn_distance && max_plane_distance == o.max_plane_distance && max_line_distance == o.max_line_distance;
     }
 };
+// The NDT variants of the Gauss–Newton solve take the two values locgpu_icp_method leaves free.
+constexpr int kMethodNdtDirect = 3, kMethodNdtInc = 4;
+constexpr bool method_is_ndt(int method) { return method == kMethodNdtDirect || method == kMethodNdtInc; }
+static_assert(!method_is_ndt(LOCGPU_P2P) && !method_is_ndt(LOCGPU_P2LINE) && !method_is_ndt(LOCGPU_P2PLANE) && !method_is_ndt(LOCGPU_P2PLANE_MAP),
+              "an NDT method value collides with a locgpu_icp_method");
+// Neighbours per query the method's fit reads: the nearest point (or its plane), the five a line or plane is fitted to; NDT has no search.
+constexpr int method_k(int method) { return method_is_ndt(method) ? 0 : ((method == LOCGPU_P2P || method == LOCGPU_P2PLANE_MAP) ? 1 : 5); }
 
 __device__ __forceinline__ float as_f32(uint32_t u) { return __uint_as_float(u); }
 

@@ -104,8 +104,8 @@ void locgpu_ndt_opts_default(locgpu_ndt_opts* o) {
     o->min_pts_in_voxel = 3;
     o->eps = 1e-2;
     o->res_outlier_th = 20.0;
-    o->nearby_type = 1;
-    o->method = 1;
+    o->nearby_type = kNearby6;
+    o->method = kNdtOptDirect;
     o->capacity = 100000;
 }
 
@@ -387,14 +387,16 @@ void locgpu_batch_destroy(locgpu_batch* b) {
 
 namespace locgpu {
 
-// Scan pools and sharded batches do not take the map-plane method (locgpu.h).
-static int refuse_map_planes_sharded(locgpu_ctx* ctx, const locgpu_batch* b, const GnParams& prm) {
-    if (b && b->sharded && prm.method == LOCGPU_P2PLANE_MAP)
+// The batch argument of entry point `who` (args_ok: its other pointers are there). Scan pools and sharded batches do not take the
+// map-plane method (locgpu.h).
+static int check_batch(locgpu_ctx* ctx, const locgpu_batch* b, bool args_ok, const AlignSpec& spec, const char* who) {
+    if (!b || b->ctx != ctx || !args_ok) return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": bad arguments");
+    if (b->sharded && spec.prm.method == LOCGPU_P2PLANE_MAP)
         return fail(ctx, LOCGPU_ERR_INVALID, "icp: LOCGPU_P2PLANE_MAP is not available on a sharded batch");
     return LOCGPU_OK;
 }
 
-int check_icp(locgpu_ctx* ctx, const locgpu_icp_opts* o, GnParams& prm, int& k, float& alpha_eff) {
+int check_icp(locgpu_ctx* ctx, const locgpu_icp_opts* o, AlignSpec& spec) {
     if (!ctx) return LOCGPU_ERR_INVALID;
     if (!o) return fail(ctx, LOCGPU_ERR_INVALID, "icp: opts is NULL");
     { const int jrc = target_join(ctx); if (jrc != LOCGPU_OK) return jrc; }  // an asynchronous SetInputTarget ends here at the latest
@@ -406,6 +408,7 @@ int check_icp(locgpu_ctx* ctx, const locgpu_icp_opts* o, GnParams& prm, int& k, 
         const int rc = ensure_grid(ctx);
         if (rc != LOCGPU_OK) return rc;
     }
+    GnParams& prm = spec.prm;
     prm.method = o->method;
     prm.max_iteration = o->max_iteration;
     prm.min_effective_pts = o->min_effective_pts;
@@ -417,9 +420,8 @@ int check_icp(locgpu_ctx* ctx, const locgpu_icp_opts* o, GnParams& prm, int& k, 
         const int rc = ensure_map_planes(ctx);
         if (rc != LOCGPU_OK) return rc;
     }
-    k = (o->method == LOCGPU_P2P || o->method == LOCGPU_P2PLANE_MAP) ? 1 : 5;
-    alpha_eff = o->approximate ? o->ann_alpha : 1.0f;
-    if (o->search_mode == LOCGPU_SEARCH_GRID_EXACT) alpha_eff = -1.0f;  // marker: grid search (exact by construction; `approximate` is ignored)
+    spec.grid = o->search_mode == LOCGPU_SEARCH_GRID_EXACT;  // exact by construction: `approximate` and ann_alpha are ignored
+    spec.alpha = (o->approximate && !spec.grid) ? o->ann_alpha : 1.0f;
     // k > size_: GetClosestPoint logs an error and returns nothing (kdtree.cpp:149-153) ⇒ no correspondences at all.
     // The search kernel reproduces that by never filling the k-th slot; nothing to reject here.
     return LOCGPU_OK;
@@ -476,31 +478,40 @@ static int single_batch_dev(locgpu_ctx* ctx, const float4* d_src, size_t n, locg
     return LOCGPU_OK;
 }
 
+// The single-scan alignment of entry point `who`: the scan is `cloud`, resident in HBM, or else n points on the host at `src`.
+static int align_single(locgpu_ctx* ctx, const AlignSpec& spec, const char* who, bool args_ok, const void* src, size_t n, size_t stride_bytes,
+                        const locgpu_cloud* cloud, const double init_pose[7], double out_pose[7], locgpu_align_stats* stats) {
+    if (!args_ok) return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": bad arguments");
+    locgpu_batch* b = nullptr;
+    int rc;
+    if (cloud) {
+        const hipError_t ce = cloud_input_ready(ctx, cloud);
+        if (ce == hipErrorInvalidDevice) return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": the cloud belongs to a context on another GPU");
+        if (!hip_ok(ctx, ce, (std::string(who) + ": ordering behind the cloud's context").c_str())) return LOCGPU_ERR_NO_DEVICE;
+        rc = single_batch_dev(ctx, cloud->d, cloud->n, &b);
+    } else {
+        rc = single_batch(ctx, src, n, stride_bytes, &b);
+    }
+    return rc != LOCGPU_OK ? rc : run_align(ctx, b, init_pose, spec, out_pose, stats);
+}
+
 }  // namespace locgpu
 
 extern "C" {
 
 int locgpu_icp_align_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const locgpu_icp_opts* opts, double* out_poses,
                            locgpu_align_stats* stats) {
-    GnParams prm{};
-    int k;
-    float alpha_eff;
-    const int rc = check_icp(ctx, opts, prm, k, alpha_eff);
-    if (rc != LOCGPU_OK) return rc;
-    if (!b || b->ctx != ctx || !init_poses || !out_poses) return fail(ctx, LOCGPU_ERR_INVALID, "icp_align_batch: bad arguments");
-    { const int src = refuse_map_planes_sharded(ctx, b, prm); if (src != LOCGPU_OK) return src; }
-    return run_align(ctx, b, init_poses, prm, k, alpha_eff, false, out_poses, stats);
+    AlignSpec spec;
+    int rc = check_icp(ctx, opts, spec);
+    if (rc == LOCGPU_OK) rc = check_batch(ctx, b, init_poses && out_poses, spec, "icp_align_batch");
+    return rc != LOCGPU_OK ? rc : run_align(ctx, b, init_poses, spec, out_poses, stats);
 }
 
 int locgpu_icp_align_batch_begin(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const locgpu_icp_opts* opts) {
-    GnParams prm{};
-    int k;
-    float alpha_eff;
-    const int rc = check_icp(ctx, opts, prm, k, alpha_eff);
-    if (rc != LOCGPU_OK) return rc;
-    if (!b || b->ctx != ctx || !init_poses) return fail(ctx, LOCGPU_ERR_INVALID, "icp_align_batch_begin: bad arguments");
-    { const int src = refuse_map_planes_sharded(ctx, b, prm); if (src != LOCGPU_OK) return src; }
-    return align_begin(ctx, b, init_poses, prm, k, alpha_eff, false);
+    AlignSpec spec;
+    int rc = check_icp(ctx, opts, spec);
+    if (rc == LOCGPU_OK) rc = check_batch(ctx, b, init_poses != nullptr, spec, "icp_align_batch_begin");
+    return rc != LOCGPU_OK ? rc : align_begin(ctx, b, init_poses, spec);
 }
 
 int locgpu_align_batch_end(locgpu_ctx* ctx, locgpu_batch* b, double* out_poses, locgpu_align_stats* stats) {
@@ -511,27 +522,16 @@ int locgpu_align_batch_end(locgpu_ctx* ctx, locgpu_batch* b, double* out_poses, 
 
 int locgpu_icp_align(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double init_pose[7], const locgpu_icp_opts* opts,
                      double out_pose[7], locgpu_align_stats* stats) {
-    GnParams prm{};
-    int k;
-    float alpha_eff;
-    int rc = check_icp(ctx, opts, prm, k, alpha_eff);
-    if (rc != LOCGPU_OK) return rc;
-    if (!src || !init_pose || !out_pose) return fail(ctx, LOCGPU_ERR_INVALID, "icp_align: bad arguments");
-    locgpu_batch* b = nullptr;
-    rc = single_batch(ctx, src, n, stride_bytes, &b);
-    if (rc != LOCGPU_OK) return rc;
-    return run_align(ctx, b, init_pose, prm, k, alpha_eff, false, out_pose, stats);
+    AlignSpec spec;
+    const int rc = check_icp(ctx, opts, spec);
+    return rc != LOCGPU_OK ? rc : align_single(ctx, spec, "icp_align", src && init_pose && out_pose, src, n, stride_bytes, nullptr, init_pose, out_pose, stats);
 }
 
 int locgpu_icp_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, const locgpu_icp_opts* opts, double* hb) {
-    GnParams prm{};
-    int k;
-    float alpha_eff;
-    const int rc = check_icp(ctx, opts, prm, k, alpha_eff);
-    if (rc != LOCGPU_OK) return rc;
-    if (!b || b->ctx != ctx || !poses || !hb) return fail(ctx, LOCGPU_ERR_INVALID, "icp_hb_batch: bad arguments");
-    { const int src = refuse_map_planes_sharded(ctx, b, prm); if (src != LOCGPU_OK) return src; }
-    return eval_hb_batch(ctx, b, poses, prm, k, alpha_eff, hb);
+    AlignSpec spec;
+    int rc = check_icp(ctx, opts, spec);
+    if (rc == LOCGPU_OK) rc = check_batch(ctx, b, poses && hb, spec, "icp_hb_batch");
+    return rc != LOCGPU_OK ? rc : eval_hb_batch(ctx, b, poses, spec, hb);
 }
 
 int locgpu_debug_batch_nn(locgpu_ctx* ctx, locgpu_batch* b, int k, int32_t* out) {
@@ -553,17 +553,15 @@ int locgpu_debug_batch_nn(locgpu_ctx* ctx, locgpu_batch* b, int k, int32_t* out)
 
 int locgpu_icp_hb(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double pose[7], const locgpu_icp_opts* opts, double H[36],
                   double B[6], int64_t* effective_num, int* ok) {
-    GnParams prm{};
-    int k;
-    float alpha_eff;
-    int rc = check_icp(ctx, opts, prm, k, alpha_eff);
+    AlignSpec spec;
+    int rc = check_icp(ctx, opts, spec);
     if (rc != LOCGPU_OK) return rc;
     if (!src || !pose || !H || !B) return fail(ctx, LOCGPU_ERR_INVALID, "icp_hb: bad arguments");
     locgpu_batch* b = nullptr;
     rc = single_batch(ctx, src, n, stride_bytes, &b);
     if (rc != LOCGPU_OK) return rc;
     double hb[44];
-    rc = locgpu_icp_hb_batch(ctx, b, pose, opts, hb);
+    rc = eval_hb_batch(ctx, b, pose, spec, hb);
     if (rc != LOCGPU_OK) return rc;
     std::memcpy(H, hb, 36 * sizeof(double));
     std::memcpy(B, hb + 36, 6 * sizeof(double));
@@ -711,42 +709,37 @@ static int scan_match_output(locgpu_ctx* ctx, locgpu_batch* b, size_t n, int rc,
     return write_output_cloud(ctx, b, b->d_src, n, pose, *dst, out_stride & ~LOCGPU_OUT_FIELDS_DONE);
 }
 
-int locgpu_icp_scan_match(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double init_pose[7], const locgpu_icp_opts* opts,
-                          double out_pose[7], locgpu_align_stats* stats, void* out_cloud, size_t out_stride_bytes, locgpu_out_cloud_fn out_fn, void* out_user) {
-    GnParams prm{};
-    int k;
-    float alpha_eff;
-    int rc = check_icp(ctx, opts, prm, k, alpha_eff);
-    if (rc != LOCGPU_OK) return rc;
-    if (!src || !init_pose || !out_pose || ((out_cloud || out_fn) && (out_stride_bytes & ~LOCGPU_OUT_FIELDS_DONE) < 12)) return fail(ctx, LOCGPU_ERR_INVALID, "icp_scan_match: bad arguments");
+// ScanMatch of either matcher: align the scan, then transform it by the result into the caller's output cloud.
+static int scan_match(locgpu_ctx* ctx, const AlignSpec& spec, const char* who, const void* src, size_t n, size_t stride_bytes, const double init_pose[7],
+                      double result_pose[7], locgpu_align_stats* stats, void* out_cloud, size_t out_stride_bytes, locgpu_out_cloud_fn out_fn, void* out_user) {
+    if (!src || !init_pose || !result_pose || ((out_cloud || out_fn) && (out_stride_bytes & ~LOCGPU_OUT_FIELDS_DONE) < 12)) return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": bad arguments");
     locgpu_batch* b = nullptr;
-    rc = single_batch(ctx, src, n, stride_bytes, &b);
-    if (rc != LOCGPU_OK) return rc;
-    void* dst = nullptr;
-    scan_match_fields(ctx, src, n, stride_bytes, out_cloud, out_stride_bytes, out_fn, out_user, &dst);
-    rc = run_align(ctx, b, init_pose, prm, k, alpha_eff, false, out_pose, stats);
-    return scan_match_output(ctx, b, n, rc, out_pose, &dst, out_stride_bytes);
-}
-
-int locgpu_ndt_scan_match(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double init_pose[7], double result_pose[7],
-                          locgpu_align_stats* stats, void* out_cloud, size_t out_stride_bytes, locgpu_out_cloud_fn out_fn, void* out_user) {
-    GnParams prm{};
-    int rc = check_ndt(ctx, prm);
-    if (rc != LOCGPU_OK) return rc;
-    if (!src || !init_pose || !result_pose || ((out_cloud || out_fn) && (out_stride_bytes & ~LOCGPU_OUT_FIELDS_DONE) < 12)) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_scan_match: bad arguments");
-    locgpu_batch* b = nullptr;
-    rc = single_batch(ctx, src, n, stride_bytes, &b);
+    int rc = single_batch(ctx, src, n, stride_bytes, &b);
     if (rc != LOCGPU_OK) return rc;
     void* dst = nullptr;
     scan_match_fields(ctx, src, n, stride_bytes, out_cloud, out_stride_bytes, out_fn, out_user, &dst);
     double pose[7];
     locgpu_align_stats st{};
-    rc = run_align(ctx, b, init_pose, prm, 0, 1.0f, true, pose, &st);
-    if (stats) *stats = st;
-    // det(H) == 0 (status 1): AlignNdt returns before it assigns result_pose (ndt_registration.cpp:435-436) — the caller's value stays,
+    rc = run_align(ctx, b, init_pose, spec, pose, &st);
+    if (stats && (rc == LOCGPU_OK || spec.ndt())) *stats = st;  // a failed call: ICP leaves *stats alone, NDT zeroes it
+    // NDT, det(H) == 0 (status 1): AlignNdt returns before it assigns result_pose (ndt_registration.cpp:435-436) — the caller's value stays,
     // and the output cloud is transformed by THAT pose (:258)
-    if (rc == LOCGPU_OK && st.status != 1) std::memcpy(result_pose, pose, sizeof(pose));
+    if (rc == LOCGPU_OK && !(spec.ndt() && st.status == 1)) std::memcpy(result_pose, pose, sizeof(pose));
     return scan_match_output(ctx, b, n, rc, result_pose, &dst, out_stride_bytes);
+}
+
+int locgpu_icp_scan_match(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double init_pose[7], const locgpu_icp_opts* opts,
+                          double out_pose[7], locgpu_align_stats* stats, void* out_cloud, size_t out_stride_bytes, locgpu_out_cloud_fn out_fn, void* out_user) {
+    AlignSpec spec;
+    const int rc = check_icp(ctx, opts, spec);
+    return rc != LOCGPU_OK ? rc : scan_match(ctx, spec, "icp_scan_match", src, n, stride_bytes, init_pose, out_pose, stats, out_cloud, out_stride_bytes, out_fn, out_user);
+}
+
+int locgpu_ndt_scan_match(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double init_pose[7], double result_pose[7],
+                          locgpu_align_stats* stats, void* out_cloud, size_t out_stride_bytes, locgpu_out_cloud_fn out_fn, void* out_user) {
+    AlignSpec spec;
+    const int rc = check_ndt(ctx, spec);
+    return rc != LOCGPU_OK ? rc : scan_match(ctx, spec, "ndt_scan_match", src, n, stride_bytes, init_pose, result_pose, stats, out_cloud, out_stride_bytes, out_fn, out_user);
 }
 
 int locgpu_transform_cloud(locgpu_ctx* ctx, const double pose[7], const void* src, size_t n, size_t src_stride_bytes, void* out,
@@ -911,10 +904,8 @@ void locgpu_init_search_opts_default(locgpu_init_search_opts* o) {
 
 int locgpu_icp_init_search(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double* candidates, int m, const locgpu_icp_opts* opts,
                            const locgpu_init_search_opts* sopts, double* out_poses, locgpu_fitness* out_fit, locgpu_align_stats* stats, int* best) {
-    GnParams prm{};
-    int k;
-    float alpha_eff;
-    int rc = check_icp(ctx, opts, prm, k, alpha_eff);
+    AlignSpec spec;
+    int rc = check_icp(ctx, opts, spec);
     if (rc != LOCGPU_OK) return rc;
     locgpu_init_search_opts so;
     if (sopts) so = *sopts; else locgpu_init_search_opts_default(&so);
@@ -931,7 +922,7 @@ int locgpu_icp_init_search(locgpu_ctx* ctx, const void* src, size_t n, size_t st
         const int cnt = std::min(chunk, m - off);
         // every chunk sums as the plain batch of all m candidates would: chunking never shows in a pose
         rc = reshape_shared(ctx, b, cnt, n, m);
-        if (rc == LOCGPU_OK) rc = run_align(ctx, b, candidates + 7 * (size_t)off, prm, k, alpha_eff, false, out_poses + 7 * (size_t)off, stats ? stats + off : nullptr);
+        if (rc == LOCGPU_OK) rc = run_align(ctx, b, candidates + 7 * (size_t)off, spec, out_poses + 7 * (size_t)off, stats ? stats + off : nullptr);
         if (rc == LOCGPU_OK) rc = fitness_on_batch(ctx, b, out_poses + 7 * (size_t)off, so.max_range, out_fit + off);
     }
     if (rc != LOCGPU_OK) return rc;
@@ -1082,11 +1073,13 @@ void ndt_free(locgpu_ctx* ctx) {
     if (ctx->ndt) { ndt_table_free(*ctx->ndt); delete ctx->ndt; ctx->ndt = nullptr; }
     if (ctx->inc) { inc_ndt_destroy(ctx->inc); ctx->inc = nullptr; }
 }
-int check_ndt(locgpu_ctx* ctx, GnParams& prm) {
+int check_ndt(locgpu_ctx* ctx, AlignSpec& spec) {
     if (!ctx) return LOCGPU_ERR_INVALID;
-    const bool inc = ctx->ndt_opts.method == 2;
+    const bool inc = ctx->ndt_opts.method == kNdtOptIncremental;
     if ((inc && !ctx->inc) || (!inc && !ctx->ndt)) return fail(ctx, LOCGPU_ERR_NO_TARGET, "ndt: SetInputTarget has not been called");
-    prm.method = inc ? 4 : 3;
+    spec = AlignSpec{};
+    GnParams& prm = spec.prm;
+    prm.method = inc ? kMethodNdtInc : kMethodNdtDirect;
     prm.max_iteration = ctx->ndt_opts.max_iteration;
     prm.min_effective_pts = ctx->ndt_opts.min_effective_pts;
     prm.eps = ctx->ndt_opts.eps;
@@ -1102,11 +1095,12 @@ extern "C" {
 static int ndt_set_target_dev(locgpu_ctx* ctx, const float4* d_pts, const float4* host, size_t n, const locgpu_ndt_opts* opts) {
     locgpu_ndt_opts o;
     if (opts) o = *opts; else locgpu_ndt_opts_default(&o);
-    if (!(o.voxel_size > 0.0) || (o.nearby_type != 0 && o.nearby_type != 1) || (o.method != 1 && o.method != 2) || (o.method == 2 && o.capacity < 2))
+    if (!(o.voxel_size > 0.0) || (o.nearby_type != kNearbyCenter && o.nearby_type != kNearby6) || (o.method != kNdtOptDirect && o.method != kNdtOptIncremental) ||
+        (o.method == kNdtOptIncremental && o.capacity < 2))
         return fail(ctx, LOCGPU_ERR_INVALID, "ndt_set_target: bad options");
-    if (o.method == 2) {
+    if (o.method == kNdtOptIncremental) {
         // incremental: keep the voxel set unless the grid itself changed
-        if (ctx->inc && (ctx->ndt_opts.method != 2 || ctx->ndt_opts.voxel_size != o.voxel_size || ctx->ndt_opts.capacity != o.capacity)) {
+        if (ctx->inc && (ctx->ndt_opts.method != kNdtOptIncremental || ctx->ndt_opts.voxel_size != o.voxel_size || ctx->ndt_opts.capacity != o.capacity)) {
             inc_ndt_destroy(ctx->inc);
             ctx->inc = nullptr;
         }
@@ -1134,7 +1128,7 @@ static int ndt_set_target_dev(locgpu_ctx* ctx, const float4* d_pts, const float4
     if (e != hipSuccess) { ndt_free(ctx); hip_ok(ctx, e, "ndt_build"); return LOCGPU_ERR_NO_DEVICE; }
     if (bad_key) { ndt_free(ctx); return fail(ctx, LOCGPU_ERR_INVALID, "ndt_set_target: a point lies outside the +-2^20-voxel key range"); }
     ctx->ndt->res_outlier_th = o.res_outlier_th;
-    ctx->ndt->n_nearby = o.nearby_type == 0 ? 1 : 7;
+    ctx->ndt->n_nearby = ndt_n_nearby(o.nearby_type);
     ctx->ndt_opts = o;
     ctx->target_epoch++;
     return LOCGPU_OK;
@@ -1158,7 +1152,7 @@ int locgpu_ndt_set_target(locgpu_ctx* ctx, const void* pts, size_t n, size_t str
 
 int locgpu_ndt_target_info(const locgpu_ctx* ctx, int64_t out[3]) {
     if (!ctx || !out) return LOCGPU_ERR_INVALID;
-    if (ctx->ndt_opts.method == 2 && ctx->inc) { out[0] = (int64_t)inc_ndt_num_voxels(ctx->inc); out[1] = ctx->ndt_opts.capacity; out[2] = 0; return LOCGPU_OK; }
+    if (ctx->ndt_opts.method == kNdtOptIncremental && ctx->inc) { out[0] = (int64_t)inc_ndt_num_voxels(ctx->inc); out[1] = ctx->ndt_opts.capacity; out[2] = 0; return LOCGPU_OK; }
     if (!ctx->ndt) { out[0] = out[1] = out[2] = 0; return LOCGPU_ERR_NO_TARGET; }
     out[0] = (int64_t)ctx->ndt->n_vox;
     out[1] = (int64_t)ctx->ndt->cap;
@@ -1168,7 +1162,7 @@ int locgpu_ndt_target_info(const locgpu_ctx* ctx, int64_t out[3]) {
 
 int locgpu_ndt_dump(locgpu_ctx* ctx, int32_t* keys, double* mu, double* info, size_t cap, size_t* n_out) {
     if (!ctx || !n_out) return LOCGPU_ERR_INVALID;
-    if (ctx->ndt_opts.method == 2 && ctx->inc) {
+    if (ctx->ndt_opts.method == kNdtOptIncremental && ctx->inc) {
         LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
         LOCGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
         *n_out = inc_ndt_dump(ctx->inc, keys, mu, info, cap);
@@ -1184,31 +1178,24 @@ int locgpu_ndt_dump(locgpu_ctx* ctx, int32_t* keys, double* mu, double* info, si
 }
 
 int locgpu_ndt_align_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, double* out_poses, locgpu_align_stats* stats) {
-    GnParams prm{};
-    const int rc = check_ndt(ctx, prm);
-    if (rc != LOCGPU_OK) return rc;
-    if (!b || b->ctx != ctx || !init_poses || !out_poses) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_align_batch: bad arguments");
-    return run_align(ctx, b, init_poses, prm, 0, 1.0f, true, out_poses, stats);
+    AlignSpec spec;
+    int rc = check_ndt(ctx, spec);
+    if (rc == LOCGPU_OK) rc = check_batch(ctx, b, init_poses && out_poses, spec, "ndt_align_batch");
+    return rc != LOCGPU_OK ? rc : run_align(ctx, b, init_poses, spec, out_poses, stats);
 }
 
 int locgpu_ndt_align_batch_begin(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses) {
-    GnParams prm{};
-    const int rc = check_ndt(ctx, prm);
-    if (rc != LOCGPU_OK) return rc;
-    if (!b || b->ctx != ctx || !init_poses) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_align_batch_begin: bad arguments");
-    return align_begin(ctx, b, init_poses, prm, 0, 1.0f, true);
+    AlignSpec spec;
+    int rc = check_ndt(ctx, spec);
+    if (rc == LOCGPU_OK) rc = check_batch(ctx, b, init_poses != nullptr, spec, "ndt_align_batch_begin");
+    return rc != LOCGPU_OK ? rc : align_begin(ctx, b, init_poses, spec);
 }
 
 int locgpu_ndt_align(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double init_pose[7], double out_pose[7],
                      locgpu_align_stats* stats) {
-    GnParams prm{};
-    int rc = check_ndt(ctx, prm);
-    if (rc != LOCGPU_OK) return rc;
-    if (!src || !init_pose || !out_pose) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_align: bad arguments");
-    locgpu_batch* b = nullptr;
-    rc = single_batch(ctx, src, n, stride_bytes, &b);
-    if (rc != LOCGPU_OK) return rc;
-    return run_align(ctx, b, init_pose, prm, 0, 1.0f, true, out_pose, stats);
+    AlignSpec spec;
+    const int rc = check_ndt(ctx, spec);
+    return rc != LOCGPU_OK ? rc : align_single(ctx, spec, "ndt_align", src && init_pose && out_pose, src, n, stride_bytes, nullptr, init_pose, out_pose, stats);
 }
 
 // ---- matcher entry points on clouds resident in HBM (cloud_filters.hpp) ----
@@ -1224,29 +1211,15 @@ int locgpu_ndt_set_target_cloud(locgpu_ctx* ctx, const locgpu_cloud* target, con
 
 int locgpu_icp_align_cloud(locgpu_ctx* ctx, const locgpu_cloud* src, const double init_pose[7], const locgpu_icp_opts* opts, double out_pose[7],
                            locgpu_align_stats* stats) {
-    GnParams prm{};
-    int k;
-    float alpha_eff;
-    int rc = check_icp(ctx, opts, prm, k, alpha_eff);
-    if (rc != LOCGPU_OK) return rc;
-    if (!src || !src->ctx || !init_pose || !out_pose) return fail(ctx, LOCGPU_ERR_INVALID, "icp_align_cloud: bad arguments");
-    { const hipError_t ce = cloud_input_ready(ctx, src); if (ce == hipErrorInvalidDevice) return fail(ctx, LOCGPU_ERR_INVALID, "icp_align_cloud: the cloud belongs to a context on another GPU"); if (!hip_ok(ctx, ce, "icp_align_cloud: ordering behind the cloud's context")) return LOCGPU_ERR_NO_DEVICE; }
-    locgpu_batch* b = nullptr;
-    rc = single_batch_dev(ctx, src->d, src->n, &b);
-    if (rc != LOCGPU_OK) return rc;
-    return run_align(ctx, b, init_pose, prm, k, alpha_eff, false, out_pose, stats);
+    AlignSpec spec;
+    const int rc = check_icp(ctx, opts, spec);
+    return rc != LOCGPU_OK ? rc : align_single(ctx, spec, "icp_align_cloud", src && src->ctx && init_pose && out_pose, nullptr, 0, 0, src, init_pose, out_pose, stats);
 }
 
 int locgpu_ndt_align_cloud(locgpu_ctx* ctx, const locgpu_cloud* src, const double init_pose[7], double out_pose[7], locgpu_align_stats* stats) {
-    GnParams prm{};
-    int rc = check_ndt(ctx, prm);
-    if (rc != LOCGPU_OK) return rc;
-    if (!src || !src->ctx || !init_pose || !out_pose) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_align_cloud: bad arguments");
-    { const hipError_t ce = cloud_input_ready(ctx, src); if (ce == hipErrorInvalidDevice) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_align_cloud: the cloud belongs to a context on another GPU"); if (!hip_ok(ctx, ce, "ndt_align_cloud: ordering behind the cloud's context")) return LOCGPU_ERR_NO_DEVICE; }
-    locgpu_batch* b = nullptr;
-    rc = single_batch_dev(ctx, src->d, src->n, &b);
-    if (rc != LOCGPU_OK) return rc;
-    return run_align(ctx, b, init_pose, prm, 0, 1.0f, true, out_pose, stats);
+    AlignSpec spec;
+    const int rc = check_ndt(ctx, spec);
+    return rc != LOCGPU_OK ? rc : align_single(ctx, spec, "ndt_align_cloud", src && src->ctx && init_pose && out_pose, nullptr, 0, 0, src, init_pose, out_pose, stats);
 }
 
 }  // extern "C"

@@ -71,10 +71,7 @@ struct locgpu_pool {
     locgpu_ctx* ctx = nullptr;
     locgpu_batch* b = nullptr;  // storage: a batch of `slots` scans
     int slots = 0, chunk = 4, split_scans = 0;
-    bool ndt = false;
-    GnParams prm{};
-    int k = 0;
-    float alpha_eff = 0.f;
+    AlignSpec spec;           // what every scan of the pool is aligned by
     locgpu_icp_opts icp{};
     bool with_comm = false;   // the context has a communicator: exchange step every iteration
     bool multi_rank = false;  // ... of more than one rank: nothing may depend on this rank's timing
@@ -136,7 +133,7 @@ void pool_collect(locgpu_pool* P) {
         if (hipEventElapsedTime(&ms, P->ev_t0, P->ev_t1) == hipSuccess) { P->chunk_ms += ms; P->chunks++; }
         P->timed = false;
     }
-    b->stage_ev.collect(P->ctx, P->ndt);  // per-stage times go where a batch alignment's go (locgpu_profile_read)
+    b->stage_ev.collect(P->ctx, P->spec.ndt());  // per-stage times go where a batch alignment's go (locgpu_profile_read)
     P->in_flight = false;
 }
 
@@ -147,17 +144,18 @@ bool pool_launch_iteration(locgpu_pool* P) {
     hipStream_t s = b->stream;
     const int* mine = P->d_list;
     const int* theirs = P->d_list + P->slots;
+    const GnParams& prm = P->spec.prm;
     StageEvents& ev = b->stage_ev;  // profile mode 1 only: four marks per iteration — search | fit + accumulate | solve (+ exchange)
     ev.mode = ctx->profile == 1 ? 1 : 0;
     // the slots index the arena through d_src_of, and the sums split as a plain batch of scans_per_job scans would
-    const LocalStage w{P->d_arena, b->d_state, mine, P->n_mine, P->d_src_of, P->split_scans, P->prm, P->k, P->alpha_eff, P->ndt, nullptr, nullptr, false, "pool"};
+    const LocalStage w{P->d_arena, b->d_state, mine, P->n_mine, P->d_src_of, P->split_scans, P->spec, nullptr, nullptr, false, "pool"};
     const int n_partial_blocks = launch_local_stage(ctx, b, w, s);
     if (n_partial_blocks < 0) return false;
     // The exchange-and-solve tail. Against a sharded batch's (gn_driver.hip): two slot lists instead of contiguous ranges, no
     // LOCGPU_COMM_DIRECT, a ring of kAccRing exchange buffers.
-    unsigned int* list_counts = P->ndt ? nullptr : b->d_redo_count;
+    unsigned int* list_counts = P->spec.ndt() ? nullptr : b->d_redo_count;
     if (!P->with_comm) {
-        launch_gn_solve(b->d_partials, n_partial_blocks, b->d_state, P->n_mine, P->prm, 1, nullptr, list_counts, s, mine);
+        launch_gn_solve(b->d_partials, n_partial_blocks, b->d_state, P->n_mine, prm, 1, nullptr, list_counts, s, mine);
         ev.mark(s);
         return hip_ok(ctx, hipGetLastError(), "pool: kernel launch");
     }
@@ -170,15 +168,15 @@ bool pool_launch_iteration(locgpu_pool* P) {
         // A slot's sums are complete on the rank that holds it: the owner solves at once and goes on to the next search, the
         // all-reduce and the replicas' solve follow on the communication stream (gn_driver.hip, sharded batches).
         hipStream_t cs = ctx->comm_stream;
-        if (P->n_mine > 0) launch_gn_solve(acc, 1, b->d_state, P->n_mine, P->prm, 1, nullptr, list_counts, s, mine);
+        if (P->n_mine > 0) launch_gn_solve(acc, 1, b->d_state, P->n_mine, prm, 1, nullptr, list_counts, s, mine);
         if (!hip_ok(ctx, hipEventRecord(P->ev_ready, s), "pool: hipEventRecord") || !hip_ok(ctx, hipStreamWaitEvent(cs, P->ev_ready, 0), "pool: hipStreamWaitEvent")) return false;
         if (!comm_all_reduce_f64(ctx, acc, (size_t)P->slots * kAccW, cs)) return false;
-        if (P->n_theirs > 0) launch_gn_solve(acc, 1, b->d_state, P->n_theirs, P->prm, 1, nullptr, nullptr, cs, theirs);
+        if (P->n_theirs > 0) launch_gn_solve(acc, 1, b->d_state, P->n_theirs, prm, 1, nullptr, nullptr, cs, theirs);
     } else {
         // everything on the pool's stream: sums → all-reduce → every rank solves every open slot
         if (!comm_all_reduce_f64(ctx, acc, (size_t)P->slots * kAccW, s)) return false;
-        if (P->n_mine > 0) launch_gn_solve(acc, 1, b->d_state, P->n_mine, P->prm, 1, nullptr, list_counts, s, mine);
-        if (P->n_theirs > 0) launch_gn_solve(acc, 1, b->d_state, P->n_theirs, P->prm, 1, nullptr, nullptr, s, theirs);
+        if (P->n_mine > 0) launch_gn_solve(acc, 1, b->d_state, P->n_mine, prm, 1, nullptr, list_counts, s, mine);
+        if (P->n_theirs > 0) launch_gn_solve(acc, 1, b->d_state, P->n_theirs, prm, 1, nullptr, nullptr, s, theirs);
     }
     ev.mark(s);
     return hip_ok(ctx, hipGetLastError(), "pool: kernel launch");
@@ -315,11 +313,9 @@ int locgpu_pool_create(locgpu_ctx* ctx, const locgpu_pool_opts* o, locgpu_pool**
     P->slots = o->slots;
     P->chunk = o->chunk > 0 ? o->chunk : 4;
     P->split_scans = o->scans_per_job > 0 ? o->scans_per_job : o->slots;
-    P->ndt = o->matcher == 1;
     P->icp = o->icp;
-    int rc = P->ndt ? check_ndt(ctx, P->prm) : check_icp(ctx, &o->icp, P->prm, P->k, P->alpha_eff);
-    if (rc == LOCGPU_OK && !P->ndt && P->alpha_eff < 0.f) rc = fail(ctx, LOCGPU_ERR_INVALID, "pool_create: the grid search is not available in a pool");
-    if (rc == LOCGPU_OK && P->ndt) P->alpha_eff = 1.0f;
+    int rc = o->matcher == 1 ? check_ndt(ctx, P->spec) : check_icp(ctx, &o->icp, P->spec);
+    if (rc == LOCGPU_OK && P->spec.grid) rc = fail(ctx, LOCGPU_ERR_INVALID, "pool_create: the grid search is not available in a pool");
     if (rc != LOCGPU_OK) { delete P; return rc; }
     P->with_comm = ctx->comm != nullptr;
     P->multi_rank = P->with_comm && ctx->comm_world > 1;
@@ -395,10 +391,8 @@ int locgpu_pool_submit(locgpu_pool* P, const void* const* srcs, const size_t* co
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
     // the target the pool was created against is still the context's (a pool does not outlive a SetInputTarget)
     {
-        GnParams prm{};
-        int k = 0;
-        float a = 0.f;
-        const int rc = P->ndt ? check_ndt(ctx, prm) : check_icp(ctx, &P->icp, prm, k, a);
+        AlignSpec again;
+        const int rc = P->spec.ndt() ? check_ndt(ctx, again) : check_icp(ctx, &P->icp, again);
         if (rc != LOCGPU_OK) return rc;
     }
     // room in the arena: let scans finish. Every rank accounts n_total regions for the job, whichever scans it holds: the calls a

@@ -267,6 +267,42 @@ def test_graph_mode_with_grid_search(gpu_ctx, api, small_world):
         b.close()
 
 
+def test_graph_key_covers_every_field_of_the_request(gpu_ctx, api, small_world):
+    """A batch's captured graphs are keyed by the whole request: a sequence of requests that differ in one field each (pruning
+    factor, approximate or exact, method, tree or grid, ICP or NDT) replays, on one batch, what an identical batch computes
+    eagerly, bit for bit. A grid request ignores `approximate` and ann_alpha."""
+    m, s, init = small_world["map"], small_world["scan2k"], small_world["init_pose"]
+    gpu_ctx.icp_set_target(m)
+    gpu_ctx.ndt_set_target(m)
+    inits = np.stack([init, init])
+    inits[1, 4] += 0.05
+    tree, grid = api.SEARCH_TREE_FAITHFUL, api.SEARCH_GRID_EXACT
+    first = api.icp_opts(method=api.P2P, search_mode=tree, approximate=1)
+    requests = [first,
+                api.icp_opts(method=api.P2P, search_mode=tree, approximate=1, ann_alpha=0.5),
+                api.icp_opts(method=api.P2P, search_mode=tree, approximate=0),
+                api.icp_opts(method=api.P2PLANE, search_mode=tree, approximate=0),
+                api.icp_opts(method=api.P2PLANE, search_mode=grid, approximate=0),
+                api.icp_opts(method=api.P2PLANE, search_mode=grid, approximate=1),
+                None,  # direct NDT
+                first]
+    graphed, eager = gpu_ctx.batch([s, s]), gpu_ctx.batch([s, s])
+    try:
+        for step, opts in enumerate(requests):
+            def align(b):
+                return gpu_ctx.ndt_align_batch(b, inits) if opts is None else gpu_ctx.icp_align_batch(b, inits, opts)
+            gpu_ctx.graph_enable(True)
+            got, gst = align(graphed)
+            gpu_ctx.graph_enable(False)
+            want, wst = align(eager)
+            np.testing.assert_array_equal(got, want, err_msg="request %d" % step)
+            assert [x["iterations"] for x in gst] == [x["iterations"] for x in wst], step
+    finally:
+        gpu_ctx.graph_enable(False)
+        graphed.close()
+        eager.close()
+
+
 # ----------------------------------------------------------------------------------------------- degenerate neighbourhoods
 def _lines_map(rng, exact):
     """A map made of straight lines only: every 5-neighbourhood is collinear, so FitPlane's 5×4 matrix has rank 2.
