@@ -273,7 +273,7 @@ LOCGPU_API int locgpu_icp_fitness_resident(locgpu_ctx* ctx, const double pose[7]
 /* ---- A batch whose n_entries entries all read ONE resident cloud (no reference counterpart: the reference's only way to try several
  * initial poses is to call ScanMatch again, icp_registration.cpp:216-244). The cloud is uploaded once, here; poses, flags, neighbour
  * lists, sums and stats are per entry as in any batch, and locgpu_icp_align_batch / _begin / locgpu_align_batch_end /
- * locgpu_icp_hb_batch / locgpu_ndt_align_batch / locgpu_icp_fitness_batch treat it as the batch of n_entries uploaded copies of the
+ * locgpu_icp_hb_batch / locgpu_ndt_align_batch / locgpu_icp_fitness_batch / locgpu_ndt_fitness_batch treat it as the batch of n_entries uploaded copies of the
  * cloud, bit for bit, without the copies (16 B per point and entry). Not shardable and not poolable; locgpu_batch_upload_async into
  * it is refused with LOCGPU_ERR_INVALID (make a new one for another cloud). */
 LOCGPU_API int locgpu_batch_create_shared(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, int n_entries, locgpu_batch** out);
@@ -383,6 +383,53 @@ LOCGPU_API int locgpu_ndt_dump(locgpu_ctx* ctx, int32_t* keys, double* mu, doubl
  * When stats->status == 1 the reference leaves result_pose unassigned; out_pose then holds init_pose. */
 LOCGPU_API int locgpu_ndt_align(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double init_pose[7],
                                 double out_pose[7], locgpu_align_stats* stats);
+
+/* ---- NdtRegistration::GetFitnessScore, which the reference leaves a stub that returns 0 (ndt_registration.cpp:466-471): how good an
+ * alignment is against the DIRECT NDT target, in the terms of the alignment itself — the χ² residual AlignNdt forms for its gate
+ * (ndt_registration.cpp:416-421) and then drops. For a source cloud, a pose T and the target's voxel_size, nearby_type and
+ * res_outlier_th (locgpu_ndt_set_target):
+ *   a point with a non-finite coordinate is skipped and not counted (the rule of the ICP score above);
+ *   qs    = T·p in FP64; its voxel key is (int)(qs · inv_voxel_size) per axis, truncation toward zero (ndt_registration.cpp:404);
+ *   the voxels looked up are key + nearby_grids_ (ndt_registration.cpp:57-58): 1 for CENTER, 7 for NEARBY6. A key outside ±2^20 or a
+ *           voxel that is not in the table contributes nothing;
+ *   for every voxel found: e = qs − μ, res = ((e·info[:,0])·e.x + (e·info[:,1])·e.y) + (e·info[:,2])·e.z with
+ *           e·info[:,c] = (e.x·info[0][c] + e.y·info[1][c]) + e.z·info[2][c] — eᵀ·info·e as the alignment's kernel associates it;
+ *   a voxel is accepted iff !(isnan(res) || res > res_outlier_th) (AlignNdt's gate, ndt_registration.cpp:417-421);
+ *   a point with at least one accepted voxel is an inlier, and its value is the MINIMUM accepted res — the voxel that explains the
+ *           point best, whatever the order of the probes;
+ *   score = Σ_inliers min res / inliers, +infinity when there is no inlier.
+ * In the locgpu_fitness of these four entry points `score` is therefore a mean χ² residual, DIMENSIONLESS (not m²), `inliers` the
+ * points with an accepted voxel and `finite_points` the points that were looked up at all. Same determinism as the ICP score: no
+ * atomics on the sums and a fixed split that does not depend on the batch — a cloud and a pose give the same bits alone, among
+ * other poses, in a batch of any size, from a shared-source batch and in any chunk of a search.
+ * All four: LOCGPU_ERR_NO_TARGET before locgpu_ndt_set_target; LOCGPU_ERR_INVALID when the current NDT target is the incremental
+ * one (method 2: another table, residuals weighted differently — not scored), and for NULL arguments. */
+/* Score of ONE cloud under n_poses >= 1 poses (n_poses × 7 doubles; out: n_poses entries; score: mean χ², dimensionless). The cloud is
+ * uploaded once; with more than one pose the call goes through the context's shared-source batch (locgpu_icp_init_search says what
+ * that retains). LOCGPU_ERR_INVALID for n == 0 or n_poses < 1. */
+LOCGPU_API int locgpu_ndt_fitness(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double* poses, int n_poses,
+                                  locgpu_fitness* out);
+/* Score of every scan of a batch under its own pose (poses: n_scans × 7; out: n_scans entries; score: mean χ², dimensionless).
+ * Ordinary and shared-source batches; a sharded batch is refused with LOCGPU_ERR_INVALID. Equals locgpu_ndt_fitness of each scan
+ * bit for bit. */
+LOCGPU_API int locgpu_ndt_fitness_batch(locgpu_ctx* ctx, locgpu_batch* batch, const double* poses, locgpu_fitness* out);
+/* Score (mean χ², dimensionless) of the source cloud that the context's most recent host-pointer single-scan call
+ * (locgpu_ndt_scan_match, locgpu_ndt_align, ...) left in HBM, under `pose`: no second upload. This is what
+ * NdtRegistration::GetFitnessScore binds to after EnableFitnessScore: nothing is added to ScanMatch itself
+ * (ndt_registration.cpp:238-260). LOCGPU_ERR_INVALID when no such cloud is resident. */
+LOCGPU_API int locgpu_ndt_fitness_resident(locgpu_ctx* ctx, const double pose[7], locgpu_fitness* out);
+/* Initial-pose search with the NDT matcher (no reference counterpart; the flow the reference ships matches with direct NDT from
+ * SetInitPose(SE3()) or a GNSS position with an IMU heading, lio_matching_flow.cpp:203-205,227-262). As locgpu_icp_init_search: each
+ * of the m candidates runs exactly the loop locgpu_ndt_align_batch runs on a batch of m copies of the cloud, bit for bit; every result
+ * is scored as above (out_fit[i].score: mean χ², dimensionless) and *best is the lowest score among the candidates with inliers >= 1
+ * and inliers / finite_points >= sopts->min_inlier_ratio, ties to the lower index, -1 when none qualifies. sopts->max_range is NOT
+ * used: the gate of the score is the target's res_outlier_th. A candidate whose alignment ended with status 1 (det(H) == 0) keeps
+ * its initial pose, as in locgpu_ndt_align_batch, and is scored there. Chunks and retained workspace: those of
+ * locgpu_icp_init_search (at most 256 candidates and 1 GiB per chunk, grow-only on the context).
+ * LOCGPU_ERR_INVALID also for m < 1, n == 0, a negative or NaN min_inlier_ratio. */
+LOCGPU_API int locgpu_ndt_init_search(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double* candidates, int m,
+                                      const locgpu_init_search_opts* sopts, double* out_poses, locgpu_fitness* out_fit,
+                                      locgpu_align_stats* stats, int* best);
 
 /* ---- hipGraph mode (BASELINE config 5, streaming loop). When on, an align call replays instantiated graphs of Gauss–Newton
  * iterations instead of launching kernel by kernel: one graph of the first eight iterations (with the state upload and

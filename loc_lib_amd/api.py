@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "locgpu_icp_scan_match", "locgpu_ndt_scan_match",
     "locgpu_icp_fitness", "locgpu_icp_fitness_batch", "locgpu_icp_fitness_resident", "locgpu_batch_create_shared",
     "locgpu_init_search_opts_default", "locgpu_icp_init_search", "locgpu_pose_grid",
+    "locgpu_ndt_fitness", "locgpu_ndt_fitness_batch", "locgpu_ndt_fitness_resident", "locgpu_ndt_init_search",
     "locgpu_icp_build_map_planes", "locgpu_icp_map_planes_info", "locgpu_icp_map_planes_dump",
 ]
 COMM_ID_BYTES = 128
@@ -160,6 +161,9 @@ def lib():
             "locgpu_init_search_opts_default": (None, [vp]),
             "locgpu_icp_init_search": (i32, [vp, vp, sz, sz, vp, i32, vp, vp, vp, vp, vp, vp]),
             "locgpu_pose_grid": (i32, [vp, dbl, dbl, dbl, dbl, vp, sz, vp]),
+            "locgpu_ndt_fitness": (i32, [vp, vp, sz, sz, vp, i32, vp]), "locgpu_ndt_fitness_batch": (i32, [vp, vp, vp, vp]),
+            "locgpu_ndt_fitness_resident": (i32, [vp, vp, vp]),
+            "locgpu_ndt_init_search": (i32, [vp, vp, sz, sz, vp, i32, vp, vp, vp, vp, vp]),
             "locgpu_icp_build_map_planes": (i32, [vp]), "locgpu_icp_map_planes_info": (i32, [vp, vp]),
             "locgpu_icp_map_planes_dump": (i32, [vp, vp, vp, sz, vp]),
         }
@@ -561,6 +565,45 @@ class Context:
         self._check(lib().locgpu_ndt_align(self._h, s.ctypes.data, s.shape[0], s.strides[0], _pose(init_pose).ctypes.data, out.ctypes.data,
                                            ctypes.byref(st)))
         return out, _stats_dict(st)
+
+    # ---- the score and the candidate search against the direct NDT target (locgpu.h: score = mean χ² residual, dimensionless)
+    def ndt_fitness(self, src, poses, raw=False):
+        """Score of one cloud under one pose ([7] → dict) or several ([n, 7] → list of dicts). raw=True: the ctypes array."""
+        s = _cloud(src)
+        p = _pose(poses)
+        one = p.ndim == 1
+        p = p.reshape(-1, 7)
+        out = (Fitness * max(p.shape[0], 1))()
+        self._check(lib().locgpu_ndt_fitness(self._h, s.ctypes.data, s.shape[0], s.strides[0], p.ctypes.data, p.shape[0], out))
+        if raw:
+            return out
+        return _fitness_dict(out[0]) if one else [_fitness_dict(f) for f in out]
+
+    def ndt_fitness_batch(self, batch, poses, raw=False):
+        batch.upload_wait()
+        p = _pose(poses).reshape(batch.n_scans, 7)
+        out = (Fitness * batch.n_scans)()
+        self._check(lib().locgpu_ndt_fitness_batch(self._h, batch._h, p.ctypes.data, out))
+        return out if raw else [_fitness_dict(f) for f in out]
+
+    def ndt_fitness_resident(self, pose):
+        """Score of the source cloud the last host-pointer single-scan call left in HBM (what the façade's GetFitnessScore uses)."""
+        out = Fitness()
+        self._check(lib().locgpu_ndt_fitness_resident(self._h, _pose(pose).ctypes.data, ctypes.byref(out)))
+        return _fitness_dict(out)
+
+    def ndt_init_search(self, src, candidates, sopts=None, raw=False):
+        """Returns (poses [m, 7], fitness (list of dicts; raw=True: the ctypes array), stats, best index or -1)."""
+        s = _cloud(src)
+        c = _pose(candidates).reshape(-1, 7)
+        m = c.shape[0]
+        out = np.zeros((m, 7))
+        fit = (Fitness * max(m, 1))()
+        st = (AlignStats * max(m, 1))()
+        best = ctypes.c_int(-2)
+        self._check(lib().locgpu_ndt_init_search(self._h, s.ctypes.data, s.shape[0], s.strides[0], c.ctypes.data, m,
+                                                 ctypes.byref(sopts) if sopts is not None else None, out.ctypes.data, fit, st, ctypes.byref(best)))
+        return out, (fit if raw else [_fitness_dict(f) for f in fit]), [_stats_dict(x) for x in st], int(best.value)
 
     def graph_enable(self, on=True):
         """Replay a captured hipGraph of all Gauss–Newton iterations per align call (BASELINE config 5)."""

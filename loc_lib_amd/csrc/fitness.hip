@@ -86,11 +86,15 @@ __global__ __launch_bounds__(64) void icp_fitness_sum_kernel(const double* __res
 
 int icp_fitness_rows(int max_n) { return (max_n + kFitPts * kBlock - 1) / (kFitPts * kBlock); }
 
+void launch_fitness_sum(const double* partials, int rows, int n_scans, double* out, unsigned int* list_counts, hipStream_t s) {
+    hipLaunchKernelGGL(icp_fitness_sum_kernel, dim3(n_scans), dim3(64), 0, s, partials, rows, out, list_counts);
+}
+
 void launch_icp_fitness(const FitnessArgs& a, hipStream_t s) {
     const int rows = icp_fitness_rows(a.max_n);
     hipLaunchKernelGGL(icp_fitness_accum_kernel, dim3(rows, a.n_scans), dim3(kBlock), 0, s, a.tree, a.src, a.counts, a.st, a.nn, a.max_n, a.gate2, a.partials,
                        a.src_of);
-    hipLaunchKernelGGL(icp_fitness_sum_kernel, dim3(a.n_scans), dim3(64), 0, s, a.partials, rows, a.out, a.list_counts);
+    launch_fitness_sum(a.partials, rows, a.n_scans, a.out, a.list_counts, s);
 }
 
 }  // namespace locgpu

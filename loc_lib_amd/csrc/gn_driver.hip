@@ -578,6 +578,29 @@ int fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, doub
     return LOCGPU_OK;
 }
 
+// Score of every entry of `b` under its pose against the direct NDT table: the probe-and-reduce kernel of ndt_fitness.hip, then the
+// ICP score's fixed-order sum. Touches nothing of the search stage (no neighbour lists, no work-list counters).
+int ndt_fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, locgpu_fitness* out) {
+    if (b->sharded) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_fitness: sharded batches are not scored");
+    if (b->pending.active) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_fitness: an alignment of this batch has been begun and not finished");
+    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+    { const int urc = batch_ready(ctx, b); if (urc != LOCGPU_OK) return urc; }
+    init_states(b, poses);
+    hipStream_t s = b->stream;
+    LOCGPU_HIP(ctx, hipMemcpyAsync(b->d_state, b->h_state, b->n_total * sizeof(PoseState), hipMemcpyHostToDevice, s));
+    launch_ndt_fitness(ctx->ndt, batch_src(b), b->d_counts, b->d_state, b->max_n, b->n_scans, b->d_partials, b->d_hb, s, b->d_src_of);
+    LOCGPU_HIP(ctx, hipGetLastError());
+    LOCGPU_HIP(ctx, hipMemcpyAsync(b->h_hb, b->d_hb, (size_t)b->n_scans * kFitW * sizeof(double), hipMemcpyDeviceToHost, s));
+    LOCGPU_HIP(ctx, hipStreamSynchronize(s));
+    for (int i = 0; i < b->n_scans; ++i) {
+        const double* r = b->h_hb + (size_t)i * kFitW;
+        out[i].inliers = (int64_t)r[1];
+        out[i].finite_points = (int64_t)r[2];
+        out[i].score = out[i].inliers > 0 ? r[0] / (double)out[i].inliers : HUGE_VAL;
+    }
+    return LOCGPU_OK;
+}
+
 int eval_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, const AlignSpec& spec, double* hb) {
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
     { const int grc = ensure_grid_lists(ctx, b, spec); if (grc != LOCGPU_OK) return grc; }

@@ -56,6 +56,8 @@ int run_align(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const 
 int eval_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, const AlignSpec& spec, double* hb);
 // Score of every entry of `b` under its pose: k = 1 exact search stage, then the reduction of fitness.hip.
 int fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, double max_range, locgpu_fitness* out);
+// Score of every entry of `b` under its pose against the context's direct NDT table (ndt_fitness.hip).
+int ndt_fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, locgpu_fitness* out);
 // The plane table of LOCGPU_P2PLANE_MAP for the current target (map_planes.hip); no-op when it is there.
 int ensure_map_planes(locgpu_ctx* ctx);
 

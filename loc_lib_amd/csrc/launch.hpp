@@ -99,6 +99,9 @@ struct FitnessArgs {
 };
 int icp_fitness_rows(int max_n);
 void launch_icp_fitness(const FitnessArgs& a, hipStream_t s);
+// The last step of a score, shared with the NDT score (ndt_fitness.hip): adds the `rows` block rows {Σ, inliers, finite points, ·} of
+// every scan in a fixed order → out[scan][kFitW]. list_counts (optional): the search stage's work-list counters, zeroed.
+void launch_fitness_sum(const double* partials, int rows, int n_scans, double* out, unsigned int* list_counts, hipStream_t s);
 struct M12f { float v[12]; };  // rows of pose.matrix().cast<float>() (icp_registration.cpp:241), a kernel argument
 void launch_transform_cloud(const float4* src, size_t n, const M12f& m12, float* dst_xyz, hipStream_t s);
 // Plane table of LOCGPU_P2PLANE_MAP (map_planes.hip). queries: the coordinates of leaves [first, first + n) as the source points of a

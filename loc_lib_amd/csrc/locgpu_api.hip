@@ -835,6 +835,57 @@ int fitness_target(locgpu_ctx* ctx) {
     if (!ctx->d_tree) return fail(ctx, LOCGPU_ERR_NO_TARGET, "icp_fitness: SetInputTarget has not been called");
     return LOCGPU_OK;
 }
+
+// The NDT score reads the DIRECT table: the incremental voxel set has another table and weights its residuals differently.
+int ndt_fitness_target(locgpu_ctx* ctx, const char* who) {
+    if (ctx->ndt_opts.method == kNdtOptIncremental) {
+        if (!ctx->inc) return fail(ctx, LOCGPU_ERR_NO_TARGET, std::string(who) + ": SetInputTarget has not been called");
+        return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": the current NDT target is the incremental one (method 2); the score and the search are defined for the direct target only");
+    }
+    if (!ctx->ndt) return fail(ctx, LOCGPU_ERR_NO_TARGET, std::string(who) + ": SetInputTarget has not been called");
+    return LOCGPU_OK;
+}
+
+// One cloud under n_poses > 1 poses, through the context's shared-source batch in chunks; score(batch, poses, out) scores a chunk.
+template <class Score>
+int fitness_in_chunks(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double* poses, int n_poses, locgpu_fitness* out, Score score) {
+    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+    locgpu_batch* b = nullptr;
+    int chunk = 0;
+    int rc = search_batch(ctx, src, n, stride_bytes, n_poses, &chunk, &b);
+    for (int off = 0; rc == LOCGPU_OK && off < n_poses; off += chunk) {
+        const int cnt = std::min(chunk, n_poses - off);
+        rc = reshape_shared(ctx, b, cnt, n, 0);
+        if (rc == LOCGPU_OK) rc = score(b, poses + 7 * (size_t)off, out + off);
+    }
+    return rc;
+}
+
+// The candidate search of either matcher: every chunk of the context's shared-source batch is aligned under `spec`, scored by
+// score(batch, poses, out), and the winner picked by the rule of locgpu.h.
+template <class Score>
+int init_search_in_chunks(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double* candidates, int m, const AlignSpec& spec,
+                          double min_inlier_ratio, double* out_poses, locgpu_fitness* out_fit, locgpu_align_stats* stats, int* best, Score score) {
+    *best = -1;
+    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+    locgpu_batch* b = nullptr;
+    int chunk = 0;
+    int rc = search_batch(ctx, src, n, stride_bytes, m, &chunk, &b);
+    for (int off = 0; rc == LOCGPU_OK && off < m; off += chunk) {
+        const int cnt = std::min(chunk, m - off);
+        // every chunk sums as the plain batch of all m candidates would: chunking never shows in a pose
+        rc = reshape_shared(ctx, b, cnt, n, m);
+        if (rc == LOCGPU_OK) rc = run_align(ctx, b, candidates + 7 * (size_t)off, spec, out_poses + 7 * (size_t)off, stats ? stats + off : nullptr);
+        if (rc == LOCGPU_OK) rc = score(b, out_poses + 7 * (size_t)off, out_fit + off);
+    }
+    if (rc != LOCGPU_OK) return rc;
+    for (int i = 0; i < m; ++i) {
+        const locgpu_fitness& f = out_fit[i];
+        if (f.inliers <= 0 || !((double)f.inliers >= min_inlier_ratio * (double)f.finite_points)) continue;
+        if (*best < 0 || f.score < out_fit[*best].score) *best = i;  // ties stay with the lower index
+    }
+    return LOCGPU_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -875,15 +926,8 @@ int locgpu_icp_fitness(locgpu_ctx* ctx, const void* src, size_t n, size_t stride
         rc = single_batch(ctx, src, n, stride_bytes, &b);
         return rc != LOCGPU_OK ? rc : fitness_on_batch(ctx, b, poses, max_range, out);
     }
-    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
-    int chunk = 0;
-    rc = search_batch(ctx, src, n, stride_bytes, n_poses, &chunk, &b);
-    for (int off = 0; rc == LOCGPU_OK && off < n_poses; off += chunk) {
-        const int cnt = std::min(chunk, n_poses - off);
-        rc = reshape_shared(ctx, b, cnt, n, 0);
-        if (rc == LOCGPU_OK) rc = fitness_on_batch(ctx, b, poses + 7 * (size_t)off, max_range, out + off);
-    }
-    return rc;
+    return fitness_in_chunks(ctx, src, n, stride_bytes, poses, n_poses, out,
+                             [&](locgpu_batch* sb, const double* p, locgpu_fitness* o) { return fitness_on_batch(ctx, sb, p, max_range, o); });
 }
 
 int locgpu_icp_fitness_resident(locgpu_ctx* ctx, const double pose[7], double max_range, locgpu_fitness* out) {
@@ -913,25 +957,60 @@ int locgpu_icp_init_search(locgpu_ctx* ctx, const void* src, size_t n, size_t st
         !(so.min_inlier_ratio >= 0.0))
         return fail(ctx, LOCGPU_ERR_INVALID, "icp_init_search: bad arguments");
     if (n > 0x7FFFFF00u) return fail(ctx, LOCGPU_ERR_INVALID, "icp_init_search: too many points");
-    *best = -1;
-    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
-    locgpu_batch* b = nullptr;
-    int chunk = 0;
-    rc = search_batch(ctx, src, n, stride_bytes, m, &chunk, &b);
-    for (int off = 0; rc == LOCGPU_OK && off < m; off += chunk) {
-        const int cnt = std::min(chunk, m - off);
-        // every chunk sums as the plain batch of all m candidates would: chunking never shows in a pose
-        rc = reshape_shared(ctx, b, cnt, n, m);
-        if (rc == LOCGPU_OK) rc = run_align(ctx, b, candidates + 7 * (size_t)off, spec, out_poses + 7 * (size_t)off, stats ? stats + off : nullptr);
-        if (rc == LOCGPU_OK) rc = fitness_on_batch(ctx, b, out_poses + 7 * (size_t)off, so.max_range, out_fit + off);
-    }
+    return init_search_in_chunks(ctx, src, n, stride_bytes, candidates, m, spec, so.min_inlier_ratio, out_poses, out_fit, stats, best,
+                                 [&](locgpu_batch* sb, const double* p, locgpu_fitness* o) { return fitness_on_batch(ctx, sb, p, so.max_range, o); });
+}
+
+// ---- the same three scores and the search against the direct NDT target (ndt_fitness.hip)
+int locgpu_ndt_fitness_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, locgpu_fitness* out) {
+    if (!ctx) return LOCGPU_ERR_INVALID;
+    const int rc = ndt_fitness_target(ctx, "ndt_fitness_batch");
     if (rc != LOCGPU_OK) return rc;
-    for (int i = 0; i < m; ++i) {
-        const locgpu_fitness& f = out_fit[i];
-        if (f.inliers <= 0 || !((double)f.inliers >= so.min_inlier_ratio * (double)f.finite_points)) continue;
-        if (*best < 0 || f.score < out_fit[*best].score) *best = i;  // ties stay with the lower index
+    if (!b || b->ctx != ctx || !poses || !out) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_fitness_batch: bad arguments");
+    if (b->n_scans < 1) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_fitness_batch: the batch holds no scan");
+    return ndt_fitness_on_batch(ctx, b, poses, out);
+}
+
+int locgpu_ndt_fitness(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double* poses, int n_poses, locgpu_fitness* out) {
+    if (!ctx) return LOCGPU_ERR_INVALID;
+    int rc = ndt_fitness_target(ctx, "ndt_fitness");
+    if (rc != LOCGPU_OK) return rc;
+    if (!src || n == 0 || stride_bytes < 12 || !poses || n_poses < 1 || !out) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_fitness: bad arguments");
+    if (n > 0x7FFFFF00u) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_fitness: too many points");
+    if (n_poses == 1) {
+        locgpu_batch* b = nullptr;
+        rc = single_batch(ctx, src, n, stride_bytes, &b);
+        return rc != LOCGPU_OK ? rc : ndt_fitness_on_batch(ctx, b, poses, out);
     }
-    return LOCGPU_OK;
+    return fitness_in_chunks(ctx, src, n, stride_bytes, poses, n_poses, out,
+                             [&](locgpu_batch* sb, const double* p, locgpu_fitness* o) { return ndt_fitness_on_batch(ctx, sb, p, o); });
+}
+
+int locgpu_ndt_fitness_resident(locgpu_ctx* ctx, const double pose[7], locgpu_fitness* out) {
+    if (!ctx) return LOCGPU_ERR_INVALID;
+    const int rc = ndt_fitness_target(ctx, "ndt_fitness_resident");
+    if (rc != LOCGPU_OK) return rc;
+    if (!pose || !out) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_fitness_resident: bad arguments");
+    locgpu_batch* b = ctx->single;
+    if (!b || b->d_src_ext || b->counts[0] <= 0) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_fitness_resident: no source cloud of a single-scan call is resident");
+    return ndt_fitness_on_batch(ctx, b, pose, out);
+}
+
+int locgpu_ndt_init_search(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double* candidates, int m,
+                           const locgpu_init_search_opts* sopts, double* out_poses, locgpu_fitness* out_fit, locgpu_align_stats* stats, int* best) {
+    if (!ctx) return LOCGPU_ERR_INVALID;
+    int rc = ndt_fitness_target(ctx, "ndt_init_search");
+    if (rc != LOCGPU_OK) return rc;
+    AlignSpec spec;
+    rc = check_ndt(ctx, spec);
+    if (rc != LOCGPU_OK) return rc;
+    locgpu_init_search_opts so;
+    if (sopts) so = *sopts; else locgpu_init_search_opts_default(&so);
+    if (!src || n == 0 || stride_bytes < 12 || !candidates || m < 1 || !out_poses || !out_fit || !best || !(so.min_inlier_ratio >= 0.0))
+        return fail(ctx, LOCGPU_ERR_INVALID, "ndt_init_search: bad arguments");
+    if (n > 0x7FFFFF00u) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_init_search: too many points");
+    return init_search_in_chunks(ctx, src, n, stride_bytes, candidates, m, spec, so.min_inlier_ratio, out_poses, out_fit, stats, best,
+                                 [&](locgpu_batch* sb, const double* p, locgpu_fitness* o) { return ndt_fitness_on_batch(ctx, sb, p, o); });
 }
 
 int locgpu_pose_grid(const double centre[7], double xy_half, double xy_step, double yaw_half, double yaw_step, double* out, size_t cap, size_t* n_out) {

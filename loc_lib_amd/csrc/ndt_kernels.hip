@@ -19,10 +19,6 @@
 #endif
 namespace locgpu {
 
-__device__ __forceinline__ void ndt_key_of(const D3& p, double inv, int& kx, int& ky, int& kz) {
-    kx = (int)(p.x * inv); ky = (int)(p.y * inv); kz = (int)(p.z * inv);  // C++ double→int: truncation toward zero
-}
-
 // key of every point; a point outside the ±2^20-voxel range raises *bad (the ingest is refused)
 __global__ __launch_bounds__(kBlock) void ndt_key_kernel(const float4* __restrict__ pts, size_t n, double inv, unsigned long long* __restrict__ pkey,
                                                          uint32_t* __restrict__ pidx, int* __restrict__ bad) {

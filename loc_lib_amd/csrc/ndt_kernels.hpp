@@ -62,6 +62,11 @@ __host__ __device__ inline size_t ndt_hash32(unsigned long long key, size_t cap_
     return (size_t)h & cap_mask;
 }
 
+// Voxel of a point: `(pt * inv_voxel_size_).cast<int>()` (ndt cpp:100,404).
+__device__ __forceinline__ void ndt_key_of(const D3& p, double inv, int& kx, int& ky, int& kz) {
+    kx = (int)(p.x * inv); ky = (int)(p.y * inv); kz = (int)(p.z * inv);  // C++ double→int: truncation toward zero
+}
+
 // Build (SetDirectNdtTargetCloud, ndt_registration.cpp:87-148). Returns hipError; *bad_key is set when a point falls
 // outside the ±2^20-voxel key range.
 hipError_t ndt_build(NdtTable& t, const float4* d_pts, size_t n, double voxel_size, int min_pts_in_voxel, hipStream_t s, bool* bad_key);
@@ -74,5 +79,10 @@ hipError_t ndt_dump(const NdtTable& t, int* keys, double* mu, double* info, size
 // that many scans would (AccumArgs::split_scans).
 int launch_ndt_accum(const NdtTable* t, const float4* src, const int* counts, const PoseState* st, int max_n, int n_scans, double* partials,
                      hipStream_t s, const int* active = nullptr, int n_active = 0, int split_scans = 0, const int* src_of = nullptr);
+
+// Fitness score against the direct table (ndt_fitness.hip): per scan {Σ over the inliers of the smallest accepted residual, inliers,
+// finite points, 0} → out[scan][kFitW] (launch.hpp). partials: room for n_scans × icp_fitness_rows(max_n) × kFitW doubles.
+void launch_ndt_fitness(const NdtTable* t, const float4* src, const int* counts, const PoseState* st, int max_n, int n_scans, double* partials,
+                        double* out, hipStream_t s, const int* src_of = nullptr);
 
 }  // namespace locgpu

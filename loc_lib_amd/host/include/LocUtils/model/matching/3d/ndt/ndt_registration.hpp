@@ -4,6 +4,7 @@
 #pragma once
 #include <cstddef>
 #include <memory>
+#include <vector>
 
 #include "LocUtils/model/matching/3d/matching_interface.h"
 
@@ -43,6 +44,18 @@ public:
     float GetFitnessScore() override;
 
     void SetDevice(int device_id);
+    // Opt-in (no reference counterpart; the reference's GetFitnessScore is a stub that returns 0, ndt_registration.cpp:466-471): after
+    // it GetFitnessScore() scores the last ScanMatch against the DIRECT NDT target — the mean over the inlier points of the smallest
+    // accepted χ² residual eᵀ·info·e among the voxels AlignNdt probes, dimensionless (include/locgpu.h, locgpu_ndt_fitness) — on the
+    // source copy ScanMatch left in HBM, lazily, when it is asked for. ScanMatch itself is unchanged. +infinity before any ScanMatch,
+    // when no point has an accepted voxel, with NdtMethod::INCREMENTAL_NDT (not scored: LastError says so) and when the library fails.
+    // Without the opt-in GetFitnessScore() stays the reference's 0.0f.
+    void EnableFitnessScore();
+    // Initial-pose search (locgpu_ndt_init_search): aligns `source` from every candidate with this matcher's options, scores every
+    // result as above and returns the best one — the lowest score among the candidates of which at least half the points are inliers.
+    // false (best_score = +infinity, best_pose untouched) without a target, with an empty input, when no candidate qualifies and with
+    // NdtMethod::INCREMENTAL_NDT (LastError says so). Leaves what GetFitnessScore() reports alone.
+    bool InitialPoseSearch(const CloudPtr& source, const std::vector<SE3>& candidates, SE3& best_pose, float& best_score);
     // Text of the last liblocgpu error — or the refusal when the options name a branch that is not on the GPU path (NdtMethod::PCL_NDT,
     // ndt_registration.cpp:69,246; remove_centroid_ = true, :380-384): SetInputTarget and ScanMatch then return false and touch nothing.
     const char* LastError() const;
@@ -54,6 +67,9 @@ private:
     locgpu_ctx* ctx_ = nullptr;
     int device_id_ = 0;
     bool has_target_ = false;
+    bool fitness_enabled_ = false;
+    bool have_last_pose_ = false;  // a ScanMatch has left its source in HBM and its result in last_pose_
+    SE3 last_pose_;
 };
 
 }  // namespace LocUtils

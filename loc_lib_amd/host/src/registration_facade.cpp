@@ -8,6 +8,7 @@
 //  * `use_ann` can only switch approximate search ON, and it is on by default (icp_registration.hpp:76-79 +
 //    kdtree.h:128): every reference ICP run uses the alpha=0.1 pruned search, so does this one;
 //  * the output cloud is `*result = *source` with x,y,z replaced by the float32 transform (icp cpp:241).
+#include <cmath>
 #include <cstring>
 
 #include "../../../include/locgpu.h"
@@ -191,6 +192,7 @@ bool NdtRegistration::CaculateMatrixHAndB(const CloudPtr&, const SE3&, Mat6d&, V
 bool NdtRegistration::ScanMatch(const CloudPtr& input_source, const SE3& predict_pose, CloudPtr& result_cloud_ptr, SE3& result_pose) {
     if (Unsupported()) return false;  // a refusal, loudly (LastError): neither result_pose nor the output cloud is touched
     if (!input_source) return true;
+    have_last_pose_ = false;
     if (has_target_ && !input_source->points.empty()) {
         // result_pose is in-out: status 2 (incremental, too few residuals) assigns the current pose (ndt cpp:351); status 1 (det(H) == 0)
         // means AlignNdt returned before assigning it (ndt cpp:435-436) — the library leaves it as the caller had it and transforms the
@@ -198,14 +200,42 @@ bool NdtRegistration::ScanMatch(const CloudPtr& input_source, const SE3& predict
         OutputCloud oc{input_source.get(), result_cloud_ptr.get()};
         locgpu_align_stats st;
         if (locgpu_ndt_scan_match(ctx_, input_source->points.data(), input_source->points.size(), sizeof(PointType), predict_pose.data(),
-                                  result_pose.data(), &st, nullptr, sizeof(PointType) | LOCGPU_OUT_FIELDS_DONE, size_output_cloud, &oc) == LOCGPU_OK)
+                                  result_pose.data(), &st, nullptr, sizeof(PointType) | LOCGPU_OUT_FIELDS_DONE, size_output_cloud, &oc) == LOCGPU_OK) {
+            last_pose_ = result_pose;  // what a later GetFitnessScore scores (the source stays in HBM until the next call)
+            have_last_pose_ = true;
             return true;  // ndt_registration.cpp:260
+        }
     }
     if (ctx_) write_output_cloud(ctx_, input_source, result_pose, result_cloud_ptr);
     return true;  // ndt_registration.cpp:260
 }
 
-float NdtRegistration::GetFitnessScore() { return 0.0f; }  // ndt_registration.cpp:466-471
+void NdtRegistration::EnableFitnessScore() { fitness_enabled_ = true; }
+
+float NdtRegistration::GetFitnessScore() {
+    if (!fitness_enabled_) return 0.0f;  // ndt_registration.cpp:466-471: the reference's stub
+    locgpu_fitness f;
+    // the incremental method is refused by the library (LOCGPU_ERR_INVALID; its text is LastError())
+    if (!have_last_pose_ || locgpu_ndt_fitness_resident(ctx_, last_pose_.data(), &f) != LOCGPU_OK) return INFINITY;
+    return (float)f.score;
+}
+
+bool NdtRegistration::InitialPoseSearch(const CloudPtr& source, const std::vector<SE3>& candidates, SE3& best_pose, float& best_score) {
+    best_score = INFINITY;
+    if (Unsupported() || !has_target_ || !source || source->points.empty() || candidates.empty()) return false;
+    const size_t m = candidates.size();
+    std::vector<double> in(7 * m), out(7 * m);
+    for (size_t i = 0; i < m; ++i) std::memcpy(&in[7 * i], candidates[i].data(), 7 * sizeof(double));
+    std::vector<locgpu_fitness> fit(m);
+    int best = -1;
+    // the search runs on the context's shared-source batch: the source copy of the last ScanMatch stays where it is
+    if (locgpu_ndt_init_search(ctx_, source->points.data(), source->points.size(), sizeof(PointType), in.data(), (int)m, nullptr, out.data(), fit.data(), nullptr,
+                               &best) != LOCGPU_OK || best < 0)
+        return false;
+    std::memcpy(best_pose.data(), &out[7 * (size_t)best], 7 * sizeof(double));
+    best_score = (float)fit[best].score;
+    return true;
+}
 
 // ------------------------------------------------------------------------------------------------ LOAM
 LoamRegistration::LoamRegistration() {}
