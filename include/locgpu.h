@@ -95,7 +95,9 @@ typedef struct locgpu_align_stats {
     int32_t iterations;        /* Gauss–Newton iterations executed (H,B evaluations) */
     int32_t converged;         /* 1 if the loop left through |dx| < eps */
     int32_t status;            /* 0 ok; 1 direct-NDT det(H)==0 ⇒ reference returns before writing result_pose (ndt cpp:435-436);
-                                  2 incremental NDT: too few effective residuals ⇒ returns false with the current pose (ndt cpp:349-353) */
+                                  2 incremental NDT: too few effective residuals ⇒ returns false with the current pose (ndt cpp:349-353);
+                                  locgpu_loam_* only: 3 the SURFACE class's evaluation reported false, 4 the EDGE class's did ⇒
+                                  ScanMatch returns false before writing result_pose (loam_registration.cpp:56-70); surface is tested first */
     int32_t reserved;
     int64_t last_effective_num;
     double last_dx_norm;
@@ -240,6 +242,67 @@ LOCGPU_API int locgpu_icp_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const doubl
  * returns 1 in *stop when |dx| < eps. method selects the P2P "/16" quirk (icp cpp:287). */
 LOCGPU_API int locgpu_gn_update(const double hb[44], int method, int min_effective_pts, double eps, double pose[7], double dx[6],
                                 int* applied, int* stop);
+
+/* ---- LoamRegistration (LocUtils/include/LocUtils/model/matching/3d/loam/loam_registration.hpp:22-60, loam_registration.cpp:9-104), the
+ * matcher slam_demo selects with `matching_method: 0` and Lio::AddCloud(FullCloudPtr) feeds from the feature picker
+ * (locgpu_cloud_loam_extract). A locgpu_loam owns what one LoamRegistration owns — a surface matcher (P2Plane) and an edge matcher
+ * (P2Line), here two contexts on one GPU — and runs the WHOLE Gauss–Newton loop of ScanMatch (:47-90) on the device: per iteration both
+ * classes' search and fit stages and one joint solve on one stream, the stop test on the device, the host reading the flags every
+ * 8 (then 4) iterations. Per iteration: surface, then edge, evaluated at the same pose; a class is false iff its effective_num <
+ * min_effective_pts or its own det(H) == 0 (icp_registration.cpp:204-211), and a false class ends the alignment (:56-70); otherwise
+ * dx = (H_surf + H_edge)⁻¹ (B_surf + B_edge) with no effective-count test on the sum (:76-79), pose.so3() *= exp(dx.head<3>()),
+ * translation += dx.tail<3>() (:82-83), stop after the update when |dx| < eps (:85). det(H_surf + H_edge) == 0, where the reference
+ * divides by zero, is an iteration without an update (what locgpu_gn_update does); the loop goes on.
+ * Limits: the LOAM entry points run EAGER chunks only — locgpu_graph_enable, sharded batches, scan pools and the host-paced one-scan
+ * path do not apply to them — and LOCGPU_P2PLANE_MAP is refused (LOCGPU_ERR_INVALID). Calls on a handle follow the context's rule: one
+ * caller thread, synchronous, inputs copied before the call returns. */
+typedef struct locgpu_loam locgpu_loam;
+/* LoamOption, loam_registration.hpp:22-36. Inside surf / edge only method, the three gates, min_effective_pts, approximate / ann_alpha
+ * and search_mode are read: their max_iteration and eps are NOT (the loop is LoamRegistration's own, :47,85). */
+typedef struct locgpu_loam_opts {
+    locgpu_icp_opts surf;      /* surf_icp_option_{IcpMethod::P2PLANE} */
+    locgpu_icp_opts edge;      /* edge_icp_option_{IcpMethod::P2LINE}  */
+    int32_t use_surf_points;   /* 1 */
+    int32_t use_edge_points;   /* 1 */
+    int32_t max_iteration;     /* 20 */
+    double eps;                /* 1e-3 */
+} locgpu_loam_opts;
+LOCGPU_API void locgpu_loam_opts_default(locgpu_loam_opts* o);
+/* LoamRegistration::LoamRegistration(LoamOption) (loam_registration.cpp:15-20). The options are checked before any device is touched:
+ * LOCGPU_ERR_INVALID for NULL opts, both classes switched off, LOCGPU_P2PLANE_MAP or an unknown method / search mode in an enabled class.
+ * A context is created for every enabled class. locgpu_loam_last_error(NULL) gives the text of a failed create. */
+LOCGPU_API int locgpu_loam_create(int device_id, const locgpu_loam_opts* opts, locgpu_loam** out);
+LOCGPU_API void locgpu_loam_destroy(locgpu_loam* l);
+LOCGPU_API const char* locgpu_loam_last_error(const locgpu_loam* l);
+/* LoamRegistration::SetInputTarget (loam_registration.cpp:22-36): IcpRegistration::SetInputTarget of every ENABLED class (a class that
+ * is switched off is not ingested; its pointer may be NULL). LOCGPU_OK only if every enabled class was ingested; a class that failed
+ * has no target afterwards (LOCGPU_ERR_NO_TARGET from the calls below). */
+LOCGPU_API int locgpu_loam_set_target(locgpu_loam* l, const void* edge_pts, size_t n_edge, const void* surf_pts, size_t n_surf, size_t stride_bytes);
+/* One evaluation of H = H_surf + H_edge (6×6 row-major), B = B_surf + B_edge at `pose`, no update (loam_registration.cpp:53-77, each
+ * term IcpRegistration::CaculateMatrixHAndB, icp_registration.cpp:31-55). eff[2] / ok[2] (optional): each class's effective_num and
+ * the reference's bool, index 0 = surface, 1 = edge; a class that is switched off adds nothing and reports 0 / 1. The test hook of
+ * the joint reduction. */
+LOCGPU_API int locgpu_loam_hb(locgpu_loam* l, const void* edge, size_t n_edge, const void* surf, size_t n_surf, size_t stride_bytes,
+                              const double pose[7], double H[36], double B[6], int64_t eff[2], int32_t ok[2]);
+/* LoamRegistration::ScanMatch WHOLE (loam_registration.cpp:38-99). result_pose is IN-OUT like the reference's `SE3& result_pose` (and
+ * locgpu_ndt_scan_match): with stats->status 3 or 4 a class's evaluation reported false and ScanMatch returned before
+ * `result_pose = pose` (:56-70) — the caller's value stays, no output cloud is written, the call itself returns LOCGPU_OK; otherwise
+ * it receives the result. stats (optional): status as above, iterations = evaluations made, last_effective_num = the two classes'
+ * counts summed, converged / last_dx_norm as for ICP. out_cloud (optional): n_edge + n_surf points of out_stride_bytes each — the edge
+ * points followed by the surface points (:93-95) under pose.matrix().cast<float>() (:96); only x, y, z of each point are written,
+ * the other fields are the caller's. A switched-off class's scan may be NULL; when it is given its points still join the output cloud. */
+LOCGPU_API int locgpu_loam_scan_match(locgpu_loam* l, const void* edge, size_t n_edge, const void* surf, size_t n_surf, size_t stride_bytes,
+                                      const double init_pose[7], double result_pose[7], locgpu_align_stats* stats, void* out_cloud,
+                                      size_t out_stride_bytes);
+/* Many feature scans against the one pair of maps (no reference counterpart: the reference loops ScanMatch, loam_registration.cpp:38-99,
+ * over scans). Scan i is edge_srcs[i] (edge_counts[i] points) with surf_srcs[i] (surf_counts[i]); every scan runs its own loop and
+ * leaves it on its own. init_poses / out_poses: n_scans × 7; stats: n_scans entries or NULL. out_poses[i] = init_poses[i] for a scan
+ * whose evaluation failed (status 3 / 4). The handle keeps the two classes' storage batches between calls and only grows them; the
+ * partial sums are split by the call's shape, so a scan's last bits may differ between a batch and locgpu_loam_scan_match, never
+ * between two equal calls. LOCGPU_ERR_INVALID for n_scans < 1. */
+LOCGPU_API int locgpu_loam_align_batch(locgpu_loam* l, int n_scans, const void* const* edge_srcs, const size_t* edge_counts,
+                                       const void* const* surf_srcs, const size_t* surf_counts, size_t stride_bytes, const double* init_poses,
+                                       double* out_poses, locgpu_align_stats* stats);
 
 /* ---- MatchingInterface::GetFitnessScore (matching_interface.h:53), which the reference leaves a stub that returns 0
  * (icp_registration.cpp:246-250): how good an alignment is, as pcl::Registration::getFitnessScore defines it. For a source cloud,

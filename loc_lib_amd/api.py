@@ -47,6 +47,8 @@ ABI_SYMBOLS = [
     "locgpu_init_search_opts_default", "locgpu_icp_init_search", "locgpu_pose_grid",
     "locgpu_ndt_fitness", "locgpu_ndt_fitness_batch", "locgpu_ndt_fitness_resident", "locgpu_ndt_init_search",
     "locgpu_icp_build_map_planes", "locgpu_icp_map_planes_info", "locgpu_icp_map_planes_dump",
+    "locgpu_loam_opts_default", "locgpu_loam_create", "locgpu_loam_destroy", "locgpu_loam_last_error", "locgpu_loam_set_target",
+    "locgpu_loam_hb", "locgpu_loam_scan_match", "locgpu_loam_align_batch",
 ]
 COMM_ID_BYTES = 128
 NO_INTENSITY = ctypes.c_size_t(-1).value
@@ -68,6 +70,11 @@ class NdtOpts(ctypes.Structure):
     _fields_ = [("max_iteration", ctypes.c_int32), ("voxel_size", ctypes.c_double), ("min_effective_pts", ctypes.c_int32),
                 ("min_pts_in_voxel", ctypes.c_int32), ("eps", ctypes.c_double), ("res_outlier_th", ctypes.c_double),
                 ("nearby_type", ctypes.c_int32), ("method", ctypes.c_int32), ("capacity", ctypes.c_int64)]
+
+
+class LoamOpts(ctypes.Structure):
+    _fields_ = [("surf", IcpOpts), ("edge", IcpOpts), ("use_surf_points", ctypes.c_int32), ("use_edge_points", ctypes.c_int32),
+                ("max_iteration", ctypes.c_int32), ("eps", ctypes.c_double)]
 
 
 class PoolOpts(ctypes.Structure):
@@ -166,6 +173,11 @@ def lib():
             "locgpu_ndt_init_search": (i32, [vp, vp, sz, sz, vp, i32, vp, vp, vp, vp, vp]),
             "locgpu_icp_build_map_planes": (i32, [vp]), "locgpu_icp_map_planes_info": (i32, [vp, vp]),
             "locgpu_icp_map_planes_dump": (i32, [vp, vp, vp, sz, vp]),
+            "locgpu_loam_opts_default": (None, [vp]), "locgpu_loam_create": (i32, [i32, vp, vp]), "locgpu_loam_destroy": (None, [vp]),
+            "locgpu_loam_last_error": (ctypes.c_char_p, [vp]), "locgpu_loam_set_target": (i32, [vp, vp, sz, vp, sz, sz]),
+            "locgpu_loam_hb": (i32, [vp, vp, sz, vp, sz, sz, vp, vp, vp, vp, vp]),
+            "locgpu_loam_scan_match": (i32, [vp, vp, sz, vp, sz, sz, vp, vp, vp, vp, sz]),
+            "locgpu_loam_align_batch": (i32, [vp, i32, vp, vp, vp, vp, sz, vp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -229,6 +241,17 @@ def init_search_opts(**kw):
     for k, v in kw.items():
         if not hasattr(o, k):
             raise TypeError("unknown initial-pose search option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+def loam_opts(**kw):
+    """LoamOption's defaults (surface P2PLANE, edge P2LINE, 20 iterations, eps 1e-3, both classes on); `surf` / `edge` take IcpOpts."""
+    o = LoamOpts()
+    lib().locgpu_loam_opts_default(ctypes.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError("unknown LOAM option %r" % k)
         setattr(o, k, v)
     return o
 
@@ -925,6 +948,84 @@ class Pool:
 
     def __del__(self):
         self.close()
+
+
+class Loam:
+    """One LoamRegistration on one GPU (locgpu_loam): an edge matcher (P2Line) and a surface matcher (P2Plane) whose joint
+    Gauss–Newton loop runs on the device (loam_registration.cpp:22-99). A feature class that is switched off takes None."""
+
+    def __init__(self, opts=None, device_id=0):
+        self._h = ctypes.c_void_p()
+        self.opts = opts if opts is not None else loam_opts()
+        rc = lib().locgpu_loam_create(device_id, ctypes.byref(self.opts), ctypes.byref(self._h))
+        if rc != 0:
+            raise LocGpuError(rc, lib().locgpu_loam_last_error(None).decode())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().locgpu_loam_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def _check(self, rc):
+        if rc != 0:
+            raise LocGpuError(rc, lib().locgpu_loam_last_error(self._h).decode())
+
+    @staticmethod
+    def _arg(cloud):
+        """(array kept alive, pointer, count, stride) of an optional cloud"""
+        if cloud is None:
+            return None, None, 0, 0
+        c = _cloud(cloud)
+        return c, c.ctypes.data, c.shape[0], c.strides[0]
+
+    @staticmethod
+    def _stride(se, ss):
+        if se and ss and se != ss:
+            raise ValueError("edge and surface clouds must share one point stride")
+        return se or ss or 12
+
+    # ---- LoamRegistration::SetInputTarget
+    def set_target(self, edge_map, surf_map):
+        e, pe, ne, se = self._arg(edge_map)
+        s, ps, ns, ss = self._arg(surf_map)
+        self._check(lib().locgpu_loam_set_target(self._h, pe, ne, ps, ns, self._stride(se, ss)))
+
+    # ---- one evaluation of H_surf + H_edge, B_surf + B_edge; eff / ok per class, index 0 = surface, 1 = edge
+    def hb(self, edge, surf, pose):
+        e, pe, ne, se = self._arg(edge)
+        s, ps, ns, ss = self._arg(surf)
+        H, B = np.zeros(36), np.zeros(6)
+        eff, ok = np.zeros(2, dtype=np.int64), np.zeros(2, dtype=np.int32)
+        self._check(lib().locgpu_loam_hb(self._h, pe, ne, ps, ns, self._stride(se, ss), _pose(pose).ctypes.data, H.ctypes.data, B.ctypes.data,
+                                         eff.ctypes.data, ok.ctypes.data))
+        return H.reshape(6, 6), B, [int(v) for v in eff], [bool(v) for v in ok]
+
+    # ---- LoamRegistration::ScanMatch whole; result_pose in-out (status 3 / 4 leaves it, and the output cloud, as handed in)
+    def scan_match(self, edge, surf, init_pose, result_pose=None, out_cloud=None):
+        """Returns (pose, stats, output cloud [n_edge + n_surf, 3] float32: edge points, then surface points)."""
+        e, pe, ne, se = self._arg(edge)
+        s, ps, ns, ss = self._arg(surf)
+        cloud = out_cloud if out_cloud is not None else np.full((ne + ns, 3), np.nan, np.float32)
+        out = np.array(_pose(result_pose if result_pose is not None else init_pose), copy=True)
+        st = AlignStats()
+        self._check(lib().locgpu_loam_scan_match(self._h, pe, ne, ps, ns, self._stride(se, ss), _pose(init_pose).ctypes.data, out.ctypes.data,
+                                                 ctypes.byref(st), cloud.ctypes.data if cloud.size else None, cloud.strides[0]))
+        return out, _stats_dict(st), cloud
+
+    # ---- many feature scans against the one pair of maps
+    def align_batch(self, edges, surfs, init_poses):
+        """edges / surfs: lists of clouds (None for a class that is switched off). Returns (poses [n, 7], list of stats)."""
+        n = len(edges) if edges is not None else len(surfs)
+        me = Batch._marshal(edges) if edges is not None else (None, None, None, 0)
+        ms = Batch._marshal(surfs) if surfs is not None else (None, None, None, 0)
+        poses = _pose(init_poses).reshape(n, 7)
+        out = np.zeros((n, 7))
+        st = (AlignStats * n)()
+        self._check(lib().locgpu_loam_align_batch(self._h, n, me[1], me[2], ms[1], ms[2], self._stride(me[3], ms[3]), poses.ctypes.data, out.ctypes.data, st))
+        return out, [_stats_dict(x) for x in st]
 
 
 def gn_update(hb, method, min_effective_pts, eps, pose):

@@ -231,7 +231,7 @@ static int batch_ready(locgpu_ctx* ctx, locgpu_batch* b) {
 
 // The grid search hands its leftovers through a second work list. It is allocated here, by every entry point that may run the
 // grid search on `b`, BEFORE any launch: launch() can run under hipStreamBeginCapture, where hipMalloc is not allowed.
-static int ensure_grid_lists(locgpu_ctx* ctx, locgpu_batch* b, const AlignSpec& spec) {
+int ensure_grid_lists(locgpu_ctx* ctx, locgpu_batch* b, const AlignSpec& spec) {
     if (!spec.grid) return LOCGPU_OK;
     if (!b->d_grid_qkey) {
         LOCGPU_HIP(ctx, hipMalloc((void**)&b->d_grid_qkey, b->pitch * sizeof(uint32_t)));

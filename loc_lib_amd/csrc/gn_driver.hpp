@@ -38,6 +38,9 @@ struct LocalStage {
 // them. Returns the number of partial blocks per scan the solve (or launch_sum_partials) must sum; < 0 on failure (fail() was called).
 int launch_local_stage(locgpu_ctx* ctx, locgpu_batch* b, const LocalStage& w, hipStream_t s);
 
+// The grid search's work lists of `b` (no-op unless spec.grid): every caller of launch_local_stage allocates them BEFORE its launches.
+int ensure_grid_lists(locgpu_ctx* ctx, locgpu_batch* b, const AlignSpec& spec);
+
 // The owner of a scan solves it ahead of the exchange, which then runs on the communication stream. LOCGPU_SHARD_DECOUPLED=0|1
 // forces either way; default: with more than one rank.
 bool shard_decoupled(const locgpu_ctx* ctx, bool scan_sharded);

@@ -494,6 +494,78 @@ __global__ __launch_bounds__(kBlock) void gn_solve_kernel(const double* __restri
     }
 }
 
+// The LOAM matcher's solve (loam_registration.cpp:47-90): one 256-thread block per scan over TWO sets of block partials — the surface
+// class's, then the edge class's, each summed in reduce_partials' fixed order with its own blocks_per_scan. Thread 0 then applies the
+// reference's rules: a class is false iff its effective_num < min_effective_pts or its own det(H) == 0 (icp_registration.cpp:204-211),
+// surface tested first (:53-70: status 3 / 4, the alignment ends, the pose is not handed out); otherwise dx = (H_surf + H_edge)⁻¹
+// (B_surf + B_edge) with NO test on the sum (:76-79), the decoupled update (:82-83) and the stop at |dx| < eps (:85). det(H_sum) == 0 —
+// where the reference divides by zero — is an iteration without an update, as locgpu_gn_update has it. The three factorisations run
+// one after the other through the same H, B registers. Both classes' local stages read the ONE PoseState written here.
+__global__ __launch_bounds__(kBlock) void loam_solve_kernel(LoamSolveArgs a) {
+    __shared__ double s_sum[kBlock / kAccW][kAccW];
+    __shared__ double s_tot[2][kAccW];
+    const int scan = a.scans ? a.scans[blockIdx.x] : (int)blockIdx.x;
+    // both batches' search work lists are consumed by now (see gn_solve_kernel)
+    if (blockIdx.x == 0 && threadIdx.x < 4) {
+        if (a.list_counts[0]) a.list_counts[0][threadIdx.x] = 0u;
+        if (a.list_counts[1]) a.list_counts[1][threadIdx.x] = 0u;
+    }
+    if (a.st[scan].done) return;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        double t = 0.0;
+        if (a.partials[c]) t = reduce_partials(a.partials[c] + (size_t)scan * a.blocks_per_scan[c] * kAccW, a.blocks_per_scan[c], true, s_sum);
+        if (threadIdx.x < kAccW) s_tot[c][threadIdx.x] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    PoseState& ps = a.st[scan];
+    double H[36], B[6], dx[6];
+    long long eff[2] = {0, 0};
+    bool ok[2] = {true, true};  // a class that is switched off is never evaluated: it cannot report false
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        if (!a.partials[c]) continue;
+        int o = 0;
+        for (int i = 0; i < 6; ++i)
+            for (int j = i; j < 6; ++j) { H[6 * i + j] = s_tot[c][o]; H[6 * j + i] = s_tot[c][o]; ++o; }
+        for (int i = 0; i < 6; ++i) B[i] = s_tot[c][21 + i];
+        eff[c] = (long long)s_tot[c][27];
+        const double det_c = lu6_det_solve_reg(H, B, dx);
+        ok[c] = (eff[c] >= a.min_effective_pts[c]) && !(det_c == 0.0);
+    }
+    {
+        int o = 0;
+        for (int i = 0; i < 6; ++i)
+            for (int j = i; j < 6; ++j) { const double v = s_tot[0][o] + s_tot[1][o]; H[6 * i + j] = v; H[6 * j + i] = v; ++o; }
+        for (int i = 0; i < 6; ++i) { B[i] = s_tot[0][21 + i] + s_tot[1][21 + i]; dx[i] = 0.0; }
+    }
+    if (a.hb_out) {
+        double* hb = a.hb_out + (size_t)kLoamHbW * scan;
+        for (int i = 0; i < 36; ++i) hb[i] = H[i];
+        for (int i = 0; i < 6; ++i) hb[36 + i] = B[i];
+        hb[42] = (double)eff[0]; hb[43] = (double)eff[1];
+        hb[44] = ok[0] ? 1.0 : 0.0; hb[45] = ok[1] ? 1.0 : 0.0;
+    }
+    ps.last_eff = eff[0] + eff[1];
+    if (!a.do_update) return;
+    ps.iterations += 1;
+    if (!ok[0] || !ok[1]) {
+        ps.status = !ok[0] ? 3 : 4;
+        ps.done = 1;
+        return;
+    }
+    const double det = lu6_det_solve_reg(H, B, dx);
+    if (!(det == 0.0)) {
+        se3_apply_update(ps.q, ps.t, dx);
+        quat_to_R(ps.q, ps.R);
+        const double nrm = sqrt((dx[0] * dx[0] + (dx[2] * dx[2] + dx[4] * dx[4])) + (dx[1] * dx[1] + (dx[3] * dx[3] + dx[5] * dx[5])));  // as gn_update sums it
+        ps.last_dx_norm = nrm;
+        if (nrm < a.eps) { ps.converged = 1; ps.done = 1; }
+    }
+    if (ps.iterations >= a.max_iteration) ps.done = 1;
+}
+
 // First half of gn_solve_kernel for sharded batches (see launch.hpp): one block per GLOBAL scan.
 // owned (optional, scan pools): owned[g] != 0 where this rank holds the points of slot g; then first = 0 and n_local = all slots.
 __global__ __launch_bounds__(kBlock) void sum_partials_kernel(const double* __restrict__ partials, int blocks_per_scan, const PoseState* __restrict__ st_all,
@@ -556,6 +628,10 @@ int launch_icp_accum(int method, const AccumArgs& a, hipStream_t s) {
 void launch_gn_solve(const double* partials, int blocks_per_scan, PoseState* st, int n_scans, const GnParams& prm, int do_update, double* hb_out,
                      unsigned int* list_counts, hipStream_t s, const int* scans, const GnPost* post) {
     hipLaunchKernelGGL(gn_solve_kernel, dim3(n_scans), dim3(kBlock), 0, s, partials, blocks_per_scan, st, prm, do_update, hb_out, list_counts, scans, post ? *post : GnPost{});
+}
+
+void launch_loam_solve(const LoamSolveArgs& a, int n_scans, hipStream_t s) {
+    hipLaunchKernelGGL(loam_solve_kernel, dim3(n_scans), dim3(kBlock), 0, s, a);
 }
 
 void launch_sum_partials(const double* partials, int blocks_per_scan, const PoseState* st_all, int first, int n_local, int n_total, double* acc,

@@ -74,6 +74,25 @@ int launch_icp_accum(int method, const AccumArgs& a, hipStream_t s);
 // post (optional, one scan): the solve also writes an iteration word — and, once the scan is done, its result — to pinned host memory
 void launch_gn_solve(const double* partials, int blocks_per_scan, PoseState* st, int n_scans, const GnParams& prm, int do_update, double* hb_out,
                      unsigned int* list_counts, hipStream_t s, const int* scans = nullptr, const GnPost* post = nullptr);
+// The joint solve of the LOAM matcher (loam_registration.cpp:47-90; loam_align.hip): class 0 = surface, 1 = edge. One block per scan
+// sums the surface batch's partials, then the edge batch's (each with its own blocks_per_scan, in gn_solve's fixed order), tests each
+// class as IcpRegistration::CaculateMatrixHAndB does (icp_registration.cpp:204-211), solves the SUM and updates the one PoseState
+// both classes' local stages read. partials[c] == nullptr: the class is switched off. hb_out (optional): kLoamHbW doubles per scan =
+// H (36, row-major) and B (6) of the sum, effective_num[2], ok[2]. list_counts[c]: the class batch's search work-list counters, zeroed.
+constexpr int kLoamHbW = 46;
+struct LoamSolveArgs {
+    const double* partials[2];
+    int blocks_per_scan[2];
+    int min_effective_pts[2];
+    unsigned int* list_counts[2];
+    int max_iteration;
+    double eps;
+    PoseState* st;
+    int do_update;
+    double* hb_out;
+    const int* scans;  // optional: n_scans indices — block i solves scan scans[i]
+};
+void launch_loam_solve(const LoamSolveArgs& a, int n_scans, hipStream_t s);
 int icp_accum_split(int method, int max_n, int n_scans);  // points per thread of the accumulate kernels (the split of the partial sums)
 // Sharded batches: acc[g][0..28) = sum of the block partials of global scan g when this rank holds it (local index g - first),
 // zeros otherwise — in exactly the order gn_solve_kernel sums them, so that all-reduce(acc) followed by gn_solve on acc

@@ -1,0 +1,493 @@
+// loc_lib_amd/csrc/loam_align.hip — the LOAM matcher (LoamRegistration, loam_registration.cpp:22-99) behind locgpu_loam_*.
+//
+// A locgpu_loam owns what one LoamRegistration owns: a surface matcher (P2Plane) and an edge matcher (P2Line), here two locgpu_ctx on
+// one device, each with one storage batch for its feature scans, and the JOINT alignment state: one PoseState per scan that both
+// classes' local stages read and loam_solve_kernel (icp_fit.hip) writes. One Gauss–Newton iteration is, on ONE stream,
+//     launch_local_stage(surface) → launch_local_stage(edge) → loam_solve_kernel
+// in eager chunks of kFirstChunk / kNextChunk iterations between two host reads of the flags, later chunks over the open scans only —
+// the chunks of align_begin / align_finish (gn_driver.hip) without graphs, shards, pools or host pacing.
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "batch_upload.hpp"
+#include "context.hpp"
+#include "gn_driver.hpp"
+#include "launch.hpp"
+
+using namespace locgpu;
+
+namespace {
+constexpr int kSurf = 0, kEdge = 1;  // the order the reference evaluates them in (loam_registration.cpp:53-71)
+}
+
+struct locgpu_loam {
+    int device = 0;
+    locgpu_loam_opts opts{};
+    bool use[2] = {false, false};
+    locgpu_ctx* ctx[2] = {nullptr, nullptr};
+    locgpu_batch* batch[2] = {nullptr, nullptr};  // storage batches: kept between calls, grow-only, reshaped to the call's scans
+    bool has_target[2] = {false, false};
+    hipStream_t stream = nullptr;  // the first enabled class's context stream: every launch of an alignment
+    hipEvent_t ev = nullptr;       // orders `stream` behind the other context's stream
+    // joint state, for cap_scans scans
+    int cap_scans = 0;
+    PoseState* d_state = nullptr;
+    PoseState* h_state = nullptr;  // pinned
+    double* d_hb = nullptr;
+    double* h_hb = nullptr;        // pinned
+    int* d_active = nullptr;
+    int* h_active = nullptr;       // pinned
+    // output cloud of scan_match: packed x, y, z of edge then surface points; the points of a switched-off class pass through d_off
+    size_t cap_xyz = 0;
+    float* d_xyz = nullptr;
+    float* h_xyz = nullptr;        // pinned
+    size_t cap_off = 0;
+    float4* d_off = nullptr;
+    float4* h_off = nullptr;       // pinned
+    std::string err;
+};
+
+namespace {
+
+std::string g_loam_create_err;
+
+int lfail(locgpu_loam* l, int code, const std::string& msg) {
+    if (l) l->err = msg;
+    else g_loam_create_err = msg;
+    return code;
+}
+// a failure inside one of the two contexts: its text becomes the handle's
+int from_ctx(locgpu_loam* l, int c, int rc) {
+    if (rc != LOCGPU_OK) l->err = std::string(c == kSurf ? "surface: " : "edge: ") + locgpu_last_error(l->ctx[c]);
+    return rc;
+}
+bool lhip(locgpu_loam* l, hipError_t e, const char* what) {
+    if (e == hipSuccess) return true;
+    lfail(l, LOCGPU_ERR_NO_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+    return false;
+}
+#define LOAM_HIP(l, expr)                                         \
+    do {                                                          \
+        if (!lhip((l), (expr), #expr)) return LOCGPU_ERR_NO_DEVICE; \
+    } while (0)
+
+const locgpu_icp_opts& class_opts(const locgpu_loam* l, int c) { return c == kSurf ? l->opts.surf : l->opts.edge; }
+
+int check_opts(const locgpu_loam_opts* o) {
+    if (!o) return lfail(nullptr, LOCGPU_ERR_INVALID, "loam_create: opts is NULL");
+    if (!o->use_surf_points && !o->use_edge_points) return lfail(nullptr, LOCGPU_ERR_INVALID, "loam_create: both feature classes are switched off");
+    const locgpu_icp_opts* cls[2] = {&o->surf, &o->edge};
+    const int32_t use[2] = {o->use_surf_points, o->use_edge_points};
+    for (int c = 0; c < 2; ++c) {
+        if (!use[c]) continue;
+        if (cls[c]->method == LOCGPU_P2PLANE_MAP) return lfail(nullptr, LOCGPU_ERR_INVALID, "loam_create: LOCGPU_P2PLANE_MAP is not available in the LOAM matcher");
+        if (cls[c]->method < LOCGPU_P2P || cls[c]->method > LOCGPU_P2PLANE) return lfail(nullptr, LOCGPU_ERR_INVALID, "loam_create: unknown method");
+        if (cls[c]->search_mode != LOCGPU_SEARCH_TREE_FAITHFUL && cls[c]->search_mode != LOCGPU_SEARCH_GRID_EXACT)
+            return lfail(nullptr, LOCGPU_ERR_INVALID, "loam_create: unknown search mode");
+    }
+    return LOCGPU_OK;
+}
+
+void free_joint(locgpu_loam* l) {
+    if (l->d_state) (void)hipFree(l->d_state);
+    if (l->h_state) (void)hipHostFree(l->h_state);
+    if (l->d_hb) (void)hipFree(l->d_hb);
+    if (l->h_hb) (void)hipHostFree(l->h_hb);
+    if (l->d_active) (void)hipFree(l->d_active);
+    if (l->h_active) (void)hipHostFree(l->h_active);
+    l->d_state = nullptr; l->h_state = nullptr; l->d_hb = nullptr; l->h_hb = nullptr; l->d_active = nullptr; l->h_active = nullptr;
+    l->cap_scans = 0;
+}
+
+int reserve_joint(locgpu_loam* l, int n) {
+    if (n <= l->cap_scans) return LOCGPU_OK;
+    free_joint(l);
+    const bool ok = lhip(l, hipMalloc((void**)&l->d_state, (size_t)n * sizeof(PoseState)), "hipMalloc state") &&
+                    lhip(l, hipHostMalloc((void**)&l->h_state, (size_t)n * sizeof(PoseState)), "hipHostMalloc state") &&
+                    lhip(l, hipMalloc((void**)&l->d_hb, (size_t)n * kLoamHbW * sizeof(double)), "hipMalloc hb") &&
+                    lhip(l, hipHostMalloc((void**)&l->h_hb, (size_t)n * kLoamHbW * sizeof(double)), "hipHostMalloc hb") &&
+                    lhip(l, hipMalloc((void**)&l->d_active, (size_t)n * sizeof(int)), "hipMalloc active") &&
+                    lhip(l, hipHostMalloc((void**)&l->h_active, (size_t)n * sizeof(int)), "hipHostMalloc active");
+    if (!ok) { free_joint(l); return LOCGPU_ERR_OOM; }
+    l->cap_scans = n;
+    return LOCGPU_OK;
+}
+
+// Class c's storage batch shaped as n_scans scans of at most max_n points: the one of the previous call when it has the room
+// (cap_scans × cap_points — everything the kernels index goes through n_scans / max_n / pitch, so a smaller shape is the same batch as
+// one created at that size), a larger one otherwise. A one-scan call gets headroom in points, as a per-scan caller's clouds vary.
+int shape_batch(locgpu_loam* l, int c, int n_scans, size_t max_n) {
+    locgpu_ctx* ctx = l->ctx[c];
+    locgpu_batch* b = l->batch[c];
+    max_n = std::max<size_t>(max_n, 1);
+    if (!b || b->cap_scans < n_scans || b->cap_points < max_n) {
+        const int cs = std::max(n_scans, b ? b->cap_scans : 0);
+        size_t cp = std::max(max_n, b ? b->cap_points : (size_t)0);
+        if (cp == max_n && n_scans == 1) cp = max_n + max_n / 4 + 1024;
+        if (b) { (void)hipStreamSynchronize(l->stream); free_batch(b); l->batch[c] = nullptr; }
+        int rc = from_ctx(l, c, alloc_batch(ctx, cs, cp, &l->batch[c]));
+        if (rc != LOCGPU_OK) return rc;
+        b = l->batch[c];
+        b->slot = 0;
+        b->stream = ctx->stream;
+        // the uploader's pinned counts are sized by the batch's scans at its first upload: give it the capacity's worth now
+        if (!lhip(l, hipHostMalloc((void**)&b->upl.h_counts, (size_t)cs * sizeof(int)), "hipHostMalloc counts")) return LOCGPU_ERR_OOM;
+    }
+    if (b->n_scans != n_scans || (size_t)b->max_n != max_n) {
+        if ((size_t)n_scans * max_n > b->pitch) {  // the grid search's lists were sized by the old pitch (ensure_grid_lists)
+            if (b->d_grid_qkey) { (void)hipFree(b->d_grid_qkey); b->d_grid_qkey = nullptr; }
+            if (b->d_grid_sorted) { (void)hipFree(b->d_grid_sorted); b->d_grid_sorted = nullptr; }
+        }
+        b->n_scans = b->n_total = n_scans;
+        b->max_n = (int)max_n;
+        b->blocks_per_scan = (int)((max_n + kBlock - 1) / kBlock);
+        b->pitch = (size_t)n_scans * max_n;
+        b->counts.assign(n_scans, 0);
+    }
+    return LOCGPU_OK;
+}
+
+// The deep copy of the feature scans (SetSource, icp_registration.cpp:252-265) into both classes' storage batches; `stream` is ordered
+// behind the copies and behind whatever either context's own stream still runs (its target ingest).
+int upload_scans(locgpu_loam* l, int n_scans, const void* const* srcs[2], const size_t* counts[2], size_t stride) {
+    size_t max_n[2] = {0, 0};
+    for (int c = 0; c < 2; ++c) {  // every argument is checked before the first copy starts: a refused call reads nothing
+        if (!l->use[c]) continue;
+        if (!srcs[c] || !counts[c]) return lfail(l, LOCGPU_ERR_INVALID, "loam: the scans of an enabled feature class are NULL");
+        for (int i = 0; i < n_scans; ++i) {
+            if (counts[c][i] && !srcs[c][i]) return lfail(l, LOCGPU_ERR_INVALID, "loam: NULL scan pointer");
+            if (counts[c][i] > 0x7FFFFF00u) return lfail(l, LOCGPU_ERR_INVALID, "loam: too many points in a scan");
+            max_n[c] = std::max(max_n[c], counts[c][i]);
+        }
+    }
+    int rc = LOCGPU_OK;
+    bool started[2] = {false, false};
+    for (int c = 0; c < 2 && rc == LOCGPU_OK; ++c) {
+        if (!l->use[c]) continue;
+        rc = shape_batch(l, c, n_scans, max_n[c]);
+        if (rc == LOCGPU_OK) rc = from_ctx(l, c, upload_start(l->batch[c], srcs[c], counts[c], stride));
+        started[c] = rc == LOCGPU_OK;
+    }
+    for (int c = 0; c < 2; ++c) {  // the caller's clouds are read until the join: also on the way out of a failed call
+        if (!started[c]) continue;
+        const int jrc = upload_join_batch(l->batch[c]);
+        if (rc == LOCGPU_OK) rc = from_ctx(l, c, jrc);
+    }
+    if (rc != LOCGPU_OK) return rc;
+    for (int c = 0; c < 2; ++c) {
+        if (!l->use[c]) continue;
+        LOAM_HIP(l, upload_order_after(l->batch[c], l->stream));
+        if (l->ctx[c]->stream != l->stream) {
+            LOAM_HIP(l, hipEventRecord(l->ev, l->ctx[c]->stream));
+            LOAM_HIP(l, hipStreamWaitEvent(l->stream, l->ev, 0));
+        }
+    }
+    return LOCGPU_OK;
+}
+
+// Both classes' requests against their current targets (check_icp: the asynchronous ingest ends here, the grid is built on first use).
+int check_classes(locgpu_loam* l, AlignSpec spec[2], const char* who) {
+    for (int c = 0; c < 2; ++c) {
+        if (!l->use[c]) continue;
+        if (!l->has_target[c]) return lfail(l, LOCGPU_ERR_NO_TARGET, std::string(who) + ": locgpu_loam_set_target has not been called");
+        const int rc = from_ctx(l, c, check_icp(l->ctx[c], &class_opts(l, c), spec[c]));
+        if (rc != LOCGPU_OK) return rc;
+    }
+    return LOCGPU_OK;
+}
+
+// The alignment of the n scans resident in the storage batches (do_update = 1), or one evaluation at the poses (do_update = 0: the
+// sums land in l->h_hb). Leaves the stream idle and the states in l->h_state.
+int run(locgpu_loam* l, int n, const double* poses, const AlignSpec spec[2], int do_update) {
+    hipStream_t s = l->stream;
+    const int max_iteration = do_update ? l->opts.max_iteration : 1;
+    for (int i = 0; i < n; ++i) init_state(l->h_state[i], poses + 7 * (size_t)i);
+    GridSearchScratch gsc[2];
+    for (int c = 0; c < 2; ++c) {
+        if (!l->use[c]) continue;
+        locgpu_batch* b = l->batch[c];
+        const int grc = from_ctx(l, c, ensure_grid_lists(l->ctx[c], b, spec[c]));
+        if (grc != LOCGPU_OK) return grc;
+        gsc[c] = GridSearchScratch{b->d_grid_qkey, b->d_grid_sorted, b->d_grid_tile_count, b->d_grid_scan_temp};
+        b->stage_ev.mode = 0;
+        b->stage_ev.used = 0;
+        b->counters_clean = false;
+        LOAM_HIP(l, hipMemsetAsync(b->d_redo_count, 0, 4 * sizeof(unsigned int), s));
+    }
+    LOAM_HIP(l, hipMemcpyAsync(l->d_state, l->h_state, (size_t)n * sizeof(PoseState), hipMemcpyHostToDevice, s));
+    LoamSolveArgs sa{};
+    sa.max_iteration = max_iteration;
+    sa.eps = l->opts.eps;
+    sa.st = l->d_state;
+    sa.do_update = do_update;
+    sa.hb_out = do_update ? nullptr : l->d_hb;
+    for (int c = 0; c < 2; ++c) {
+        sa.partials[c] = l->use[c] ? l->batch[c]->d_partials : nullptr;
+        sa.min_effective_pts[c] = class_opts(l, c).min_effective_pts;
+        sa.list_counts[c] = l->use[c] ? l->batch[c]->d_redo_count : nullptr;
+    }
+    int launched = 0, rc = LOCGPU_OK;
+    for (bool first = true; launched < max_iteration; first = false) {
+        const int* active = nullptr;
+        int n_active = 0;
+        if (!first && n > 1) {  // later chunks run over the scans still open (enqueue_chunk, gn_driver.hip)
+            for (int i = 0; i < n; ++i)
+                if (!l->h_state[i].done) l->h_active[n_active++] = i;
+            if (n_active < n) {
+                LOAM_HIP(l, hipMemcpyAsync(l->d_active, l->h_active, (size_t)n_active * sizeof(int), hipMemcpyHostToDevice, s));
+                active = l->d_active;
+            }
+        }
+        const int todo = std::min(first ? kFirstChunk : kNextChunk, max_iteration - launched);
+        for (int it = 0; it < todo && rc == LOCGPU_OK; ++it) {
+            for (int c = 0; c < 2 && rc == LOCGPU_OK; ++c) {
+                if (!l->use[c]) continue;
+                locgpu_batch* b = l->batch[c];
+                const LocalStage w{batch_src(b), l->d_state, active, active ? n_active : 0, nullptr, 0, spec[c], nullptr, b->d_grid_qkey ? &gsc[c] : nullptr, false,
+                                   c == kSurf ? "loam surface search" : "loam edge search"};
+                const int blocks = launch_local_stage(l->ctx[c], b, w, s);
+                if (blocks < 0) rc = from_ctx(l, c, LOCGPU_ERR_DEPTH);
+                sa.blocks_per_scan[c] = blocks;
+            }
+            if (rc != LOCGPU_OK) break;
+            sa.scans = active;
+            launch_loam_solve(sa, active ? n_active : n, s);
+            if (!lhip(l, hipGetLastError(), "kernel launch")) rc = LOCGPU_ERR_NO_DEVICE;
+        }
+        if (rc != LOCGPU_OK) { (void)hipStreamSynchronize(s); return rc; }  // nothing of the chunk runs on under the next upload
+        launched += todo;
+        LOAM_HIP(l, hipMemcpyAsync(l->h_state, l->d_state, (size_t)n * sizeof(PoseState), hipMemcpyDeviceToHost, s));
+        if (!do_update) LOAM_HIP(l, hipMemcpyAsync(l->h_hb, l->d_hb, (size_t)n * kLoamHbW * sizeof(double), hipMemcpyDeviceToHost, s));
+        LOAM_HIP(l, hipStreamSynchronize(s));
+        bool all_done = true;
+        for (int i = 0; i < n; ++i)
+            if (!l->h_state[i].done) { all_done = false; break; }
+        if (all_done) break;
+    }
+    if (launched == 0) LOAM_HIP(l, hipStreamSynchronize(s));  // max_iteration < 1: the state copy still reads the pinned poses
+    for (int c = 0; c < 2; ++c)
+        if (l->use[c]) l->batch[c]->counters_clean = true;  // every search was followed by its solve kernel, which zeroes them
+    return LOCGPU_OK;
+}
+
+void write_stats(const PoseState& ps, locgpu_align_stats* st) {
+    if (!st) return;
+    st->iterations = ps.iterations; st->converged = ps.converged; st->status = ps.status; st->reserved = 0;
+    st->last_effective_num = ps.last_eff; st->last_dx_norm = ps.last_dx_norm;
+}
+
+// *cloud += *edge; *cloud += *surf; pcl::transformPointCloud(*cloud, *result, pose.matrix().cast<float>()) (loam_registration.cpp:93-96):
+// x, y, z of the edge points, then of the surface points, into the caller's points. An enabled class's points are in HBM from the
+// alignment; a switched-off class's (when the caller hands them) are uploaded here.
+int write_output(locgpu_loam* l, const void* src[2], const size_t n_pts[2], size_t stride, const double pose[7], void* out, size_t out_stride) {
+    const size_t n_all = n_pts[kEdge] + n_pts[kSurf];
+    if (n_all == 0) return LOCGPU_OK;
+    hipStream_t s = l->stream;
+    if (n_all > l->cap_xyz) {
+        if (l->d_xyz) (void)hipFree(l->d_xyz);
+        if (l->h_xyz) (void)hipHostFree(l->h_xyz);
+        l->d_xyz = nullptr; l->h_xyz = nullptr; l->cap_xyz = 0;
+        const size_t cap = n_all + n_all / 4 + 1024;
+        if (!lhip(l, hipMalloc((void**)&l->d_xyz, cap * 3 * sizeof(float)), "hipMalloc output cloud") ||
+            !lhip(l, hipHostMalloc((void**)&l->h_xyz, cap * 3 * sizeof(float)), "hipHostMalloc output cloud"))
+            return LOCGPU_ERR_OOM;
+        l->cap_xyz = cap;
+    }
+    double R[9];
+    quat_to_R(pose, R);
+    M12f m;
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) m.v[4 * r + c] = (float)R[3 * r + c];
+        m.v[4 * r + 3] = (float)pose[4 + r];
+    }
+    const int order[2] = {kEdge, kSurf};
+    size_t at = 0;
+    for (int k = 0; k < 2; ++k) {
+        const int c = order[k];
+        const size_t n = n_pts[c];
+        if (n == 0) continue;
+        const float4* d_pts = nullptr;
+        if (l->use[c]) {
+            d_pts = l->batch[c]->d_src;  // scan 0 of the one-scan shape
+        } else {
+            if (n > l->cap_off) {
+                if (l->d_off) (void)hipFree(l->d_off);
+                if (l->h_off) (void)hipHostFree(l->h_off);
+                l->d_off = nullptr; l->h_off = nullptr; l->cap_off = 0;
+                const size_t cap = n + n / 4 + 1024;
+                if (!lhip(l, hipMalloc((void**)&l->d_off, cap * sizeof(float4)), "hipMalloc output cloud") ||
+                    !lhip(l, hipHostMalloc((void**)&l->h_off, cap * sizeof(float4)), "hipHostMalloc output cloud"))
+                    return LOCGPU_ERR_OOM;
+                l->cap_off = cap;
+            }
+            pack_points((const char*)src[c], stride, n, l->h_off);
+            LOAM_HIP(l, hipMemcpyAsync(l->d_off, l->h_off, n * sizeof(float4), hipMemcpyHostToDevice, s));
+            d_pts = l->d_off;
+        }
+        launch_transform_cloud(d_pts, n, m, l->d_xyz + 3 * at, s);
+        at += n;
+    }
+    LOAM_HIP(l, hipGetLastError());
+    LOAM_HIP(l, hipMemcpyAsync(l->h_xyz, l->d_xyz, n_all * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+    LOAM_HIP(l, hipStreamSynchronize(s));
+    char* ob = (char*)out;
+    for (size_t i = 0; i < n_all; ++i) std::memcpy(ob + i * out_stride, l->h_xyz + 3 * i, 12);
+    return LOCGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void locgpu_loam_opts_default(locgpu_loam_opts* o) {
+    if (!o) return;
+    locgpu_icp_opts_default(&o->surf);
+    locgpu_icp_opts_default(&o->edge);
+    o->surf.method = LOCGPU_P2PLANE;  // LoamOption::surf_icp_option_{IcpMethod::P2PLANE}, loam_registration.hpp:25
+    o->edge.method = LOCGPU_P2LINE;   // edge_icp_option_{IcpMethod::P2LINE}, :26
+    o->use_surf_points = 1;
+    o->use_edge_points = 1;
+    o->max_iteration = 20;
+    o->eps = 1e-3;
+}
+
+int locgpu_loam_create(int device_id, const locgpu_loam_opts* opts, locgpu_loam** out) {
+    if (!out) return lfail(nullptr, LOCGPU_ERR_INVALID, "loam_create: out is NULL");
+    *out = nullptr;
+    int rc = check_opts(opts);  // before any device call: a refusal needs no GPU
+    if (rc != LOCGPU_OK) return rc;
+    auto* l = new locgpu_loam();
+    l->device = device_id;
+    l->opts = *opts;
+    l->use[kSurf] = opts->use_surf_points != 0;
+    l->use[kEdge] = opts->use_edge_points != 0;
+    for (int c = 0; c < 2 && rc == LOCGPU_OK; ++c) {
+        if (!l->use[c]) continue;
+        rc = locgpu_create(device_id, &l->ctx[c]);
+        if (rc != LOCGPU_OK) g_loam_create_err = locgpu_last_error(nullptr);
+        else if (!l->stream) l->stream = l->ctx[c]->stream;
+    }
+    if (rc == LOCGPU_OK && hipEventCreateWithFlags(&l->ev, hipEventDisableTiming) != hipSuccess) rc = lfail(nullptr, LOCGPU_ERR_NO_DEVICE, "loam_create: hipEventCreate");
+    if (rc != LOCGPU_OK) { locgpu_loam_destroy(l); return rc; }
+    *out = l;
+    return LOCGPU_OK;
+}
+
+void locgpu_loam_destroy(locgpu_loam* l) {
+    if (!l) return;
+    (void)hipSetDevice(l->device);
+    if (l->stream) (void)hipStreamSynchronize(l->stream);
+    for (int c = 0; c < 2; ++c) {
+        if (l->batch[c]) free_batch(l->batch[c]);
+        l->batch[c] = nullptr;
+    }
+    free_joint(l);
+    if (l->d_xyz) (void)hipFree(l->d_xyz);
+    if (l->h_xyz) (void)hipHostFree(l->h_xyz);
+    if (l->d_off) (void)hipFree(l->d_off);
+    if (l->h_off) (void)hipHostFree(l->h_off);
+    if (l->ev) (void)hipEventDestroy(l->ev);
+    for (int c = 0; c < 2; ++c) locgpu_destroy(l->ctx[c]);
+    delete l;
+}
+
+const char* locgpu_loam_last_error(const locgpu_loam* l) { return l ? l->err.c_str() : g_loam_create_err.c_str(); }
+
+int locgpu_loam_set_target(locgpu_loam* l, const void* edge_pts, size_t n_edge, const void* surf_pts, size_t n_surf, size_t stride_bytes) {
+    if (!l) return LOCGPU_ERR_INVALID;
+    const void* pts[2] = {surf_pts, edge_pts};
+    const size_t n[2] = {n_surf, n_edge};
+    int rc = LOCGPU_OK;
+    // like the reference (loam_registration.cpp:24-34) every enabled class is handed its cloud, whatever happened to the other
+    for (int c = 0; c < 2; ++c) {
+        if (!l->use[c]) continue;
+        const int r = from_ctx(l, c, locgpu_icp_set_target(l->ctx[c], pts[c], n[c], stride_bytes));
+        l->has_target[c] = r == LOCGPU_OK;
+        if (r != LOCGPU_OK && rc == LOCGPU_OK) rc = r;
+    }
+    return rc;
+}
+
+int locgpu_loam_hb(locgpu_loam* l, const void* edge, size_t n_edge, const void* surf, size_t n_surf, size_t stride_bytes, const double pose[7], double H[36],
+                   double B[6], int64_t eff[2], int32_t ok[2]) {
+    if (!l) return LOCGPU_ERR_INVALID;
+    if (!pose || !H || !B || stride_bytes < 12) return lfail(l, LOCGPU_ERR_INVALID, "loam_hb: bad arguments");
+    AlignSpec spec[2];
+    int rc = check_classes(l, spec, "loam_hb");
+    if (rc != LOCGPU_OK) return rc;
+    LOAM_HIP(l, hipSetDevice(l->device));
+    const void* s1[2] = {surf, edge};
+    const size_t c1[2] = {n_surf, n_edge};
+    const void* const* srcs[2] = {&s1[kSurf], &s1[kEdge]};
+    const size_t* counts[2] = {&c1[kSurf], &c1[kEdge]};
+    rc = reserve_joint(l, 1);
+    if (rc == LOCGPU_OK) rc = upload_scans(l, 1, srcs, counts, stride_bytes);
+    if (rc == LOCGPU_OK) rc = run(l, 1, pose, spec, 0);
+    if (rc != LOCGPU_OK) return rc;
+    std::memcpy(H, l->h_hb, 36 * sizeof(double));
+    std::memcpy(B, l->h_hb + 36, 6 * sizeof(double));
+    for (int c = 0; c < 2; ++c) {
+        if (eff) eff[c] = (int64_t)l->h_hb[42 + c];
+        if (ok) ok[c] = l->h_hb[44 + c] != 0.0;
+    }
+    return LOCGPU_OK;
+}
+
+int locgpu_loam_scan_match(locgpu_loam* l, const void* edge, size_t n_edge, const void* surf, size_t n_surf, size_t stride_bytes, const double init_pose[7],
+                           double result_pose[7], locgpu_align_stats* stats, void* out_cloud, size_t out_stride_bytes) {
+    if (!l) return LOCGPU_ERR_INVALID;
+    if (!init_pose || !result_pose || stride_bytes < 12 || (out_cloud && out_stride_bytes < 12)) return lfail(l, LOCGPU_ERR_INVALID, "loam_scan_match: bad arguments");
+    AlignSpec spec[2];
+    int rc = check_classes(l, spec, "loam_scan_match");
+    if (rc != LOCGPU_OK) return rc;
+    LOAM_HIP(l, hipSetDevice(l->device));
+    const void* s1[2] = {surf, edge};
+    const size_t c1[2] = {n_surf, n_edge};
+    const void* const* srcs[2] = {&s1[kSurf], &s1[kEdge]};
+    const size_t* counts[2] = {&c1[kSurf], &c1[kEdge]};
+    rc = reserve_joint(l, 1);
+    if (rc == LOCGPU_OK) rc = upload_scans(l, 1, srcs, counts, stride_bytes);
+    if (rc == LOCGPU_OK) rc = run(l, 1, init_pose, spec, 1);
+    if (rc != LOCGPU_OK) return rc;
+    const PoseState& ps = l->h_state[0];
+    write_stats(ps, stats);
+    if (ps.status != 0) return LOCGPU_OK;  // `return false` before `result_pose = pose` (loam_registration.cpp:56-70): the caller's value and cloud stay
+    for (int j = 0; j < 4; ++j) result_pose[j] = ps.q[j];
+    for (int j = 0; j < 3; ++j) result_pose[4 + j] = ps.t[j];
+    if (!out_cloud) return LOCGPU_OK;
+    // a switched-off class takes part in the output cloud when the caller hands its points (the reference adds both, :93-95)
+    const size_t n_out[2] = {(l->use[kSurf] || surf) ? n_surf : 0, (l->use[kEdge] || edge) ? n_edge : 0};
+    return write_output(l, s1, n_out, stride_bytes, result_pose, out_cloud, out_stride_bytes);
+}
+
+int locgpu_loam_align_batch(locgpu_loam* l, int n_scans, const void* const* edge_srcs, const size_t* edge_counts, const void* const* surf_srcs,
+                            const size_t* surf_counts, size_t stride_bytes, const double* init_poses, double* out_poses, locgpu_align_stats* stats) {
+    if (!l) return LOCGPU_ERR_INVALID;
+    if (n_scans < 1 || n_scans > 65535 || !init_poses || !out_poses || stride_bytes < 12) return lfail(l, LOCGPU_ERR_INVALID, "loam_align_batch: bad arguments (1 <= n_scans <= 65535)");
+    AlignSpec spec[2];
+    int rc = check_classes(l, spec, "loam_align_batch");
+    if (rc != LOCGPU_OK) return rc;
+    LOAM_HIP(l, hipSetDevice(l->device));
+    const void* const* srcs[2] = {surf_srcs, edge_srcs};
+    const size_t* counts[2] = {surf_counts, edge_counts};
+    rc = reserve_joint(l, n_scans);
+    if (rc == LOCGPU_OK) rc = upload_scans(l, n_scans, srcs, counts, stride_bytes);
+    if (rc == LOCGPU_OK) rc = run(l, n_scans, init_poses, spec, 1);
+    if (rc != LOCGPU_OK) return rc;
+    for (int i = 0; i < n_scans; ++i) {
+        const PoseState& ps = l->h_state[i];
+        double* o = out_poses + 7 * (size_t)i;
+        if (ps.status != 0) {
+            std::memcpy(o, init_poses + 7 * (size_t)i, 7 * sizeof(double));
+        } else {
+            for (int j = 0; j < 4; ++j) o[j] = ps.q[j];
+            for (int j = 0; j < 3; ++j) o[4 + j] = ps.t[j];
+        }
+        write_stats(ps, stats ? stats + i : nullptr);
+    }
+    return LOCGPU_OK;
+}
+
+}  // extern "C"
