@@ -253,9 +253,11 @@ LOCGPU_API int locgpu_gn_update(const double hb[44], int method, int min_effecti
  * dx = (H_surf + H_edge)⁻¹ (B_surf + B_edge) with no effective-count test on the sum (:76-79), pose.so3() *= exp(dx.head<3>()),
  * translation += dx.tail<3>() (:82-83), stop after the update when |dx| < eps (:85). det(H_surf + H_edge) == 0, where the reference
  * divides by zero, is an iteration without an update (what locgpu_gn_update does); the loop goes on.
- * Limits: the LOAM entry points run EAGER chunks only — locgpu_graph_enable, sharded batches, scan pools and the host-paced one-scan
- * path do not apply to them — and LOCGPU_P2PLANE_MAP is refused (LOCGPU_ERR_INVALID). Calls on a handle follow the context's rule: one
- * caller thread, synchronous, inputs copied before the call returns. */
+ * Limits: the LOAM entry points run EAGER chunks only — locgpu_graph_enable (hipGraph), sharded batches, scan pools and the host-paced
+ * one-scan path do not apply to them — LOCGPU_P2PLANE_MAP (map planes) is refused (LOCGPU_ERR_INVALID), and only the single-scan calls
+ * have a resident form (locgpu_loam_set_target_cloud, locgpu_loam_scan_match_cloud, locgpu_loam_fitness_resident, locgpu_loam_submap_*,
+ * declared with the resident clouds below): there is no batched resident form. Calls on a handle follow the context's rule: one
+ * caller thread, synchronous, host inputs copied before the call returns. */
 typedef struct locgpu_loam locgpu_loam;
 /* LoamOption, loam_registration.hpp:22-36. Inside surf / edge only method, the three gates, min_effective_pts, approximate / ann_alpha
  * and search_mode are read: their max_iteration and eps are NOT (the loop is LoamRegistration's own, :47,85). */
@@ -625,6 +627,59 @@ LOCGPU_API int locgpu_submap_add_keyframe(locgpu_submap* m, const locgpu_cloud* 
 LOCGPU_API int locgpu_submap_cloud(locgpu_submap* m, locgpu_cloud** map);          /* borrowed: owned by the submap */
 LOCGPU_API int locgpu_submap_last_keyframe(locgpu_submap* m, locgpu_cloud** kf);   /* borrowed: the newest world-frame keyframe */
 LOCGPU_API int locgpu_submap_info(const locgpu_submap* m, int* n_keyframes, size_t* map_points);
+
+/* ---- The LOAM matcher on resident clouds: Lio::AddCloud(FullCloudPtr) (lio.cpp:311-410) with AlignWithLocalMap(edge, surf) (:475-502)
+ * without a PCIe hop between the feature picker (locgpu_cloud_loam_extract), the voxel filter, the match and the pair of local maps.
+ * Every cloud argument may belong to ANY context on the handle's GPU — a plain locgpu_ctx front-end context included: the rule
+ * "a cloud of context A may be the source on context B" above. The handle's stream is ordered behind the call that produced each
+ * cloud; a cloud on another GPU is refused with LOCGPU_ERR_INVALID. Eager only, like every LOAM entry point: no graph argument. */
+/* LoamRegistration::SetInputTarget (loam_registration.cpp:22-36) from resident clouds: every ENABLED class's
+ * locgpu_icp_set_target_cloud. Semantics of locgpu_loam_set_target: a switched-off class's cloud may be NULL, LOCGPU_OK only if every
+ * enabled class was ingested, a class that failed has no target afterwards. */
+LOCGPU_API int locgpu_loam_set_target_cloud(locgpu_loam* l, const locgpu_cloud* edge_map, const locgpu_cloud* surf_map);
+/* The same (loam_registration.cpp:22-36; Lio re-ingests both maps every keyframe, lio.cpp:408) with both host tree builds on worker
+ * threads, under the rules of locgpu_icp_set_target_cloud_async: returns once the clouds are copied out, the previous targets stay in
+ * place until the ingest finishes inside the next call that reads the target (match, H/B, fitness), which also reports its errors. */
+LOCGPU_API int locgpu_loam_set_target_cloud_async(locgpu_loam* l, const locgpu_cloud* edge_map, const locgpu_cloud* surf_map);
+/* LoamRegistration::ScanMatch WHOLE (loam_registration.cpp:38-99) on resident feature clouds: locgpu_loam_scan_match without the
+ * upload — the scans are NOT copied, the kernels read them where the clouds hold them (they must not be modified during the call).
+ * result_pose is IN-OUT and stats are as there: with status 3 / 4 the caller's result_pose and `out` are left untouched and the call
+ * returns LOCGPU_OK. out (optional): receives n_edge + n_surf points, the edge points followed by the surface points (:93-95), x, y, z
+ * under pose.matrix().cast<float>() (:96) in the rounding order of locgpu_loam_scan_match's output cloud, the intensity lane carried
+ * through, is_dense = the AND of the inputs' flags; written on the device, never staged on the host. out must be distinct from edge
+ * and surf. A switched-off class's cloud may be NULL; when it is given its points still join `out`. */
+LOCGPU_API int locgpu_loam_scan_match_cloud(locgpu_loam* l, const locgpu_cloud* edge, const locgpu_cloud* surf, const double init_pose[7],
+                                            double result_pose[7], locgpu_align_stats* stats, locgpu_cloud* out);
+/* MatchingInterface::GetFitnessScore for the LOAM matcher (the reference's ScanMatch, loam_registration.cpp:38-99, computes none):
+ * out[0] = surface, out[1] = edge, each exactly locgpu_icp_fitness of that class's scan against that class's map under `pose` —
+ * exact nearest neighbour, fixed reduction order. No joint number is invented: the caller combines the two. The scans are the ones
+ * the handle's most recent single-scan call left in HBM: locgpu_loam_scan_match / locgpu_loam_hb (the handle's own copies) or
+ * locgpu_loam_scan_match_cloud — which keeps REFERENCES, so those two clouds must still be alive and unmodified. A switched-off
+ * class (and an empty scan) reports {+inf, 0, 0}. LOCGPU_ERR_INVALID when nothing is resident (no such call yet, or a
+ * locgpu_loam_align_batch since); LOCGPU_ERR_NO_TARGET without a target. */
+LOCGPU_API int locgpu_loam_fitness_resident(locgpu_loam* l, const double pose[7], double max_range, locgpu_fitness out[2]);
+
+/* The PAIR of local maps of Lio::AddCloud(FullCloudPtr) (lio.cpp:331-409) in HBM: local_map_edge_ / local_map_surf_ with their queues
+ * edge_scans_in_local_map_ / surf_scans_in_local_map_ — one queue length (num_kfs) for both, pushed and popped together (:382-388) —
+ * as two locgpu_submap. add_keyframe(edge, surf, pose): both clouds go through the DOUBLE-precision matrix (:343-344, :379-380; what
+ * locgpu_cloud_transform does) and join their queues and maps. Two details of the reference, restated:
+ *  (a) The FIRST keyframe seeds both maps UNFILTERED: :338-339 filter the still-empty maps, :348-349 then assign the transformed
+ *      scans, and the first target is those scans (:346). So the first add_keyframe does not voxel-filter; every later one appends
+ *      (:399-403) or drops the oldest and rebuilds (:385-398), then filters both maps in place (:405-406).
+ *  (b) Which cloud a keyframe is made of is the CALLER's: the submap takes what it is handed. In the reference the first keyframe is
+ *      made of the picker's UNFILTERED features (AddCloud returns at :356, before AlignWithLocalMap at :359), every later one of the
+ *      voxel-FILTERED features, because AlignWithLocalMap filters edge_cloud and surf_cloud in place through the shared pointers
+ *      (:485-486) before :379-380 transform them. A caller that mirrors Lio hands the picker's clouds first and the filtered ones
+ *      (the clouds it matched) from then on.
+ * pose NULL: the clouds are already in the world frame. Both clouds are required (an empty one is fine) and may belong to any context
+ * on the submap's GPU. The caller then hands locgpu_loam_submap_clouds() to locgpu_loam_set_target_cloud[_async] (:346, :408). After a
+ * failed add_keyframe the two queues may differ: destroy the submap. */
+typedef struct locgpu_loam_submap locgpu_loam_submap;
+LOCGPU_API int locgpu_loam_submap_create(locgpu_ctx* ctx, int num_kfs, float leaf, locgpu_loam_submap** out);
+LOCGPU_API void locgpu_loam_submap_destroy(locgpu_loam_submap* m);
+LOCGPU_API int locgpu_loam_submap_add_keyframe(locgpu_loam_submap* m, const locgpu_cloud* edge, const locgpu_cloud* surf, const double pose[7]);
+LOCGPU_API int locgpu_loam_submap_clouds(locgpu_loam_submap* m, locgpu_cloud** edge_map, locgpu_cloud** surf_map); /* borrowed */
+LOCGPU_API int locgpu_loam_submap_info(const locgpu_loam_submap* m, int* n_keyframes, size_t* edge_points, size_t* surf_points);
 
 #ifdef __cplusplus
 }

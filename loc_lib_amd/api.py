@@ -49,6 +49,8 @@ ABI_SYMBOLS = [
     "locgpu_icp_build_map_planes", "locgpu_icp_map_planes_info", "locgpu_icp_map_planes_dump",
     "locgpu_loam_opts_default", "locgpu_loam_create", "locgpu_loam_destroy", "locgpu_loam_last_error", "locgpu_loam_set_target",
     "locgpu_loam_hb", "locgpu_loam_scan_match", "locgpu_loam_align_batch",
+    "locgpu_loam_set_target_cloud", "locgpu_loam_set_target_cloud_async", "locgpu_loam_scan_match_cloud", "locgpu_loam_fitness_resident",
+    "locgpu_loam_submap_create", "locgpu_loam_submap_destroy", "locgpu_loam_submap_add_keyframe", "locgpu_loam_submap_clouds", "locgpu_loam_submap_info",
 ]
 COMM_ID_BYTES = 128
 NO_INTENSITY = ctypes.c_size_t(-1).value
@@ -178,6 +180,11 @@ def lib():
             "locgpu_loam_hb": (i32, [vp, vp, sz, vp, sz, sz, vp, vp, vp, vp, vp]),
             "locgpu_loam_scan_match": (i32, [vp, vp, sz, vp, sz, sz, vp, vp, vp, vp, sz]),
             "locgpu_loam_align_batch": (i32, [vp, i32, vp, vp, vp, vp, sz, vp, vp, vp]),
+            "locgpu_loam_set_target_cloud": (i32, [vp, vp, vp]), "locgpu_loam_set_target_cloud_async": (i32, [vp, vp, vp]),
+            "locgpu_loam_scan_match_cloud": (i32, [vp, vp, vp, vp, vp, vp, vp]), "locgpu_loam_fitness_resident": (i32, [vp, vp, dbl, vp]),
+            "locgpu_loam_submap_create": (i32, [vp, i32, f32, vp]), "locgpu_loam_submap_destroy": (None, [vp]),
+            "locgpu_loam_submap_add_keyframe": (i32, [vp, vp, vp, vp]), "locgpu_loam_submap_clouds": (i32, [vp, vp, vp]),
+            "locgpu_loam_submap_info": (i32, [vp, vp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -795,6 +802,40 @@ class Submap:
         self.close()
 
 
+class LoamSubmap:
+    """The pair of keyframe local maps of Lio::AddCloud(FullCloudPtr) in HBM (locgpu_loam_submap, lio.cpp:331-409): one queue length for
+    both classes; the first keyframe seeds both maps unfiltered, every later one is appended (or the maps rebuilt) and filtered."""
+
+    def __init__(self, ctx, num_kfs, leaf):
+        self.ctx = ctx
+        self._h = ctypes.c_void_p()
+        ctx._check(lib().locgpu_loam_submap_create(ctx._h, int(num_kfs), float(leaf), ctypes.byref(self._h)))
+
+    def add_keyframe(self, edge, surf, pose=None):
+        self.ctx._check(lib().locgpu_loam_submap_add_keyframe(self._h, edge._h, surf._h, _pose(pose).ctypes.data if pose is not None else None))
+
+    def clouds(self):
+        """(edge map, surface map), borrowed: what Loam.set_target_cloud takes."""
+        e, s = ctypes.c_void_p(), ctypes.c_void_p()
+        self.ctx._check(lib().locgpu_loam_submap_clouds(self._h, ctypes.byref(e), ctypes.byref(s)))
+        return Cloud(self.ctx, _borrowed=e), Cloud(self.ctx, _borrowed=s)
+
+    @property
+    def info(self):
+        """(keyframes, edge map points, surface map points)"""
+        k, ne, ns = ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+        self.ctx._check(lib().locgpu_loam_submap_info(self._h, ctypes.byref(k), ctypes.byref(ne), ctypes.byref(ns)))
+        return int(k.value), int(ne.value), int(ns.value)
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            lib().locgpu_loam_submap_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        self.close()
+
+
 class MarshalledScans:
     """The (pointer, count) arrays of a list of host scans, built once: what a C/C++ caller of locgpu_batch_upload_async holds
     anyway. Pass it wherever a list of scans is accepted to skip the per-call Python marshalling (≈0.4 ms for 256 scans)."""
@@ -1014,6 +1055,29 @@ class Loam:
         self._check(lib().locgpu_loam_scan_match(self._h, pe, ne, ps, ns, self._stride(se, ss), _pose(init_pose).ctypes.data, out.ctypes.data,
                                                  ctypes.byref(st), cloud.ctypes.data if cloud.size else None, cloud.strides[0]))
         return out, _stats_dict(st), cloud
+
+    # ---- the same on resident clouds (api.Cloud of any Context on this GPU; None for a class that is switched off)
+    def set_target_cloud(self, edge_map, surf_map, wait=True):
+        """wait=False: returns once both clouds are copied out; the host tree builds run on worker threads and the next call that
+        reads the target completes the ingest."""
+        fn = lib().locgpu_loam_set_target_cloud if wait else lib().locgpu_loam_set_target_cloud_async
+        self._check(fn(self._h, edge_map._h if edge_map is not None else None, surf_map._h if surf_map is not None else None))
+
+    def scan_match_cloud(self, edge, surf, init_pose, result_pose=None, out=None):
+        """Returns (pose, stats). out (an api.Cloud distinct from edge and surf, optional) receives the edge points, then the surface
+        points, under the result; status 3 / 4 leaves it, and result_pose, as handed in."""
+        pose = np.array(_pose(result_pose if result_pose is not None else init_pose), copy=True)
+        st = AlignStats()
+        self._check(lib().locgpu_loam_scan_match_cloud(self._h, edge._h if edge is not None else None, surf._h if surf is not None else None,
+                                                       _pose(init_pose).ctypes.data, pose.ctypes.data, ctypes.byref(st), out._h if out is not None else None))
+        return pose, _stats_dict(st)
+
+    def fitness_resident(self, pose, max_range=1.0):
+        """[surface, edge] scores (dicts as Context.icp_fitness) of the scans the last single-scan call left in HBM; after
+        scan_match_cloud those are the caller's clouds, which must still be alive and unmodified."""
+        out = (Fitness * 2)()
+        self._check(lib().locgpu_loam_fitness_resident(self._h, _pose(pose).ctypes.data, float(max_range), out))
+        return [_fitness_dict(out[0]), _fitness_dict(out[1])]
 
     # ---- many feature scans against the one pair of maps
     def align_batch(self, edges, surfs, init_poses):

@@ -19,6 +19,12 @@ struct locgpu_submap {
     locgpu_cloud* map = nullptr;      // local_map_
 };
 
+// The pair of local maps of Lio::AddCloud(FullCloudPtr) (lio.cpp:331-409): local_map_edge_ / local_map_surf_ and their queues.
+struct locgpu_loam_submap {
+    locgpu_submap* edge = nullptr;
+    locgpu_submap* surf = nullptr;
+};
+
 namespace {
 
 int hip_fail(locgpu_ctx* ctx, hipError_t e, const char* what) {
@@ -267,8 +273,8 @@ void locgpu_submap_destroy(locgpu_submap* m) {
     delete m;
 }
 
-int locgpu_submap_add_keyframe(locgpu_submap* m, const locgpu_cloud* scan, const double pose[7]) {
-    if (!m) return LOCGPU_ERR_INVALID;
+// filter = false: the map is left as appended (the first keyframe of the LOAM pair of maps, lio.cpp:348-349).
+static int submap_add(locgpu_submap* m, const locgpu_cloud* scan, const double pose[7], bool filter) {
     locgpu_ctx* ctx = m->ctx;
     if (!scan || !scan->ctx) return fail(ctx, LOCGPU_ERR_INVALID, "submap_add_keyframe: bad cloud");
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
@@ -303,10 +309,16 @@ int locgpu_submap_add_keyframe(locgpu_submap* m, const locgpu_cloud* scan, const
         e = append_dev(ctx, m->map, kf);
     }
     if (e != hipSuccess) return hip_fail(ctx, e, "submap_add_keyframe: append");
+    if (!filter) return LOCGPU_OK;
     int status = 0;
     e = voxel_filter_dev(ctx, m->map, m->leaf, m->map, &status);  // :300 local_map_filter_ptr_->Filter(local_map_, local_map_)
     if (e != hipSuccess) return hip_fail(ctx, e, "submap_add_keyframe: voxel filter");
     return LOCGPU_OK;
+}
+
+int locgpu_submap_add_keyframe(locgpu_submap* m, const locgpu_cloud* scan, const double pose[7]) {
+    if (!m) return LOCGPU_ERR_INVALID;
+    return submap_add(m, scan, pose, true);
 }
 
 int locgpu_submap_cloud(locgpu_submap* m, locgpu_cloud** map) {
@@ -326,6 +338,55 @@ int locgpu_submap_info(const locgpu_submap* m, int* n_keyframes, size_t* map_poi
     if (!m) return LOCGPU_ERR_INVALID;
     if (n_keyframes) *n_keyframes = (int)m->scans.size();
     if (map_points) *map_points = m->map->n;
+    return LOCGPU_OK;
+}
+
+// ---- the LOAM pair of keyframe local maps (lio.cpp:331-409) ----
+int locgpu_loam_submap_create(locgpu_ctx* ctx, int num_kfs, float leaf, locgpu_loam_submap** out) {
+    if (!ctx || !out) return LOCGPU_ERR_INVALID;
+    *out = nullptr;
+    auto* m = new locgpu_loam_submap();
+    int rc = locgpu_submap_create(ctx, num_kfs, leaf, &m->edge);
+    if (rc == LOCGPU_OK) rc = locgpu_submap_create(ctx, num_kfs, leaf, &m->surf);
+    if (rc != LOCGPU_OK) { locgpu_loam_submap_destroy(m); return rc; }
+    *out = m;
+    return LOCGPU_OK;
+}
+
+void locgpu_loam_submap_destroy(locgpu_loam_submap* m) {
+    if (!m) return;
+    locgpu_submap_destroy(m->edge);
+    locgpu_submap_destroy(m->surf);
+    delete m;
+}
+
+int locgpu_loam_submap_add_keyframe(locgpu_loam_submap* m, const locgpu_cloud* edge, const locgpu_cloud* surf, const double pose[7]) {
+    if (!m) return LOCGPU_ERR_INVALID;
+    locgpu_ctx* ctx = m->edge->ctx;
+    // both clouds are checked before either queue is touched: the queues are pushed and popped together (lio.cpp:382-388)
+    if (!edge || !edge->ctx || !surf || !surf->ctx) return fail(ctx, LOCGPU_ERR_INVALID, "loam_submap_add_keyframe: bad cloud");
+    if (edge->ctx->device != ctx->device || surf->ctx->device != ctx->device) return fail(ctx, LOCGPU_ERR_INVALID, "loam_submap_add_keyframe: a cloud belongs to a context on another GPU");
+    // The first keyframe IS both maps, unfiltered — the caller hands the picker's unfiltered features (:343-349; :338-339 filtered
+    // the maps while they were still empty). Every later one — in Lio made of the voxel-filtered features AlignWithLocalMap left in
+    // edge_cloud / surf_cloud (:485-486, :379-380) — is appended or triggers the rebuild, and both maps are filtered in place (:385-406).
+    const bool filter = !m->edge->scans.empty();
+    int rc = submap_add(m->edge, edge, pose, filter);
+    if (rc == LOCGPU_OK) rc = submap_add(m->surf, surf, pose, filter);
+    return rc;
+}
+
+int locgpu_loam_submap_clouds(locgpu_loam_submap* m, locgpu_cloud** edge_map, locgpu_cloud** surf_map) {
+    if (!m || !edge_map || !surf_map) return LOCGPU_ERR_INVALID;
+    *edge_map = m->edge->map;
+    *surf_map = m->surf->map;
+    return LOCGPU_OK;
+}
+
+int locgpu_loam_submap_info(const locgpu_loam_submap* m, int* n_keyframes, size_t* edge_points, size_t* surf_points) {
+    if (!m) return LOCGPU_ERR_INVALID;
+    if (n_keyframes) *n_keyframes = (int)m->edge->scans.size();
+    if (edge_points) *edge_points = m->edge->map->n;
+    if (surf_points) *surf_points = m->surf->map->n;
     return LOCGPU_OK;
 }
 

@@ -207,6 +207,8 @@ int check_ndt(locgpu_ctx* ctx, AlignSpec& spec);
 // icp_target.hip
 int target_join(locgpu_ctx* ctx, bool install = true);  // finishes a pending locgpu_icp_set_target_cloud_async (no-op without one)
 void free_target_scratch(locgpu_ctx* ctx);              // the ingest buffers the context keeps between SetInputTarget calls
+// SetInputTarget from a resident cloud of any context on ctx's GPU; async: the host tree build runs on a worker thread
+int icp_set_target_from_cloud(locgpu_ctx* ctx, const locgpu_cloud* target, bool async);
 int ensure_grid(locgpu_ctx* ctx);                       // the exact-search grid of the current target (built on first use)
 void free_grid(locgpu_ctx* ctx);
 // comm.hip: collectives over the context's communicator, in place, on stream `s`

@@ -156,6 +156,33 @@ int locgpu::target_join(locgpu_ctx* ctx, bool install) {
     return rc;
 }
 
+// SetInputTarget from a resident cloud (locgpu_icp_set_target_cloud[_async]; the LOAM handle's classes, whose clouds always belong to
+// another context: ctx's stream is then ordered behind the call that produced the cloud).
+int locgpu::icp_set_target_from_cloud(locgpu_ctx* ctx, const locgpu_cloud* target, bool async) {
+    if (target->n == 0) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target: empty cloud or stride < 12");
+    (void)target_join(ctx, false);  // a pending asynchronous ingest is superseded
+    // The mean-split tree is built on the host (its float32 sums are sequential by definition, kdtree.cpp:94-123), so the
+    // cloud crosses PCIe once in each direction: 16 B/point down, the packed tree (≈24 B/point) up.
+    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+    {
+        const hipError_t ce = cloud_input_ready(ctx, target);
+        if (ce == hipErrorInvalidDevice) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target_cloud: the cloud belongs to a context on another GPU");
+        if (!hip_ok(ctx, ce, "icp_set_target_cloud: ordering behind the cloud's context")) return LOCGPU_ERR_NO_DEVICE;
+    }
+    float4* stage = nullptr;
+    if (!hip_ok(ctx, cloud_stage(ctx, target->n, &stage), "pinned staging")) return LOCGPU_ERR_OOM;
+    LOCGPU_HIP(ctx, hipMemcpyAsync(stage, target->d, target->n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    LOCGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (!async) return locgpu_icp_set_target(ctx, stage, target->n, sizeof(float4));
+    locgpu::PendingTarget* p = take_target_scratch(ctx);
+    p->xyz.resize(3 * target->n);  // the deep copy of SetInputTarget (icp_registration.cpp:16): the staging block is free again after it
+    for (size_t i = 0; i < target->n; ++i) std::memcpy(&p->xyz[3 * i], &stage[i], 12);
+    const size_t n = target->n;
+    p->worker = std::thread([p, n] { p->ok = build_packed_kdtree(p->xyz.data(), n, p->tree, p->err); });
+    ctx->pending_target = p;
+    return LOCGPU_OK;
+}
+
 extern "C" {
 
 int locgpu_icp_set_target(locgpu_ctx* ctx, const void* pts, size_t n, size_t stride_bytes) {
@@ -260,35 +287,13 @@ int locgpu_icp_target_info(const locgpu_ctx* ctx, int64_t out[4]) {
 int locgpu_icp_set_target_cloud(locgpu_ctx* ctx, const locgpu_cloud* target) {
     if (!ctx) return LOCGPU_ERR_INVALID;
     if (!target || target->ctx != ctx) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target_cloud: bad cloud");
-    if (target->n == 0) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target: empty cloud or stride < 12");
-    (void)target_join(ctx, false);  // a pending asynchronous ingest is superseded
-    // The mean-split tree is built on the host (its float32 sums are sequential by definition, kdtree.cpp:94-123), so the
-    // cloud crosses PCIe once in each direction: 16 B/point down, the packed tree (≈24 B/point) up.
-    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
-    float4* stage = nullptr;
-    if (!hip_ok(ctx, cloud_stage(ctx, target->n, &stage), "pinned staging")) return LOCGPU_ERR_OOM;
-    LOCGPU_HIP(ctx, hipMemcpyAsync(stage, target->d, target->n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    LOCGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return locgpu_icp_set_target(ctx, stage, target->n, sizeof(float4));
+    return icp_set_target_from_cloud(ctx, target, false);
 }
 
 int locgpu_icp_set_target_cloud_async(locgpu_ctx* ctx, const locgpu_cloud* target) {
     if (!ctx) return LOCGPU_ERR_INVALID;
     if (!target || target->ctx != ctx) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target_cloud: bad cloud");
-    if (target->n == 0) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target: empty cloud or stride < 12");
-    (void)target_join(ctx, false);  // an earlier pending ingest is superseded
-    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
-    float4* stage = nullptr;
-    if (!hip_ok(ctx, cloud_stage(ctx, target->n, &stage), "pinned staging")) return LOCGPU_ERR_OOM;
-    LOCGPU_HIP(ctx, hipMemcpyAsync(stage, target->d, target->n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    LOCGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    locgpu::PendingTarget* p = take_target_scratch(ctx);
-    p->xyz.resize(3 * target->n);  // the deep copy of SetInputTarget (icp_registration.cpp:16): the staging block is free again after it
-    for (size_t i = 0; i < target->n; ++i) std::memcpy(&p->xyz[3 * i], &stage[i], 12);
-    const size_t n = target->n;
-    p->worker = std::thread([p, n] { p->ok = build_packed_kdtree(p->xyz.data(), n, p->tree, p->err); });
-    ctx->pending_target = p;
-    return LOCGPU_OK;
+    return icp_set_target_from_cloud(ctx, target, true);
 }
 
 }  // extern "C"

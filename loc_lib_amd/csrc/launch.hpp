@@ -123,6 +123,8 @@ void launch_icp_fitness(const FitnessArgs& a, hipStream_t s);
 void launch_fitness_sum(const double* partials, int rows, int n_scans, double* out, unsigned int* list_counts, hipStream_t s);
 struct M12f { float v[12]; };  // rows of pose.matrix().cast<float>() (icp_registration.cpp:241), a kernel argument
 void launch_transform_cloud(const float4* src, size_t n, const M12f& m12, float* dst_xyz, hipStream_t s);
+// loam_stream.hip: edge points then surface points under m12 into out (n_edge + n_surf float4, w carried through); out overlaps neither
+void launch_loam_join_transform(const float4* edge, size_t n_edge, const float4* surf, size_t n_surf, const M12f& m12, float4* out, hipStream_t s);
 // Plane table of LOCGPU_P2PLANE_MAP (map_planes.hip). queries: the coordinates of leaves [first, first + n) as the source points of a
 // one-scan search batch (counts[0] = n). fit: the chunk's k = 5 lists → rows planes[slot >> 1], *n_valid += valid planes.
 // dump: rows by original point index into zeroed out_n4 [n_points][4] / out_valid [n_points].

@@ -6,12 +6,16 @@
 //     launch_local_stage(surface) → launch_local_stage(edge) → loam_solve_kernel
 // in eager chunks of kFirstChunk / kNextChunk iterations between two host reads of the flags, later chunks over the open scans only —
 // the chunks of align_begin / align_finish (gn_driver.hip) without graphs, shards, pools or host pacing.
+// The _cloud entry points run the same loop on feature clouds that are already in HBM (the batches' d_src_ext, as single_batch_dev of
+// locgpu_api.hip does) and write the output cloud on the device (loam_stream.hip).
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "batch_upload.hpp"
+#include "cloud_filters.hpp"
 #include "context.hpp"
 #include "gn_driver.hpp"
 #include "launch.hpp"
@@ -29,6 +33,7 @@ struct locgpu_loam {
     locgpu_ctx* ctx[2] = {nullptr, nullptr};
     locgpu_batch* batch[2] = {nullptr, nullptr};  // storage batches: kept between calls, grow-only, reshaped to the call's scans
     bool has_target[2] = {false, false};
+    bool resident = false;  // the storage batches hold (or, after a _cloud call, point at) the scans of a single-scan call: locgpu_loam_fitness_resident
     hipStream_t stream = nullptr;  // the first enabled class's context stream: every launch of an alignment
     hipEvent_t ev = nullptr;       // orders `stream` behind the other context's stream
     // joint state, for cap_scans scans
@@ -167,6 +172,7 @@ int upload_scans(locgpu_loam* l, int n_scans, const void* const* srcs[2], const 
     for (int c = 0; c < 2 && rc == LOCGPU_OK; ++c) {
         if (!l->use[c]) continue;
         rc = shape_batch(l, c, n_scans, max_n[c]);
+        if (rc == LOCGPU_OK) l->batch[c]->d_src_ext = nullptr;  // the kernels read the batch's own copy
         if (rc == LOCGPU_OK) rc = from_ctx(l, c, upload_start(l->batch[c], srcs[c], counts[c], stride));
         started[c] = rc == LOCGPU_OK;
     }
@@ -180,6 +186,46 @@ int upload_scans(locgpu_loam* l, int n_scans, const void* const* srcs[2], const 
         if (!l->use[c]) continue;
         LOAM_HIP(l, upload_order_after(l->batch[c], l->stream));
         if (l->ctx[c]->stream != l->stream) {
+            LOAM_HIP(l, hipEventRecord(l->ev, l->ctx[c]->stream));
+            LOAM_HIP(l, hipStreamWaitEvent(l->stream, l->ev, 0));
+        }
+    }
+    return LOCGPU_OK;
+}
+
+// The context whose stream is the handle's.
+locgpu_ctx* stream_ctx(locgpu_loam* l) { return l->use[kSurf] ? l->ctx[kSurf] : l->ctx[kEdge]; }
+
+// `c` as a read-only input of the handle (cloud_input_ready, as align_single of locgpu_api.hip): the handle's stream goes behind
+// the call that produced it.
+int cloud_ready(locgpu_loam* l, const locgpu_cloud* c, const char* who) {
+    const hipError_t ce = cloud_input_ready(stream_ctx(l), c);
+    if (ce == hipErrorInvalidDevice) return lfail(l, LOCGPU_ERR_INVALID, std::string(who) + ": a cloud belongs to a context on another GPU");
+    if (ce == hipErrorInvalidValue) return lfail(l, LOCGPU_ERR_INVALID, std::string(who) + ": bad cloud");
+    return lhip(l, ce, "ordering behind the cloud's context") ? LOCGPU_OK : LOCGPU_ERR_NO_DEVICE;
+}
+
+// The resident counterpart of upload_scans for one scan: both classes' storage batches get the shape of the host-pointer call on
+// the same clouds (so the sums split alike and the poses are its poses, bit for bit) and read the points where the clouds hold them.
+int attach_scans(locgpu_loam* l, const locgpu_cloud* const clouds[2], const char* who) {
+    for (int c = 0; c < 2; ++c) {  // every argument is checked before anything is enqueued
+        if (!l->use[c]) continue;
+        if (!clouds[c] || !clouds[c]->ctx) return lfail(l, LOCGPU_ERR_INVALID, std::string(who) + ": the scan of an enabled feature class is NULL");
+    }
+    for (int c = 0; c < 2; ++c) {
+        if (!l->use[c]) continue;
+        int rc = cloud_ready(l, clouds[c], who);
+        if (rc == LOCGPU_OK) rc = shape_batch(l, c, 1, clouds[c]->n);
+        if (rc != LOCGPU_OK) return rc;
+        locgpu_batch* b = l->batch[c];
+        const int jrc = from_ctx(l, c, upload_join_batch(b));  // a failed earlier upload stays with the batch until one replaces it: say so
+        if (jrc != LOCGPU_OK) return jrc;
+        b->d_src_ext = clouds[c]->n ? clouds[c]->d : nullptr;
+        b->counts[0] = (int)clouds[c]->n;
+        b->upl.h_counts[0] = b->counts[0];  // pinned, the uploader's (idle: every host-pointer call joins its upload before it returns)
+        LOAM_HIP(l, upload_order_after(b, l->stream));
+        LOAM_HIP(l, hipMemcpyAsync(b->d_counts, b->upl.h_counts, sizeof(int), hipMemcpyHostToDevice, l->stream));
+        if (l->ctx[c]->stream != l->stream) {  // behind that context's target ingest
             LOAM_HIP(l, hipEventRecord(l->ev, l->ctx[c]->stream));
             LOAM_HIP(l, hipStreamWaitEvent(l->stream, l->ev, 0));
         }
@@ -410,6 +456,26 @@ int locgpu_loam_set_target(locgpu_loam* l, const void* edge_pts, size_t n_edge, 
     return rc;
 }
 
+static int set_target_cloud(locgpu_loam* l, const locgpu_cloud* edge_map, const locgpu_cloud* surf_map, bool async) {
+    if (!l) return LOCGPU_ERR_INVALID;
+    const locgpu_cloud* maps[2] = {surf_map, edge_map};
+    int rc = LOCGPU_OK;
+    // like locgpu_loam_set_target (loam_registration.cpp:24-34): every enabled class is handed its cloud, whatever happened to the other
+    for (int c = 0; c < 2; ++c) {
+        if (!l->use[c]) continue;
+        int r;
+        if (!maps[c] || !maps[c]->ctx) r = lfail(l, LOCGPU_ERR_INVALID, "loam_set_target_cloud: the map of an enabled feature class is NULL");
+        else r = from_ctx(l, c, icp_set_target_from_cloud(l->ctx[c], maps[c], async));
+        l->has_target[c] = r == LOCGPU_OK;
+        if (r != LOCGPU_OK && rc == LOCGPU_OK) rc = r;
+    }
+    return rc;
+}
+
+int locgpu_loam_set_target_cloud(locgpu_loam* l, const locgpu_cloud* edge_map, const locgpu_cloud* surf_map) { return set_target_cloud(l, edge_map, surf_map, false); }
+
+int locgpu_loam_set_target_cloud_async(locgpu_loam* l, const locgpu_cloud* edge_map, const locgpu_cloud* surf_map) { return set_target_cloud(l, edge_map, surf_map, true); }
+
 int locgpu_loam_hb(locgpu_loam* l, const void* edge, size_t n_edge, const void* surf, size_t n_surf, size_t stride_bytes, const double pose[7], double H[36],
                    double B[6], int64_t eff[2], int32_t ok[2]) {
     if (!l) return LOCGPU_ERR_INVALID;
@@ -422,10 +488,12 @@ int locgpu_loam_hb(locgpu_loam* l, const void* edge, size_t n_edge, const void* 
     const size_t c1[2] = {n_surf, n_edge};
     const void* const* srcs[2] = {&s1[kSurf], &s1[kEdge]};
     const size_t* counts[2] = {&c1[kSurf], &c1[kEdge]};
+    l->resident = false;
     rc = reserve_joint(l, 1);
     if (rc == LOCGPU_OK) rc = upload_scans(l, 1, srcs, counts, stride_bytes);
     if (rc == LOCGPU_OK) rc = run(l, 1, pose, spec, 0);
     if (rc != LOCGPU_OK) return rc;
+    l->resident = true;
     std::memcpy(H, l->h_hb, 36 * sizeof(double));
     std::memcpy(B, l->h_hb + 36, 6 * sizeof(double));
     for (int c = 0; c < 2; ++c) {
@@ -447,10 +515,12 @@ int locgpu_loam_scan_match(locgpu_loam* l, const void* edge, size_t n_edge, cons
     const size_t c1[2] = {n_surf, n_edge};
     const void* const* srcs[2] = {&s1[kSurf], &s1[kEdge]};
     const size_t* counts[2] = {&c1[kSurf], &c1[kEdge]};
+    l->resident = false;
     rc = reserve_joint(l, 1);
     if (rc == LOCGPU_OK) rc = upload_scans(l, 1, srcs, counts, stride_bytes);
     if (rc == LOCGPU_OK) rc = run(l, 1, init_pose, spec, 1);
     if (rc != LOCGPU_OK) return rc;
+    l->resident = true;
     const PoseState& ps = l->h_state[0];
     write_stats(ps, stats);
     if (ps.status != 0) return LOCGPU_OK;  // `return false` before `result_pose = pose` (loam_registration.cpp:56-70): the caller's value and cloud stay
@@ -460,6 +530,77 @@ int locgpu_loam_scan_match(locgpu_loam* l, const void* edge, size_t n_edge, cons
     // a switched-off class takes part in the output cloud when the caller hands its points (the reference adds both, :93-95)
     const size_t n_out[2] = {(l->use[kSurf] || surf) ? n_surf : 0, (l->use[kEdge] || edge) ? n_edge : 0};
     return write_output(l, s1, n_out, stride_bytes, result_pose, out_cloud, out_stride_bytes);
+}
+
+int locgpu_loam_scan_match_cloud(locgpu_loam* l, const locgpu_cloud* edge, const locgpu_cloud* surf, const double init_pose[7], double result_pose[7],
+                                 locgpu_align_stats* stats, locgpu_cloud* out) {
+    if (!l) return LOCGPU_ERR_INVALID;
+    if (!init_pose || !result_pose || (out && (!out->ctx || out == edge || out == surf))) return lfail(l, LOCGPU_ERR_INVALID, "loam_scan_match_cloud: bad arguments (out must be distinct from edge and surf)");
+    AlignSpec spec[2];
+    int rc = check_classes(l, spec, "loam_scan_match_cloud");
+    if (rc != LOCGPU_OK) return rc;
+    LOAM_HIP(l, hipSetDevice(l->device));
+    const locgpu_cloud* clouds[2] = {surf, edge};
+    // a switched-off class takes part in the output cloud when the caller hands its points (the reference adds both, :93-95)
+    const size_t n_out[2] = {surf && surf->ctx ? surf->n : 0, edge && edge->ctx ? edge->n : 0};
+    if (out && n_out[kSurf] + n_out[kEdge] > 0x7FFFFF00u) return lfail(l, LOCGPU_ERR_INVALID, "loam_scan_match_cloud: the output cloud exceeds 2^31 points");
+    l->resident = false;
+    rc = reserve_joint(l, 1);
+    if (rc == LOCGPU_OK) rc = attach_scans(l, clouds, "loam_scan_match_cloud");
+    if (rc == LOCGPU_OK) rc = run(l, 1, init_pose, spec, 1);
+    if (rc != LOCGPU_OK) return rc;
+    l->resident = true;
+    const PoseState& ps = l->h_state[0];
+    write_stats(ps, stats);
+    if (ps.status != 0) return LOCGPU_OK;  // `return false` before `result_pose = pose` (loam_registration.cpp:56-70): the caller's value and cloud stay
+    for (int j = 0; j < 4; ++j) result_pose[j] = ps.q[j];
+    for (int j = 0; j < 3; ++j) result_pose[4 + j] = ps.t[j];
+    if (!out) return LOCGPU_OK;
+    // *cloud += *edge; *cloud += *surf; transformPointCloud(*cloud, *result, pose.matrix().cast<float>()) (:93-96), on the device
+    for (int c = 0; c < 2; ++c)
+        if (!l->use[c] && n_out[c]) { rc = cloud_ready(l, clouds[c], "loam_scan_match_cloud"); if (rc != LOCGPU_OK) return rc; }
+    rc = cloud_ready(l, out, "loam_scan_match_cloud");  // behind whatever its owner last did with it
+    if (rc != LOCGPU_OK) return rc;
+    const size_t n_all = n_out[kEdge] + n_out[kSurf];
+    if (!lhip(l, cloud_reserve(out, n_all, false), "loam_scan_match_cloud: hipMalloc output cloud")) return LOCGPU_ERR_OOM;
+    double R[9];
+    quat_to_R(result_pose, R);
+    M12f m;
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) m.v[4 * r + c] = (float)R[3 * r + c];
+        m.v[4 * r + 3] = (float)result_pose[4 + r];
+    }
+    launch_loam_join_transform(n_out[kEdge] ? edge->d : nullptr, n_out[kEdge], n_out[kSurf] ? surf->d : nullptr, n_out[kSurf], m, out->d, l->stream);
+    LOAM_HIP(l, hipGetLastError());
+    LOAM_HIP(l, hipStreamSynchronize(l->stream));  // the call is synchronous: the owner of `out` may use it at once
+    out->n = n_all;
+    out->is_dense = 1;  // operator+= ANDs the flags (a cloud that was not handed adds nothing)
+    for (int c = 0; c < 2; ++c)
+        if (clouds[c] && clouds[c]->ctx && !clouds[c]->is_dense) out->is_dense = 0;
+    (void)cloud_mark_ready(out);
+    return LOCGPU_OK;
+}
+
+int locgpu_loam_fitness_resident(locgpu_loam* l, const double pose[7], double max_range, locgpu_fitness out[2]) {
+    if (!l) return LOCGPU_ERR_INVALID;
+    if (!pose || !out || std::isnan(max_range)) return lfail(l, LOCGPU_ERR_INVALID, "loam_fitness_resident: bad arguments");
+    if (!l->resident) return lfail(l, LOCGPU_ERR_INVALID, "loam_fitness_resident: no scans of a single-scan call are resident");
+    for (int c = 0; c < 2; ++c) {
+        if (!l->use[c]) continue;
+        if (!l->has_target[c]) return lfail(l, LOCGPU_ERR_NO_TARGET, "loam_fitness_resident: locgpu_loam_set_target has not been called");
+        const int jrc = from_ctx(l, c, target_join(l->ctx[c]));  // an asynchronous ingest ends here at the latest
+        if (jrc != LOCGPU_OK) return jrc;
+        if (!l->ctx[c]->d_tree) return lfail(l, LOCGPU_ERR_NO_TARGET, "loam_fitness_resident: locgpu_loam_set_target has not been called");
+    }
+    for (int c = 0; c < 2; ++c) {
+        out[c].score = HUGE_VAL;
+        out[c].inliers = out[c].finite_points = 0;
+        if (!l->use[c] || l->batch[c]->counts[0] <= 0) continue;
+        // the class's one-scan storage batch on its own context: locgpu_icp_fitness of that scan against that map, its bits
+        const int rc = from_ctx(l, c, fitness_on_batch(l->ctx[c], l->batch[c], pose, max_range, &out[c]));
+        if (rc != LOCGPU_OK) return rc;
+    }
+    return LOCGPU_OK;
 }
 
 int locgpu_loam_align_batch(locgpu_loam* l, int n_scans, const void* const* edge_srcs, const size_t* edge_counts, const void* const* surf_srcs,
@@ -472,6 +613,7 @@ int locgpu_loam_align_batch(locgpu_loam* l, int n_scans, const void* const* edge
     LOAM_HIP(l, hipSetDevice(l->device));
     const void* const* srcs[2] = {surf_srcs, edge_srcs};
     const size_t* counts[2] = {surf_counts, edge_counts};
+    l->resident = false;  // the storage batches take the batch's shape
     rc = reserve_joint(l, n_scans);
     if (rc == LOCGPU_OK) rc = upload_scans(l, n_scans, srcs, counts, stride_bytes);
     if (rc == LOCGPU_OK) rc = run(l, n_scans, init_poses, spec, 1);
