@@ -448,6 +448,15 @@ LOCGPU_API int locgpu_ndt_dump(locgpu_ctx* ctx, int32_t* keys, double* mu, doubl
  * When stats->status == 1 the reference leaves result_pose unassigned; out_pose then holds init_pose. */
 LOCGPU_API int locgpu_ndt_align(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double init_pose[7],
                                 double out_pose[7], locgpu_align_stats* stats);
+/* One evaluation of the sums AlignNdt / AlignIncNdt form per iteration (ndt_registration.cpp:399-433, :286-347) at `pose`, without the
+ * update, against the current NDT target, direct or incremental — what locgpu_icp_hb is for the ICP methods (tests and tools read the
+ * normal equations of an NDT iteration through it). H 6×6 row-major, B, effective_num (direct: source points, :432; incremental:
+ * accepted residuals, :347); *ok: direct det(H) != 0 && effective_num >= min_effective_pts (:435-440), incremental effective_num >=
+ * min_effective_pts (:349). Changes nothing an alignment depends on. */
+LOCGPU_API int locgpu_ndt_hb(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double pose[7], double H[36], double B[6],
+                             int64_t* effective_num, int* ok);
+/* The same for every scan of a batch at its pose. hb: n_scans × 44 doubles = H36, B6, effective_num, ok (the row of locgpu_icp_hb_batch). */
+LOCGPU_API int locgpu_ndt_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, double* hb);
 
 /* ---- NdtRegistration::GetFitnessScore, which the reference leaves a stub that returns 0 (ndt_registration.cpp:466-471): how good an
  * alignment is against the DIRECT NDT target, in the terms of the alignment itself — the χ² residual AlignNdt forms for its gate

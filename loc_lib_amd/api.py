@@ -45,7 +45,7 @@ ABI_SYMBOLS = [
     "locgpu_icp_scan_match", "locgpu_ndt_scan_match",
     "locgpu_icp_fitness", "locgpu_icp_fitness_batch", "locgpu_icp_fitness_resident", "locgpu_batch_create_shared",
     "locgpu_init_search_opts_default", "locgpu_icp_init_search", "locgpu_pose_grid",
-    "locgpu_ndt_fitness", "locgpu_ndt_fitness_batch", "locgpu_ndt_fitness_resident", "locgpu_ndt_init_search",
+    "locgpu_ndt_fitness", "locgpu_ndt_fitness_batch", "locgpu_ndt_fitness_resident", "locgpu_ndt_init_search", "locgpu_ndt_hb", "locgpu_ndt_hb_batch",
     "locgpu_icp_build_map_planes", "locgpu_icp_map_planes_info", "locgpu_icp_map_planes_dump",
     "locgpu_loam_opts_default", "locgpu_loam_create", "locgpu_loam_destroy", "locgpu_loam_last_error", "locgpu_loam_set_target",
     "locgpu_loam_hb", "locgpu_loam_scan_match", "locgpu_loam_align_batch",
@@ -172,6 +172,7 @@ def lib():
             "locgpu_pose_grid": (i32, [vp, dbl, dbl, dbl, dbl, vp, sz, vp]),
             "locgpu_ndt_fitness": (i32, [vp, vp, sz, sz, vp, i32, vp]), "locgpu_ndt_fitness_batch": (i32, [vp, vp, vp, vp]),
             "locgpu_ndt_fitness_resident": (i32, [vp, vp, vp]),
+            "locgpu_ndt_hb": (i32, [vp, vp, sz, sz, vp, vp, vp, vp, vp]), "locgpu_ndt_hb_batch": (i32, [vp, vp, vp, vp]),
             "locgpu_ndt_init_search": (i32, [vp, vp, sz, sz, vp, i32, vp, vp, vp, vp, vp]),
             "locgpu_icp_build_map_planes": (i32, [vp]), "locgpu_icp_map_planes_info": (i32, [vp, vp]),
             "locgpu_icp_map_planes_dump": (i32, [vp, vp, vp, sz, vp]),
@@ -595,6 +596,22 @@ class Context:
         self._check(lib().locgpu_ndt_align(self._h, s.ctypes.data, s.shape[0], s.strides[0], _pose(init_pose).ctypes.data, out.ctypes.data,
                                            ctypes.byref(st)))
         return out, _stats_dict(st)
+
+    # ---- one iteration's H, B, effective_num, ok at a pose against the current NDT target, without the update
+    def ndt_hb(self, src, pose):
+        s = _cloud(src)
+        H, B = np.zeros(36), np.zeros(6)
+        eff, ok = ctypes.c_int64(0), ctypes.c_int(0)
+        self._check(lib().locgpu_ndt_hb(self._h, s.ctypes.data, s.shape[0], s.strides[0], _pose(pose).ctypes.data, H.ctypes.data, B.ctypes.data,
+                                        ctypes.byref(eff), ctypes.byref(ok)))
+        return bool(ok.value), H.reshape(6, 6), B, int(eff.value)
+
+    def ndt_hb_batch(self, batch, poses):
+        batch.upload_wait()
+        p = _pose(poses).reshape(batch.n_scans, 7)
+        hb = np.zeros((batch.n_scans, 44))
+        self._check(lib().locgpu_ndt_hb_batch(self._h, batch._h, p.ctypes.data, hb.ctypes.data))
+        return hb
 
     # ---- the score and the candidate search against the direct NDT target (locgpu.h: score = mean χ² residual, dimensionless)
     def ndt_fitness(self, src, poses, raw=False):

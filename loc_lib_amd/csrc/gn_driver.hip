@@ -601,21 +601,25 @@ int ndt_fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, 
     return LOCGPU_OK;
 }
 
-int eval_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, const AlignSpec& spec, double* hb) {
+int eval_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, const AlignSpec& spec, double* hb, const char* who) {
+    const bool ndt = spec.ndt();
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
-    { const int grc = ensure_grid_lists(ctx, b, spec); if (grc != LOCGPU_OK) return grc; }
+    if (b->pending.active) return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": an alignment of this batch has been begun and not finished");
+    if (!ndt) { const int grc = ensure_grid_lists(ctx, b, spec); if (grc != LOCGPU_OK) return grc; }
     { const int urc = batch_ready(ctx, b); if (urc != LOCGPU_OK) return urc; }
-    if (b->pending.active) return fail(ctx, LOCGPU_ERR_INVALID, "icp_hb_batch: an alignment of this batch has been begun and not finished");
     init_states(b, poses);
-    b->counters_clean = false;
-    LOCGPU_HIP(ctx, hipMemsetAsync(b->d_redo_count, 0, 4 * sizeof(unsigned int), b->stream));
+    // NDT has no search stage: its evaluation leaves the work-list counters, and what the batch knows about them, as they are
+    if (!ndt) {
+        b->counters_clean = false;
+        LOCGPU_HIP(ctx, hipMemsetAsync(b->d_redo_count, 0, 4 * sizeof(unsigned int), b->stream));
+    }
     LOCGPU_HIP(ctx, hipMemcpyAsync(b->d_state, b->h_state, b->n_total * sizeof(PoseState), hipMemcpyHostToDevice, b->stream));
     b->stage_ev.used = 0;
     IterLauncher it{ctx, b, spec};
     if (!it.launch(0)) return LOCGPU_ERR_NO_DEVICE;
     LOCGPU_HIP(ctx, hipMemcpyAsync(b->h_hb, b->d_hb, (size_t)b->n_total * 44 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     LOCGPU_HIP(ctx, hipStreamSynchronize(b->stream));
-    b->stage_ev.collect(ctx, false);
+    b->stage_ev.collect(ctx, ndt);
     std::memcpy(hb, b->h_hb, (size_t)b->n_total * 44 * sizeof(double));
     return LOCGPU_OK;
 }

@@ -56,7 +56,7 @@ int align_begin(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, cons
 int align_finish(locgpu_ctx* ctx, locgpu_batch* b, double* out_poses, locgpu_align_stats* stats);
 int run_align(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const AlignSpec& spec, double* out_poses, locgpu_align_stats* stats);
 // H, B, effective_num and ok of every scan of `b` at `poses` (one iteration without the update) → hb[n_total][44].
-int eval_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, const AlignSpec& spec, double* hb);
+int eval_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, const AlignSpec& spec, double* hb, const char* who);
 // Score of every entry of `b` under its pose: k = 1 exact search stage, then the reduction of fitness.hip.
 int fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, double max_range, locgpu_fitness* out);
 // Score of every entry of `b` under its pose against the context's direct NDT table (ndt_fitness.hip).

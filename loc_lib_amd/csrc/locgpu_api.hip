@@ -531,7 +531,7 @@ int locgpu_icp_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, c
     AlignSpec spec;
     int rc = check_icp(ctx, opts, spec);
     if (rc == LOCGPU_OK) rc = check_batch(ctx, b, poses && hb, spec, "icp_hb_batch");
-    return rc != LOCGPU_OK ? rc : eval_hb_batch(ctx, b, poses, spec, hb);
+    return rc != LOCGPU_OK ? rc : eval_hb_batch(ctx, b, poses, spec, hb, "icp_hb_batch");
 }
 
 int locgpu_debug_batch_nn(locgpu_ctx* ctx, locgpu_batch* b, int k, int32_t* out) {
@@ -561,7 +561,7 @@ int locgpu_icp_hb(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_byte
     rc = single_batch(ctx, src, n, stride_bytes, &b);
     if (rc != LOCGPU_OK) return rc;
     double hb[44];
-    rc = eval_hb_batch(ctx, b, pose, spec, hb);
+    rc = eval_hb_batch(ctx, b, pose, spec, hb, "icp_hb");
     if (rc != LOCGPU_OK) return rc;
     std::memcpy(H, hb, 36 * sizeof(double));
     std::memcpy(B, hb + 36, 6 * sizeof(double));
@@ -1275,6 +1275,32 @@ int locgpu_ndt_align(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_b
     AlignSpec spec;
     const int rc = check_ndt(ctx, spec);
     return rc != LOCGPU_OK ? rc : align_single(ctx, spec, "ndt_align", src && init_pose && out_pose, src, n, stride_bytes, nullptr, init_pose, out_pose, stats);
+}
+
+int locgpu_ndt_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, double* hb) {
+    AlignSpec spec;
+    int rc = check_ndt(ctx, spec);
+    if (rc == LOCGPU_OK) rc = check_batch(ctx, b, poses && hb, spec, "ndt_hb_batch");
+    return rc != LOCGPU_OK ? rc : eval_hb_batch(ctx, b, poses, spec, hb, "ndt_hb_batch");
+}
+
+int locgpu_ndt_hb(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double pose[7], double H[36], double B[6], int64_t* effective_num,
+                  int* ok) {
+    AlignSpec spec;
+    int rc = check_ndt(ctx, spec);
+    if (rc != LOCGPU_OK) return rc;
+    if (!src || !pose || !H || !B) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_hb: bad arguments");
+    locgpu_batch* b = nullptr;
+    rc = single_batch(ctx, src, n, stride_bytes, &b);
+    if (rc != LOCGPU_OK) return rc;
+    double hb[44];
+    rc = eval_hb_batch(ctx, b, pose, spec, hb, "ndt_hb");
+    if (rc != LOCGPU_OK) return rc;
+    std::memcpy(H, hb, 36 * sizeof(double));
+    std::memcpy(B, hb + 36, 6 * sizeof(double));
+    if (effective_num) *effective_num = (int64_t)hb[42];
+    if (ok) *ok = hb[43] != 0.0;
+    return LOCGPU_OK;
 }
 
 // ---- matcher entry points on clouds resident in HBM (cloud_filters.hpp) ----

@@ -590,40 +590,50 @@ public:
         }
     }
 
+    // One iteration's sums of AlignNdt at `pose` (ndt cpp:399-433), H and err accumulated from zero. Returns effective_num.
+    size_t DirectSums(const std::vector<F3>& src, const SE3& pose, double H[36], double err[6]) const {
+        size_t effective_num = 0;
+        std::memset(H, 0, 36 * sizeof(double));
+        std::memset(err, 0, 6 * sizeof(double));
+        const M3 R = rotation_matrix(pose);
+        for (size_t i = 0; i < src.size(); ++i) {
+            const V3 q = Icp::ToVec3d(src[i]);
+            const V3 qs = transform(pose, q);
+            const Key key = KeyOf(qs);
+            for (const Key& off : nearby) {
+                const Key ko{key[0] + off[0], key[1] + off[1], key[2] + off[2]};
+                auto it = grids.find(ko);
+                if (it != grids.end()) {
+                    const NdtVoxel& v = it->second;
+                    const V3 e = qs - v.mu;
+                    const double ev[3] = {e.x, e.y, e.z};
+                    // `e.transpose() * v.info_ * e` (ndt cpp:416) is (eᵀ·info)·e by C++ precedence: the 1×3 row vector first — Eigen
+                    // evaluates a nested product into a temporary — then its dot product with e
+                    double t[3];
+                    for (int c = 0; c < 3; ++c) t[c] = (ev[0] * v.info[c] + ev[1] * v.info[3 + c]) + ev[2] * v.info[6 + c];
+                    const double res = (t[0] * ev[0] + t[1] * ev[1]) + t[2] * ev[2];
+                    if (std::isnan(res) || res > opt.res_outlier_th) continue;
+                    const M3 Rh = mul(R, hat(q));
+                    double J[3][6];
+                    for (int r = 0; r < 3; ++r)
+                        for (int c = 0; c < 3; ++c) { J[r][c] = -Rh(r, c); J[r][3 + c] = (r == c) ? 1.0 : 0.0; }
+                    Icp::AddJtJ(H, err, J, 3, ev);  // NOT info-weighted (A25)
+                }
+            }
+            effective_num++;  // once per source point (ndt cpp:432)
+        }
+        return effective_num;
+    }
+    // The trace rows' `ok` of the direct method: the iteration neither aborts on det(H) == 0 (ndt cpp:435-436) nor is skipped for too few points.
+    bool DirectOk(double det, size_t effective_num) const { return det != 0 && effective_num >= (size_t)opt.min_effective_pts; }
+
     // ndt cpp:374-464. status: 0 ok (result written), 1 = det(H)==0 ⇒ `return false` before result_pose is assigned (A26).
     int AlignDirect(const std::vector<F3>& src, const SE3& init, SE3& result, IterTrace* trace, int trace_cap, int* iters_out) {
         SE3 pose = init;
         int iters = 0;
         for (int iter = 0; iter < opt.max_iteration; ++iter) {
-            size_t effective_num = 0;
-            double H[36] = {0}, err[6] = {0}, dx[6] = {0};
-            const M3 R = rotation_matrix(pose);
-            for (size_t i = 0; i < src.size(); ++i) {
-                const V3 q = Icp::ToVec3d(src[i]);
-                const V3 qs = transform(pose, q);
-                const Key key = KeyOf(qs);
-                for (const Key& off : nearby) {
-                    const Key ko{key[0] + off[0], key[1] + off[1], key[2] + off[2]};
-                    auto it = grids.find(ko);
-                    if (it != grids.end()) {
-                        const NdtVoxel& v = it->second;
-                        const V3 e = qs - v.mu;
-                        const double ev[3] = {e.x, e.y, e.z};
-                        // `e.transpose() * v.info_ * e` (ndt cpp:416) is (eᵀ·info)·e by C++ precedence: the 1×3 row vector first — Eigen
-                        // evaluates a nested product into a temporary — then its dot product with e
-                        double t[3];
-                        for (int c = 0; c < 3; ++c) t[c] = (ev[0] * v.info[c] + ev[1] * v.info[3 + c]) + ev[2] * v.info[6 + c];
-                        const double res = (t[0] * ev[0] + t[1] * ev[1]) + t[2] * ev[2];
-                        if (std::isnan(res) || res > opt.res_outlier_th) continue;
-                        const M3 Rh = mul(R, hat(q));
-                        double J[3][6];
-                        for (int r = 0; r < 3; ++r)
-                            for (int c = 0; c < 3; ++c) { J[r][c] = -Rh(r, c); J[r][3 + c] = (r == c) ? 1.0 : 0.0; }
-                        Icp::AddJtJ(H, err, J, 3, ev);  // NOT info-weighted (A25)
-                    }
-                }
-                effective_num++;  // once per source point (ndt cpp:432)
-            }
+            double H[36], err[6], dx[6] = {0};
+            const size_t effective_num = DirectSums(src, pose, H, err);
             ++iters;
             double x[6] = {0};
             const double det = lu6_det_solve(H, err, x);
@@ -632,7 +642,7 @@ public:
                 std::memcpy(trace[iter].B, err, sizeof(err));
                 std::memset(trace[iter].dx, 0, sizeof(dx));
                 trace[iter].effective_num = (double)effective_num;
-                trace[iter].ok = (det != 0 && effective_num >= (size_t)opt.min_effective_pts) ? 1.0 : 0.0;
+                trace[iter].ok = DirectOk(det, effective_num) ? 1.0 : 0.0;
             }
             if (det == 0) { if (iters_out) *iters_out = iters; return 1; }
             if (effective_num < (size_t)opt.min_effective_pts) continue;
@@ -646,55 +656,64 @@ public:
         return 0;
     }
 
+    // One iteration's sums of AlignIncNdt at `pose` (ndt cpp:286-347), H and err accumulated from zero. Returns effective_num.
+    int IncSums(const std::vector<F3>& src, const SE3& pose, double H[36], double err[6]) const {
+        int effective_num = 0;
+        std::memset(H, 0, 36 * sizeof(double));
+        std::memset(err, 0, 6 * sizeof(double));
+        const M3 R = rotation_matrix(pose);
+        for (size_t i = 0; i < src.size(); ++i) {
+            const V3 q = Icp::ToVec3d(src[i]);
+            const V3 qs = transform(pose, q);
+            const Key key = KeyOf(qs);
+            for (const Key& off : nearby) {
+                const Key ko{key[0] + off[0], key[1] + off[1], key[2] + off[2]};
+                auto it = inc_grids.find(ko);
+                if (it == inc_grids.end() || !it->second->second.ndt_estimated) continue;
+                const NdtVoxel& v = it->second->second;
+                const V3 e = qs - v.mu;
+                const double ev[3] = {e.x, e.y, e.z};
+                // here the chi² test is formed as e·(info·e): info·e is what the err term below needs anyway (ndt cpp:308 writes the same
+                // `e.transpose() * v.info_ * e` as the direct variant: the two groupings differ by rounding only, and only in this test)
+                double ie[3];
+                for (int r = 0; r < 3; ++r) ie[r] = (v.info[3 * r] * ev[0] + v.info[3 * r + 1] * ev[1]) + v.info[3 * r + 2] * ev[2];
+                const double res = (ev[0] * ie[0] + ev[1] * ie[1]) + ev[2] * ie[2];
+                if (std::isnan(res) || res > opt.res_outlier_th) continue;
+                const M3 Rh = mul(R, hat(q));
+                double J[3][6];
+                for (int r = 0; r < 3; ++r)
+                    for (int c = 0; c < 3; ++c) { J[r][c] = -Rh(r, c); J[r][3 + c] = (r == c) ? 1.0 : 0.0; }
+                // H += Jᵀ info J ; err += -Jᵀ info e (ndt cpp:345-346)
+                double IJ[3][6];
+                for (int r = 0; r < 3; ++r)
+                    for (int c = 0; c < 6; ++c) IJ[r][c] = (v.info[3 * r] * J[0][c] + v.info[3 * r + 1] * J[1][c]) + v.info[3 * r + 2] * J[2][c];
+                for (int a = 0; a < 6; ++a) {
+                    for (int b = 0; b < 6; ++b) H[6 * a + b] += (J[0][a] * IJ[0][b] + J[1][a] * IJ[1][b]) + J[2][a] * IJ[2][b];
+                    err[a] += -((J[0][a] * ie[0] + J[1][a] * ie[1]) + J[2][a] * ie[2]);
+                }
+                effective_num++;
+            }
+        }
+        return effective_num;
+    }
+    bool IncOk(int effective_num) const { return effective_num >= opt.min_effective_pts; }  // ndt cpp:349
+
     // ndt cpp:262-372. status 0 ok, 2 = effective_num too small (result = last pose, returns false).
     int AlignInc(const std::vector<F3>& src, const SE3& init, SE3& result, IterTrace* trace, int trace_cap, int* iters_out) {
         SE3 pose = init;
         int iters = 0;
         for (int iter = 0; iter < opt.max_iteration; ++iter) {
-            double H[36] = {0}, err[6] = {0}, dx[6] = {0};
-            int effective_num = 0;
-            const M3 R = rotation_matrix(pose);
-            for (size_t i = 0; i < src.size(); ++i) {
-                const V3 q = Icp::ToVec3d(src[i]);
-                const V3 qs = transform(pose, q);
-                const Key key = KeyOf(qs);
-                for (const Key& off : nearby) {
-                    const Key ko{key[0] + off[0], key[1] + off[1], key[2] + off[2]};
-                    auto it = inc_grids.find(ko);
-                    if (it == inc_grids.end() || !it->second->second.ndt_estimated) continue;
-                    const NdtVoxel& v = it->second->second;
-                    const V3 e = qs - v.mu;
-                    const double ev[3] = {e.x, e.y, e.z};
-                    // here the chi² test is formed as e·(info·e): info·e is what the err term below needs anyway (ndt cpp:308 writes the same
-                    // `e.transpose() * v.info_ * e` as the direct variant: the two groupings differ by rounding only, and only in this test)
-                    double ie[3];
-                    for (int r = 0; r < 3; ++r) ie[r] = (v.info[3 * r] * ev[0] + v.info[3 * r + 1] * ev[1]) + v.info[3 * r + 2] * ev[2];
-                    const double res = (ev[0] * ie[0] + ev[1] * ie[1]) + ev[2] * ie[2];
-                    if (std::isnan(res) || res > opt.res_outlier_th) continue;
-                    const M3 Rh = mul(R, hat(q));
-                    double J[3][6];
-                    for (int r = 0; r < 3; ++r)
-                        for (int c = 0; c < 3; ++c) { J[r][c] = -Rh(r, c); J[r][3 + c] = (r == c) ? 1.0 : 0.0; }
-                    // H += Jᵀ info J ; err += -Jᵀ info e (ndt cpp:345-346)
-                    double IJ[3][6];
-                    for (int r = 0; r < 3; ++r)
-                        for (int c = 0; c < 6; ++c) IJ[r][c] = (v.info[3 * r] * J[0][c] + v.info[3 * r + 1] * J[1][c]) + v.info[3 * r + 2] * J[2][c];
-                    for (int a = 0; a < 6; ++a) {
-                        for (int b = 0; b < 6; ++b) H[6 * a + b] += (J[0][a] * IJ[0][b] + J[1][a] * IJ[1][b]) + J[2][a] * IJ[2][b];
-                        err[a] += -((J[0][a] * ie[0] + J[1][a] * ie[1]) + J[2][a] * ie[2]);
-                    }
-                    effective_num++;
-                }
-            }
+            double H[36], err[6], dx[6] = {0};
+            const int effective_num = IncSums(src, pose, H, err);
             ++iters;
             if (trace && iter < trace_cap) {
                 std::memcpy(trace[iter].H, H, sizeof(H));
                 std::memcpy(trace[iter].B, err, sizeof(err));
                 std::memset(trace[iter].dx, 0, sizeof(dx));
                 trace[iter].effective_num = effective_num;
-                trace[iter].ok = effective_num >= opt.min_effective_pts ? 1.0 : 0.0;
+                trace[iter].ok = IncOk(effective_num) ? 1.0 : 0.0;
             }
-            if (effective_num < opt.min_effective_pts) { result = pose; if (iters_out) *iters_out = iters; return 2; }
+            if (!IncOk(effective_num)) { result = pose; if (iters_out) *iters_out = iters; return 2; }
             lu6_det_solve(H, err, dx);
             if (trace && iter < trace_cap) std::memcpy(trace[iter].dx, dx, sizeof(dx));
             apply_update(pose, dx);
@@ -907,6 +926,23 @@ int locref_ndt_align(void* mp, const float* src, size_t n, size_t stride_floats,
     else st = m->AlignDirect(s, se3_from_array(init), res, (IterTrace*)trace, trace_cap, iters_out);
     if (st != 1) se3_to_array(res, out_pose);
     return st;
+}
+// One iteration's sums at `pose` — the first trip of AlignDirect / AlignInc and nothing after it: H, B, effective_num; returns the `ok`
+// the trace rows carry.
+int locref_ndt_hb(void* mp, const float* src, size_t n, size_t stride_floats, const double pose[7], double H[36], double B[6],
+                  double* effective_num) {
+    auto* m = (Ndt*)mp;
+    const std::vector<F3> s = LoadCloud(src, n, stride_floats);
+    const SE3 T = se3_from_array(pose);
+    if (m->opt.method == 2) {
+        const int eff = m->IncSums(s, T, H, B);
+        if (effective_num) *effective_num = eff;
+        return m->IncOk(eff) ? 1 : 0;
+    }
+    const size_t eff = m->DirectSums(s, T, H, B);
+    if (effective_num) *effective_num = (double)eff;
+    double x[6] = {0};
+    return m->DirectOk(lu6_det_solve(H, B, x), eff) ? 1 : 0;
 }
 
 // ---- output cloud: pcl::transformPointCloud with pose.matrix().cast<float>() (A19) ----

@@ -59,6 +59,7 @@ def lib():
             "locref_ndt_num_voxels": (_sz, [_vp]),
             "locref_ndt_dump": (_sz, [_vp, _vp, _vp, _vp, _sz]),
             "locref_ndt_align": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _i, _vp]),
+            "locref_ndt_hb": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
             "locref_transform_cloud_f32": (None, [_vp, _vp, _sz, _sz, _vp, _sz]),
             "locref_remove_nan": (_sz, [_vp, _sz, _i, _vp]),
             "locref_crop_box": (_sz, [_vp, _sz, _i, _vp, _vp, _vp]),
@@ -269,6 +270,14 @@ class Ndt:
         info = np.zeros((n, 9))
         lib().locref_ndt_dump(self._h, keys.ctypes.data, mu.ctypes.data, info.ctypes.data, n)
         return keys, mu, info.reshape(n, 3, 3)
+
+    def hb(self, src, pose):
+        """One iteration's sums at `pose` (what the first trace row of align() from `pose` holds): (ok, H, B, effective_num)."""
+        src = _f32(src)
+        H, B, eff = np.zeros(36), np.zeros(6), np.zeros(1)
+        ok = lib().locref_ndt_hb(self._h, src.ctypes.data, src.shape[0], src.shape[1], _pose(pose).ctypes.data, H.ctypes.data,
+                                 B.ctypes.data, eff.ctypes.data)
+        return bool(ok), H.reshape(6, 6), B, int(eff[0])
 
     def align(self, src, init_pose, trace_cap=20):
         src = _f32(src)

@@ -27,10 +27,24 @@ def test_library_exports_every_declared_symbol(api):
 def test_header_cites_reference_for_every_entry_point():
     text = open(os.path.join(ROOT, "include", "locgpu.h")).read()
     for fn in ("locgpu_icp_set_target", "locgpu_knn", "locgpu_icp_hb", "locgpu_icp_align", "locgpu_transform_cloud",
-               "locgpu_ndt_set_target", "locgpu_ndt_align"):
+               "locgpu_ndt_set_target", "locgpu_ndt_align", "locgpu_ndt_hb"):
         pos = text.index(fn + "(")
         block = text[max(0, pos - 900):pos]
         assert re.search(r"\.(cpp|h|hpp):\d+", block), fn
+
+
+def test_ndt_hb_entry_points_are_bound_and_refuse_a_null_context(api):
+    L = api.lib()
+    for name in ("locgpu_ndt_hb", "locgpu_ndt_hb_batch"):
+        assert hasattr(L, name) and name in api.ABI_SYMBOLS, name
+    assert callable(api.Context.ndt_hb) and callable(api.Context.ndt_hb_batch)
+    pose = np.array([0, 0, 0, 1, 0, 0, 0], dtype=np.float64)
+    pts = np.zeros((4, 3), np.float32)
+    H, B, hb = np.full(36, 7.0), np.full(6, 7.0), np.full(44, 7.0)
+    # no context at all: LOCGPU_ERR_INVALID before anything is touched
+    assert L.locgpu_ndt_hb(None, pts.ctypes.data, 4, 12, pose.ctypes.data, H.ctypes.data, B.ctypes.data, None, None) == -1
+    assert L.locgpu_ndt_hb_batch(None, None, pose.ctypes.data, hb.ctypes.data) == -1
+    assert (H == 7.0).all() and (B == 7.0).all() and (hb == 7.0).all()
 
 
 def test_option_defaults_are_the_reference_defaults(api):

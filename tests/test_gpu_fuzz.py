@@ -35,6 +35,14 @@ def test_fuzz_loam_short():
     assert "mismatches 0" in _run("fuzz_loam.py", "--cases", "80", "--seed", "7")
 
 
+def test_fuzz_hb_short():
+    """12 cases = two of each map kind, five evaluations each (the three ICP methods, direct and incremental NDT with random options) on
+    maps capped at 10^4 points; the tool returns 1 on an effective_num / ok mismatch or an H / B error above the project's bars (two
+    ill-posed comparisons have finite bars of their own, written in the tool; a breach counts as over the bar)."""
+    out = _run("fuzz_hb.py", "--cases", "12", "--seed", "11", "--max-log10-map", "4.0")
+    assert "eff/ok mismatches: 0 H/B over the bar: 0" in out, out[-2000:]
+
+
 def test_fuzz_ndt_short():
     """Hard again: every mismatch fails, there is no retry path. Round 3 saw ONE incremental case go wrong once
     in ≈1 700; round 4 rebuilt the incremental target ingest on the device with every buffer written before it is read and sequential
