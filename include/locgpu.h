@@ -254,10 +254,11 @@ LOCGPU_API int locgpu_gn_update(const double hb[44], int method, int min_effecti
  * translation += dx.tail<3>() (:82-83), stop after the update when |dx| < eps (:85). det(H_surf + H_edge) == 0, where the reference
  * divides by zero, is an iteration without an update (what locgpu_gn_update does); the loop goes on.
  * Limits: the LOAM entry points run EAGER chunks only — locgpu_graph_enable (hipGraph), sharded batches, scan pools and the host-paced
- * one-scan path do not apply to them — LOCGPU_P2PLANE_MAP (map planes) is refused (LOCGPU_ERR_INVALID), and only the single-scan calls
- * have a resident form (locgpu_loam_set_target_cloud, locgpu_loam_scan_match_cloud, locgpu_loam_fitness_resident, locgpu_loam_submap_*,
- * declared with the resident clouds below): there is no batched resident form. Calls on a handle follow the context's rule: one
- * caller thread, synchronous, host inputs copied before the call returns. */
+ * one-scan path do not apply to them — LOCGPU_P2PLANE_MAP (map planes) is refused (LOCGPU_ERR_INVALID). Resident forms (declared with
+ * the resident clouds below): the single-scan calls (locgpu_loam_set_target_cloud, locgpu_loam_scan_match_cloud,
+ * locgpu_loam_fitness_resident, locgpu_loam_submap_*) and the SHARED-SOURCE batched form — one pair of scans under many poses
+ * (locgpu_loam_fitness_cloud, locgpu_loam_init_search_cloud); there is no batched resident form of n DIFFERENT scans. Calls on a
+ * handle follow the context's rule: one caller thread, synchronous, host inputs copied before the call returns. */
 typedef struct locgpu_loam locgpu_loam;
 /* LoamOption, loam_registration.hpp:22-36. Inside surf / edge only method, the three gates, min_effective_pts, approximate / ann_alpha
  * and search_mode are read: their max_iteration and eps are NOT (the loop is LoamRegistration's own, :47,85). */
@@ -274,6 +275,14 @@ LOCGPU_API void locgpu_loam_opts_default(locgpu_loam_opts* o);
  * LOCGPU_ERR_INVALID for NULL opts, both classes switched off, LOCGPU_P2PLANE_MAP or an unknown method / search mode in an enabled class.
  * A context is created for every enabled class. locgpu_loam_last_error(NULL) gives the text of a failed create. */
 LOCGPU_API int locgpu_loam_create(int device_id, const locgpu_loam_opts* opts, locgpu_loam** out);
+/* The same matcher over two EXISTING ICP contexts on one GPU — what a caller that already holds an edge and a surface context with
+ * their targets (the façade's LoamRegistration) needs for the score and the search below. The handle borrows the contexts, their
+ * targets and their options' workspaces: it creates none, locgpu_loam_destroy leaves them alive, and whether a class has a target is
+ * asked of its context at every call (LOCGPU_ERR_NO_TARGET while it has none), so a later locgpu_icp_set_target on the context is
+ * seen. A switched-off class's context may be NULL. The contexts' owner must not use them during a call on the handle and must
+ * destroy the handle first. LOCGPU_ERR_INVALID — before any device is touched — for NULL opts, the refusals of locgpu_loam_create,
+ * a NULL context of an enabled class, one context given twice, or contexts on different GPUs. */
+LOCGPU_API int locgpu_loam_create_on(locgpu_ctx* surf_ctx, locgpu_ctx* edge_ctx, const locgpu_loam_opts* opts, locgpu_loam** out);
 LOCGPU_API void locgpu_loam_destroy(locgpu_loam* l);
 LOCGPU_API const char* locgpu_loam_last_error(const locgpu_loam* l);
 /* LoamRegistration::SetInputTarget (loam_registration.cpp:22-36): IcpRegistration::SetInputTarget of every ENABLED class (a class that
@@ -363,6 +372,39 @@ LOCGPU_API void locgpu_init_search_opts_default(locgpu_init_search_opts* o);
 LOCGPU_API int locgpu_icp_init_search(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double* candidates, int m,
                                       const locgpu_icp_opts* opts, const locgpu_init_search_opts* sopts, double* out_poses,
                                       locgpu_fitness* out_fit, locgpu_align_stats* stats, int* best);
+/* ---- The JOINT score of a LOAM alignment and its initial-pose search (MatchingInterface::GetFitnessScore, which
+ * LoamRegistration leaves a stub that returns 0, loam_registration.cpp:101-104; Loc starts this matcher from SetInitPose(SE3()) or a
+ * GNSS position like the other two, lio_matching_flow.cpp:292-313). For a pose T and max_range every ENABLED class c — the surface
+ * scan against the surface map, the edge scan against the edge map — scores {Σ_c, inliers_c, finite_c} exactly as locgpu_icp_fitness
+ * defines it (exact 1-NN, fixed 1024-point split); then
+ *   joint.score = (Σ_surf + Σ_edge) / (inliers_surf + inliers_edge), surface added first, +inf with no inlier in either class;
+ *   joint.inliers / joint.finite_points = the sums of the two classes'; a switched-off class adds nothing and reports {+inf, 0, 0}.
+ * A POOLED mean, not a sum of two means: LoamRegistration's normal equations are a plain sum over all points of both classes
+ * (loam_registration.cpp:76-79), and the score weights a point the same way. The joint Σ is formed on the device from the un-rounded
+ * class sums. out holds THREE entries per pose: [3i] joint, [3i + 1] surface, [3i + 2] edge; the two class entries are the bits
+ * locgpu_icp_fitness gives on a context holding that class's map, and all three are the same bits alone, among other poses and in
+ * any chunk of a search.
+ * locgpu_loam_fitness: one pair of scans (each copied once) under n_poses >= 1 poses (n_poses × 7). A switched-off class's scan is
+ * not read and may be NULL; an enabled class's scan may be empty when the other is not. The handle's storage batches take a
+ * SHARED-SOURCE form — every entry reads the one region of points — so locgpu_loam_fitness_resident has nothing resident afterwards.
+ * LOCGPU_ERR_NO_TARGET without a target; LOCGPU_ERR_INVALID for n_poses < 1, both scans empty, a NaN max_range. */
+LOCGPU_API int locgpu_loam_fitness(locgpu_loam* l, const void* edge, size_t n_edge, const void* surf, size_t n_surf, size_t stride_bytes,
+                                   const double* poses, int n_poses, double max_range, locgpu_fitness* out /* n_poses × 3 */);
+/* The candidate search of locgpu_icp_init_search for the LOAM matcher: each of the m candidates (m × 7) runs exactly the joint
+ * Gauss–Newton loop locgpu_loam_align_batch runs on m copies of the pair of scans, bit for bit — without the copies — and every
+ * result is scored as above under sopts->max_range (out_poses m × 7, out_fit m × 3, stats m or NULL). *best = the lowest JOINT score
+ * among the candidates with joint inliers >= 1 and joint inliers / finite_points >= min_inlier_ratio, ties to the lower index; -1
+ * when none qualifies (the outputs are filled all the same). A candidate whose evaluation failed (status 3 / 4) keeps its initial
+ * pose, as in locgpu_loam_align_batch, and is scored there. sopts NULL = defaults. m is processed in equal chunks of at most 256
+ * candidates and at most 1 GiB of per-candidate workspace summed over both classes (44 B per point and candidate: the storage
+ * batches are plain ones, whose source rows stay unused beyond the first; a single candidate is always allowed). The handle keeps
+ * that workspace, the candidates' joint state and one pinned copy of each scan for the next call — grow-only — until
+ * locgpu_loam_destroy. Errors as locgpu_loam_fitness, and LOCGPU_ERR_INVALID for m < 1 or a negative or NaN min_inlier_ratio; every
+ * argument is checked before anything is copied or enqueued. */
+LOCGPU_API int locgpu_loam_init_search(locgpu_loam* l, const void* edge, size_t n_edge, const void* surf, size_t n_surf, size_t stride_bytes,
+                                       const double* candidates, int m, const locgpu_init_search_opts* sopts, double* out_poses,
+                                       locgpu_fitness* out_fit /* m × 3 */, locgpu_align_stats* stats, int* best);
+
 /* Host helper (no device, no context): the candidate poses centre ∘ (yaw about the centre's z axis, then x / y offsets in the
  * centre's frame) for yaw = a · yaw_step, x = i · xy_step, y = j · xy_step with |a| <= floor(yaw_half / yaw_step + 1e-9),
  * |i|, |j| <= floor(xy_half / xy_step + 1e-9) — the kind of uncertainty a GNSS position with an IMU heading has
@@ -661,12 +703,21 @@ LOCGPU_API int locgpu_loam_scan_match_cloud(locgpu_loam* l, const locgpu_cloud* 
                                             double result_pose[7], locgpu_align_stats* stats, locgpu_cloud* out);
 /* MatchingInterface::GetFitnessScore for the LOAM matcher (the reference's ScanMatch, loam_registration.cpp:38-99, computes none):
  * out[0] = surface, out[1] = edge, each exactly locgpu_icp_fitness of that class's scan against that class's map under `pose` —
- * exact nearest neighbour, fixed reduction order. No joint number is invented: the caller combines the two. The scans are the ones
+ * exact nearest neighbour, fixed reduction order. No joint number here (locgpu_loam_fitness defines and gives one). The scans are the ones
  * the handle's most recent single-scan call left in HBM: locgpu_loam_scan_match / locgpu_loam_hb (the handle's own copies) or
  * locgpu_loam_scan_match_cloud — which keeps REFERENCES, so those two clouds must still be alive and unmodified. A switched-off
  * class (and an empty scan) reports {+inf, 0, 0}. LOCGPU_ERR_INVALID when nothing is resident (no such call yet, or a
  * locgpu_loam_align_batch since); LOCGPU_ERR_NO_TARGET without a target. */
 LOCGPU_API int locgpu_loam_fitness_resident(locgpu_loam* l, const double pose[7], double max_range, locgpu_fitness out[2]);
+/* locgpu_loam_fitness and locgpu_loam_init_search on resident feature clouds: the same bits without the uploads. The scans are NOT
+ * copied — every entry of a class reads its cloud where it lies, so the clouds must not be modified during the call. A switched-off
+ * class's cloud may be NULL; a cloud on another GPU is refused with LOCGPU_ERR_INVALID before anything is enqueued. This is the LOAM
+ * matcher's batched resident form: one pair of scans under many poses, not n different scans. */
+LOCGPU_API int locgpu_loam_fitness_cloud(locgpu_loam* l, const locgpu_cloud* edge, const locgpu_cloud* surf, const double* poses, int n_poses,
+                                         double max_range, locgpu_fitness* out /* n_poses × 3 */);
+LOCGPU_API int locgpu_loam_init_search_cloud(locgpu_loam* l, const locgpu_cloud* edge, const locgpu_cloud* surf, const double* candidates, int m,
+                                             const locgpu_init_search_opts* sopts, double* out_poses, locgpu_fitness* out_fit /* m × 3 */,
+                                             locgpu_align_stats* stats, int* best);
 
 /* The PAIR of local maps of Lio::AddCloud(FullCloudPtr) (lio.cpp:331-409) in HBM: local_map_edge_ / local_map_surf_ with their queues
  * edge_scans_in_local_map_ / surf_scans_in_local_map_ — one queue length (num_kfs) for both, pushed and popped together (:382-388) —

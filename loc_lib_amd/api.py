@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "locgpu_loam_hb", "locgpu_loam_scan_match", "locgpu_loam_align_batch",
     "locgpu_loam_set_target_cloud", "locgpu_loam_set_target_cloud_async", "locgpu_loam_scan_match_cloud", "locgpu_loam_fitness_resident",
     "locgpu_loam_submap_create", "locgpu_loam_submap_destroy", "locgpu_loam_submap_add_keyframe", "locgpu_loam_submap_clouds", "locgpu_loam_submap_info",
+    "locgpu_loam_create_on", "locgpu_loam_fitness", "locgpu_loam_fitness_cloud", "locgpu_loam_init_search", "locgpu_loam_init_search_cloud",
 ]
 COMM_ID_BYTES = 128
 NO_INTENSITY = ctypes.c_size_t(-1).value
@@ -186,6 +187,11 @@ def lib():
             "locgpu_loam_submap_create": (i32, [vp, i32, f32, vp]), "locgpu_loam_submap_destroy": (None, [vp]),
             "locgpu_loam_submap_add_keyframe": (i32, [vp, vp, vp, vp]), "locgpu_loam_submap_clouds": (i32, [vp, vp, vp]),
             "locgpu_loam_submap_info": (i32, [vp, vp, vp, vp]),
+            "locgpu_loam_create_on": (i32, [vp, vp, vp, vp]),
+            "locgpu_loam_fitness": (i32, [vp, vp, sz, vp, sz, sz, vp, i32, dbl, vp]),
+            "locgpu_loam_fitness_cloud": (i32, [vp, vp, vp, vp, i32, dbl, vp]),
+            "locgpu_loam_init_search": (i32, [vp, vp, sz, vp, sz, sz, vp, i32, vp, vp, vp, vp, vp]),
+            "locgpu_loam_init_search_cloud": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -1019,6 +1025,20 @@ class Loam:
         if rc != 0:
             raise LocGpuError(rc, lib().locgpu_loam_last_error(None).decode())
 
+    @classmethod
+    def on(cls, surf_ctx, edge_ctx, opts=None):
+        """The matcher over two existing Contexts (locgpu_loam_create_on): their targets are borrowed, and they outlive the handle.
+        None for the context of a class that is switched off."""
+        self = cls.__new__(cls)
+        self._h = ctypes.c_void_p()
+        self.opts = opts if opts is not None else loam_opts()
+        self._ctxs = (surf_ctx, edge_ctx)  # kept alive: the handle must go first
+        rc = lib().locgpu_loam_create_on(surf_ctx._h if surf_ctx is not None else None, edge_ctx._h if edge_ctx is not None else None,
+                                         ctypes.byref(self.opts), ctypes.byref(self._h))
+        if rc != 0:
+            raise LocGpuError(rc, lib().locgpu_loam_last_error(None).decode())
+        return self
+
     def close(self):
         if getattr(self, "_h", None):
             lib().locgpu_loam_destroy(self._h)
@@ -1095,6 +1115,46 @@ class Loam:
         out = (Fitness * 2)()
         self._check(lib().locgpu_loam_fitness_resident(self._h, _pose(pose).ctypes.data, float(max_range), out))
         return [_fitness_dict(out[0]), _fitness_dict(out[1])]
+
+    # ---- the joint score and the initial-pose search: one pair of scans under many poses. Three entries per pose: joint, surface, edge
+    @staticmethod
+    def _fit3(fit, m, raw):
+        return fit if raw else [[_fitness_dict(fit[3 * i + j]) for j in range(3)] for i in range(m)]
+
+    def fitness(self, edge, surf, poses, max_range=1.0, raw=False):
+        """Per pose [joint, surface, edge] (dicts as Context.icp_fitness; raw=True: the ctypes array of 3 entries per pose)."""
+        e, pe, ne, se = self._arg(edge)
+        s, ps, ns, ss = self._arg(surf)
+        p = _pose(poses).reshape(-1, 7)
+        out = (Fitness * (3 * max(len(p), 1)))()
+        self._check(lib().locgpu_loam_fitness(self._h, pe, ne, ps, ns, self._stride(se, ss), p.ctypes.data, len(p), float(max_range), out))
+        return self._fit3(out, len(p), raw)
+
+    def fitness_cloud(self, edge, surf, poses, max_range=1.0, raw=False):
+        p = _pose(poses).reshape(-1, 7)
+        out = (Fitness * (3 * max(len(p), 1)))()
+        self._check(lib().locgpu_loam_fitness_cloud(self._h, edge._h if edge is not None else None, surf._h if surf is not None else None, p.ctypes.data,
+                                                    len(p), float(max_range), out))
+        return self._fit3(out, len(p), raw)
+
+    def _search(self, call, head, candidates, sopts, raw):
+        c = _pose(candidates).reshape(-1, 7)
+        m = c.shape[0]
+        out = np.zeros((m, 7))
+        fit = (Fitness * (3 * max(m, 1)))()
+        st = (AlignStats * max(m, 1))()
+        best = ctypes.c_int(-2)
+        self._check(call(self._h, *head, c.ctypes.data, m, ctypes.byref(sopts) if sopts is not None else None, out.ctypes.data, fit, st, ctypes.byref(best)))
+        return out, self._fit3(fit, m, raw), [_stats_dict(x) for x in st], int(best.value)
+
+    def init_search(self, edge, surf, candidates, sopts=None, raw=False):
+        """Returns (poses [m, 7], per candidate [joint, surface, edge] fitness, stats, best index by the joint score or -1)."""
+        e, pe, ne, se = self._arg(edge)
+        s, ps, ns, ss = self._arg(surf)
+        return self._search(lib().locgpu_loam_init_search, (pe, ne, ps, ns, self._stride(se, ss)), candidates, sopts, raw)
+
+    def init_search_cloud(self, edge, surf, candidates, sopts=None, raw=False):
+        return self._search(lib().locgpu_loam_init_search_cloud, (edge._h if edge is not None else None, surf._h if surf is not None else None), candidates, sopts, raw)
 
     # ---- many feature scans against the one pair of maps
     def align_batch(self, edges, surfs, init_poses):

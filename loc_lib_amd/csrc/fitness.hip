@@ -84,17 +84,69 @@ __global__ __launch_bounds__(64) void icp_fitness_sum_kernel(const double* __res
     if (lane == 3) out[(size_t)scan * kFitW + 3] = 0.0;
 }
 
+// The joint score of the LOAM matcher (loam_align.hip): one wave per candidate adds the surface batch's rows, then the edge batch's —
+// each class exactly as icp_fitness_sum_kernel adds them (lane l rows l, l + 64, …, then lane 0..2 the 64 lane sums in order), with its
+// own rows per scan — so out[cand][1 + c] holds the bits locgpu_icp_fitness gives for class c, and out[cand][0] = surface + edge formed
+// from those UN-ROUNDED class sums (surface first), not from two means. partials[c] == nullptr: the class is switched off and adds
+// zeros. out[cand][3][kFitW] = {Σd², inliers, finite points, 0} of joint, surface, edge. list_counts[c]: the class batch's search
+// work-list counters, consumed by now — zeroed for the next search (as loam_solve_kernel does). No atomics.
+__global__ __launch_bounds__(64) void loam_fitness_sum_kernel(const double* __restrict__ part_surf, int rows_surf, const double* __restrict__ part_edge,
+                                                              int rows_edge, double* __restrict__ out, unsigned int* __restrict__ counts_surf,
+                                                              unsigned int* __restrict__ counts_edge) {
+    __shared__ double s_lane[3][64];
+    const int cand = blockIdx.x, lane = threadIdx.x;
+    if (blockIdx.x == 0 && lane < 4) {
+        if (counts_surf) counts_surf[lane] = 0u;
+        if (counts_edge) counts_edge[lane] = 0u;
+    }
+    double* o = out + (size_t)cand * 3 * kFitW;
+    double joint = 0.0;  // lanes 0..2: Σ, inliers, finite points of both classes
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const double* part = c == 0 ? part_surf : part_edge;
+        const int rows = part ? (c == 0 ? rows_surf : rows_edge) : 0;
+        const double* p = part + (size_t)cand * rows * kFitW;  // not read when rows == 0
+        double a = 0.0, b = 0.0, d = 0.0;
+        for (int r = lane; r < rows; r += 64) {
+            a += p[(size_t)r * kFitW + 0];
+            b += p[(size_t)r * kFitW + 1];
+            d += p[(size_t)r * kFitW + 2];
+        }
+        if (c == 1) __syncthreads();  // the surface class's lane sums have been read
+        s_lane[0][lane] = a; s_lane[1][lane] = b; s_lane[2][lane] = d;
+        __syncthreads();
+        if (lane < 3) {
+            double t = s_lane[lane][0];
+            for (int l = 1; l < 64; ++l) t += s_lane[lane][l];
+            o[(1 + c) * kFitW + lane] = t;
+            joint += t;
+        }
+        if (lane == 3) o[(1 + c) * kFitW + 3] = 0.0;
+    }
+    if (lane < 3) o[lane] = joint;
+    if (lane == 3) o[3] = 0.0;
+}
+
 int icp_fitness_rows(int max_n) { return (max_n + kFitPts * kBlock - 1) / (kFitPts * kBlock); }
 
 void launch_fitness_sum(const double* partials, int rows, int n_scans, double* out, unsigned int* list_counts, hipStream_t s) {
     hipLaunchKernelGGL(icp_fitness_sum_kernel, dim3(n_scans), dim3(64), 0, s, partials, rows, out, list_counts);
 }
 
-void launch_icp_fitness(const FitnessArgs& a, hipStream_t s) {
+int launch_icp_fitness_accum(const FitnessArgs& a, hipStream_t s) {
     const int rows = icp_fitness_rows(a.max_n);
     hipLaunchKernelGGL(icp_fitness_accum_kernel, dim3(rows, a.n_scans), dim3(kBlock), 0, s, a.tree, a.src, a.counts, a.st, a.nn, a.max_n, a.gate2, a.partials,
                        a.src_of);
+    return rows;
+}
+
+void launch_icp_fitness(const FitnessArgs& a, hipStream_t s) {
+    const int rows = launch_icp_fitness_accum(a, s);
     launch_fitness_sum(a.partials, rows, a.n_scans, a.out, a.list_counts, s);
+}
+
+void launch_loam_fitness_sum(const double* const partials[2], const int rows[2], int n_cands, double* out, unsigned int* const list_counts[2], hipStream_t s) {
+    hipLaunchKernelGGL(loam_fitness_sum_kernel, dim3(n_cands), dim3(64), 0, s, partials[0], rows[0], partials[1], rows[1], out, list_counts[0], list_counts[1]);
 }
 
 }  // namespace locgpu

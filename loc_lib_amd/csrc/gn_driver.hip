@@ -34,6 +34,8 @@ inline int first_chunk_len(const locgpu_batch* b) {
     return std::min(kLongFirstChunk, std::max(3, b->last_iterations + 1));
 }
 
+}  // namespace
+
 // The search stage's arguments over storage batch `b`: tree, depth, lists and counters are the context's and the batch's; what a
 // caller varies afterwards (active, src_of, visit_totals) starts empty.
 SearchArgs make_search_args(const locgpu_ctx* ctx, const locgpu_batch* b, const float4* src, const PoseState* st, int k, float alpha_eff, bool skip_nonfinite) {
@@ -42,7 +44,6 @@ SearchArgs make_search_args(const locgpu_ctx* ctx, const locgpu_batch* b, const 
     if (!ctx->tree_bounded) sa.redo_list = nullptr;  // huge / non-finite map coordinates: exact tree kernel only
     return sa;
 }
-}  // namespace
 
 void init_state(PoseState& ps, const double pose[7]) {
     std::memset(&ps, 0, sizeof(ps));

@@ -45,6 +45,10 @@ int ensure_grid_lists(locgpu_ctx* ctx, locgpu_batch* b, const AlignSpec& spec);
 // forces either way; default: with more than one rank.
 bool shard_decoupled(const locgpu_ctx* ctx, bool scan_sharded);
 
+// The search stage's arguments over storage batch `b`: tree, depth, lists and counters are the context's and the batch's; what a
+// caller varies afterwards (active, src_of, visit_totals) starts empty.
+SearchArgs make_search_args(const locgpu_ctx* ctx, const locgpu_batch* b, const float4* src, const PoseState* st, int k, float alpha_eff, bool skip_nonfinite);
+
 void init_state(PoseState& ps, const double pose[7]);
 // A finished scan's pose and statistics; status 1 (direct NDT aborted: the reference leaves result_pose unassigned) hands back `init`.
 void write_scan_result(const PoseState& ps, const double* init, double* out_pose, locgpu_align_stats* stats);

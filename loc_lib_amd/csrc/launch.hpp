@@ -118,6 +118,12 @@ struct FitnessArgs {
 };
 int icp_fitness_rows(int max_n);
 void launch_icp_fitness(const FitnessArgs& a, hipStream_t s);
+// Its first half alone: the block rows of every scan → a.partials (a.out and a.list_counts are not read). Returns the rows per scan.
+int launch_icp_fitness_accum(const FitnessArgs& a, hipStream_t s);
+// The joint score of the LOAM matcher (fitness.hip): class 0 = surface, 1 = edge; partials[c] with rows[c] rows per candidate as
+// launch_icp_fitness_accum left them in the class's batch (nullptr: the class is switched off). out[n_cands][3][kFitW]: joint, surface,
+// edge, each {Σd², inliers, finite points, 0}. list_counts[c] (optional): the class batch's search work-list counters, zeroed.
+void launch_loam_fitness_sum(const double* const partials[2], const int rows[2], int n_cands, double* out, unsigned int* const list_counts[2], hipStream_t s);
 // The last step of a score, shared with the NDT score (ndt_fitness.hip): adds the `rows` block rows {Σ, inliers, finite points, ·} of
 // every scan in a fixed order → out[scan][kFitW]. list_counts (optional): the search stage's work-list counters, zeroed.
 void launch_fitness_sum(const double* partials, int rows, int n_scans, double* out, unsigned int* list_counts, hipStream_t s);

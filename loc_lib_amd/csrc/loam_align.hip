@@ -8,6 +8,8 @@
 // the chunks of align_begin / align_finish (gn_driver.hip) without graphs, shards, pools or host pacing.
 // The _cloud entry points run the same loop on feature clouds that are already in HBM (the batches' d_src_ext, as single_batch_dev of
 // locgpu_api.hip does) and write the output cloud on the device (loam_stream.hip).
+// The joint score and the candidate search (locgpu_loam_fitness*, locgpu_loam_init_search*) give the storage batches their third,
+// shared-source form — every entry of a class reads the ONE pair of scans — and go through the chunk driver of search_chunks.hpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -19,6 +21,7 @@
 #include "context.hpp"
 #include "gn_driver.hpp"
 #include "launch.hpp"
+#include "search_chunks.hpp"
 
 using namespace locgpu;
 
@@ -31,6 +34,7 @@ struct locgpu_loam {
     locgpu_loam_opts opts{};
     bool use[2] = {false, false};
     locgpu_ctx* ctx[2] = {nullptr, nullptr};
+    bool borrowed = false;  // locgpu_loam_create_on: the contexts, their targets and their lifetime are the caller's
     locgpu_batch* batch[2] = {nullptr, nullptr};  // storage batches: kept between calls, grow-only, reshaped to the call's scans
     bool has_target[2] = {false, false};
     bool resident = false;  // the storage batches hold (or, after a _cloud call, point at) the scans of a single-scan call: locgpu_loam_fitness_resident
@@ -44,6 +48,18 @@ struct locgpu_loam {
     double* h_hb = nullptr;        // pinned
     int* d_active = nullptr;
     int* h_active = nullptr;       // pinned
+    double* d_fit = nullptr;       // [cap_scans][3][kFitW]: the joint score's sums — joint, surface, edge
+    double* h_fit = nullptr;       // pinned
+    // Shared-source form of the storage batches (share_scans): every entry of class c reads ONE region of n_shared[c] points — the
+    // batch's own d_src, filled once through h_shared[c], or a caller's cloud through d_src_ext. src_of[c] / split_scans are what run()
+    // hands to LocalStage::src_of / split_scans: nullptr / 0 in the two other forms (upload_scans, attach_scans).
+    int* d_src_of[2] = {nullptr, nullptr};      // a zero per entry
+    int cap_src_of[2] = {0, 0};
+    float4* h_shared[2] = {nullptr, nullptr};   // pinned staging of a host scan
+    size_t cap_shared[2] = {0, 0};
+    size_t n_shared[2] = {0, 0};
+    const int* src_of[2] = {nullptr, nullptr};
+    int split_scans = 0;
     // output cloud of scan_match: packed x, y, z of edge then surface points; the points of a switched-off class pass through d_off
     size_t cap_xyz = 0;
     float* d_xyz = nullptr;
@@ -102,6 +118,9 @@ void free_joint(locgpu_loam* l) {
     if (l->h_hb) (void)hipHostFree(l->h_hb);
     if (l->d_active) (void)hipFree(l->d_active);
     if (l->h_active) (void)hipHostFree(l->h_active);
+    if (l->d_fit) (void)hipFree(l->d_fit);
+    if (l->h_fit) (void)hipHostFree(l->h_fit);
+    l->d_fit = nullptr; l->h_fit = nullptr;
     l->d_state = nullptr; l->h_state = nullptr; l->d_hb = nullptr; l->h_hb = nullptr; l->d_active = nullptr; l->h_active = nullptr;
     l->cap_scans = 0;
 }
@@ -114,7 +133,9 @@ int reserve_joint(locgpu_loam* l, int n) {
                     lhip(l, hipMalloc((void**)&l->d_hb, (size_t)n * kLoamHbW * sizeof(double)), "hipMalloc hb") &&
                     lhip(l, hipHostMalloc((void**)&l->h_hb, (size_t)n * kLoamHbW * sizeof(double)), "hipHostMalloc hb") &&
                     lhip(l, hipMalloc((void**)&l->d_active, (size_t)n * sizeof(int)), "hipMalloc active") &&
-                    lhip(l, hipHostMalloc((void**)&l->h_active, (size_t)n * sizeof(int)), "hipHostMalloc active");
+                    lhip(l, hipHostMalloc((void**)&l->h_active, (size_t)n * sizeof(int)), "hipHostMalloc active") &&
+                    lhip(l, hipMalloc((void**)&l->d_fit, (size_t)n * 3 * kFitW * sizeof(double)), "hipMalloc fit") &&
+                    lhip(l, hipHostMalloc((void**)&l->h_fit, (size_t)n * 3 * kFitW * sizeof(double)), "hipHostMalloc fit");
     if (!ok) { free_joint(l); return LOCGPU_ERR_OOM; }
     l->cap_scans = n;
     return LOCGPU_OK;
@@ -132,7 +153,9 @@ int shape_batch(locgpu_loam* l, int c, int n_scans, size_t max_n) {
         size_t cp = std::max(max_n, b ? b->cap_points : (size_t)0);
         if (cp == max_n && n_scans == 1) cp = max_n + max_n / 4 + 1024;
         if (b) { (void)hipStreamSynchronize(l->stream); free_batch(b); l->batch[c] = nullptr; }
+        const int slot = ctx->next_slot;
         int rc = from_ctx(l, c, alloc_batch(ctx, cs, cp, &l->batch[c]));
+        ctx->next_slot = slot;  // the handle's storage does not take part in the rotation of a (borrowed) context's batches over its streams
         if (rc != LOCGPU_OK) return rc;
         b = l->batch[c];
         b->slot = 0;
@@ -158,6 +181,8 @@ int shape_batch(locgpu_loam* l, int c, int n_scans, size_t max_n) {
 // behind the copies and behind whatever either context's own stream still runs (its target ingest).
 int upload_scans(locgpu_loam* l, int n_scans, const void* const* srcs[2], const size_t* counts[2], size_t stride) {
     size_t max_n[2] = {0, 0};
+    l->src_of[kSurf] = l->src_of[kEdge] = nullptr;  // every scan reads its own region, and the sums split by this call's shape
+    l->split_scans = 0;
     for (int c = 0; c < 2; ++c) {  // every argument is checked before the first copy starts: a refused call reads nothing
         if (!l->use[c]) continue;
         if (!srcs[c] || !counts[c]) return lfail(l, LOCGPU_ERR_INVALID, "loam: the scans of an enabled feature class are NULL");
@@ -212,6 +237,8 @@ int attach_scans(locgpu_loam* l, const locgpu_cloud* const clouds[2], const char
         if (!l->use[c]) continue;
         if (!clouds[c] || !clouds[c]->ctx) return lfail(l, LOCGPU_ERR_INVALID, std::string(who) + ": the scan of an enabled feature class is NULL");
     }
+    l->src_of[kSurf] = l->src_of[kEdge] = nullptr;
+    l->split_scans = 0;
     for (int c = 0; c < 2; ++c) {
         if (!l->use[c]) continue;
         int rc = cloud_ready(l, clouds[c], who);
@@ -233,12 +260,82 @@ int attach_scans(locgpu_loam* l, const locgpu_cloud* const clouds[2], const char
     return LOCGPU_OK;
 }
 
+// The third way to fill the storage batches, beside upload_scans and attach_scans: the ONE pair of scans of a score under many poses or
+// of a candidate search. Class c's batch is shaped for `entries` entries of n[c] points (the largest chunk: share_entries shapes every
+// chunk inside it) and its region 0 holds the scan — copied once from host[c], or read where clouds[c] holds it (clouds != nullptr).
+int share_scans(locgpu_loam* l, const char* who, const void* const host[2], const locgpu_cloud* const* clouds, const size_t n[2], size_t stride, int entries) {
+    for (int c = 0; c < 2; ++c) {
+        if (!l->use[c]) continue;
+        int rc = clouds && n[c] ? cloud_ready(l, clouds[c], who) : LOCGPU_OK;
+        if (rc == LOCGPU_OK) rc = shape_batch(l, c, entries, n[c]);
+        if (rc != LOCGPU_OK) return rc;
+        locgpu_batch* b = l->batch[c];
+        const int jrc = from_ctx(l, c, upload_join_batch(b));  // a failed earlier upload stays with the batch until one replaces it: say so
+        if (jrc != LOCGPU_OK) return jrc;
+        LOAM_HIP(l, upload_order_after(b, l->stream));
+        if (l->cap_src_of[c] < b->cap_scans) {
+            if (l->d_src_of[c]) (void)hipFree(l->d_src_of[c]);
+            l->d_src_of[c] = nullptr; l->cap_src_of[c] = 0;
+            if (!lhip(l, hipMalloc((void**)&l->d_src_of[c], (size_t)b->cap_scans * sizeof(int)), "hipMalloc src_of")) return LOCGPU_ERR_OOM;
+            l->cap_src_of[c] = b->cap_scans;
+            LOAM_HIP(l, hipMemsetAsync(l->d_src_of[c], 0, (size_t)b->cap_scans * sizeof(int), l->stream));
+        }
+        b->d_src_ext = nullptr;
+        if (clouds) {
+            if (n[c]) b->d_src_ext = clouds[c]->d;
+        } else if (n[c]) {
+            if (l->cap_shared[c] < n[c]) {
+                if (l->h_shared[c]) (void)hipHostFree(l->h_shared[c]);
+                l->h_shared[c] = nullptr; l->cap_shared[c] = 0;
+                const size_t cap = n[c] + n[c] / 4 + 1024;
+                if (!lhip(l, hipHostMalloc((void**)&l->h_shared[c], cap * sizeof(float4)), "hipHostMalloc shared scan")) return LOCGPU_ERR_OOM;
+                l->cap_shared[c] = cap;
+            }
+            pack_points((const char*)host[c], stride, n[c], l->h_shared[c]);  // the deep copy of SetSource (icp_registration.cpp:252-265), once
+            LOAM_HIP(l, hipMemcpyAsync(b->d_src, l->h_shared[c], n[c] * sizeof(float4), hipMemcpyHostToDevice, l->stream));
+        }
+        if (l->ctx[c]->stream != l->stream) {  // behind that context's target ingest
+            LOAM_HIP(l, hipEventRecord(l->ev, l->ctx[c]->stream));
+            LOAM_HIP(l, hipStreamWaitEvent(l->stream, l->ev, 0));
+        }
+        l->n_shared[c] = n[c];
+        l->src_of[c] = l->d_src_of[c];
+    }
+    l->split_scans = 0;
+    return LOCGPU_OK;
+}
+
+// One chunk of the shared-source form: `cnt` entries of the resident pair of scans, counts[i] = n for every entry; split > 0: the
+// accumulate kernels split their sums as the plain batch of that many scans would (the m of the whole search).
+int share_entries(locgpu_loam* l, int cnt, int split) {
+    for (int c = 0; c < 2; ++c) {
+        if (!l->use[c]) continue;
+        const int rc = shape_batch(l, c, cnt, l->n_shared[c]);  // inside the capacity share_scans made: nothing is allocated
+        if (rc != LOCGPU_OK) return rc;
+        locgpu_batch* b = l->batch[c];
+        b->counts.assign(cnt, (int)l->n_shared[c]);
+        for (int i = 0; i < cnt; ++i) b->upl.h_counts[i] = (int)l->n_shared[c];  // pinned, the uploader's (idle); the previous chunk has left the stream
+        LOAM_HIP(l, hipMemcpyAsync(b->d_counts, b->upl.h_counts, (size_t)cnt * sizeof(int), hipMemcpyHostToDevice, l->stream));
+    }
+    l->split_scans = split;
+    return LOCGPU_OK;
+}
+
+// Class c has a target: the handle's own record, or — on borrowed contexts — whatever the context holds at this call.
+int class_target(locgpu_loam* l, int c, const char* who) {
+    if (!l->borrowed && !l->has_target[c]) return lfail(l, LOCGPU_ERR_NO_TARGET, std::string(who) + ": locgpu_loam_set_target has not been called");
+    const int jrc = from_ctx(l, c, target_join(l->ctx[c]));  // an asynchronous ingest ends here at the latest
+    if (jrc != LOCGPU_OK) return jrc;
+    if (!l->ctx[c]->d_tree) return lfail(l, LOCGPU_ERR_NO_TARGET, std::string(who) + ": the " + (c == kSurf ? "surface" : "edge") + " class has no target");
+    return LOCGPU_OK;
+}
+
 // Both classes' requests against their current targets (check_icp: the asynchronous ingest ends here, the grid is built on first use).
 int check_classes(locgpu_loam* l, AlignSpec spec[2], const char* who) {
     for (int c = 0; c < 2; ++c) {
         if (!l->use[c]) continue;
-        if (!l->has_target[c]) return lfail(l, LOCGPU_ERR_NO_TARGET, std::string(who) + ": locgpu_loam_set_target has not been called");
-        const int rc = from_ctx(l, c, check_icp(l->ctx[c], &class_opts(l, c), spec[c]));
+        if (!l->borrowed && !l->has_target[c]) return lfail(l, LOCGPU_ERR_NO_TARGET, std::string(who) + ": locgpu_loam_set_target has not been called");
+        const int rc = from_ctx(l, c, check_icp(l->ctx[c], &class_opts(l, c), spec[c]));  // a borrowed context without a target: its LOCGPU_ERR_NO_TARGET
         if (rc != LOCGPU_OK) return rc;
     }
     return LOCGPU_OK;
@@ -291,7 +388,7 @@ int run(locgpu_loam* l, int n, const double* poses, const AlignSpec spec[2], int
             for (int c = 0; c < 2 && rc == LOCGPU_OK; ++c) {
                 if (!l->use[c]) continue;
                 locgpu_batch* b = l->batch[c];
-                const LocalStage w{batch_src(b), l->d_state, active, active ? n_active : 0, nullptr, 0, spec[c], nullptr, b->d_grid_qkey ? &gsc[c] : nullptr, false,
+                const LocalStage w{batch_src(b), l->d_state, active, active ? n_active : 0, l->src_of[c], l->split_scans, spec[c], nullptr, b->d_grid_qkey ? &gsc[c] : nullptr, false,
                                    c == kSurf ? "loam surface search" : "loam edge search"};
                 const int blocks = launch_local_stage(l->ctx[c], b, w, s);
                 if (blocks < 0) rc = from_ctx(l, c, LOCGPU_ERR_DEPTH);
@@ -322,6 +419,135 @@ void write_stats(const PoseState& ps, locgpu_align_stats* st) {
     if (!st) return;
     st->iterations = ps.iterations; st->converged = ps.converged; st->status = ps.status; st->reserved = 0;
     st->last_effective_num = ps.last_eff; st->last_dx_norm = ps.last_dx_norm;
+}
+
+// Poses and statistics of the n scans run() left in l->h_state; a scan whose evaluation failed (status 3 / 4) hands back its init_pose.
+void write_results(const locgpu_loam* l, int n, const double* init_poses, double* out_poses, locgpu_align_stats* stats) {
+    for (int i = 0; i < n; ++i) {
+        const PoseState& ps = l->h_state[i];
+        double* o = out_poses + 7 * (size_t)i;
+        if (ps.status != 0) {
+            std::memcpy(o, init_poses + 7 * (size_t)i, 7 * sizeof(double));
+        } else {
+            for (int j = 0; j < 4; ++j) o[j] = ps.q[j];
+            for (int j = 0; j < 3; ++j) o[4 + j] = ps.t[j];
+        }
+        write_stats(ps, stats ? stats + i : nullptr);
+    }
+}
+
+void to_fitness(const double r[kFitW], locgpu_fitness* f) {
+    f->inliers = (int64_t)r[1];
+    f->finite_points = (int64_t)r[2];
+    f->score = f->inliers > 0 ? r[0] / (double)f->inliers : HUGE_VAL;
+}
+
+// The joint score of the n entries resident in the storage batches under their poses → out[3i] joint, [3i + 1] surface, [3i + 2] edge.
+// Per class the k = 1 exact search stage and the accumulate kernel of locgpu_icp_fitness (fitness_on_batch, gn_driver.hip) over the
+// joint states, then ONE sum kernel for both (loam_fitness_sum_kernel, fitness.hip). Leaves the stream idle.
+int score(locgpu_loam* l, int n, const double* poses, double max_range, locgpu_fitness* out) {
+    hipStream_t s = l->stream;
+    for (int i = 0; i < n; ++i) init_state(l->h_state[i], poses + 7 * (size_t)i);
+    LOAM_HIP(l, hipMemcpyAsync(l->d_state, l->h_state, (size_t)n * sizeof(PoseState), hipMemcpyHostToDevice, s));
+    const double* partials[2] = {nullptr, nullptr};
+    int rows[2] = {0, 0};
+    unsigned int* list_counts[2] = {nullptr, nullptr};
+    for (int c = 0; c < 2; ++c) {
+        if (!l->use[c]) continue;
+        locgpu_batch* b = l->batch[c];
+        if (!b->counters_clean) LOAM_HIP(l, hipMemsetAsync(b->d_redo_count, 0, 4 * sizeof(unsigned int), s));
+        b->counters_clean = false;
+        // the exact walk whatever the class's options say, skipping the points pcl::isFinite rejects (fitness_on_batch)
+        SearchArgs sa = make_search_args(l->ctx[c], b, batch_src(b), l->d_state, 1, 1.0f, true);
+        sa.src_of = l->src_of[c];
+        if (!launch_icp_search(sa, s)) { (void)hipStreamSynchronize(s); return lfail(l, LOCGPU_ERR_DEPTH, "loam_fitness: unsupported tree depth"); }
+        FitnessArgs fa{l->ctx[c]->d_tree, batch_src(b), b->d_counts, l->d_state, b->d_nn, b->max_n, b->n_scans, (float)(max_range * max_range), b->d_partials, nullptr, nullptr};
+        fa.src_of = l->src_of[c];
+        rows[c] = launch_icp_fitness_accum(fa, s);
+        partials[c] = b->d_partials;
+        list_counts[c] = b->d_redo_count;
+    }
+    launch_loam_fitness_sum(partials, rows, n, l->d_fit, list_counts, s);
+    LOAM_HIP(l, hipGetLastError());
+    LOAM_HIP(l, hipMemcpyAsync(l->h_fit, l->d_fit, (size_t)n * 3 * kFitW * sizeof(double), hipMemcpyDeviceToHost, s));
+    LOAM_HIP(l, hipStreamSynchronize(s));
+    for (int c = 0; c < 2; ++c)
+        if (l->use[c]) l->batch[c]->counters_clean = true;  // the sum kernel zeroed them behind the searches
+    for (int i = 0; i < 3 * n; ++i) to_fitness(l->h_fit + (size_t)i * kFitW, out + i);
+    return LOCGPU_OK;
+}
+
+// Per-entry workspace of the shared-source form, per point: the plain storage batch's source row 16 B, neighbour lists 20 B and two
+// work lists 8 B. A chunk's bound (search_chunks.hpp) is over both classes.
+constexpr size_t kLoamSearchBytesPerPoint = 44;
+
+// The arguments every shared-source entry point shares, checked before anything is copied or enqueued; n[] comes back as the points
+// of the ENABLED classes (a switched-off class's scan is not read).
+int check_shared(locgpu_loam* l, const char* who, const void* const host[2], const locgpu_cloud* const* clouds, size_t n[2], size_t stride, bool args_ok) {
+    if (!args_ok || (!clouds && stride < 12)) return lfail(l, LOCGPU_ERR_INVALID, std::string(who) + ": bad arguments");
+    for (int c = 0; c < 2; ++c) {
+        if (!l->use[c]) { n[c] = 0; continue; }
+        if (clouds) {
+            if (!clouds[c] || !clouds[c]->ctx) return lfail(l, LOCGPU_ERR_INVALID, std::string(who) + ": the scan of an enabled feature class is NULL");
+            if (clouds[c]->ctx->device != l->device) return lfail(l, LOCGPU_ERR_INVALID, std::string(who) + ": a cloud belongs to a context on another GPU");
+            n[c] = clouds[c]->n;
+        } else if (n[c] && !host[c]) {
+            return lfail(l, LOCGPU_ERR_INVALID, std::string(who) + ": NULL scan pointer");
+        }
+        if (n[c] > 0x7FFFFF00u) return lfail(l, LOCGPU_ERR_INVALID, std::string(who) + ": too many points in a scan");
+    }
+    if (n[kSurf] + n[kEdge] == 0) return lfail(l, LOCGPU_ERR_INVALID, std::string(who) + ": both scans are empty");
+    return LOCGPU_OK;
+}
+
+int shared_chunk(const size_t n[2], int m) { return search_chunk(kLoamSearchBytesPerPoint * (std::max<size_t>(n[kSurf], 1) + std::max<size_t>(n[kEdge], 1)), m); }
+
+int fitness_shared(locgpu_loam* l, const char* who, const void* const host[2], const locgpu_cloud* const* clouds, size_t n[2], size_t stride, const double* poses,
+                   int n_poses, double max_range, locgpu_fitness* out) {
+    if (!l) return LOCGPU_ERR_INVALID;
+    int rc = check_shared(l, who, host, clouds, n, stride, poses && out && n_poses >= 1 && !std::isnan(max_range));
+    for (int c = 0; c < 2 && rc == LOCGPU_OK; ++c)
+        if (l->use[c]) rc = class_target(l, c, who);
+    if (rc != LOCGPU_OK) return rc;
+    LOAM_HIP(l, hipSetDevice(l->device));
+    const int chunk = shared_chunk(n, n_poses);
+    l->resident = false;  // the storage batches take the shared-source form
+    rc = reserve_joint(l, chunk);
+    if (rc == LOCGPU_OK) rc = share_scans(l, who, host, clouds, n, stride, chunk);
+    if (rc != LOCGPU_OK) return rc;
+    return fitness_in_chunks(n_poses, chunk, [&](int off, int cnt) {
+        const int erc = share_entries(l, cnt, 0);
+        return erc != LOCGPU_OK ? erc : score(l, cnt, poses + 7 * (size_t)off, max_range, out + 3 * (size_t)off);
+    });
+}
+
+int search_shared(locgpu_loam* l, const char* who, const void* const host[2], const locgpu_cloud* const* clouds, size_t n[2], size_t stride, const double* candidates,
+                  int m, const locgpu_init_search_opts* sopts, double* out_poses, locgpu_fitness* out_fit, locgpu_align_stats* stats, int* best) {
+    if (!l) return LOCGPU_ERR_INVALID;
+    locgpu_init_search_opts so;
+    if (sopts) so = *sopts; else locgpu_init_search_opts_default(&so);
+    int rc = check_shared(l, who, host, clouds, n, stride,
+                          candidates && m >= 1 && out_poses && out_fit && best && !std::isnan(so.max_range) && so.min_inlier_ratio >= 0.0);
+    if (rc != LOCGPU_OK) return rc;
+    AlignSpec spec[2];
+    rc = check_classes(l, spec, who);
+    if (rc != LOCGPU_OK) return rc;
+    LOAM_HIP(l, hipSetDevice(l->device));
+    const int chunk = shared_chunk(n, m);
+    l->resident = false;  // the storage batches take the shared-source form
+    rc = reserve_joint(l, chunk);
+    if (rc == LOCGPU_OK) rc = share_scans(l, who, host, clouds, n, stride, chunk);
+    if (rc != LOCGPU_OK) return rc;
+    return init_search_in_chunks(m, chunk, so.min_inlier_ratio, out_fit, 3, best, [&](int off, int cnt) {
+        const double* init = candidates + 7 * (size_t)off;
+        double* poses = out_poses + 7 * (size_t)off;
+        // every chunk sums as locgpu_loam_align_batch on all m copies would: chunking never shows in a pose
+        int crc = share_entries(l, cnt, m);
+        if (crc == LOCGPU_OK) crc = run(l, cnt, init, spec, 1);
+        if (crc != LOCGPU_OK) return crc;
+        write_results(l, cnt, init, poses, stats ? stats + off : nullptr);
+        return score(l, cnt, poses, so.max_range, out_fit + 3 * (size_t)off);
+    });
 }
 
 // *cloud += *edge; *cloud += *surf; pcl::transformPointCloud(*cloud, *result, pose.matrix().cast<float>()) (loam_registration.cpp:93-96):
@@ -421,6 +647,35 @@ int locgpu_loam_create(int device_id, const locgpu_loam_opts* opts, locgpu_loam*
     return LOCGPU_OK;
 }
 
+int locgpu_loam_create_on(locgpu_ctx* surf_ctx, locgpu_ctx* edge_ctx, const locgpu_loam_opts* opts, locgpu_loam** out) {
+    if (!out) return lfail(nullptr, LOCGPU_ERR_INVALID, "loam_create_on: out is NULL");
+    *out = nullptr;
+    if (!opts) return lfail(nullptr, LOCGPU_ERR_INVALID, "loam_create_on: opts is NULL");
+    locgpu_ctx* ctx[2] = {surf_ctx, edge_ctx};
+    const int32_t use[2] = {opts->use_surf_points, opts->use_edge_points};
+    for (int c = 0; c < 2; ++c)
+        if (use[c] && !ctx[c]) return lfail(nullptr, LOCGPU_ERR_INVALID, "loam_create_on: the context of an enabled feature class is NULL");
+    int rc = check_opts(opts);  // before any device call: a refusal needs no GPU
+    if (rc != LOCGPU_OK) return rc;
+    if (use[kSurf] && use[kEdge] && (surf_ctx == edge_ctx || surf_ctx->device != edge_ctx->device))
+        return lfail(nullptr, LOCGPU_ERR_INVALID, "loam_create_on: the two classes need two different contexts on one GPU");
+    auto* l = new locgpu_loam();
+    l->borrowed = true;
+    l->opts = *opts;
+    for (int c = 0; c < 2; ++c) {
+        l->use[c] = use[c] != 0;
+        if (!l->use[c]) continue;
+        l->ctx[c] = ctx[c];
+        if (!l->stream) { l->stream = ctx[c]->stream; l->device = ctx[c]->device; }
+    }
+    if (hipSetDevice(l->device) != hipSuccess || hipEventCreateWithFlags(&l->ev, hipEventDisableTiming) != hipSuccess) {
+        locgpu_loam_destroy(l);
+        return lfail(nullptr, LOCGPU_ERR_NO_DEVICE, "loam_create_on: hipEventCreate");
+    }
+    *out = l;
+    return LOCGPU_OK;
+}
+
 void locgpu_loam_destroy(locgpu_loam* l) {
     if (!l) return;
     (void)hipSetDevice(l->device);
@@ -435,7 +690,11 @@ void locgpu_loam_destroy(locgpu_loam* l) {
     if (l->d_off) (void)hipFree(l->d_off);
     if (l->h_off) (void)hipHostFree(l->h_off);
     if (l->ev) (void)hipEventDestroy(l->ev);
-    for (int c = 0; c < 2; ++c) locgpu_destroy(l->ctx[c]);
+    for (int c = 0; c < 2; ++c) {
+        if (l->d_src_of[c]) (void)hipFree(l->d_src_of[c]);
+        if (l->h_shared[c]) (void)hipHostFree(l->h_shared[c]);
+        if (!l->borrowed) locgpu_destroy(l->ctx[c]);  // borrowed contexts stay alive, with their targets
+    }
     delete l;
 }
 
@@ -587,7 +846,7 @@ int locgpu_loam_fitness_resident(locgpu_loam* l, const double pose[7], double ma
     if (!l->resident) return lfail(l, LOCGPU_ERR_INVALID, "loam_fitness_resident: no scans of a single-scan call are resident");
     for (int c = 0; c < 2; ++c) {
         if (!l->use[c]) continue;
-        if (!l->has_target[c]) return lfail(l, LOCGPU_ERR_NO_TARGET, "loam_fitness_resident: locgpu_loam_set_target has not been called");
+        if (!l->borrowed && !l->has_target[c]) return lfail(l, LOCGPU_ERR_NO_TARGET, "loam_fitness_resident: locgpu_loam_set_target has not been called");
         const int jrc = from_ctx(l, c, target_join(l->ctx[c]));  // an asynchronous ingest ends here at the latest
         if (jrc != LOCGPU_OK) return jrc;
         if (!l->ctx[c]->d_tree) return lfail(l, LOCGPU_ERR_NO_TARGET, "loam_fitness_resident: locgpu_loam_set_target has not been called");
@@ -601,6 +860,34 @@ int locgpu_loam_fitness_resident(locgpu_loam* l, const double pose[7], double ma
         if (rc != LOCGPU_OK) return rc;
     }
     return LOCGPU_OK;
+}
+
+int locgpu_loam_fitness(locgpu_loam* l, const void* edge, size_t n_edge, const void* surf, size_t n_surf, size_t stride_bytes, const double* poses, int n_poses,
+                        double max_range, locgpu_fitness* out) {
+    const void* host[2] = {surf, edge};
+    size_t n[2] = {n_surf, n_edge};
+    return fitness_shared(l, "loam_fitness", host, nullptr, n, stride_bytes, poses, n_poses, max_range, out);
+}
+
+int locgpu_loam_fitness_cloud(locgpu_loam* l, const locgpu_cloud* edge, const locgpu_cloud* surf, const double* poses, int n_poses, double max_range,
+                              locgpu_fitness* out) {
+    const locgpu_cloud* clouds[2] = {surf, edge};
+    size_t n[2] = {0, 0};
+    return fitness_shared(l, "loam_fitness_cloud", nullptr, clouds, n, 0, poses, n_poses, max_range, out);
+}
+
+int locgpu_loam_init_search(locgpu_loam* l, const void* edge, size_t n_edge, const void* surf, size_t n_surf, size_t stride_bytes, const double* candidates, int m,
+                            const locgpu_init_search_opts* sopts, double* out_poses, locgpu_fitness* out_fit, locgpu_align_stats* stats, int* best) {
+    const void* host[2] = {surf, edge};
+    size_t n[2] = {n_surf, n_edge};
+    return search_shared(l, "loam_init_search", host, nullptr, n, stride_bytes, candidates, m, sopts, out_poses, out_fit, stats, best);
+}
+
+int locgpu_loam_init_search_cloud(locgpu_loam* l, const locgpu_cloud* edge, const locgpu_cloud* surf, const double* candidates, int m,
+                                  const locgpu_init_search_opts* sopts, double* out_poses, locgpu_fitness* out_fit, locgpu_align_stats* stats, int* best) {
+    const locgpu_cloud* clouds[2] = {surf, edge};
+    size_t n[2] = {0, 0};
+    return search_shared(l, "loam_init_search_cloud", nullptr, clouds, n, 0, candidates, m, sopts, out_poses, out_fit, stats, best);
 }
 
 int locgpu_loam_align_batch(locgpu_loam* l, int n_scans, const void* const* edge_srcs, const size_t* edge_counts, const void* const* surf_srcs,
@@ -618,17 +905,7 @@ int locgpu_loam_align_batch(locgpu_loam* l, int n_scans, const void* const* edge
     if (rc == LOCGPU_OK) rc = upload_scans(l, n_scans, srcs, counts, stride_bytes);
     if (rc == LOCGPU_OK) rc = run(l, n_scans, init_poses, spec, 1);
     if (rc != LOCGPU_OK) return rc;
-    for (int i = 0; i < n_scans; ++i) {
-        const PoseState& ps = l->h_state[i];
-        double* o = out_poses + 7 * (size_t)i;
-        if (ps.status != 0) {
-            std::memcpy(o, init_poses + 7 * (size_t)i, 7 * sizeof(double));
-        } else {
-            for (int j = 0; j < 4; ++j) o[j] = ps.q[j];
-            for (int j = 0; j < 3; ++j) o[4 + j] = ps.t[j];
-        }
-        write_stats(ps, stats ? stats + i : nullptr);
-    }
+    write_results(l, n_scans, init_poses, out_poses, stats);
     return LOCGPU_OK;
 }
 

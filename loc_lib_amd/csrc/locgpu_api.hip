@@ -19,6 +19,7 @@
 #include "launch.hpp"
 #include "ndt_inc.hpp"
 #include "ndt_kernels.hpp"
+#include "search_chunks.hpp"
 
 using namespace locgpu;
 
@@ -759,10 +760,8 @@ int locgpu_transform_cloud(locgpu_ctx* ctx, const double pose[7], const void* sr
 }  // extern "C"
 
 namespace {
-// The context's own shared-source batch (locgpu_icp_fitness with several poses, locgpu_icp_init_search) is bounded: at most
-// kSearchEntries entries per chunk and kSearchBytes of per-entry workspace (neighbour lists 20 B + two work lists 8 B per point and entry).
-constexpr int kSearchEntries = 256;
-constexpr size_t kSearchBytes = (size_t)1 << 30;
+// The context's own shared-source batch (locgpu_icp_fitness with several poses, locgpu_icp_init_search) is bounded as search_chunks.hpp
+// says; its per-entry workspace is neighbour lists 20 B + two work lists 8 B per point and entry.
 constexpr size_t kSearchBytesPerPoint = 28;
 
 void drop_graphs(locgpu_batch* b) {
@@ -805,10 +804,7 @@ int upload_shared(locgpu_ctx* ctx, locgpu_batch* b, const void* src, size_t n, s
 // The context's shared-source batch with the cloud resident, for m entries in all: *chunk = entries per chunk (equal chunks, the
 // last one may be shorter).
 int search_batch(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, int m, int* chunk, locgpu_batch** out) {
-    const size_t fit = kSearchBytes / (kSearchBytesPerPoint * n);
-    const int chunk_max = (int)std::min<size_t>(kSearchEntries, std::max<size_t>(fit, 1));
-    const int n_chunks = (m + chunk_max - 1) / chunk_max;
-    *chunk = (m + n_chunks - 1) / n_chunks;
+    *chunk = search_chunk(kSearchBytesPerPoint * n, m);
     locgpu_batch* b = ctx->search;
     if (!b || b->cap_scans < *chunk || b->cap_points < n) {
         // grow-only while the bound holds; else exactly what this call needs
@@ -846,45 +842,39 @@ int ndt_fitness_target(locgpu_ctx* ctx, const char* who) {
     return LOCGPU_OK;
 }
 
-// One cloud under n_poses > 1 poses, through the context's shared-source batch in chunks; score(batch, poses, out) scores a chunk.
+// One cloud under n_poses > 1 poses, through the context's shared-source batch in chunks (search_chunks.hpp); score(batch, poses, out)
+// scores a chunk.
 template <class Score>
-int fitness_in_chunks(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double* poses, int n_poses, locgpu_fitness* out, Score score) {
+int ctx_fitness_in_chunks(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double* poses, int n_poses, locgpu_fitness* out, Score score) {
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
     locgpu_batch* b = nullptr;
     int chunk = 0;
-    int rc = search_batch(ctx, src, n, stride_bytes, n_poses, &chunk, &b);
-    for (int off = 0; rc == LOCGPU_OK && off < n_poses; off += chunk) {
-        const int cnt = std::min(chunk, n_poses - off);
-        rc = reshape_shared(ctx, b, cnt, n, 0);
-        if (rc == LOCGPU_OK) rc = score(b, poses + 7 * (size_t)off, out + off);
-    }
-    return rc;
+    const int rc = search_batch(ctx, src, n, stride_bytes, n_poses, &chunk, &b);
+    if (rc != LOCGPU_OK) return rc;
+    return fitness_in_chunks(n_poses, chunk, [&](int off, int cnt) {
+        const int src_rc = reshape_shared(ctx, b, cnt, n, 0);
+        return src_rc != LOCGPU_OK ? src_rc : score(b, poses + 7 * (size_t)off, out + off);
+    });
 }
 
-// The candidate search of either matcher: every chunk of the context's shared-source batch is aligned under `spec`, scored by
-// score(batch, poses, out), and the winner picked by the rule of locgpu.h.
+// The candidate search of either matcher over the context's shared-source batch: every chunk is aligned under `spec` and scored by
+// score(batch, poses, out); the driver of search_chunks.hpp picks the winner.
 template <class Score>
-int init_search_in_chunks(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double* candidates, int m, const AlignSpec& spec,
-                          double min_inlier_ratio, double* out_poses, locgpu_fitness* out_fit, locgpu_align_stats* stats, int* best, Score score) {
+int ctx_init_search_in_chunks(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double* candidates, int m, const AlignSpec& spec,
+                              double min_inlier_ratio, double* out_poses, locgpu_fitness* out_fit, locgpu_align_stats* stats, int* best, Score score) {
     *best = -1;
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
     locgpu_batch* b = nullptr;
     int chunk = 0;
-    int rc = search_batch(ctx, src, n, stride_bytes, m, &chunk, &b);
-    for (int off = 0; rc == LOCGPU_OK && off < m; off += chunk) {
-        const int cnt = std::min(chunk, m - off);
+    const int brc = search_batch(ctx, src, n, stride_bytes, m, &chunk, &b);
+    if (brc != LOCGPU_OK) return brc;
+    return init_search_in_chunks(m, chunk, min_inlier_ratio, out_fit, 1, best, [&](int off, int cnt) {
         // every chunk sums as the plain batch of all m candidates would: chunking never shows in a pose
-        rc = reshape_shared(ctx, b, cnt, n, m);
+        int rc = reshape_shared(ctx, b, cnt, n, m);
         if (rc == LOCGPU_OK) rc = run_align(ctx, b, candidates + 7 * (size_t)off, spec, out_poses + 7 * (size_t)off, stats ? stats + off : nullptr);
         if (rc == LOCGPU_OK) rc = score(b, out_poses + 7 * (size_t)off, out_fit + off);
-    }
-    if (rc != LOCGPU_OK) return rc;
-    for (int i = 0; i < m; ++i) {
-        const locgpu_fitness& f = out_fit[i];
-        if (f.inliers <= 0 || !((double)f.inliers >= min_inlier_ratio * (double)f.finite_points)) continue;
-        if (*best < 0 || f.score < out_fit[*best].score) *best = i;  // ties stay with the lower index
-    }
-    return LOCGPU_OK;
+        return rc;
+    });
 }
 }  // namespace
 
@@ -926,7 +916,7 @@ int locgpu_icp_fitness(locgpu_ctx* ctx, const void* src, size_t n, size_t stride
         rc = single_batch(ctx, src, n, stride_bytes, &b);
         return rc != LOCGPU_OK ? rc : fitness_on_batch(ctx, b, poses, max_range, out);
     }
-    return fitness_in_chunks(ctx, src, n, stride_bytes, poses, n_poses, out,
+    return ctx_fitness_in_chunks(ctx, src, n, stride_bytes, poses, n_poses, out,
                              [&](locgpu_batch* sb, const double* p, locgpu_fitness* o) { return fitness_on_batch(ctx, sb, p, max_range, o); });
 }
 
@@ -957,7 +947,7 @@ int locgpu_icp_init_search(locgpu_ctx* ctx, const void* src, size_t n, size_t st
         !(so.min_inlier_ratio >= 0.0))
         return fail(ctx, LOCGPU_ERR_INVALID, "icp_init_search: bad arguments");
     if (n > 0x7FFFFF00u) return fail(ctx, LOCGPU_ERR_INVALID, "icp_init_search: too many points");
-    return init_search_in_chunks(ctx, src, n, stride_bytes, candidates, m, spec, so.min_inlier_ratio, out_poses, out_fit, stats, best,
+    return ctx_init_search_in_chunks(ctx, src, n, stride_bytes, candidates, m, spec, so.min_inlier_ratio, out_poses, out_fit, stats, best,
                                  [&](locgpu_batch* sb, const double* p, locgpu_fitness* o) { return fitness_on_batch(ctx, sb, p, so.max_range, o); });
 }
 
@@ -982,7 +972,7 @@ int locgpu_ndt_fitness(locgpu_ctx* ctx, const void* src, size_t n, size_t stride
         rc = single_batch(ctx, src, n, stride_bytes, &b);
         return rc != LOCGPU_OK ? rc : ndt_fitness_on_batch(ctx, b, poses, out);
     }
-    return fitness_in_chunks(ctx, src, n, stride_bytes, poses, n_poses, out,
+    return ctx_fitness_in_chunks(ctx, src, n, stride_bytes, poses, n_poses, out,
                              [&](locgpu_batch* sb, const double* p, locgpu_fitness* o) { return ndt_fitness_on_batch(ctx, sb, p, o); });
 }
 
@@ -1009,7 +999,7 @@ int locgpu_ndt_init_search(locgpu_ctx* ctx, const void* src, size_t n, size_t st
     if (!src || n == 0 || stride_bytes < 12 || !candidates || m < 1 || !out_poses || !out_fit || !best || !(so.min_inlier_ratio >= 0.0))
         return fail(ctx, LOCGPU_ERR_INVALID, "ndt_init_search: bad arguments");
     if (n > 0x7FFFFF00u) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_init_search: too many points");
-    return init_search_in_chunks(ctx, src, n, stride_bytes, candidates, m, spec, so.min_inlier_ratio, out_poses, out_fit, stats, best,
+    return ctx_init_search_in_chunks(ctx, src, n, stride_bytes, candidates, m, spec, so.min_inlier_ratio, out_poses, out_fit, stats, best,
                                  [&](locgpu_batch* sb, const double* p, locgpu_fitness* o) { return ndt_fitness_on_batch(ctx, sb, p, o); });
 }
 

@@ -48,7 +48,8 @@ public:
     // defines it (locgpu.h, locgpu_icp_fitness): it is computed on that call, from the source copy ScanMatch left in HBM and the
     // result pose — ScanMatch itself does nothing more than before. +inf when no point lies within max_range; 0 before the first
     // ScanMatch or when the library fails (LastError). WITHOUT the opt-in GetFitnessScore() keeps returning the reference's 0.0f.
-    // NdtRegistration and LoamRegistration keep the stub: an NDT context has no nearest-neighbour structure to score against.
+    // NdtRegistration and LoamRegistration have opt-ins of their own (their headers): an NDT context has no nearest-neighbour
+    // structure to score against, and a LOAM alignment has two.
     void EnableFitnessScore(double max_range);
     // Not in the reference: a labelled FAST MODE, never the source of a parity claim. With it on and method_ == P2PLANE the matcher
     // fits ONE plane per map point when the target is set (SetInputTarget builds the table; locgpu_icp_build_map_planes) and every

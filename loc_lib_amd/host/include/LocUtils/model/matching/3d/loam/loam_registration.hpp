@@ -4,6 +4,8 @@
 // (loam_registration.cpp:38-99). Here both evaluations run on the GPU over resident batches; the 6×6 solve stays on the host.
 #pragma once
 #include <memory>
+#include <string>
+#include <vector>
 
 #include "LocUtils/model/matching/3d/icp/icp_registration.hpp"
 #include "LocUtils/model/matching/3d/matching_interface.h"
@@ -12,6 +14,7 @@
 
 struct locgpu_ctx;
 struct locgpu_batch;
+struct locgpu_loam;
 
 namespace LocUtils {
 
@@ -43,6 +46,23 @@ public:
     float GetFitnessScore() override;
     void SetDevice(int device_id);
 
+    // Not in the reference, where GetFitnessScore is a stub that returns 0 (loam_registration.cpp:101-104). After
+    // EnableFitnessScore(max_range [m]) GetFitnessScore() returns the JOINT score of the last ScanMatch at its result pose (locgpu.h,
+    // locgpu_loam_fitness: the pooled mean squared distance of both classes' inliers, each class against its own map). It is computed
+    // on that call, on copies of the two scans ScanMatch was given — kept only after the opt-in — through a handle that borrows this
+    // matcher's two contexts (locgpu_loam_create_on), made on first use. ScanMatch's results are what they were. +infinity before
+    // the first successful ScanMatch, when no point lies within max_range and when the library fails (LastError). WITHOUT the opt-in
+    // GetFitnessScore() keeps returning the reference's 0.0f.
+    void EnableFitnessScore(double max_range);
+    // Not in the reference: aligns the pair of feature scans from every candidate pose with this matcher's options in one batched
+    // call on the GPU (locgpu_loam_init_search: each scan is uploaded once, every candidate runs the device-side joint loop), scores
+    // every result (EnableFitnessScore's range, 1 m by default) and hands back the best: the lowest joint score among the results
+    // with at least half of their points within range. false — best_score = +infinity, best_pose untouched — when no candidate
+    // qualifies, a target is missing, or the library fails (LastError). Leaves what GetFitnessScore() reports alone.
+    bool InitialPoseSearch(const CloudPtr& edge_input, const CloudPtr& surf_input, const std::vector<SE3>& candidates, SE3& best_pose, float& best_score);
+    // Text of the last failure of the two calls above (the reference only logs through glog).
+    const char* LastError() const;
+
 private:
     LoamOption options_;
     locgpu_ctx* edge_ctx_ = nullptr;  // icp_edge_ptr_ (P2Line)
@@ -53,6 +73,14 @@ private:
     size_t edge_cap_ = 0, surf_cap_ = 0;
     int device_id_ = 0;
     bool has_edge_ = false, has_surf_ = false;
+    // the score and the search: a handle over edge_ctx_ / surf_ctx_ (borrowed), and what the last ScanMatch left to score
+    bool EnsureSearchHandle();
+    locgpu_loam* search_ = nullptr;
+    bool fitness_enabled_ = false, have_last_pose_ = false;
+    double fitness_range_ = 1.0;
+    SE3 last_pose_;
+    CloudPtr last_edge_, last_surf_;  // deep copies, made only after EnableFitnessScore
+    std::string last_error_;
 };
 
 }  // namespace LocUtils

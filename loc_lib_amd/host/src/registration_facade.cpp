@@ -241,13 +241,77 @@ bool NdtRegistration::InitialPoseSearch(const CloudPtr& source, const std::vecto
 LoamRegistration::LoamRegistration() {}
 LoamRegistration::LoamRegistration(LoamOption option) : options_(option) {}
 LoamRegistration::~LoamRegistration() {
+    locgpu_loam_destroy(search_);  // first: it borrows the two contexts
     locgpu_batch_destroy(edge_batch_);
     locgpu_batch_destroy(surf_batch_);
     locgpu_destroy(edge_ctx_);
     locgpu_destroy(surf_ctx_);
 }
 void LoamRegistration::SetDevice(int device_id) { device_id_ = device_id; }
-float LoamRegistration::GetFitnessScore() { return 0.0f; }  // loam_registration.cpp:101-104
+const char* LoamRegistration::LastError() const { return last_error_.c_str(); }
+void LoamRegistration::EnableFitnessScore(double max_range) {
+    fitness_enabled_ = true;
+    fitness_range_ = max_range;
+}
+
+// The handle of the score and the search: the matcher's own loop options over the two contexts SetInputTarget filled. A class without
+// a context yet (no SetInputTarget) cannot be borrowed: that is the missing target.
+bool LoamRegistration::EnsureSearchHandle() {
+    if (search_) return true;
+    if ((options_.use_surf_points_ && !surf_ctx_) || (options_.use_edge_points_ && !edge_ctx_)) { last_error_ = "LoamRegistration: SetInputTarget has not been called"; return false; }
+    locgpu_loam_opts o;
+    locgpu_loam_opts_default(&o);
+    o.surf = to_c(options_.surf_icp_option_);
+    o.edge = to_c(options_.edge_icp_option_);
+    o.use_surf_points = options_.use_surf_points_;
+    o.use_edge_points = options_.use_edge_points_;
+    o.max_iteration = options_.max_iteration_;
+    o.eps = options_.eps_;
+    if (locgpu_loam_create_on(options_.use_surf_points_ ? surf_ctx_ : nullptr, options_.use_edge_points_ ? edge_ctx_ : nullptr, &o, &search_) != LOCGPU_OK) {
+        last_error_ = locgpu_loam_last_error(nullptr);
+        return false;
+    }
+    return true;
+}
+
+float LoamRegistration::GetFitnessScore() {
+    if (!fitness_enabled_) return 0.0f;  // loam_registration.cpp:101-104: the reference's stub
+    if (!have_last_pose_) { last_error_ = "LoamRegistration::GetFitnessScore: no ScanMatch has succeeded yet"; return INFINITY; }
+    if (!EnsureSearchHandle()) return INFINITY;
+    locgpu_fitness f[3];
+    const bool e = options_.use_edge_points_ && last_edge_, s = options_.use_surf_points_ && last_surf_;
+    if (locgpu_loam_fitness(search_, e ? last_edge_->points.data() : nullptr, e ? last_edge_->points.size() : 0, s ? last_surf_->points.data() : nullptr,
+                            s ? last_surf_->points.size() : 0, sizeof(PointType), last_pose_.data(), 1, fitness_range_, f) != LOCGPU_OK) {
+        last_error_ = locgpu_loam_last_error(search_);
+        return INFINITY;
+    }
+    return (float)f[0].score;
+}
+
+bool LoamRegistration::InitialPoseSearch(const CloudPtr& edge_input, const CloudPtr& surf_input, const std::vector<SE3>& candidates, SE3& best_pose,
+                                         float& best_score) {
+    best_score = INFINITY;
+    if (candidates.empty()) { last_error_ = "LoamRegistration::InitialPoseSearch: no candidates"; return false; }
+    if (!EnsureSearchHandle()) return false;
+    locgpu_init_search_opts so;
+    locgpu_init_search_opts_default(&so);
+    so.max_range = fitness_range_;
+    const size_t m = candidates.size();
+    std::vector<double> in(7 * m), out(7 * m);
+    for (size_t i = 0; i < m; ++i) std::memcpy(&in[7 * i], candidates[i].data(), 7 * sizeof(double));
+    std::vector<locgpu_fitness> fit(3 * m);
+    int best = -1;
+    const bool e = options_.use_edge_points_ && edge_input, s = options_.use_surf_points_ && surf_input;
+    if (locgpu_loam_init_search(search_, e ? edge_input->points.data() : nullptr, e ? edge_input->points.size() : 0, s ? surf_input->points.data() : nullptr,
+                                s ? surf_input->points.size() : 0, sizeof(PointType), in.data(), (int)m, &so, out.data(), fit.data(), nullptr, &best) != LOCGPU_OK) {
+        last_error_ = locgpu_loam_last_error(search_);
+        return false;
+    }
+    if (best < 0) { last_error_ = "LoamRegistration::InitialPoseSearch: no candidate qualifies"; return false; }
+    std::memcpy(best_pose.data(), &out[7 * (size_t)best], 7 * sizeof(double));
+    best_score = (float)fit[3 * (size_t)best].score;
+    return true;
+}
 
 bool LoamRegistration::SetInputTarget(const CloudPtr& edge_input, const CloudPtr& surf_input) {
     if (options_.use_edge_points_ && edge_input && (edge_ctx_ || locgpu_create(device_id_, &edge_ctx_) == LOCGPU_OK))
@@ -268,6 +332,7 @@ bool LoamRegistration::ScanMatch(const CloudPtr& edge_input, const CloudPtr& sur
     const CloudPtr* inputs[2] = {&surf_input, &edge_input};
     const bool have[2] = {has_surf_, has_edge_};
     bool ok = true;
+    have_last_pose_ = false;
     for (int i = 0; i < 2 && ok; ++i) {
         if (!sides[i].use) continue;
         if (!have[i] || !*inputs[i] || (*inputs[i])->points.empty()) { ok = false; break; }
@@ -301,6 +366,12 @@ bool LoamRegistration::ScanMatch(const CloudPtr& edge_input, const CloudPtr& sur
     }
     if (!ok) return false;
     result_pose = pose;
+    if (fitness_enabled_) {  // what a later GetFitnessScore scores: nothing of this is kept without the opt-in
+        last_edge_.reset(edge_input ? new PointCloudType(*edge_input) : nullptr);
+        last_surf_.reset(surf_input ? new PointCloudType(*surf_input) : nullptr);
+        last_pose_ = pose;
+        have_last_pose_ = true;
+    }
     // *cloud += *edge; *cloud += *surf; transformPointCloud (loam_registration.cpp:93-96)
     CloudPtr cloud(new PointCloudType);
     if (edge_input) cloud->points.insert(cloud->points.end(), edge_input->points.begin(), edge_input->points.end());
