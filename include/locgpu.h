@@ -653,6 +653,38 @@ LOCGPU_API int locgpu_crop_box(locgpu_ctx* ctx, const void* pts, size_t n, size_
 LOCGPU_API int locgpu_remove_nan(locgpu_ctx* ctx, const void* pts, size_t n, size_t stride_bytes, size_t intensity_offset, int is_dense, void* out,
                                  size_t* out_n, int* out_is_dense);
 
+/* ---- The front-end on a whole BATCH (csrc/batch_filters.hip). The reference runs RemoveNanPoint → VoxelFilter::Filter on every scan
+ * before ScanMatch (loc.cpp:217-218, lio.cpp:236; voxel_filter.cpp:19-25, point_cloud_utils.h:13-20); locgpu_batch_preprocess does
+ * that for every scan of `src` in one pass — one set of launches, one sort, one read-back of n_scans {count, status} pairs:
+ *   dst's scan s = x, y, z of locgpu_cloud_voxel_filter(locgpu_cloud_remove_nan(scan s of src), leaf),
+ * byte for byte: the same points, count and order (centroids in ascending voxel index, float32 sums in input order), the fourth lane
+ * 0. A scan is always tested for non-finite points (a batch carries no is_dense flag). Each scan has its own bounding box, min_b,
+ * div_b and overflow test; equal coordinates in different scans never share a voxel; results do not depend on n_scans or on the run.
+ * out_status[s] (n_scans entries or NULL) is the single-cloud filter's outcome: 0 filtered; 1 PCL's "leaf size is too small" rule —
+ * the scan comes out as its finite points in input order, bits unchanged; 2 no finite point — count 0. out_counts[s] (n_scans or
+ * NULL) = the filtered counts.
+ * dst is an ordinary batch of the same context and n_scans — typically locgpu_batch_create_empty(ctx, n_scans, M) with M far below
+ * src's capacity, so that the alignment's work lists and partial sums are sized by the FILTERED scans; dst == src works in place.
+ * When a filtered scan has more than dst's max_points_per_scan points the call returns LOCGPU_ERR_INVALID, out_counts holds the
+ * needed counts, locgpu_last_error names the largest, and dst is exactly as it was (points and counts). LOCGPU_ERR_INVALID, with a
+ * text, also for sharded or shared-source batches, a batch whose alignment is begun and not ended, batches of different contexts or
+ * n_scans, a leaf that is <= 0 or not finite, and NULL batches. A pending upload of src (and of dst) is waited for, as by every align
+ * call. The call returns when the pass has run and dst's counts are known on the host; a captured graph of dst stays valid (it reads
+ * the counts on the device). Scratch is grow-only on the context: about 44 B per point slot of src (60 B in place). */
+LOCGPU_API int locgpu_batch_preprocess(locgpu_batch* src, float leaf, locgpu_batch* dst, int32_t* out_counts /* n_scans or NULL */,
+                                       int32_t* out_status /* n_scans or NULL */);
+/* Fills the batch's scans from n = n_scans resident clouds by a device-to-device copy that writes {x, y, z, 0}: the batched resident
+ * form of n different scans for ICP and NDT. Clouds of any context on the batch's GPU are accepted (the copy is ordered behind what
+ * their contexts have enqueued; the call is blocking, the clouds are free again when it returns). Counts are left as
+ * locgpu_batch_upload_async + locgpu_batch_upload_wait leave them. Refusals: those of locgpu_batch_upload_async, a cloud with more
+ * points than the batch was created for, a cloud on another GPU, n != n_scans. */
+LOCGPU_API int locgpu_batch_upload_clouds(locgpu_batch* b, const locgpu_cloud* const* clouds, int n);
+/* Reads scan `scan` of a batch back: *n (optional) = its count; out == NULL returns the count only. Otherwise x, y, z of each point
+ * go to out + i * stride_bytes (stride_bytes >= 12; with stride_bytes >= 16 the fourth lane, which no kernel of the matcher reads,
+ * is written too). LOCGPU_ERR_INVALID for a scan index outside [0, n_scans), capacity < the count, a shared-source batch or a batch
+ * whose alignment is begun and not ended. */
+LOCGPU_API int locgpu_batch_download_scan(locgpu_batch* b, int scan, void* out, size_t capacity, size_t stride_bytes, size_t* n);
+
 /* LoamFeatureExtract::Extract + ExtractFromSector, LocUtils/src/model/feature_extract/loam_feature_extract.cpp:19-151 (called on every
  * scan by Lio::AddCloud(FullCloudPtr), lio.cpp:323): per-ring curvature, six sectors per ring, at most 20 edge points per sector,
  * every unmarked point a surface point; outputs ring by ring, sector by sector, edges in descending and surface points in

@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "locgpu_loam_set_target_cloud", "locgpu_loam_set_target_cloud_async", "locgpu_loam_scan_match_cloud", "locgpu_loam_fitness_resident",
     "locgpu_loam_submap_create", "locgpu_loam_submap_destroy", "locgpu_loam_submap_add_keyframe", "locgpu_loam_submap_clouds", "locgpu_loam_submap_info",
     "locgpu_loam_create_on", "locgpu_loam_fitness", "locgpu_loam_fitness_cloud", "locgpu_loam_init_search", "locgpu_loam_init_search_cloud",
+    "locgpu_batch_preprocess", "locgpu_batch_upload_clouds", "locgpu_batch_download_scan",
 ]
 COMM_ID_BYTES = 128
 NO_INTENSITY = ctypes.c_size_t(-1).value
@@ -192,6 +193,8 @@ def lib():
             "locgpu_loam_fitness_cloud": (i32, [vp, vp, vp, vp, i32, dbl, vp]),
             "locgpu_loam_init_search": (i32, [vp, vp, sz, vp, sz, sz, vp, i32, vp, vp, vp, vp, vp]),
             "locgpu_loam_init_search_cloud": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+            "locgpu_batch_preprocess": (i32, [vp, f32, vp, vp, vp]), "locgpu_batch_upload_clouds": (i32, [vp, vp, i32]),
+            "locgpu_batch_download_scan": (i32, [vp, i32, vp, sz, sz, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -931,6 +934,38 @@ class Batch:
             rc = lib().locgpu_batch_upload_wait(self._h)
             self._keep = None
             self.ctx._check(rc)
+
+    def preprocess(self, leaf, out=None):
+        """RemoveNanPoint → VoxelFilter::Filter on every scan of the batch in one pass (locgpu_batch_preprocess), into ``out`` (a batch
+        of the same context and n_scans; None = in place). Returns (counts, status) as int32 arrays; when a filtered scan does not fit
+        ``out`` the LocGpuError carries the needed counts as ``.counts``."""
+        self.upload_wait()
+        dst = self if out is None else out
+        dst.upload_wait()
+        counts, status = np.zeros(self.n_local, np.int32), np.zeros(self.n_local, np.int32)
+        rc = lib().locgpu_batch_preprocess(self._h, float(leaf), dst._h, counts.ctypes.data, status.ctypes.data)
+        if rc != 0:
+            err = LocGpuError(rc, lib().locgpu_last_error(self.ctx._h).decode())
+            err.counts = counts
+            raise err
+        return counts, status
+
+    def upload_clouds(self, clouds):
+        """Fill the batch's scans from resident clouds (device-to-device, {x, y, z, 0}); clouds of other contexts on the GPU are accepted."""
+        self.upload_wait()
+        clouds = list(clouds)
+        arr = (ctypes.c_void_p * max(len(clouds), 1))(*[c._h for c in clouds])
+        self.ctx._check(lib().locgpu_batch_upload_clouds(self._h, arr, len(clouds)))
+
+    def download_scan(self, s):
+        """Scan ``s`` of the batch as an [n, 4] float32 array: x, y, z and the fourth lane as the batch holds it."""
+        self.upload_wait()
+        n = ctypes.c_size_t(0)
+        self.ctx._check(lib().locgpu_batch_download_scan(self._h, int(s), None, 0, 16, ctypes.byref(n)))
+        out = np.zeros((int(n.value), 4), np.float32)
+        if n.value:
+            self.ctx._check(lib().locgpu_batch_download_scan(self._h, int(s), out.ctypes.data, int(n.value), 16, ctypes.byref(n)))
+        return out
 
     def close(self):
         if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):

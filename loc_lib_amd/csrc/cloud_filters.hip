@@ -361,6 +361,7 @@ hipError_t copy_through(locgpu_ctx* ctx, const locgpu_cloud* in, locgpu_cloud* o
 }  // namespace
 
 void filters_free(locgpu_ctx* ctx) {
+    batch_filters_free(ctx);
     FilterScratch* S = ctx->filt;
     if (!S) return;
     for (int j = 0; j < 2; ++j) {

@@ -55,6 +55,7 @@ hipError_t cloud_input_ready(locgpu_ctx* ctx, const locgpu_cloud* c);
 // Called by the owner's entry points behind every call that wrote `c`: records c->ready on the owner's stream.
 hipError_t cloud_mark_ready(locgpu_cloud* c);
 void filters_free(locgpu_ctx* ctx);
+void batch_filters_free(locgpu_ctx* ctx);  // batch_filters.hip: the batch front-end's workspaces (called by filters_free)
 hipError_t cloud_reserve(locgpu_cloud* c, size_t n, bool keep);
 hipError_t cloud_stage(locgpu_ctx* ctx, size_t n, float4** out);
 hipError_t cloud_stage_release(locgpu_ctx* ctx);  // pinned staging of at least n points
