@@ -257,7 +257,8 @@ LOCGPU_API int locgpu_gn_update(const double hb[44], int method, int min_effecti
  * one-scan path do not apply to them — LOCGPU_P2PLANE_MAP (map planes) is refused (LOCGPU_ERR_INVALID). Resident forms (declared with
  * the resident clouds below): the single-scan calls (locgpu_loam_set_target_cloud, locgpu_loam_scan_match_cloud,
  * locgpu_loam_fitness_resident, locgpu_loam_submap_*) and the SHARED-SOURCE batched form — one pair of scans under many poses
- * (locgpu_loam_fitness_cloud, locgpu_loam_init_search_cloud); there is no batched resident form of n DIFFERENT scans. Calls on a
+ * (locgpu_loam_fitness_cloud, locgpu_loam_init_search_cloud); the calls of this block take no batched resident form of n DIFFERENT scans:
+ * locgpu_loam_align_batches, declared with the batch front-end below, does. Calls on a
  * handle follow the context's rule: one caller thread, synchronous, host inputs copied before the call returns. */
 typedef struct locgpu_loam locgpu_loam;
 /* LoamOption, loam_registration.hpp:22-36. Inside surf / edge only method, the three gates, min_effective_pts, approximate / ann_alpha
@@ -698,6 +699,44 @@ LOCGPU_API int locgpu_loam_extract(locgpu_ctx* ctx, const void* pts, size_t n, s
                                    size_t ring_offset, int num_scan, void* edge_out, size_t* n_edge, void* surf_out, size_t* n_surf,
                                    size_t out_stride_bytes, size_t out_intensity_offset);
 
+/* ---- LOAM on a whole BATCH (csrc/batch_loam.hip, csrc/loam_align.hip): Lio::AddCloud(FullCloudPtr)'s step — the feature picker
+ * (LoamFeatureExtract::Extract, loam_feature_extract.cpp:19-151, called at lio.cpp:323), the voxel filter of both feature clouds
+ * (lio.cpp:485-486: locgpu_batch_preprocess in place on each feature batch) and the match — for n DIFFERENT scans that stay in HBM.
+ * locgpu_batch_loam_extract: scan s of `edge` and of `surf` becomes x, y, z of
+ *   locgpu_cloud_loam_extract(scan s of src, rings[s], num_scan),
+ * byte for byte: the same points, counts and order, the fourth lane +0 as locgpu_batch_preprocess leaves it. rings[s] = one byte per
+ * point of scan s (host memory, read before the call returns). Every rule of the single-cloud picker holds per scan: rings shorter
+ * than 131 points are skipped, rings >= num_scan are ignored, each sector goes without its last element, at most 20 edges per sector
+ * (the 21st pick is marked, not emitted), the +-5 marking stops at a gap^2 > 0.05, equal curvatures are ordered by ring position. A
+ * scan's result does not depend on n_scans, on its position in the batch, or on the run; the pass uses no atomics.
+ * One pass — one stable sort keyed scan * num_scan + ring, one set of launches, one read-back of n_scans {edge count, surface count,
+ * status} — where the single-cloud call makes seven launches, a sort and two synchronisations per scan.
+ * src, edge and surf are three DISTINCT ordinary batches of one context with one n_scans. Limits: 1 <= num_scan <= 256 and
+ * n_scans * num_scan <= 65535 (checked before anything is allocated; it bounds the grids and the per-sector scratch).
+ * out_edge_counts / out_surf_counts / out_status: n_scans entries each, or NULL. Capacity: when a scan's edge (surface) count exceeds
+ * edge's (surf's) max_points_per_scan the call returns LOCGPU_ERR_INVALID, the out arrays hold the needed counts, and BOTH
+ * destinations are exactly as they were, points and counts. A scan with a ring of more than 6 x 2048 points gets out_status[s] = 1
+ * (otherwise 0): the call returns LOCGPU_ERR_INVALID, locgpu_last_error names the first such scan, both destinations are untouched
+ * — the single-cloud picker's refusal, per scan. LOCGPU_ERR_INVALID, with a text, also for sharded or shared-source batches, a batch
+ * whose alignment is begun and not ended, batches of different contexts or n_scans, a NULL batch, NULL rings, and a NULL rings[s] for
+ * a scan with points. A pending upload of any of the three batches is waited for. The call returns when the pass has run and the
+ * counts of edge and surf are known on the host (device counts, locgpu_batch_download_scan and the next upload agree, as after
+ * locgpu_batch_preprocess). Scratch is grow-only on the context: about 65 B per point slot of src and 340 B per sector. */
+LOCGPU_API int locgpu_batch_loam_extract(locgpu_batch* src, const uint8_t* const* rings /* n_scans host arrays, counts[s] bytes each */,
+                                         int num_scan, locgpu_batch* edge, locgpu_batch* surf, int32_t* out_edge_counts,
+                                         int32_t* out_surf_counts, int32_t* out_status /* each n_scans or NULL */);
+/* locgpu_loam_align_batch (LoamRegistration::ScanMatch per scan, loam_registration.cpp:38-99) on two RESIDENT batches: scan i is scan i
+ * of `edge` with scan i of `surf`. Poses and stats are bit for bit those of locgpu_loam_align_batch on the scans that
+ * locgpu_batch_download_scan returns, whatever the two batches' max_points_per_scan are: the handle's storage batches are shaped by
+ * the largest COUNT of each class and the rows are brought over by one strided device-to-device copy per class (counts device to
+ * device). The batches may belong to any context on the handle's GPU and are not modified. The call is blocking: pending uploads are
+ * waited for and the handle's stream is ordered behind the batches' contexts. A switched-off class's batch may be NULL; the two
+ * batches must have equal n_scans (1..65535). LOCGPU_ERR_INVALID for sharded and shared-source batches, a batch whose alignment is
+ * begun and not ended, a NULL batch of an enabled class, a batch on another GPU. Afterwards nothing of a single scan is resident:
+ * locgpu_loam_fitness_resident is refused until the next single-scan call, as after locgpu_loam_align_batch. Eager only. */
+LOCGPU_API int locgpu_loam_align_batches(locgpu_loam* l, locgpu_batch* edge, locgpu_batch* surf, const double* init_poses, double* out_poses,
+                                         locgpu_align_stats* stats);
+
 /* The local map of Lio::AddCloud's keyframe branch (lio.cpp:268-306), kept in HBM: a queue of at most num_kfs world-frame
  * keyframe clouds (scans_in_local_map_) and the voxel-filtered local map (local_map_) that is the next matching target.
  * add_keyframe(scan, pose): key_frame_scan = transform(scan, pose) (pose NULL: scan is already in the world frame); push;
@@ -739,12 +778,12 @@ LOCGPU_API int locgpu_loam_scan_match_cloud(locgpu_loam* l, const locgpu_cloud* 
  * the handle's most recent single-scan call left in HBM: locgpu_loam_scan_match / locgpu_loam_hb (the handle's own copies) or
  * locgpu_loam_scan_match_cloud — which keeps REFERENCES, so those two clouds must still be alive and unmodified. A switched-off
  * class (and an empty scan) reports {+inf, 0, 0}. LOCGPU_ERR_INVALID when nothing is resident (no such call yet, or a
- * locgpu_loam_align_batch since); LOCGPU_ERR_NO_TARGET without a target. */
+ * locgpu_loam_align_batch / locgpu_loam_align_batches since); LOCGPU_ERR_NO_TARGET without a target. */
 LOCGPU_API int locgpu_loam_fitness_resident(locgpu_loam* l, const double pose[7], double max_range, locgpu_fitness out[2]);
 /* locgpu_loam_fitness and locgpu_loam_init_search on resident feature clouds: the same bits without the uploads. The scans are NOT
  * copied — every entry of a class reads its cloud where it lies, so the clouds must not be modified during the call. A switched-off
  * class's cloud may be NULL; a cloud on another GPU is refused with LOCGPU_ERR_INVALID before anything is enqueued. This is the LOAM
- * matcher's batched resident form: one pair of scans under many poses, not n different scans. */
+ * matcher's shared-source resident form: one pair of scans under many poses (n different scans: locgpu_loam_align_batches below). */
 LOCGPU_API int locgpu_loam_fitness_cloud(locgpu_loam* l, const locgpu_cloud* edge, const locgpu_cloud* surf, const double* poses, int n_poses,
                                          double max_range, locgpu_fitness* out /* n_poses × 3 */);
 LOCGPU_API int locgpu_loam_init_search_cloud(locgpu_loam* l, const locgpu_cloud* edge, const locgpu_cloud* surf, const double* candidates, int m,

@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "locgpu_loam_submap_create", "locgpu_loam_submap_destroy", "locgpu_loam_submap_add_keyframe", "locgpu_loam_submap_clouds", "locgpu_loam_submap_info",
     "locgpu_loam_create_on", "locgpu_loam_fitness", "locgpu_loam_fitness_cloud", "locgpu_loam_init_search", "locgpu_loam_init_search_cloud",
     "locgpu_batch_preprocess", "locgpu_batch_upload_clouds", "locgpu_batch_download_scan",
+    "locgpu_batch_loam_extract", "locgpu_loam_align_batches",
 ]
 COMM_ID_BYTES = 128
 NO_INTENSITY = ctypes.c_size_t(-1).value
@@ -195,6 +196,7 @@ def lib():
             "locgpu_loam_init_search_cloud": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
             "locgpu_batch_preprocess": (i32, [vp, f32, vp, vp, vp]), "locgpu_batch_upload_clouds": (i32, [vp, vp, i32]),
             "locgpu_batch_download_scan": (i32, [vp, i32, vp, sz, sz, vp]),
+            "locgpu_batch_loam_extract": (i32, [vp, vp, i32, vp, vp, vp, vp, vp]), "locgpu_loam_align_batches": (i32, [vp, vp, vp, vp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -912,8 +914,8 @@ class Batch:
         scans = [_cloud(s) for s in scans]
         if not scans:
             raise ValueError("empty batch")
-        stride = scans[0].strides[0]
-        if any(s.strides[0] != stride for s in scans):
+        stride = next((s.strides[0] for s in scans if s.shape[0]), 16)  # an empty scan has no stride of its own
+        if any(s.shape[0] and s.strides[0] != stride for s in scans):
             raise ValueError("all scans of a batch must share one point stride")
         ptrs = (ctypes.c_void_p * len(scans))(*[s.ctypes.data for s in scans])
         cnts = (ctypes.c_size_t * len(scans))(*[s.shape[0] for s in scans])
@@ -949,6 +951,26 @@ class Batch:
             err.counts = counts
             raise err
         return counts, status
+
+    def loam_extract(self, rings, num_scan, edge, surf):
+        """The LOAM feature picker on every scan of the batch in one pass (locgpu_batch_loam_extract): scan s of ``edge`` / ``surf``
+        (two other batches of the same context and n_scans) becomes Cloud.loam_extract of scan s with ``rings[s]`` (uint8, one per
+        point). Returns (edge counts, surface counts, status) as int32 arrays; a refused call raises a LocGpuError that carries the
+        needed counts and the per-scan status as ``.edge_counts``, ``.surf_counts`` and ``.status``."""
+        self.upload_wait()
+        edge.upload_wait()
+        surf.upload_wait()
+        rings = [np.ascontiguousarray(r, dtype=np.uint8) if r is not None else None for r in rings]
+        if len(rings) != self.n_local:
+            raise ValueError("loam_extract needs %d ring arrays" % self.n_local)
+        ptrs = (ctypes.c_void_p * max(len(rings), 1))(*[(r.ctypes.data if r is not None and r.size else None) for r in rings])
+        ne, ns, status = (np.zeros(self.n_local, np.int32) for _ in range(3))
+        rc = lib().locgpu_batch_loam_extract(self._h, ptrs, int(num_scan), edge._h, surf._h, ne.ctypes.data, ns.ctypes.data, status.ctypes.data)
+        if rc != 0:
+            err = LocGpuError(rc, lib().locgpu_last_error(self.ctx._h).decode())
+            err.edge_counts, err.surf_counts, err.status = ne, ns, status
+            raise err
+        return ne, ns, status
 
     def upload_clouds(self, clouds):
         """Fill the batch's scans from resident clouds (device-to-device, {x, y, z, 0}); clouds of other contexts on the GPU are accepted."""
@@ -1202,6 +1224,22 @@ class Loam:
         st = (AlignStats * n)()
         self._check(lib().locgpu_loam_align_batch(self._h, n, me[1], me[2], ms[1], ms[2], self._stride(me[3], ms[3]), poses.ctypes.data, out.ctypes.data, st))
         return out, [_stats_dict(x) for x in st]
+
+
+    def align_batches(self, edge, surf, init_poses):
+        """align_batch on two resident batches (api.Batch of any Context on this GPU; None for a class that is switched off): scan i
+        of ``edge`` with scan i of ``surf``. Returns (poses [n, 7], list of stats), the bits of align_batch on the downloaded scans."""
+        some = edge if edge is not None else surf
+        n = some.n_local
+        for b in (edge, surf):
+            if b is not None:
+                b.upload_wait()
+        poses = _pose(init_poses).reshape(n, 7)
+        out = np.zeros((n, 7))
+        st = (AlignStats * max(n, 1))()
+        self._check(lib().locgpu_loam_align_batches(self._h, edge._h if edge is not None else None, surf._h if surf is not None else None, poses.ctypes.data,
+                                                    out.ctypes.data, st))
+        return out, [_stats_dict(st[i]) for i in range(n)]
 
 
 def gn_update(hb, method, min_effective_pts, eps, pose):

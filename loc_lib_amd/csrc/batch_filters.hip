@@ -447,6 +447,8 @@ int hip_fail(locgpu_ctx* ctx, hipError_t e, const char* what) {
     return e == hipErrorOutOfMemory ? LOCGPU_ERR_OOM : LOCGPU_ERR_NO_DEVICE;
 }
 
+}  // namespace
+
 // The context's stream behind everything that may still touch `b`'s points: its pending upload (the host side is waited for) and the
 // idle launches a paced one-scan alignment may have left queued.
 int order_behind_batch(locgpu_ctx* ctx, locgpu_batch* b, const char* who) {
@@ -467,8 +469,6 @@ void set_host_counts(locgpu_batch* b, const int* counts) {
         if (b->upl.h_counts) b->upl.h_counts[s] = counts[s];
     }
 }
-
-}  // namespace
 
 void batch_filters_free(locgpu_ctx* ctx) {
     BatchFilterScratch* S = static_cast<BatchFilterScratch*>(ctx->bfilt);

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 struct locgpu_ctx;
+struct locgpu_batch;
 
 // A cloud resident in HBM: one float4 {x, y, z, intensity} per point. `is_dense` is pcl::PointCloud::is_dense — the
 // PCL filters trust it (a dense cloud is never tested for NaN), so it travels with the data.
@@ -56,6 +57,12 @@ hipError_t cloud_input_ready(locgpu_ctx* ctx, const locgpu_cloud* c);
 hipError_t cloud_mark_ready(locgpu_cloud* c);
 void filters_free(locgpu_ctx* ctx);
 void batch_filters_free(locgpu_ctx* ctx);  // batch_filters.hip: the batch front-end's workspaces (called by filters_free)
+// batch_filters.hip, for every pass over a batch's points on its context's stream (batch_loam.hip too). order_behind_batch: the stream
+// goes behind everything that may still touch b's points — its pending upload (the host side is waited for) and the idle launches a
+// paced one-scan alignment may have left queued; returns a locgpu_status. set_host_counts: the batch's three copies of its counts
+// agree again after d_counts was written on the device.
+int order_behind_batch(locgpu_ctx* ctx, locgpu_batch* b, const char* who);
+void set_host_counts(locgpu_batch* b, const int* counts);
 hipError_t cloud_reserve(locgpu_cloud* c, size_t n, bool keep);
 hipError_t cloud_stage(locgpu_ctx* ctx, size_t n, float4** out);
 hipError_t cloud_stage_release(locgpu_ctx* ctx);  // pinned staging of at least n points
@@ -70,6 +77,7 @@ hipError_t append_dev(locgpu_ctx* ctx, locgpu_cloud* dst, const locgpu_cloud* sr
 
 // loam_features.hip
 void loam_free(locgpu_ctx* ctx);
+void batch_loam_free(locgpu_ctx* ctx);  // batch_loam.hip: the batched picker's workspaces (called by loam_free)
 hipError_t loam_extract_dev(locgpu_ctx* ctx, const locgpu_cloud* in, const unsigned char* ring, int num_scan, locgpu_cloud* edge, locgpu_cloud* surf,
                             bool* too_long);
 

@@ -96,6 +96,7 @@ struct locgpu_ctx {
     locgpu::FilterScratch* filt = nullptr;  // workspaces of the cloud filters (cloud_filters.hip)
     void* loam = nullptr;                   // workspaces of the LOAM feature picker (loam_features.hip)
     void* bfilt = nullptr;                  // workspaces of the batch front-end (batch_filters.hip)
+    void* bloam = nullptr;                  // workspaces of the batched LOAM feature picker (batch_loam.hip)
 
     // reusable one-scan batch for the single-scan entry points
     locgpu_batch* single = nullptr;

@@ -260,6 +260,49 @@ int attach_scans(locgpu_loam* l, const locgpu_cloud* const clouds[2], const char
     return LOCGPU_OK;
 }
 
+// The fourth way to fill the storage batches: n DIFFERENT scans that are already resident, in the caller's batches. Class c's storage
+// batch gets the shape locgpu_loam_align_batch gives it on the same scans — n_scans × the largest COUNT, whatever the caller's batch was
+// created for (a batch filtered in place keeps its raw capacity) — so the sums split alike and the poses are that call's poses, bit
+// for bit. The rows come over in ONE strided device-to-device copy (the host-pointer call copies them too, over PCIe), the device
+// counts device to device; the host counts are the batch's. The caller's batches are read, never written.
+int attach_batches(locgpu_loam* l, locgpu_batch* const in[2], int n_scans, const char* who) {
+    l->src_of[kSurf] = l->src_of[kEdge] = nullptr;
+    l->split_scans = 0;
+    for (int c = 0; c < 2; ++c) {
+        if (!l->use[c]) continue;
+        locgpu_batch* from = in[c];
+        const int urc = upload_join_batch(from);  // a pending upload of the caller's batch: its host side ends here
+        if (urc != LOCGPU_OK) return lfail(l, urc, std::string(who) + ": " + locgpu_last_error(from->ctx));
+        size_t max_cnt = 0;
+        for (int i = 0; i < n_scans; ++i) max_cnt = std::max(max_cnt, (size_t)std::max(from->counts[i], 0));
+        const int rc = shape_batch(l, c, n_scans, max_cnt);
+        if (rc != LOCGPU_OK) return rc;
+        locgpu_batch* b = l->batch[c];
+        const int jrc = from_ctx(l, c, upload_join_batch(b));  // a failed earlier upload stays with the batch until one replaces it: say so
+        if (jrc != LOCGPU_OK) return jrc;
+        b->d_src_ext = nullptr;  // the kernels read the storage batch's own rows
+        for (int i = 0; i < n_scans; ++i) b->counts[i] = b->upl.h_counts[i] = from->counts[i];
+        LOAM_HIP(l, upload_order_after(b, l->stream));
+        // behind whatever wrote the caller's batch: its upload, its context's stream (the picker, the filter), its own compute stream
+        LOAM_HIP(l, upload_order_after(from, l->stream));
+        hipStream_t writers[2] = {from->ctx->stream, from->stream};
+        for (int k = 0; k < 2; ++k) {
+            if (!writers[k] || writers[k] == l->stream || (k == 1 && writers[1] == writers[0])) continue;
+            LOAM_HIP(l, hipEventRecord(l->ev, writers[k]));
+            LOAM_HIP(l, hipStreamWaitEvent(l->stream, l->ev, 0));
+        }
+        if (max_cnt)
+            LOAM_HIP(l, hipMemcpy2DAsync(b->d_src, (size_t)b->max_n * sizeof(float4), from->d_src, (size_t)from->max_n * sizeof(float4), max_cnt * sizeof(float4),
+                                         (size_t)n_scans, hipMemcpyDeviceToDevice, l->stream));
+        LOAM_HIP(l, hipMemcpyAsync(b->d_counts, from->d_counts, (size_t)n_scans * sizeof(int), hipMemcpyDeviceToDevice, l->stream));
+        if (l->ctx[c]->stream != l->stream) {  // behind that context's target ingest
+            LOAM_HIP(l, hipEventRecord(l->ev, l->ctx[c]->stream));
+            LOAM_HIP(l, hipStreamWaitEvent(l->stream, l->ev, 0));
+        }
+    }
+    return LOCGPU_OK;
+}
+
 // The third way to fill the storage batches, beside upload_scans and attach_scans: the ONE pair of scans of a score under many poses or
 // of a candidate search. Class c's batch is shaped for `entries` entries of n[c] points (the largest chunk: share_entries shapes every
 // chunk inside it) and its region 0 holds the scan — copied once from host[c], or read where clouds[c] holds it (clouds != nullptr).
@@ -903,6 +946,36 @@ int locgpu_loam_align_batch(locgpu_loam* l, int n_scans, const void* const* edge
     l->resident = false;  // the storage batches take the batch's shape
     rc = reserve_joint(l, n_scans);
     if (rc == LOCGPU_OK) rc = upload_scans(l, n_scans, srcs, counts, stride_bytes);
+    if (rc == LOCGPU_OK) rc = run(l, n_scans, init_poses, spec, 1);
+    if (rc != LOCGPU_OK) return rc;
+    write_results(l, n_scans, init_poses, out_poses, stats);
+    return LOCGPU_OK;
+}
+
+int locgpu_loam_align_batches(locgpu_loam* l, locgpu_batch* edge, locgpu_batch* surf, const double* init_poses, double* out_poses, locgpu_align_stats* stats) {
+    if (!l) return LOCGPU_ERR_INVALID;
+    if (!init_poses || !out_poses) return lfail(l, LOCGPU_ERR_INVALID, "loam_align_batches: bad arguments");
+    locgpu_batch* in[2] = {surf, edge};
+    int n_scans = -1;
+    for (int c = 0; c < 2; ++c) {  // every argument is checked before anything is enqueued; a switched-off class's batch is not looked at
+        if (!l->use[c]) continue;
+        const locgpu_batch* b = in[c];
+        if (!b || !b->ctx) return lfail(l, LOCGPU_ERR_INVALID, "loam_align_batches: the batch of an enabled feature class is NULL");
+        if (b->ctx->device != l->device) return lfail(l, LOCGPU_ERR_INVALID, "loam_align_batches: a batch belongs to a context on another GPU");
+        if (b->sharded) return lfail(l, LOCGPU_ERR_INVALID, "loam_align_batches: sharded batches are not supported");
+        if (b->shared_src) return lfail(l, LOCGPU_ERR_INVALID, "loam_align_batches: shared-source batches are not supported");
+        if (b->pending.active) return lfail(l, LOCGPU_ERR_INVALID, "loam_align_batches: an alignment of a batch has been begun and not finished");
+        if (n_scans >= 0 && b->n_scans != n_scans) return lfail(l, LOCGPU_ERR_INVALID, "loam_align_batches: the two batches hold different numbers of scans");
+        n_scans = b->n_scans;
+    }
+    if (n_scans < 1 || n_scans > 65535) return lfail(l, LOCGPU_ERR_INVALID, "loam_align_batches: 1 <= n_scans <= 65535");
+    AlignSpec spec[2];
+    int rc = check_classes(l, spec, "loam_align_batches");
+    if (rc != LOCGPU_OK) return rc;
+    LOAM_HIP(l, hipSetDevice(l->device));
+    l->resident = false;  // the storage batches take the batch's shape
+    rc = reserve_joint(l, n_scans);
+    if (rc == LOCGPU_OK) rc = attach_batches(l, in, n_scans, "loam_align_batches");
     if (rc == LOCGPU_OK) rc = run(l, n_scans, init_poses, spec, 1);
     if (rc != LOCGPU_OK) return rc;
     write_results(l, n_scans, init_poses, out_poses, stats);

@@ -22,14 +22,13 @@
 
 #include "cloud_filters.hpp"
 #include "context.hpp"
+#include "loam_sector.hpp"
 
 namespace locgpu {
 
 namespace {
 
-constexpr int kLB = 256;
-constexpr int kMaxSector = 2048;   // longest sector (ring length / 6) the LDS sort holds
-constexpr int kMaxEdges = 20;
+using namespace loam;  // kLB, kMaxSector, kMaxEdges and the per-point / per-sector bodies (loam_sector.hpp)
 
 struct LoamParams {
     uint32_t n_edge, n_surf;
@@ -47,13 +46,7 @@ __global__ __launch_bounds__(kLB) void ring_key_kernel(const unsigned char* __re
 __global__ void ring_start_kernel(const uint32_t* __restrict__ keys, uint32_t n, int num_scan, uint32_t* __restrict__ start) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r > num_scan) return;
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (keys[mid] < (uint32_t)r) lo = mid + 1;
-        else hi = mid;
-    }
-    start[r] = lo;
+    start[r] = key_lower_bound(keys, n, (uint32_t)r);
 }
 
 __global__ __launch_bounds__(kLB) void ring_gather_kernel(const float4* __restrict__ pts, const uint32_t* __restrict__ vals, size_t n, float4* __restrict__ out) {
@@ -67,121 +60,19 @@ __global__ __launch_bounds__(kLB) void curvature_kernel(const float4* __restrict
                                                         double* __restrict__ curv) {
     const int r = blockIdx.y;
     const uint32_t base = ring_start[r], size = ring_start[r + 1] - base;
-    if (size < 131) return;
+    if (size < kMinRing) return;
     const uint32_t j = blockIdx.x * kLB + threadIdx.x + 5;
     if (j + 5 >= size) return;
-    const float4* P = L + base + j;
-    const float fx = P[-5].x + P[-4].x + P[-3].x + P[-2].x + P[-1].x - 10 * P[0].x + P[1].x + P[2].x + P[3].x + P[4].x + P[5].x;
-    const float fy = P[-5].y + P[-4].y + P[-3].y + P[-2].y + P[-1].y - 10 * P[0].y + P[1].y + P[2].y + P[3].y + P[4].y + P[5].y;
-    const float fz = P[-5].z + P[-4].z + P[-3].z + P[-2].z + P[-1].z - 10 * P[0].z + P[1].z + P[2].z + P[3].z + P[4].z + P[5].z;
-    const double dx = fx, dy = fy, dz = fz;
-    curv[base + j] = dx * dx + dy * dy + dz * dz;
+    curv[base + j] = ring_curvature(L + base + j);
 }
 
-__device__ __forceinline__ bool gap_too_large(const float4& a, const float4& b) {
-    const double dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;  // float differences, widened (:123-126)
-    return dx * dx + dy * dy + dz * dz > 0.05;
-}
-
-// One workgroup per (sector, ring). Writes the sector's edges to edge_slot[task·20 …] and its surface points to
-// surf_slot[ring_base + 5 + sector_start …] (sectors do not overlap there), plus the two counts.
+// One workgroup per (sector, ring): sector_body (loam_sector.hpp).
 __global__ __launch_bounds__(kLB) void sector_kernel(const float4* __restrict__ L, const double* __restrict__ curv, const uint32_t* __restrict__ ring_start,
                                                      float4* __restrict__ edge_slot, float4* __restrict__ surf_slot, uint32_t* __restrict__ edge_cnt,
                                                      uint32_t* __restrict__ surf_cnt, LoamParams* P) {
-    __shared__ double s_val[kMaxSector];
-    __shared__ int s_id[kMaxSector];
-    __shared__ unsigned char s_picked[kMaxSector + 16];
-    __shared__ int s_edges[kMaxEdges];
-    __shared__ int s_n_edge;
-    __shared__ uint32_t s_wave[kLB / 64];
-    const int sec = blockIdx.x, r = blockIdx.y, task = r * 6 + sec, tid = threadIdx.x;
+    const int sec = blockIdx.x, r = blockIdx.y;
     const uint32_t base = ring_start[r], size = ring_start[r + 1] - base;
-    if (size < 131) {
-        if (tid == 0) { edge_cnt[task] = 0; surf_cnt[task] = 0; }
-        return;
-    }
-    const int total = (int)size - 10;
-    const int len = total / 6;
-    const int s_start = len * sec;
-    const int s_end = sec == 5 ? total - 1 : len * (sec + 1) - 1;
-    const int m = s_end - s_start;  // the sub-vector excludes element `sector_end`
-    if (m > kMaxSector) {
-        if (tid == 0) { edge_cnt[task] = 0; surf_cnt[task] = 0; P->too_long = 1; }
-        return;
-    }
-    if (m <= 0) {
-        if (tid == 0) { edge_cnt[task] = 0; surf_cnt[task] = 0; }
-        return;
-    }
-    int pow2 = 1;
-    while (pow2 < m) pow2 <<= 1;
-    for (int t = tid; t < pow2; t += kLB) {
-        const int id = 5 + s_start + t;  // cloud_curvature[k].id_ = k + 5
-        s_val[t] = t < m ? curv[base + id] : __builtin_inf();
-        s_id[t] = t < m ? id : 0x7FFFFFFF;
-    }
-    for (int t = tid; t < m + 16; t += kLB) s_picked[t] = 0;
-    __syncthreads();
-    // bitonic sort ascending by (value, id)
-    for (int k = 2; k <= pow2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < pow2; t += kLB) {
-                const int x = t ^ j;
-                if (x > t) {
-                    const double va = s_val[t], vb = s_val[x];
-                    const int ia = s_id[t], ib = s_id[x];
-                    const bool a_gt_b = va > vb || (va == vb && ia > ib);
-                    const bool up = (t & k) == 0;
-                    if (a_gt_b == up) { s_val[t] = vb; s_val[x] = va; s_id[t] = ib; s_id[x] = ia; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    // the pick loop (:100-139), sequential by definition; picked flags are indexed by id − s_start (ids reach 5 beyond either end)
-    if (tid == 0) {
-        int n_picked = 0, n_edge = 0;
-        const float4* R = L + base;
-        for (int i = m - 1; i >= 0; --i) {
-            const int ind = s_id[i];
-            if (s_picked[ind - s_start]) continue;
-            if (s_val[i] <= 0.1) break;
-            n_picked++;
-            s_picked[ind - s_start] = 1;
-            if (n_picked <= kMaxEdges) s_edges[n_edge++] = ind;
-            else break;
-            for (int k = 1; k <= 5; k++) {
-                if (gap_too_large(R[ind + k], R[ind + k - 1])) break;
-                s_picked[ind + k - s_start] = 1;
-            }
-            for (int k = -1; k >= -5; k--) {
-                if (gap_too_large(R[ind + k], R[ind + k + 1])) break;
-                s_picked[ind + k - s_start] = 1;
-            }
-        }
-        s_n_edge = n_edge;
-        edge_cnt[task] = (uint32_t)n_edge;
-    }
-    __syncthreads();
-    for (int e = tid; e < s_n_edge; e += kLB) edge_slot[(size_t)task * kMaxEdges + e] = L[base + s_edges[e]];
-    // surface points: unpicked elements in ascending sorted order (:143-149) — ordered compaction, 256 positions per round
-    uint32_t running = 0;
-    const int lane = tid & 63, wave = tid >> 6;
-    for (int t0 = 0; t0 < m; t0 += kLB) {
-        const int t = t0 + tid;
-        int ind = 0;
-        bool keep = false;
-        if (t < m) { ind = s_id[t]; keep = !s_picked[ind - s_start]; }
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) s_wave[wave] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-        for (int w = 0; w < kLB / 64; ++w) { before += w < wave ? s_wave[w] : 0u; all += s_wave[w]; }
-        if (keep) surf_slot[base + 5 + s_start + running + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = L[base + ind];
-        running += all;
-        __syncthreads();
-    }
-    if (tid == 0) surf_cnt[task] = running;
+    sector_body(L, curv, base, size, sec, (size_t)(r * 6 + sec), edge_slot, surf_slot, edge_cnt, surf_cnt, &P->too_long);
 }
 
 // exclusive scan of the per-task counts (≤ 256·6 tasks) by one workgroup; totals into P
@@ -205,8 +96,7 @@ __global__ __launch_bounds__(kLB) void sector_scatter_kernel(const float4* __res
     const uint32_t ne = edge_cnt[task], ns = surf_cnt[task];
     if (ne == 0 && ns == 0) return;
     const uint32_t base = ring_start[r], size = ring_start[r + 1] - base;
-    const int len = ((int)size - 10) / 6;
-    const uint32_t src = base + 5 + (uint32_t)(len * sec);
+    const uint32_t src = base + 5 + (uint32_t)sector_start(size, sec);
     for (uint32_t e = threadIdx.x; e < ne; e += kLB) edge_out[edge_off[task] + e] = edge_slot[(size_t)task * kMaxEdges + e];
     for (uint32_t s = threadIdx.x; s < ns; s += kLB) surf_out[surf_off[task] + s] = surf_slot[src + s];
 }
@@ -290,6 +180,7 @@ hipError_t ensure(locgpu_ctx* ctx, size_t n, int num_scan) {
 void loam_free(locgpu_ctx* ctx) {
     free_scratch((LoamScratch*)ctx->loam);
     ctx->loam = nullptr;
+    batch_loam_free(ctx);
 }
 
 // in: cloud resident in HBM; ring: host bytes, one per point. *too_long is set when a sector exceeds the LDS sort capacity.
