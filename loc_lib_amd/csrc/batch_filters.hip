@@ -315,93 +315,61 @@ __global__ __launch_bounds__(kBF) void bp_gather_clouds_kernel(const TableEntry*
     }
 }
 
+}  // namespace
+
+// Two groups that grow together: per slot {keys, vals, head, rank} and per scan {params … h_table}. The buffer grown last (rank,
+// h_table) has the capacity of its whole group.
 struct BatchFilterScratch {
-    size_t cap = 0;  // slots
-    unsigned long long* keys[2] = {nullptr, nullptr};
-    uint32_t* vals[2] = {nullptr, nullptr};
-    uint32_t* head = nullptr;
-    uint32_t* rank = nullptr;
-    void* temp = nullptr;
-    size_t temp_bytes = 0;
-    float4* stage = nullptr;  // in place only
-    size_t stage_cap = 0;
-    int scans_cap = 0;
-    VoxelParams* params = nullptr;
-    ScanSeg* seg = nullptr;
-    float* partial = nullptr;
-    int2* res = nullptr;      // [scans + 1]
-    int2* h_res = nullptr;    // pinned
-    TableEntry* table = nullptr;
-    TableEntry* h_table = nullptr;  // pinned
+    DevBuf<unsigned long long> keys[2];
+    DevBuf<uint32_t> vals[2], head, rank;
+    DevBuf<unsigned char> temp;
+    DevBuf<float4> stage;  // in place only
+    DevBuf<VoxelParams> params;
+    DevBuf<ScanSeg> seg;
+    DevBuf<float> partial;
+    DevBuf<int2> res;      // [scans + 1]
+    PinnedBuf<int2> h_res;
+    DevBuf<TableEntry> table;
+    PinnedBuf<TableEntry> h_table;
 };
+
+namespace {
 
 BatchFilterScratch* scratch(locgpu_ctx* ctx) {
     if (!ctx->bfilt) ctx->bfilt = new BatchFilterScratch();
-    return static_cast<BatchFilterScratch*>(ctx->bfilt);
-}
-
-#define LOCGPU_TRY(expr)                   \
-    do {                                   \
-        const hipError_t e__ = (expr);     \
-        if (e__ != hipSuccess) return e__; \
-    } while (0)
-
-template <class T>
-hipError_t regrow(T** p, size_t count) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    return hipMalloc((void**)p, count * sizeof(T));
+    return ctx->bfilt;
 }
 
 hipError_t ensure_scans(locgpu_ctx* ctx, int n_scans) {
     BatchFilterScratch* S = scratch(ctx);
-    if (n_scans <= S->scans_cap) return hipSuccess;
-    S->scans_cap = 0;
+    if ((size_t)n_scans <= S->h_table.cap()) return hipSuccess;
     const size_t cap = (size_t)n_scans + 16;
-    LOCGPU_TRY(regrow(&S->params, cap));
-    LOCGPU_TRY(regrow(&S->seg, cap));
-    LOCGPU_TRY(regrow(&S->partial, cap * kBoxBlocksMax * 6));
-    LOCGPU_TRY(regrow(&S->res, cap + 1));
-    LOCGPU_TRY(regrow(&S->table, cap));
-    if (S->h_res) (void)hipHostFree(S->h_res);
-    if (S->h_table) (void)hipHostFree(S->h_table);
-    S->h_res = nullptr; S->h_table = nullptr;
-    LOCGPU_TRY(hipHostMalloc((void**)&S->h_res, (cap + 1) * sizeof(int2)));
-    LOCGPU_TRY(hipHostMalloc((void**)&S->h_table, cap * sizeof(TableEntry)));
-    S->scans_cap = (int)cap;
-    return hipSuccess;
+    LOCGPU_TRY(S->params.alloc(cap));
+    LOCGPU_TRY(S->seg.alloc(cap));
+    LOCGPU_TRY(S->partial.alloc(cap * kBoxBlocksMax * 6));
+    LOCGPU_TRY(S->res.alloc(cap + 1));
+    LOCGPU_TRY(S->table.alloc(cap));
+    LOCGPU_TRY(S->h_res.alloc(cap + 1));
+    return S->h_table.alloc(cap);
 }
 
 hipError_t ensure_slots(locgpu_ctx* ctx, size_t n, unsigned end_bit, bool in_place) {
     BatchFilterScratch* S = scratch(ctx);
-    if (n > S->cap) {
-        S->cap = 0;
-        const size_t cap = n + n / 4 + 1024;
+    if (n > S->rank.cap()) {
+        const size_t cap = with_headroom(n);
         for (int j = 0; j < 2; ++j) {
-            LOCGPU_TRY(regrow(&S->keys[j], cap));
-            LOCGPU_TRY(regrow(&S->vals[j], cap));
+            LOCGPU_TRY(S->keys[j].alloc(cap));
+            LOCGPU_TRY(S->vals[j].alloc(cap));
         }
-        LOCGPU_TRY(regrow(&S->head, cap));
-        LOCGPU_TRY(regrow(&S->rank, cap));
-        S->cap = cap;
+        LOCGPU_TRY(S->head.alloc(cap));
+        LOCGPU_TRY(S->rank.alloc(cap));
     }
     size_t b1 = 0, b2 = 0;
-    LOCGPU_TRY(prim::sort_pairs((void*)nullptr, b1, S->keys[0], S->keys[1], S->vals[0], S->vals[1], n, 0, end_bit, ctx->stream));
-    LOCGPU_TRY(prim::exclusive_sum((void*)nullptr, b2, S->head, S->rank, n, ctx->stream));
+    LOCGPU_TRY(prim::sort_pairs((void*)nullptr, b1, S->keys[0].get(), S->keys[1].get(), S->vals[0].get(), S->vals[1].get(), n, 0, end_bit, ctx->stream));
+    LOCGPU_TRY(prim::exclusive_sum((void*)nullptr, b2, S->head.get(), S->rank.get(), n, ctx->stream));
     const size_t need = std::max(b1, b2) + 256;
-    if (need > S->temp_bytes) {
-        S->temp_bytes = 0;
-        if (S->temp) (void)hipFree(S->temp);
-        S->temp = nullptr;
-        LOCGPU_TRY(hipMalloc(&S->temp, need + need / 4));
-        S->temp_bytes = need + need / 4;
-    }
-    if (in_place && n > S->stage_cap) {
-        S->stage_cap = 0;
-        const size_t cap = n + n / 4 + 1024;
-        LOCGPU_TRY(regrow(&S->stage, cap));
-        S->stage_cap = cap;
-    }
+    if (need > S->temp.cap()) LOCGPU_TRY(S->temp.alloc(need + need / 4));
+    if (in_place && n > S->stage.cap()) LOCGPU_TRY(S->stage.alloc(with_headroom(n)));
     return hipSuccess;
 }
 
@@ -426,17 +394,17 @@ hipError_t preprocess_dev(locgpu_ctx* ctx, locgpu_batch* src, float leaf, locgpu
     hipLaunchKernelGGL(bp_setup_kernel, dim3(n_scans), dim3(64), 0, s, S->params, S->seg, S->partial, n_partial, inv);
     hipLaunchKernelGGL(bp_key_kernel, dim3(blocks_for(max_n), n_scans), dim3(kBF), 0, s, src->d_src, src->d_counts, max_n, S->params, S->keys[0], S->vals[0]);
     LOCGPU_TRY(hipGetLastError());
-    size_t tb = S->temp_bytes;
-    LOCGPU_TRY(prim::sort_pairs(S->temp, tb, S->keys[0], S->keys[1], S->vals[0], S->vals[1], n, 0, end_bit, s));
+    size_t tb = S->temp.cap();
+    LOCGPU_TRY(prim::sort_pairs(S->temp, tb, S->keys[0].get(), S->keys[1].get(), S->vals[0].get(), S->vals[1].get(), n, 0, end_bit, s));
     hipLaunchKernelGGL(bp_head_kernel, dim3(blocks_for(n)), dim3(kBF), 0, s, S->keys[1], n, S->params, S->head);
-    tb = S->temp_bytes;
-    LOCGPU_TRY(prim::exclusive_sum(S->temp, tb, S->head, S->rank, n, s));
-    uint32_t* start = S->vals[0];  // free again after the sort; a rank is below n
+    tb = S->temp.cap();
+    LOCGPU_TRY(prim::exclusive_sum(S->temp, tb, S->head.get(), S->rank.get(), n, s));
+    uint32_t* start = S->vals[0].get();  // free again after the sort; a rank is below n
     hipLaunchKernelGGL(bp_starts_kernel, dim3(blocks_for(n)), dim3(kBF), 0, s, S->keys[1], S->head, S->rank, n, start, S->seg);
     hipLaunchKernelGGL(bp_finalize_kernel, dim3(1), dim3(kBF), 0, s, S->params, S->seg, n_scans, S->res);
     const uint32_t out_rows = std::min(max_n, dst_max_n);  // no scan has more output points than input points, and none may have more than dst holds
     hipLaunchKernelGGL(bp_centroid_kernel, dim3(blocks_for(out_rows), n_scans), dim3(kBF), 0, s, src->d_src, S->vals[1], start, S->seg, S->res, n_scans, dst_max_n,
-                       in_place ? S->stage : dst->d_src, in_place ? (int*)nullptr : dst->d_counts);
+                       in_place ? S->stage.get() : dst->d_src.get(), in_place ? (int*)nullptr : dst->d_counts.get());
     if (in_place) hipLaunchKernelGGL(bp_copy_back_kernel, dim3(blocks_for(out_rows), n_scans), dim3(kBF), 0, s, S->stage, S->res, max_n, dst->d_src, dst->d_counts);
     LOCGPU_TRY(hipGetLastError());
     return hipMemcpyAsync(S->h_res, S->res, ((size_t)n_scans + 1) * sizeof(int2), hipMemcpyDeviceToHost, s);
@@ -456,7 +424,7 @@ int order_behind_batch(locgpu_ctx* ctx, locgpu_batch* b, const char* who) {
     if (rc != LOCGPU_OK) return rc;
     if (!hip_ok(ctx, upload_order_after(b, ctx->stream), who)) return LOCGPU_ERR_NO_DEVICE;
     if (b->paced_tail && b->stream != ctx->stream) {
-        if (!b->tail_ev && !hip_ok(ctx, hipEventCreateWithFlags(&b->tail_ev, hipEventDisableTiming), who)) return LOCGPU_ERR_NO_DEVICE;
+        if (!hip_ok(ctx, b->tail_ev.ensure(), who)) return LOCGPU_ERR_NO_DEVICE;
         if (!hip_ok(ctx, hipEventRecord(b->tail_ev, b->stream), who) || !hip_ok(ctx, hipStreamWaitEvent(ctx->stream, b->tail_ev, 0), who)) return LOCGPU_ERR_NO_DEVICE;
     }
     return LOCGPU_OK;
@@ -471,24 +439,7 @@ void set_host_counts(locgpu_batch* b, const int* counts) {
 }
 
 void batch_filters_free(locgpu_ctx* ctx) {
-    BatchFilterScratch* S = static_cast<BatchFilterScratch*>(ctx->bfilt);
-    if (!S) return;
-    for (int j = 0; j < 2; ++j) {
-        if (S->keys[j]) (void)hipFree(S->keys[j]);
-        if (S->vals[j]) (void)hipFree(S->vals[j]);
-    }
-    if (S->head) (void)hipFree(S->head);
-    if (S->rank) (void)hipFree(S->rank);
-    if (S->temp) (void)hipFree(S->temp);
-    if (S->stage) (void)hipFree(S->stage);
-    if (S->params) (void)hipFree(S->params);
-    if (S->seg) (void)hipFree(S->seg);
-    if (S->partial) (void)hipFree(S->partial);
-    if (S->res) (void)hipFree(S->res);
-    if (S->table) (void)hipFree(S->table);
-    if (S->h_res) (void)hipHostFree(S->h_res);
-    if (S->h_table) (void)hipHostFree(S->h_table);
-    delete S;
+    delete ctx->bfilt;
     ctx->bfilt = nullptr;
 }
 
@@ -517,7 +468,7 @@ int locgpu_batch_preprocess(locgpu_batch* src, float leaf, locgpu_batch* dst, in
     if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return hip_fail(ctx, e, "batch_preprocess"); }
     src->paced_tail = dst->paced_tail = false;
     const int n_scans = src->n_scans;
-    const int2* res = static_cast<BatchFilterScratch*>(ctx->bfilt)->h_res;
+    const int2* res = ctx->bfilt->h_res;
     std::vector<int> counts(n_scans);
     for (int s = 0; s < n_scans; ++s) {
         counts[s] = res[s].x;
@@ -549,12 +500,12 @@ int locgpu_batch_upload_clouds(locgpu_batch* b, const locgpu_cloud* const* cloud
     if (rc != LOCGPU_OK) return rc;
     hipError_t e = ensure_scans(ctx, n);
     if (e != hipSuccess) return hip_fail(ctx, e, "batch_upload_clouds: scratch");
-    BatchFilterScratch* S = static_cast<BatchFilterScratch*>(ctx->bfilt);
+    BatchFilterScratch* S = ctx->bfilt;
     std::vector<int> counts(n);
     for (int s = 0; s < n; ++s) {
         e = cloud_input_ready(ctx, clouds[s]);
         if (e != hipSuccess) return hip_fail(ctx, e, "batch_upload_clouds: ordering behind the cloud's context");
-        S->h_table[s] = TableEntry{clouds[s]->d, (uint32_t)clouds[s]->n, 0u};
+        S->h_table[s] = TableEntry{clouds[s]->d.get(), (uint32_t)clouds[s]->n, 0u};
         counts[s] = (int)clouds[s]->n;
     }
     hipStream_t st = ctx->stream;

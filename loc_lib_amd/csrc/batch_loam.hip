@@ -185,85 +185,60 @@ __global__ __launch_bounds__(kLB) void bl_scatter_kernel(const float4* __restric
     }
 }
 
+}  // namespace
+
+// Three groups that grow together: per slot {d_ring … curv}, per composite ring {ring_start … edge_slot} and per scan {too_long, res,
+// h_res}. The buffer grown last (curv, edge_slot, h_res) has the capacity of its whole group.
 struct BatchLoamScratch {
-    size_t cap = 0;  // slots
-    unsigned char *d_ring = nullptr, *h_ring = nullptr;  // h_ring pinned
-    uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr};
-    float4 *L = nullptr, *surf_slot = nullptr;
-    double* curv = nullptr;
-    void* temp = nullptr;
-    size_t temp_bytes = 0;
-    size_t rings_cap = 0;  // composite rings
-    uint32_t *ring_start = nullptr, *edge_cnt = nullptr, *surf_cnt = nullptr, *edge_off = nullptr, *surf_off = nullptr;
-    float4* edge_slot = nullptr;
-    int scans_cap = 0;
-    int32_t* too_long = nullptr;
-    int4 *res = nullptr, *h_res = nullptr;  // [scans + 1]; h_res pinned
+    DevBuf<unsigned char> d_ring;
+    PinnedBuf<unsigned char> h_ring;
+    DevBuf<uint32_t> keys[2], vals[2];
+    DevBuf<float4> L, surf_slot;
+    DevBuf<double> curv;
+    DevBuf<unsigned char> temp;
+    DevBuf<uint32_t> ring_start, edge_cnt, surf_cnt, edge_off, surf_off;
+    DevBuf<float4> edge_slot;
+    DevBuf<int32_t> too_long;
+    DevBuf<int4> res;  // [scans + 1]
+    PinnedBuf<int4> h_res;
 };
 
-#define LOCGPU_TRY(expr)                   \
-    do {                                   \
-        const hipError_t e__ = (expr);     \
-        if (e__ != hipSuccess) return e__; \
-    } while (0)
-
-template <class T>
-hipError_t regrow(T** p, size_t count) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    return hipMalloc((void**)p, count * sizeof(T));
-}
+namespace {
 
 hipError_t ensure(locgpu_ctx* ctx, size_t n, size_t n_rings, int n_scans, unsigned end_bit) {
     if (!ctx->bloam) ctx->bloam = new BatchLoamScratch();
-    BatchLoamScratch* S = static_cast<BatchLoamScratch*>(ctx->bloam);
-    if (n_scans > S->scans_cap) {
-        S->scans_cap = 0;
+    BatchLoamScratch* S = ctx->bloam;
+    if ((size_t)n_scans + 1 > S->h_res.cap()) {
         const size_t cap = (size_t)n_scans + 16;
-        LOCGPU_TRY(regrow(&S->too_long, cap));
-        LOCGPU_TRY(regrow(&S->res, cap + 1));
-        if (S->h_res) (void)hipHostFree(S->h_res);
-        S->h_res = nullptr;
-        LOCGPU_TRY(hipHostMalloc((void**)&S->h_res, (cap + 1) * sizeof(int4)));
-        S->scans_cap = (int)cap;
+        LOCGPU_TRY(S->too_long.alloc(cap));
+        LOCGPU_TRY(S->res.alloc(cap + 1));
+        LOCGPU_TRY(S->h_res.alloc(cap + 1));
     }
-    if (n_rings > S->rings_cap) {
-        S->rings_cap = 0;
+    if (n_rings * 6 * kMaxEdges > S->edge_slot.cap()) {
         const size_t cap = n_rings + n_rings / 4 + 64, tasks = cap * 6;
-        LOCGPU_TRY(regrow(&S->ring_start, cap + 1));
-        LOCGPU_TRY(regrow(&S->edge_cnt, tasks));
-        LOCGPU_TRY(regrow(&S->surf_cnt, tasks));
-        LOCGPU_TRY(regrow(&S->edge_off, tasks));
-        LOCGPU_TRY(regrow(&S->surf_off, tasks));
-        LOCGPU_TRY(regrow(&S->edge_slot, tasks * kMaxEdges));
-        S->rings_cap = cap;
+        LOCGPU_TRY(S->ring_start.alloc(cap + 1));
+        LOCGPU_TRY(S->edge_cnt.alloc(tasks));
+        LOCGPU_TRY(S->surf_cnt.alloc(tasks));
+        LOCGPU_TRY(S->edge_off.alloc(tasks));
+        LOCGPU_TRY(S->surf_off.alloc(tasks));
+        LOCGPU_TRY(S->edge_slot.alloc(tasks * kMaxEdges));
     }
-    if (n > S->cap) {
-        S->cap = 0;
-        const size_t cap = n + n / 4 + 1024;
-        LOCGPU_TRY(regrow(&S->d_ring, cap));
-        if (S->h_ring) (void)hipHostFree(S->h_ring);
-        S->h_ring = nullptr;
-        LOCGPU_TRY(hipHostMalloc((void**)&S->h_ring, cap));
+    if (n > S->curv.cap()) {
+        const size_t cap = with_headroom(n);
+        LOCGPU_TRY(S->d_ring.alloc(cap));
+        LOCGPU_TRY(S->h_ring.alloc(cap));
         for (int j = 0; j < 2; ++j) {
-            LOCGPU_TRY(regrow(&S->keys[j], cap));
-            LOCGPU_TRY(regrow(&S->vals[j], cap));
+            LOCGPU_TRY(S->keys[j].alloc(cap));
+            LOCGPU_TRY(S->vals[j].alloc(cap));
         }
-        LOCGPU_TRY(regrow(&S->L, cap));
-        LOCGPU_TRY(regrow(&S->surf_slot, cap));
-        LOCGPU_TRY(regrow(&S->curv, cap));
-        S->cap = cap;
+        LOCGPU_TRY(S->L.alloc(cap));
+        LOCGPU_TRY(S->surf_slot.alloc(cap));
+        LOCGPU_TRY(S->curv.alloc(cap));
     }
     size_t tb = 0;
-    LOCGPU_TRY(prim::sort_pairs((void*)nullptr, tb, S->keys[0], S->keys[1], S->vals[0], S->vals[1], n, 0, end_bit, ctx->stream));
+    LOCGPU_TRY(prim::sort_pairs((void*)nullptr, tb, S->keys[0].get(), S->keys[1].get(), S->vals[0].get(), S->vals[1].get(), n, 0, end_bit, ctx->stream));
     const size_t need = tb + 256;
-    if (need > S->temp_bytes) {
-        S->temp_bytes = 0;
-        if (S->temp) (void)hipFree(S->temp);
-        S->temp = nullptr;
-        LOCGPU_TRY(hipMalloc(&S->temp, need + need / 4));
-        S->temp_bytes = need + need / 4;
-    }
+    if (need > S->temp.cap()) LOCGPU_TRY(S->temp.alloc(need + need / 4));
     return hipSuccess;
 }
 
@@ -279,7 +254,7 @@ hipError_t extract_dev(locgpu_ctx* ctx, locgpu_batch* src, const uint8_t* const*
     unsigned end_bit = 1;
     while ((1u << end_bit) <= n_rings) ++end_bit;
     LOCGPU_TRY(ensure(ctx, n, n_rings, n_scans, end_bit));
-    BatchLoamScratch* S = static_cast<BatchLoamScratch*>(ctx->bloam);
+    BatchLoamScratch* S = ctx->bloam;
     for (int i = 0; i < n_scans; ++i)
         if (src->counts[i] > 0) std::memcpy(S->h_ring + (size_t)i * max_n, rings[i], (size_t)src->counts[i]);
     LOCGPU_TRY(hipMemcpyAsync(S->d_ring, S->h_ring, n, hipMemcpyHostToDevice, s));
@@ -287,8 +262,8 @@ hipError_t extract_dev(locgpu_ctx* ctx, locgpu_batch* src, const uint8_t* const*
     hipLaunchKernelGGL(bl_key_kernel, dim3(blocks_for(max_n), n_scans), dim3(kLB), 0, s, S->d_ring, src->d_counts, max_n, (uint32_t)num_scan, n_rings, S->keys[0],
                        S->vals[0]);
     LOCGPU_TRY(hipGetLastError());
-    size_t tb = S->temp_bytes;
-    LOCGPU_TRY(prim::sort_pairs(S->temp, tb, S->keys[0], S->keys[1], S->vals[0], S->vals[1], n, 0, end_bit, s));  // stable: input order per ring
+    size_t tb = S->temp.cap();
+    LOCGPU_TRY(prim::sort_pairs(S->temp, tb, S->keys[0].get(), S->keys[1].get(), S->vals[0].get(), S->vals[1].get(), n, 0, end_bit, s));  // stable: input order per ring
     hipLaunchKernelGGL(bl_ring_start_kernel, dim3(blocks_for((size_t)n_rings + 1)), dim3(kLB), 0, s, S->keys[1], (uint32_t)n, n_rings, S->ring_start);
     hipLaunchKernelGGL(bl_gather_kernel, dim3(blocks_for(n)), dim3(kLB), 0, s, src->d_src, S->vals[1], S->ring_start, n_rings, S->L);
     hipLaunchKernelGGL(bl_curvature_kernel, dim3(blocks_for(n)), dim3(kLB), 0, s, S->L, S->keys[1], S->ring_start, n_rings, S->curv);
@@ -311,15 +286,7 @@ int hip_fail(locgpu_ctx* ctx, hipError_t e, const char* what) {
 }  // namespace
 
 void batch_loam_free(locgpu_ctx* ctx) {
-    BatchLoamScratch* S = static_cast<BatchLoamScratch*>(ctx->bloam);
-    if (!S) return;
-    void* ptrs[] = {S->d_ring, S->keys[0], S->keys[1], S->vals[0], S->vals[1], S->L, S->surf_slot, S->curv, S->temp, S->ring_start,
-                    S->edge_cnt, S->surf_cnt, S->edge_off, S->surf_off, S->edge_slot, S->too_long, S->res};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (S->h_ring) (void)hipHostFree(S->h_ring);
-    if (S->h_res) (void)hipHostFree(S->h_res);
-    delete S;
+    delete ctx->bloam;
     ctx->bloam = nullptr;
 }
 
@@ -361,7 +328,7 @@ int locgpu_batch_loam_extract(locgpu_batch* src, const uint8_t* const* rings, in
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return hip_fail(ctx, e, "batch_loam_extract"); }
     src->paced_tail = edge->paced_tail = surf->paced_tail = false;
-    const int4* res = static_cast<BatchLoamScratch*>(ctx->bloam)->h_res;
+    const int4* res = ctx->bloam->h_res;
     std::vector<int> ne(n_scans), ns(n_scans);
     int first_long = -1, first_big = -1;
     for (int s = 0; s < n_scans; ++s) {

@@ -45,8 +45,6 @@ struct Unit { int scan; size_t off, len; };
 
 void release_resources(Uploader& u) {
     if (u.stream) (void)hipStreamSynchronize(u.stream);
-    for (float4* p : u.h_slots) if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : u.slot_ev) if (e) (void)hipEventDestroy(e);
     u.h_slots.clear(); u.slot_ev.clear(); u.slot_busy.clear();
 }
 
@@ -56,18 +54,17 @@ bool ensure_slots(Uploader& u, size_t want_slots, std::string& err) {
     const size_t cap = (size_t)u.n_threads * Uploader::kSlotsPerThread;
     const size_t want = std::min(cap, std::max<size_t>(1, want_slots));
     while (u.h_slots.size() < want) {
-        float4* p = nullptr;
-        hipEvent_t ev = nullptr;
-        const hipError_t e1 = hipHostMalloc((void**)&p, Uploader::kSlotPoints * sizeof(float4));
-        const hipError_t e2 = e1 == hipSuccess ? hipEventCreateWithFlags(&ev, hipEventDisableTiming) : e1;
+        PinnedBuf<float4> p;
+        Event ev;
+        const hipError_t e1 = p.alloc(Uploader::kSlotPoints);
+        const hipError_t e2 = e1 == hipSuccess ? ev.ensure() : e1;
         if (e2 != hipSuccess) {
             err = std::string("upload: pinned staging: ") + hipGetErrorString(e2);
-            if (p) (void)hipHostFree(p);
             release_resources(u);
             return false;
         }
-        u.h_slots.push_back(p);
-        u.slot_ev.push_back(ev);
+        u.h_slots.push_back(std::move(p));
+        u.slot_ev.push_back(std::move(ev));
         u.slot_busy.push_back(0);
     }
     return true;
@@ -177,8 +174,8 @@ int enqueue(locgpu_batch* b, BatchUploadState& st, const void* const* srcs, cons
     // One upload of a batch (or job) at a time, end to end: the previous one's host side is through and its copies (same
     // destination, same pinned counts) have landed.
     (void)upload_join_state(ctx, &st);
-    if (!st.done && !hip_ok(ctx, hipEventCreateWithFlags(&st.done, hipEventDisableTiming), "upload: hipEventCreate")) { st.done = nullptr; return LOCGPU_ERR_OOM; }
-    if (!dst && !st.h_counts && !hip_ok(ctx, hipHostMalloc((void**)&st.h_counts, (size_t)b->n_scans * sizeof(int)), "upload: hipHostMalloc counts")) { st.h_counts = nullptr; return LOCGPU_ERR_OOM; }
+    if (!hip_ok(ctx, st.done.ensure(), "upload: hipEventCreate")) return LOCGPU_ERR_OOM;
+    if (!dst && !st.h_counts && !hip_ok(ctx, st.h_counts.alloc((size_t)b->n_scans), "upload: hipHostMalloc counts")) return LOCGPU_ERR_OOM;
     if (st.done_valid && !hip_ok(ctx, hipEventSynchronize(st.done), "batch upload: previous upload")) return LOCGPU_ERR_NO_DEVICE;
     st.rc = LOCGPU_OK;
     st.err.clear();
@@ -222,7 +219,7 @@ int upload_start(locgpu_batch* b, const void* const* srcs, const size_t* counts,
     if (b->paced_tail) {
         // belt and braces for the idle launches a paced alignment may have left queued: the copies go behind them
         b->paced_tail = false;
-        if (!b->tail_ev && !hip_ok(ctx, hipEventCreateWithFlags(&b->tail_ev, hipEventDisableTiming), "batch upload: hipEventCreate")) return LOCGPU_ERR_NO_DEVICE;
+        if (!hip_ok(ctx, b->tail_ev.ensure(), "batch upload: hipEventCreate")) return LOCGPU_ERR_NO_DEVICE;
         if (!hip_ok(ctx, hipEventRecord(b->tail_ev, b->stream), "batch upload: hipEventRecord") ||
             !hip_ok(ctx, hipStreamWaitEvent(ctx->copy_stream, b->tail_ev, 0), "batch upload: hipStreamWaitEvent")) return LOCGPU_ERR_NO_DEVICE;
     }
@@ -279,9 +276,9 @@ void upload_free_batch(locgpu_batch* b) {
     // then let the copies land
     upload_drain(ctx);
     if (b->upl.done_valid && b->upl.done) (void)hipEventSynchronize(b->upl.done);
-    if (b->upl.h_counts) (void)hipHostFree(b->upl.h_counts);
-    if (b->upl.done) (void)hipEventDestroy(b->upl.done);
-    b->upl.done = nullptr; b->upl.done_valid = false; b->upl.h_counts = nullptr; b->upl.rc = 0; b->upl.err.clear();
+    b->upl.h_counts.reset();
+    b->upl.done.reset();
+    b->upl.done_valid = false; b->upl.rc = 0; b->upl.err.clear();
 }
 
 void upload_free_ctx(locgpu_ctx* ctx) {

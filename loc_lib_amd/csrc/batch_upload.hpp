@@ -21,15 +21,17 @@
 #include <thread>
 #include <vector>
 
+#include "device_buffer.hpp"
+
 struct locgpu_batch;
 struct locgpu_ctx;
 
 namespace locgpu {
 
 struct BatchUploadState {  // per batch / per pool job
-    hipEvent_t done = nullptr;  // recorded behind the last slot of the most recent upload
+    Event done;                 // recorded behind the last slot of the most recent upload
     bool done_valid = false;
-    int* h_counts = nullptr;    // pinned copy of the per-scan point counts (batches only)
+    PinnedBuf<int> h_counts;    // pinned copy of the per-scan point counts (batches only)
     int rc = 0;                 // status of the most recent upload once its host side is through (sticky until the next upload)
     std::string err;
     std::atomic<int> pending{0};  // requests queued or being packed: the service thread still reads the caller's clouds
@@ -52,8 +54,8 @@ struct Uploader {  // per context
     hipStream_t stream = nullptr;  // copy stream
     int n_threads = 0;
     // pinned slots: touched by the service thread (and the packers it starts) only
-    std::vector<float4*> h_slots;  // up to n_threads × kSlotsPerThread, allocated on demand
-    std::vector<hipEvent_t> slot_ev;
+    std::vector<PinnedBuf<float4>> h_slots;  // up to n_threads × kSlotsPerThread, allocated on demand
+    std::vector<Event> slot_ev;
     std::vector<char> slot_busy;   // the slot's event has been recorded: its last copy may still be reading it (kept across uploads)
     std::thread worker;
     std::mutex m;

@@ -87,8 +87,8 @@ int locgpu_bfnn_set_target(locgpu_ctx* ctx, const void* pts, size_t n, size_t st
     std::vector<float4> host(n);
     const char* base = (const char*)pts;
     for (size_t i = 0; i < n; ++i) { host[i] = float4{0.f, 0.f, 0.f, 0.f}; std::memcpy(&host[i], base + i * stride_bytes, 12); }
-    if (ctx->d_bfnn) { LOCGPU_HIP(ctx, hipFree(ctx->d_bfnn)); ctx->d_bfnn = nullptr; ctx->bfnn_n = 0; }
-    LOCGPU_HIP(ctx, hipMalloc((void**)&ctx->d_bfnn, n * sizeof(float4)));
+    ctx->bfnn_n = 0;
+    LOCGPU_HIP(ctx, ctx->d_bfnn.alloc(n));
     LOCGPU_HIP(ctx, hipMemcpy(ctx->d_bfnn, host.data(), n * sizeof(float4), hipMemcpyHostToDevice));
     ctx->bfnn_n = n;
     return LOCGPU_OK;
@@ -101,10 +101,10 @@ int locgpu_bfnn_knn(locgpu_ctx* ctx, const float* queries, size_t nq, int k, int
     if ((size_t)k > ctx->bfnn_n) return fail(ctx, LOCGPU_ERR_K_TOO_LARGE, "bfnn_knn: k larger than the cloud (the reference reads past the end here)");
     if (nq == 0) return LOCGPU_OK;
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
-    float* d_q = nullptr;
-    int32_t* d_out = nullptr;
+    DevBuf<float> d_q;
+    DevBuf<int32_t> d_out;
     int rc = LOCGPU_OK;
-    if (!hip_ok(ctx, hipMalloc((void**)&d_q, nq * 12), "hipMalloc") || !hip_ok(ctx, hipMalloc((void**)&d_out, nq * k * sizeof(int32_t)), "hipMalloc")) rc = LOCGPU_ERR_OOM;
+    if (!hip_ok(ctx, d_q.alloc(nq * 3), "hipMalloc") || !hip_ok(ctx, d_out.alloc(nq * k), "hipMalloc")) rc = LOCGPU_ERR_OOM;
     hipStream_t s = ctx->stream;
     if (rc == LOCGPU_OK && !hip_ok(ctx, hipMemcpyAsync(d_q, queries, nq * 12, hipMemcpyHostToDevice, s), "H2D")) rc = LOCGPU_ERR_NO_DEVICE;
     if (rc == LOCGPU_OK) {
@@ -115,8 +115,6 @@ int locgpu_bfnn_knn(locgpu_ctx* ctx, const float* queries, size_t nq, int k, int
             !hip_ok(ctx, hipStreamSynchronize(s), "sync"))
             rc = LOCGPU_ERR_NO_DEVICE;
     }
-    if (d_q) (void)hipFree(d_q);
-    if (d_out) (void)hipFree(d_out);
     return rc;
 }
 

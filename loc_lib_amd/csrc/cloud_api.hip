@@ -39,12 +39,7 @@ locgpu_cloud* new_cloud(locgpu_ctx* ctx) {
     c->ctx = ctx;
     return c;
 }
-void free_cloud(locgpu_cloud* c) {
-    if (!c) return;
-    if (c->d) (void)hipFree(c->d);
-    if (c->ready) (void)hipEventDestroy(c->ready);
-    delete c;
-}
+void free_cloud(locgpu_cloud* c) { delete c; }
 
 int upload(locgpu_cloud* c, const void* pts, size_t n, size_t stride, size_t ioff, int is_dense) {
     locgpu_ctx* ctx = c->ctx;
@@ -119,7 +114,6 @@ int one_shot(locgpu_ctx* ctx, const char* name, const void* pts, size_t n, size_
         *out_n = c.n;
         if (out_dense) *out_dense = c.is_dense;
     }
-    if (c.d) (void)hipFree(c.d);
     return rc;
 }
 
@@ -450,9 +444,6 @@ int locgpu_loam_extract(locgpu_ctx* ctx, const void* pts, size_t n, size_t strid
     if (rc == LOCGPU_OK) rc = download(&edge, edge_out, out_stride_bytes, out_intensity_offset);
     if (rc == LOCGPU_OK) rc = download(&surf, surf_out, out_stride_bytes, out_intensity_offset);
     if (rc == LOCGPU_OK) { *n_edge = edge.n; *n_surf = surf.n; }
-    if (in.d) (void)hipFree(in.d);
-    if (edge.d) (void)hipFree(edge.d);
-    if (surf.d) (void)hipFree(surf.d);
     return rc;
 }
 

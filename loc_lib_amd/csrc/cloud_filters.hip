@@ -283,41 +283,24 @@ FilterScratch* scratch(locgpu_ctx* ctx) {
     return ctx->filt;
 }
 
-#define LOCGPU_TRY(expr)                   \
-    do {                                   \
-        const hipError_t e__ = (expr);     \
-        if (e__ != hipSuccess) return e__; \
-    } while (0)
-
 hipError_t ensure_scratch(locgpu_ctx* ctx, size_t n) {
     FilterScratch* S = scratch(ctx);
-    if (!S->d_params) {
-        LOCGPU_TRY(hipMalloc((void**)&S->d_params, sizeof(VoxelParams)));
-        LOCGPU_TRY(hipHostMalloc((void**)&S->h_params, sizeof(VoxelParams)));
-        LOCGPU_TRY(hipMalloc((void**)&S->d_partial, kMinMaxBlocks * 6 * sizeof(float)));
-    }
+    LOCGPU_TRY(S->d_params.reserve(1));
+    LOCGPU_TRY(S->h_params.reserve(1));
+    LOCGPU_TRY(S->d_partial.reserve(kMinMaxBlocks * 6));
     if (n <= S->cap) return hipSuccess;
-    const size_t cap = n + n / 4 + 1024;
+    const size_t cap = with_headroom(n);
+    S->cap = 0;
     for (int j = 0; j < 2; ++j) {
-        if (S->keys[j]) (void)hipFree(S->keys[j]);
-        if (S->vals[j]) (void)hipFree(S->vals[j]);
-        S->keys[j] = S->vals[j] = nullptr;
+        LOCGPU_TRY(S->keys[j].alloc(cap));
+        LOCGPU_TRY(S->vals[j].alloc(cap));
     }
-    if (S->head) (void)hipFree(S->head);
-    if (S->rank) (void)hipFree(S->rank);
-    if (S->temp) (void)hipFree(S->temp);
-    S->head = S->rank = nullptr; S->temp = nullptr; S->cap = 0;
-    for (int j = 0; j < 2; ++j) {
-        LOCGPU_TRY(hipMalloc((void**)&S->keys[j], cap * sizeof(uint32_t)));
-        LOCGPU_TRY(hipMalloc((void**)&S->vals[j], cap * sizeof(uint32_t)));
-    }
-    LOCGPU_TRY(hipMalloc((void**)&S->head, cap * sizeof(uint32_t)));
-    LOCGPU_TRY(hipMalloc((void**)&S->rank, cap * sizeof(uint32_t)));
+    LOCGPU_TRY(S->head.alloc(cap));
+    LOCGPU_TRY(S->rank.alloc(cap));
     size_t b1 = 0, b2 = 0;
-    LOCGPU_TRY(prim::sort_pairs(nullptr, b1, S->keys[0], S->keys[1], S->vals[0], S->vals[1], (int)cap, 0, 32, ctx->stream));
-    LOCGPU_TRY(prim::exclusive_sum(nullptr, b2, S->head, S->rank, (int)cap, ctx->stream));
-    S->temp_bytes = std::max(b1, b2) + 256;
-    LOCGPU_TRY(hipMalloc(&S->temp, S->temp_bytes));
+    LOCGPU_TRY(prim::sort_pairs(nullptr, b1, S->keys[0].get(), S->keys[1].get(), S->vals[0].get(), S->vals[1].get(), (int)cap, 0, 32, ctx->stream));
+    LOCGPU_TRY(prim::exclusive_sum(nullptr, b2, S->head.get(), S->rank.get(), (int)cap, ctx->stream));
+    LOCGPU_TRY(S->temp.alloc(std::max(b1, b2) + 256));
     S->cap = cap;
     return hipSuccess;
 }
@@ -325,20 +308,13 @@ hipError_t ensure_scratch(locgpu_ctx* ctx, size_t n) {
 // Scratch cloud buffer that results are produced into before being swapped into `out` (which may own the input).
 hipError_t ensure_tmp(locgpu_ctx* ctx, size_t n) {
     FilterScratch* S = scratch(ctx);
-    if (n <= S->tmp_cap && S->d_tmp) return hipSuccess;
-    if (S->d_tmp) (void)hipFree(S->d_tmp);
-    S->d_tmp = nullptr; S->tmp_cap = 0;
-    const size_t cap = n + n / 4 + 1024;
-    LOCGPU_TRY(hipMalloc((void**)&S->d_tmp, cap * sizeof(float4)));
-    S->tmp_cap = cap;
-    return hipSuccess;
+    if (S->d_tmp && n <= S->d_tmp.cap()) return hipSuccess;
+    return S->d_tmp.alloc(with_headroom(n));
 }
 
 // Hands the scratch result buffer (holding n points) to `out` and takes out's old storage as the new scratch.
 void swap_in(locgpu_ctx* ctx, locgpu_cloud* out, size_t n, int dense) {
-    FilterScratch* S = scratch(ctx);
-    std::swap(out->d, S->d_tmp);
-    std::swap(out->cap, S->tmp_cap);
+    out->d.swap(scratch(ctx)->d_tmp);
     out->n = n;
     out->is_dense = dense;
 }
@@ -364,42 +340,20 @@ void filters_free(locgpu_ctx* ctx) {
     batch_filters_free(ctx);
     FilterScratch* S = ctx->filt;
     if (!S) return;
-    for (int j = 0; j < 2; ++j) {
-        if (S->keys[j]) (void)hipFree(S->keys[j]);
-        if (S->vals[j]) (void)hipFree(S->vals[j]);
-    }
-    if (S->head) (void)hipFree(S->head);
-    if (S->rank) (void)hipFree(S->rank);
-    if (S->temp) (void)hipFree(S->temp);
-    if (S->d_params) (void)hipFree(S->d_params);
-    if (S->h_params) (void)hipHostFree(S->h_params);
-    if (S->d_partial) (void)hipFree(S->d_partial);
-    if (S->d_tmp) (void)hipFree(S->d_tmp);
-    if (S->stage_ev) { (void)hipEventSynchronize(S->stage_ev); (void)hipEventDestroy(S->stage_ev); }
-    if (S->h_stage) (void)hipHostFree(S->h_stage);
+    if (S->stage_ev) (void)hipEventSynchronize(S->stage_ev);
     delete S;
     ctx->filt = nullptr;
 }
 
+// The old block is freed only once the new one is there: a cloud that fails to grow keeps its points.
 hipError_t cloud_reserve(locgpu_cloud* c, size_t n, bool keep) {
-    if (n <= c->cap && c->d) return hipSuccess;
-    const size_t cap = n + n / 4 + 1024;
-    float4* d = nullptr;
-    LOCGPU_TRY(hipMalloc((void**)&d, cap * sizeof(float4)));
-    if (keep && c->d && c->n) {
-        const hipError_t e = hipMemcpyAsync(d, c->d, c->n * sizeof(float4), hipMemcpyDeviceToDevice, c->ctx->stream);
-        if (e != hipSuccess) { (void)hipFree(d); return e; }
-        LOCGPU_TRY(hipStreamSynchronize(c->ctx->stream));
-    }
-    if (c->d) (void)hipFree(c->d);
-    c->d = d;
-    c->cap = cap;
-    return hipSuccess;
+    if (c->d && n <= c->d.cap()) return hipSuccess;
+    return c->d.grow_keep(with_headroom(n), keep ? c->n : 0, c->ctx->stream);
 }
 
 hipError_t cloud_mark_ready(locgpu_cloud* c) {
     if (!c || !c->ctx) return hipErrorInvalidValue;
-    if (!c->ready) LOCGPU_TRY(hipEventCreateWithFlags(&c->ready, hipEventDisableTiming));
+    LOCGPU_TRY(c->ready.ensure());
     return hipEventRecord(c->ready, c->ctx->stream);
 }
 
@@ -415,7 +369,7 @@ hipError_t cloud_input_ready(locgpu_ctx* ctx, const locgpu_cloud* c) {
     // behind the call that produced the cloud — not behind whatever its owner has enqueued since (a filter stage running a scan
     // ahead would otherwise hold the matcher back: the two stages would take turns instead of overlapping)
     if (c->ready) return hipStreamWaitEvent(ctx->stream, c->ready, 0);
-    if (!ctx->foreign_ev) LOCGPU_TRY(hipEventCreateWithFlags(&ctx->foreign_ev, hipEventDisableTiming));
+    LOCGPU_TRY(ctx->foreign_ev.ensure());
     LOCGPU_TRY(hipEventRecord(ctx->foreign_ev, c->ctx->stream));
     return hipStreamWaitEvent(ctx->stream, ctx->foreign_ev, 0);
 }
@@ -426,13 +380,7 @@ hipError_t cloud_stage(locgpu_ctx* ctx, size_t n, float4** out) {
         LOCGPU_TRY(hipEventSynchronize(S->stage_ev));
         S->stage_busy = false;
     }
-    if (n > S->stage_cap || !S->h_stage) {
-        if (S->h_stage) (void)hipHostFree(S->h_stage);
-        S->h_stage = nullptr; S->stage_cap = 0;
-        const size_t cap = n + n / 4 + 1024;
-        LOCGPU_TRY(hipHostMalloc((void**)&S->h_stage, cap * sizeof(float4)));
-        S->stage_cap = cap;
-    }
+    if (n > S->h_stage.cap() || !S->h_stage) LOCGPU_TRY(S->h_stage.alloc(with_headroom(n)));
     *out = S->h_stage;
     return hipSuccess;
 }
@@ -440,7 +388,7 @@ hipError_t cloud_stage(locgpu_ctx* ctx, size_t n, float4** out) {
 // The staging buffer has been handed to an asynchronous copy on the context's stream: the next cloud_stage() waits for it.
 hipError_t cloud_stage_release(locgpu_ctx* ctx) {
     FilterScratch* S = scratch(ctx);
-    if (!S->stage_ev) LOCGPU_TRY(hipEventCreateWithFlags(&S->stage_ev, hipEventDisableTiming));
+    LOCGPU_TRY(S->stage_ev.ensure());
     LOCGPU_TRY(hipEventRecord(S->stage_ev, ctx->stream));
     S->stage_busy = true;
     return hipSuccess;
@@ -475,11 +423,11 @@ hipError_t voxel_filter_dev(locgpu_ctx* ctx, const locgpu_cloud* in, float leaf,
         while (end_bit < 32 && (1ull << end_bit) <= (unsigned long long)hp.invalid_key) ++end_bit;
     }
     hipLaunchKernelGGL(voxel_key_kernel, dim3(blocks_for(n)), dim3(kFB), 0, s, in->d, n, dense, S->d_params, S->keys[0], S->vals[0]);
-    size_t tb = S->temp_bytes;
-    LOCGPU_TRY(prim::sort_pairs(S->temp, tb, S->keys[0], S->keys[1], S->vals[0], S->vals[1], (int)n, 0, end_bit, s));
+    size_t tb = S->temp.cap();
+    LOCGPU_TRY(prim::sort_pairs(S->temp, tb, S->keys[0].get(), S->keys[1].get(), S->vals[0].get(), S->vals[1].get(), (int)n, 0, end_bit, s));
     hipLaunchKernelGGL(voxel_head_kernel, dim3(blocks_for(n)), dim3(kFB), 0, s, S->keys[1], n, S->d_params, dense, S->head);
-    tb = S->temp_bytes;
-    LOCGPU_TRY(prim::exclusive_sum(S->temp, tb, S->head, S->rank, (int)n, s));
+    tb = S->temp.cap();
+    LOCGPU_TRY(prim::exclusive_sum(S->temp, tb, S->head.get(), S->rank.get(), (int)n, s));
     uint32_t* start = S->keys[0];  // free again after the sort; capacity ≥ n + 1 (ensure_scratch above)
     hipLaunchKernelGGL(voxel_starts_kernel, dim3(blocks_for(n)), dim3(kFB), 0, s, S->keys[1], S->head, S->rank, n, dense, start, S->d_params);
     LOCGPU_TRY(hipGetLastError());
@@ -512,9 +460,9 @@ static hipError_t compact(locgpu_ctx* ctx, const locgpu_cloud* in, Pred pred, lo
     FilterScratch* S = scratch(ctx);
     hipStream_t s = ctx->stream;
     const unsigned n_tiles = (unsigned)((n + kTile - 1) / kTile);
-    uint32_t *tile_count = S->head, *tile_offset = S->rank;
+    uint32_t *tile_count = S->head.get(), *tile_offset = S->rank.get();
     hipLaunchKernelGGL((compact_count_kernel<Pred>), dim3(n_tiles), dim3(kFB), 0, s, in->d, n, pred, tile_count);
-    size_t tb = S->temp_bytes;
+    size_t tb = S->temp.cap();
     LOCGPU_TRY(prim::exclusive_sum(S->temp, tb, tile_count, tile_offset, (int)n_tiles, s));
     hipLaunchKernelGGL((compact_scatter_kernel<Pred>), dim3(n_tiles), dim3(kFB), 0, s, in->d, n, pred, tile_offset, tile_count, n_tiles, S->d_tmp, S->d_params);
     LOCGPU_TRY(hipGetLastError());

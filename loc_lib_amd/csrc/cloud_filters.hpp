@@ -5,6 +5,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "device_buffer.hpp"
+
 struct locgpu_ctx;
 struct locgpu_batch;
 
@@ -12,10 +14,10 @@ struct locgpu_batch;
 // PCL filters trust it (a dense cloud is never tested for NaN), so it travels with the data.
 struct locgpu_cloud {
     locgpu_ctx* ctx = nullptr;
-    float4* d = nullptr;
-    size_t n = 0, cap = 0;
+    locgpu::DevBuf<float4> d;
+    size_t n = 0;
     int is_dense = 1;
-    hipEvent_t ready = nullptr;  // recorded on the owner's stream behind the last call that wrote the cloud (cloud_mark_ready): what ANOTHER context waits for
+    locgpu::Event ready;  // recorded on the owner's stream behind the last call that wrote the cloud (cloud_mark_ready): what ANOTHER context waits for
 };
 
 namespace locgpu {
@@ -30,22 +32,16 @@ struct VoxelParams {
 };
 
 struct FilterScratch {
-    size_t cap = 0;          // points
-    uint32_t* keys[2] = {nullptr, nullptr};
-    uint32_t* vals[2] = {nullptr, nullptr};
-    uint32_t* head = nullptr;
-    uint32_t* rank = nullptr;
-    void* temp = nullptr;
-    size_t temp_bytes = 0;
-    VoxelParams* d_params = nullptr;
-    VoxelParams* h_params = nullptr;  // pinned
-    float* d_partial = nullptr;       // per-block bounding boxes of the min/max pass
-    float4* d_tmp = nullptr;          // staging for in-place filters
-    size_t tmp_cap = 0;
-    float4* h_stage = nullptr;        // pinned host staging for upload/download
-    hipEvent_t stage_ev = nullptr;  // recorded behind an upload's H2D: the staging buffer is free again once it has fired
+    size_t cap = 0;  // points the group {keys, vals, head, rank, temp} has room for
+    DevBuf<uint32_t> keys[2], vals[2], head, rank;
+    DevBuf<unsigned char> temp;  // scratch of the device-wide primitives at `cap` points
+    DevBuf<VoxelParams> d_params;
+    PinnedBuf<VoxelParams> h_params;
+    DevBuf<float> d_partial;     // per-block bounding boxes of the min/max pass
+    DevBuf<float4> d_tmp;        // staging for in-place filters
+    PinnedBuf<float4> h_stage;   // pinned host staging for upload/download
+    Event stage_ev;              // recorded behind an upload's H2D: the staging buffer is free again once it has fired
     bool stage_busy = false;
-    size_t stage_cap = 0;
 };
 
 // A cloud as a READ-ONLY input of context `ctx` (matcher source, keyframe, target): its own context's clouds need nothing (one

@@ -7,6 +7,7 @@
 
 #include "../../include/locgpu.h"
 #include "batch_upload.hpp"
+#include "device_buffer.hpp"
 #include "device_math.hpp"
 #include "grid_kernels.hpp"
 #include "icp_kernels.hpp"
@@ -14,7 +15,13 @@
 #include "host_worker.hpp"
 
 struct NdtTable;  // ndt_kernels.hpp
-namespace locgpu { struct IncNdtState; struct FilterScratch; }  // ndt_inc.hpp, cloud_filters.hpp
+namespace locgpu {
+struct IncNdtState;         // ndt_inc.hip
+struct FilterScratch;       // cloud_filters.hpp
+struct LoamScratch;         // loam_features.hip
+struct BatchFilterScratch;  // batch_filters.hip
+struct BatchLoamScratch;    // batch_loam.hip
+}  // namespace locgpu
 
 namespace locgpu {
 struct PendingTarget;
@@ -35,7 +42,7 @@ constexpr int ndt_n_nearby(int nearby_type) { return nearby_type == kNearbyCente
 // Stage marks of locgpu_profile_enable (gn_driver.hip): HIP events around the stages of every Gauss–Newton iteration enqueued on one
 // stream since the last collect().
 struct StageEvents {
-    std::vector<hipEvent_t> ev;
+    std::vector<Event> ev;
     size_t used = 0;
     int mode = 0;  // 0: record nothing (also under stream capture); 1: search | fit + accumulate | solve; 2: the search stage's edges only
     void mark(hipStream_t s, bool search_edge = false);
@@ -54,7 +61,7 @@ struct locgpu_ctx {
     hipStream_t slot_stream[kSlots] = {};
     int next_slot = 0;
     hipStream_t copy_stream = nullptr;  // host → HBM copies of the batch uploader
-    hipEvent_t foreign_ev = nullptr;    // ordering behind another context's stream when one of ITS clouds is an input here (cloud_input_ready)
+    locgpu::Event foreign_ev;           // ordering behind another context's stream when one of ITS clouds is an input here (cloud_input_ready)
     hipStream_t comm_stream = nullptr;  // every collective of the context, in host order (one communicator, one stream: no two at once)
     locgpu::Uploader* up = nullptr;     // host → HBM staging shared by the context's batches (batch_upload.hpp)
     locgpu::PendingTarget* target_scratch = nullptr;  // the previous ingest's host buffers, kept for the next one (icp_target.hip)
@@ -62,22 +69,21 @@ struct locgpu_ctx {
     std::string err;
 
     // ICP target: packed KD-tree in HBM (kdtree_build.cpp layout)
-    uint2* d_tree = nullptr;
+    locgpu::DevBuf<uint2> d_tree;  // grow-only
     size_t tree_slots = 0, num_leaves = 0, num_nodes = 0, num_points = 0;
-    size_t tree_cap_slots = 0, leaf_cap = 0;  // capacities of d_tree / d_leaf_slots (grow-only)
     int depth = 0;
     bool tree_bounded = true;  // PackedKdTree::bounded: the fast search kernel may be used
     unsigned long long target_epoch = 0;  // bumped by every set_target: captured graphs of older targets are never replayed
 
-    uint32_t* d_leaf_slots = nullptr;  // slot of every leaf, preorder (what the exact-search grid is built from)
+    locgpu::DevBuf<uint32_t> d_leaf_slots;  // grow-only: slot of every leaf, preorder (what the exact-search grid is built from)
 
     // LOCGPU_P2PLANE_MAP: one plane per leaf, row slot >> 1 = four doubles, NaNs = none (map_planes.hip). Built on first use or by
     // locgpu_icp_build_map_planes, dropped (planes_ready) by every set_target; the buffers are grow-only.
-    double* d_planes = nullptr;
-    size_t planes_cap_rows = 0, planes_rows = 0;
+    locgpu::DevBuf<double> d_planes;
+    size_t planes_rows = 0;
     bool planes_ready = false;
     long long planes_valid = 0;
-    unsigned long long* d_planes_count = nullptr;
+    locgpu::DevBuf<unsigned long long> d_planes_count;
     locgpu_batch* planes_ws = nullptr;  // one-scan search batch of the ingest's chunks
 
     // exact-search grid over the tree's leaves (built on the device on first use of LOCGPU_SEARCH_GRID_EXACT)
@@ -85,7 +91,7 @@ struct locgpu_ctx {
     locgpu::GridBuffers grid_buf;
 
     // BfnnRegistration target (bfnn.hip)
-    float4* d_bfnn = nullptr;
+    locgpu::DevBuf<float4> d_bfnn;
     size_t bfnn_n = 0;
 
     // NDT target
@@ -94,9 +100,9 @@ struct locgpu_ctx {
     locgpu_ndt_opts ndt_opts;
 
     locgpu::FilterScratch* filt = nullptr;  // workspaces of the cloud filters (cloud_filters.hip)
-    void* loam = nullptr;                   // workspaces of the LOAM feature picker (loam_features.hip)
-    void* bfilt = nullptr;                  // workspaces of the batch front-end (batch_filters.hip)
-    void* bloam = nullptr;                  // workspaces of the batched LOAM feature picker (batch_loam.hip)
+    locgpu::LoamScratch* loam = nullptr;    // workspaces of the LOAM feature picker (loam_features.hip)
+    locgpu::BatchFilterScratch* bfilt = nullptr;  // workspaces of the batch front-end (batch_filters.hip)
+    locgpu::BatchLoamScratch* bloam = nullptr;    // workspaces of the batched LOAM feature picker (batch_loam.hip)
 
     // reusable one-scan batch for the single-scan entry points
     locgpu_batch* single = nullptr;
@@ -116,10 +122,10 @@ struct locgpu_ctx {
     long long prof_n[3] = {0, 0, 0};
     bool use_graph = false;  // replay a captured hipGraph of all GN iterations instead of eager chunks
     bool count_visits = false;
-    unsigned long long* d_visits = nullptr;  // [4]: nodes, leaves, queries, distinct tree slots read (summed over launches)
-    uint32_t* d_touched = nullptr;           // instrumented pass: one bit per tree slot
+    locgpu::DevBuf<unsigned long long> d_visits;  // [4]: nodes, leaves, queries, distinct tree slots read (summed over launches)
+    locgpu::DevBuf<uint32_t> d_touched;      // instrumented pass: one bit per tree slot
     size_t touched_words = 0;
-    unsigned long long* d_search_stats = nullptr;  // [2]: queries searched / queries redone by the exact kernel
+    locgpu::DevBuf<unsigned long long> d_search_stats;  // [2]: queries searched / queries redone by the exact kernel
 };
 
 struct locgpu_batch {
@@ -132,56 +138,55 @@ struct locgpu_batch {
     // and normal equations exist for all n_total scans on every rank. Unsharded: n_total = n_scans, first = 0.
     int n_total = 0, first = 0;
     bool sharded = false;
-    double* d_acc = nullptr;  // [n_total][kAccW] per-scan sums, all-reduced over the communicator (sharded batches only)
+    locgpu::DevBuf<double> d_acc;  // [n_total][kAccW] per-scan sums, all-reduced over the communicator (sharded batches only)
     size_t pitch = 0;  // n_scans * max_n
-    float4* d_src = nullptr;
-    int* d_counts = nullptr;
-    locgpu::PoseState* d_state = nullptr;
-    uint32_t* d_nn = nullptr;      // [5][pitch]
+    locgpu::DevBuf<float4> d_src;
+    locgpu::DevBuf<int> d_counts;
+    locgpu::DevBuf<locgpu::PoseState> d_state;
+    locgpu::DevBuf<uint32_t> d_nn;  // [5][pitch]
     // Shared-source batch (locgpu_batch_create_shared): ONE region of points in d_src, read by every entry — d_src_of holds a zero per
     // entry and travels as SearchArgs / AccumArgs::src_of. The buffers are sized for cap_scans entries of cap_points points; n_scans
     // and max_n are what the current call uses of them (reshape_shared, locgpu_api.hip). split_scans > 0: the accumulate kernels
     // split their sums as a plain batch of that many scans would (AccumArgs::split_scans) — a candidate search in chunks.
     bool shared_src = false;
-    int* d_src_of = nullptr;
+    locgpu::DevBuf<int> d_src_of;
     int cap_scans = 0, split_scans = 0;
     size_t cap_points = 0;
     const float4* d_src_ext = nullptr;           // one-scan batches: the points stay where the caller's cloud holds them (no copy into d_src); nullptr = d_src
     bool counters_clean = false;                 // the search stage's work-list counters are known to be zero (the last alignment ran to its end)
     int last_iterations = -1;                    // one-scan batches: iterations of the previous alignment run on this batch (-1: none yet) — sizes the next first chunk
-    double* d_partials = nullptr;  // [n_scans][blocks_per_scan][kAccW]
-    double* d_hb = nullptr;        // [n_scans][44]
-    uint32_t* d_redo_list = nullptr;      // [pitch]
-    unsigned int* d_redo_count = nullptr;  // [2]: the two lists' counters
-    uint32_t* d_redo_list2 = nullptr;      // [pitch], allocated on first use of the grid search
-    uint32_t* d_grid_qkey = nullptr;       // [pitch] grid search: tile of each query
-    uint2* d_grid_sorted = nullptr;        // [pitch] grid search: {query, tile} in tile order
-    uint32_t* d_grid_tile_count = nullptr; // [grid_tocc_cap + 1] grid search: queries per occupied tile of this batch's iteration
-    void* d_grid_scan_temp = nullptr;      // [grid_scan_cap] workspace of the scan over them
-    size_t grid_tocc_cap = 0, grid_scan_cap = 0;
+    locgpu::DevBuf<double> d_partials;  // [n_scans][blocks_per_scan][kAccW]
+    locgpu::DevBuf<double> d_hb;        // [n_scans][44]
+    locgpu::DevBuf<uint32_t> d_redo_list;      // [pitch]
+    locgpu::DevBuf<unsigned int> d_redo_count;  // [2]: the two lists' counters
+    locgpu::DevBuf<uint32_t> d_redo_list2;      // [pitch], allocated on first use of the grid search
+    locgpu::DevBuf<uint32_t> d_grid_qkey;       // [pitch] grid search: tile of each query
+    locgpu::DevBuf<uint2> d_grid_sorted;        // [pitch] grid search: {query, tile} in tile order
+    locgpu::DevBuf<uint32_t> d_grid_tile_count; // [occupied tiles + 1] grid search: queries per occupied tile of this batch's iteration
+    locgpu::DevBuf<unsigned char> d_grid_scan_temp;  // workspace of the scan over them
     // hipGraph of {H2D state, max_iteration × (search, fit+accumulate, solve), D2H state}, keyed by the launch parameters
     hipGraphExec_t graph_exec = nullptr;       // {H2D state, first chunk of iterations, D2H state}
     hipGraphExec_t graph_exec_next = nullptr;  // {further chunk, D2H state}
     locgpu::AlignSpec graph_spec;
     const void* graph_target = nullptr;  // tree / NDT table the capture was made against
     unsigned long long graph_epoch = 0;
-    float4* h_src = nullptr;               // pinned staging of the packed source (single-scan path only; reused across calls)
-    hipEvent_t xyz_ev[8] = {};             // one-scan batch: the output cloud's pieces on their way back (write_output_cloud)
-    locgpu::PoseState* h_state = nullptr;  // pinned
+    locgpu::PinnedBuf<float4> h_src;       // pinned staging of the packed source (single-scan path only; reused across calls)
+    locgpu::Event xyz_ev[8];               // one-scan batch: the output cloud's pieces on their way back (write_output_cloud)
+    locgpu::PinnedBuf<locgpu::PoseState> h_state;
     // one-scan alignments paced from the host (gn_driver.hip, align_finish): the solve kernel posts the state here after every
     // iteration — pinned COHERENT memory: [0] a finished scan's GnPostRecord, [kPostWord] call << 32 | iterations << 1 | done, [+1] checksum
-    unsigned long long* h_post = nullptr;
+    locgpu::PinnedBuf<unsigned long long> h_post;
     static constexpr int kPostWord = 16;  // in 8-byte words: behind the record, 16-byte aligned
     unsigned int post_call = 0;
     bool paced_tail = false;       // the last alignment was paced: up to pace_ahead idle launches may still be queued on `stream`
-    hipEvent_t tail_ev = nullptr;  // ... behind which the next upload's copies are ordered (batch_upload.hip)
-    double* h_hb = nullptr;                // pinned
-    int* h_active = nullptr;               // pinned, [n_scans]: local indices of the scans still open at the last chunk boundary
-    int* d_active = nullptr;               // its device copy (see SearchArgs::active)
+    locgpu::Event tail_ev;         // ... behind which the next upload's copies are ordered (batch_upload.hip)
+    locgpu::PinnedBuf<double> h_hb;
+    locgpu::PinnedBuf<int> h_active;       // [n_scans]: local indices of the scans still open at the last chunk boundary
+    locgpu::DevBuf<int> d_active;          // its device copy (see SearchArgs::active)
     std::vector<int> counts;
     locgpu::BatchUploadState upl;          // event + pinned counts of locgpu_batch_upload_async (batch_upload.hpp)
     locgpu::StageEvents stage_ev;          // profiling events of the batch's (or the pool's) iterations (locgpu_profile_enable)
-    hipEvent_t ev_ready = nullptr, ev_reduced = nullptr;  // sharded batches: compute stream ⇄ comm stream hand-over
+    locgpu::Event ev_ready, ev_reduced;  // sharded batches: compute stream ⇄ comm stream hand-over
     // an alignment begun with *_align_batch_begin and not yet finished
     struct Pending {
         bool active = false;

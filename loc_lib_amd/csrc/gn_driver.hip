@@ -76,9 +76,9 @@ bool shard_decoupled(const locgpu_ctx* ctx, bool scan_sharded) {
 void StageEvents::mark(hipStream_t s, bool search_edge) {
     if (!mode || (mode == 2 && !search_edge)) return;
     if (ev.size() <= used) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return;
-        ev.push_back(e);
+        Event e;
+        if (e.ensure(hipEventDefault) != hipSuccess) return;
+        ev.push_back(std::move(e));
     }
     (void)hipEventRecord(ev[used++], s);
 }
@@ -112,12 +112,11 @@ int launch_local_stage(locgpu_ctx* ctx, locgpu_batch* b, const LocalStage& w, hi
         if (sa.visit_totals && !w.capturing) {  // instrumented pass: which tree slots does this launch read at all? (bench.py: compulsory bytes)
             const size_t words = (ctx->tree_slots + 2 + 31) / 32;
             if (words > ctx->touched_words) {
-                if (ctx->d_touched) (void)hipFree(ctx->d_touched);
-                ctx->d_touched = nullptr; ctx->touched_words = 0;
-                if (hipMalloc((void**)&ctx->d_touched, words * sizeof(uint32_t)) == hipSuccess && hipMemsetAsync(ctx->d_touched, 0, words * sizeof(uint32_t), s) == hipSuccess)
+                ctx->touched_words = 0;
+                if (ctx->d_touched.alloc(words) == hipSuccess && hipMemsetAsync(ctx->d_touched, 0, words * sizeof(uint32_t), s) == hipSuccess)
                     ctx->touched_words = words;
             }
-            sa.touched = ctx->touched_words ? ctx->d_touched : nullptr;
+            sa.touched = ctx->touched_words ? ctx->d_touched.get() : nullptr;
         }
         const bool ok_search = (grid_mode && !sa.visit_totals) ? launch_icp_search_grid(ctx->grid, sa, *w.grid, s) : launch_icp_search(sa, s);
         if (!ok_search) { fail(ctx, LOCGPU_ERR_DEPTH, std::string(w.who) + ": unsupported k/depth"); return -1; }
@@ -235,25 +234,19 @@ static int batch_ready(locgpu_ctx* ctx, locgpu_batch* b) {
 int ensure_grid_lists(locgpu_ctx* ctx, locgpu_batch* b, const AlignSpec& spec) {
     if (!spec.grid) return LOCGPU_OK;
     if (!b->d_grid_qkey) {
-        LOCGPU_HIP(ctx, hipMalloc((void**)&b->d_grid_qkey, b->pitch * sizeof(uint32_t)));
-        LOCGPU_HIP(ctx, hipMalloc((void**)&b->d_grid_sorted, b->pitch * sizeof(uint2)));
+        LOCGPU_HIP(ctx, b->d_grid_qkey.alloc(b->pitch));
+        LOCGPU_HIP(ctx, b->d_grid_sorted.alloc(b->pitch));
     }
     // the binning's per-tile counts and scan workspace are the batch's own as well (several alignments run at once); sized by the
     // current target's grid — a new target may have more occupied tiles
     const size_t tocc = ctx->grid.n_tocc, scan = std::max<size_t>(ctx->grid.scan_temp_bytes, 1);
-    if (!b->d_grid_tile_count || b->grid_tocc_cap < tocc) {
+    if (b->d_grid_tile_count.cap() < tocc + 1) {
         LOCGPU_HIP(ctx, hipStreamSynchronize(b->stream));
-        if (b->d_grid_tile_count) (void)hipFree(b->d_grid_tile_count);
-        b->d_grid_tile_count = nullptr;
-        LOCGPU_HIP(ctx, hipMalloc((void**)&b->d_grid_tile_count, (tocc + 1) * sizeof(uint32_t)));
-        b->grid_tocc_cap = tocc;
+        LOCGPU_HIP(ctx, b->d_grid_tile_count.alloc(tocc + 1));
     }
-    if (!b->d_grid_scan_temp || b->grid_scan_cap < scan) {
+    if (b->d_grid_scan_temp.cap() < scan) {
         LOCGPU_HIP(ctx, hipStreamSynchronize(b->stream));
-        if (b->d_grid_scan_temp) (void)hipFree(b->d_grid_scan_temp);
-        b->d_grid_scan_temp = nullptr;
-        LOCGPU_HIP(ctx, hipMalloc(&b->d_grid_scan_temp, scan));
-        b->grid_scan_cap = scan;
+        LOCGPU_HIP(ctx, b->d_grid_scan_temp.alloc(scan));
     }
     return LOCGPU_OK;
 }
@@ -349,7 +342,7 @@ inline int pace_ahead() {
 static int paced_launch(locgpu_ctx* ctx, locgpu_batch* b, int upto) {
     locgpu_batch::Pending& P = b->pending;
     IterLauncher it{ctx, b, P.spec};
-    const GnPost post{reinterpret_cast<GnPostRecord*>(b->h_post), b->h_post + locgpu_batch::kPostWord, b->post_call};
+    const GnPost post{reinterpret_cast<GnPostRecord*>(b->h_post.get()), b->h_post + locgpu_batch::kPostWord, b->post_call};
     it.post = &post;
     while (P.launched < upto) {
         if (!it.launch(1)) return LOCGPU_ERR_NO_DEVICE;
@@ -428,7 +421,7 @@ int align_begin(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, cons
     P.paced = blocking && !P.graph && b->n_total == 1 && !b->sharded && !ctx->profile && !ctx->count_visits && prm.max_iteration > 0 && pace_ahead() > 0 && !spec.grid;
     if (P.paced) {
         if (!b->h_post) {
-            LOCGPU_HIP(ctx, hipHostMalloc((void**)&b->h_post, 256, hipHostMallocCoherent));
+            LOCGPU_HIP(ctx, b->h_post.alloc(256 / sizeof(unsigned long long), hipHostMallocCoherent));
             std::memset(b->h_post, 0, 256);
         }
         b->post_call++;  // posts carry the call's number: a word left by the previous call is not this call's
@@ -501,13 +494,8 @@ int ensure_map_planes(locgpu_ctx* ctx) {
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const size_t rows = ctx->tree_slots / 2 + 2;  // slot >> 1 of every slot, the sentinel leaf behind the tree included
-    if (rows > ctx->planes_cap_rows) {
-        if (ctx->d_planes) { LOCGPU_HIP(ctx, hipFree(ctx->d_planes)); ctx->d_planes = nullptr; ctx->planes_cap_rows = 0; }
-        const size_t cap = rows + rows / 4 + 1024;
-        if (!hip_ok(ctx, hipMalloc((void**)&ctx->d_planes, cap * 4 * sizeof(double)), "hipMalloc map planes")) return LOCGPU_ERR_OOM;
-        ctx->planes_cap_rows = cap;
-    }
-    if (!ctx->d_planes_count && !hip_ok(ctx, hipMalloc((void**)&ctx->d_planes_count, sizeof(unsigned long long)), "hipMalloc map planes")) return LOCGPU_ERR_OOM;
+    if (rows * 4 > ctx->d_planes.cap() && !hip_ok(ctx, ctx->d_planes.alloc(with_headroom(rows) * 4), "hipMalloc map planes")) return LOCGPU_ERR_OOM;
+    if (!hip_ok(ctx, ctx->d_planes_count.reserve(1), "hipMalloc map planes")) return LOCGPU_ERR_OOM;
     LOCGPU_HIP(ctx, hipMemsetAsync(ctx->d_planes, 0xFF, rows * 4 * sizeof(double), s));  // all-ones doubles are NaNs: no plane
     LOCGPU_HIP(ctx, hipMemsetAsync(ctx->d_planes_count, 0, sizeof(unsigned long long), s));
     unsigned long long n_valid = 0;

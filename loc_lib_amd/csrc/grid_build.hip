@@ -143,34 +143,11 @@ __global__ __launch_bounds__(64) void tile_record_kernel(const uint32_t* __restr
     }
 }
 
-struct Tmp {  // frees its device buffers on every exit path
-    std::vector<void*> ptrs;
-    ~Tmp() { for (void* p : ptrs) (void)hipFree(p); }
-    template <class T> hipError_t alloc(T** p, size_t bytes) {
-        const hipError_t e = hipMalloc((void**)p, bytes ? bytes : 1);
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-};
-
-#define GB_TRY(expr)                      \
-    do {                                  \
-        const hipError_t e__ = (expr);    \
-        if (e__ != hipSuccess) return e__; \
-    } while (0)
-
 inline unsigned blocks_for(size_t n) { return (unsigned)((n + kGB - 1) / kGB); }
 
 }  // namespace
 
-void grid_free(GridBuffers& b) {
-    if (b.tile_hash) (void)hipFree(b.tile_hash);
-    if (b.tiles) (void)hipFree(b.tiles);
-    if (b.pts) (void)hipFree(b.pts);
-    if (b.tile_count) (void)hipFree(b.tile_count);
-    if (b.scan_temp) (void)hipFree(b.scan_temp);
-    b = GridBuffers();
-}
+void grid_free(GridBuffers& b) { b = GridBuffers(); }
 
 hipError_t grid_build_device(const uint2* d_tree, const uint32_t* d_leaf_slots, size_t n, hipStream_t s, GridBuffers& buf, GridView& view,
                              std::string& msg) {
@@ -179,56 +156,55 @@ hipError_t grid_build_device(const uint2* d_tree, const uint32_t* d_leaf_slots, 
     if (n == 0) { msg = "empty tree"; return hipErrorInvalidValue; }
     if (n >= 0xFFFFFFF0ull) { msg = "too many leaves for 32-bit point indices"; return hipErrorInvalidValue; }
     static const double target_occ = [] { const char* e = getenv("LOCGPU_GRID_OCC"); const double v = e ? atof(e) : 4.0; return v >= 1.0 ? v : 4.0; }();
-    Tmp tmp;
-    float4* d_leaves = nullptr;
-    unsigned int* d_flag = nullptr;
-    float* d_part = nullptr;
-    GB_TRY(tmp.alloc(&d_leaves, n * sizeof(float4)));
-    GB_TRY(tmp.alloc(&d_flag, 2 * sizeof(unsigned int)));
-    GB_TRY(tmp.alloc(&d_part, kBoxBlocks * 6 * sizeof(float)));
-    GB_TRY(hipMemsetAsync(d_flag, 0, 2 * sizeof(unsigned int), s));
+    DevBuf<float4> d_leaves;
+    DevBuf<unsigned int> d_flag;
+    DevBuf<float> d_part;
+    LOCGPU_TRY(d_leaves.alloc(n));
+    LOCGPU_TRY(d_flag.alloc(2));
+    LOCGPU_TRY(d_part.alloc(kBoxBlocks * 6));
+    LOCGPU_TRY(hipMemsetAsync(d_flag, 0, 2 * sizeof(unsigned int), s));
     hipLaunchKernelGGL(gather_leaves_kernel, dim3(blocks_for(n)), dim3(kGB), 0, s, d_tree, d_leaf_slots, n, d_leaves, d_flag);
     const int nb = (int)std::min<size_t>(blocks_for(n), kBoxBlocks);
     hipLaunchKernelGGL(bbox_partial_kernel, dim3(nb), dim3(kGB), 0, s, d_leaves, n, d_part);
     std::vector<float> part((size_t)nb * 6);
     unsigned int flag[2] = {0, 0};
-    GB_TRY(hipMemcpyAsync(part.data(), d_part, part.size() * sizeof(float), hipMemcpyDeviceToHost, s));
-    GB_TRY(hipMemcpyAsync(flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, s));
-    GB_TRY(hipStreamSynchronize(s));
+    LOCGPU_TRY(hipMemcpyAsync(part.data(), d_part, part.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    LOCGPU_TRY(hipMemcpyAsync(flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, s));
+    LOCGPU_TRY(hipStreamSynchronize(s));
     if (flag[0]) { msg = "grid search needs finite target coordinates"; return hipErrorInvalidValue; }
     float lo[3] = {part[0], part[1], part[2]}, hi[3] = {part[3], part[4], part[5]};
     for (int b = 1; b < nb; ++b)
         for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], part[6 * b + a]); hi[a] = std::max(hi[a], part[6 * b + 3 + a]); }
 
     // ---- cell edge
-    unsigned long long *d_k64 = nullptr, *d_k64s = nullptr;
-    GB_TRY(tmp.alloc(&d_k64, n * sizeof(unsigned long long)));
-    GB_TRY(tmp.alloc(&d_k64s, n * sizeof(unsigned long long)));
+    DevBuf<unsigned long long> d_k64, d_k64s;
+    LOCGPU_TRY(d_k64.alloc(n));
+    LOCGPU_TRY(d_k64s.alloc(n));
     size_t sort_bytes = 0;
-    GB_TRY(prim::sort_keys(nullptr, sort_bytes, d_k64, d_k64s, (int)n, 0, 64, s));
+    LOCGPU_TRY(prim::sort_keys(nullptr, sort_bytes, d_k64.get(), d_k64s.get(), (int)n, 0, 64, s));
     {
         size_t b2 = 0;
         uint32_t* z = nullptr;
-        GB_TRY(prim::sort_pairs(nullptr, b2, z, z, z, z, (int)n, 0, 32, s));
+        LOCGPU_TRY(prim::sort_pairs(nullptr, b2, z, z, z, z, (int)n, 0, 32, s));
         sort_bytes = std::max(sort_bytes, b2);
-        GB_TRY(prim::run_length_encode(nullptr, b2, z, z, z, z, (int)n, s));
+        LOCGPU_TRY(prim::run_length_encode(nullptr, b2, z, z, z, z, (int)n, s));
         sort_bytes = std::max(sort_bytes, b2);
-        GB_TRY(prim::exclusive_sum(nullptr, b2, z, z, (int)n, s));
+        LOCGPU_TRY(prim::exclusive_sum(nullptr, b2, z, z, (int)n, s));
         sort_bytes = std::max(sort_bytes, b2);
     }
-    void* d_sort_tmp = nullptr;
-    GB_TRY(tmp.alloc(&d_sort_tmp, sort_bytes));
+    DevBuf<unsigned char> d_sort_tmp;
+    LOCGPU_TRY(d_sort_tmp.alloc(std::max<size_t>(sort_bytes, 1)));
     const double ext = std::max({(double)hi[0] - lo[0], (double)hi[1] - lo[1], (double)hi[2] - lo[2], 1e-3});
     double cell = ext;
     for (double c = ext / 8192.0; c < ext; c *= 1.3) {
         hipLaunchKernelGGL(probe_key_kernel, dim3(blocks_for(n)), dim3(kGB), 0, s, d_leaves, n, lo[0], lo[1], lo[2], (float)(1.0 / c), d_k64);
         size_t tb = sort_bytes;
-        GB_TRY(prim::sort_keys(d_sort_tmp, tb, d_k64, d_k64s, (int)n, 0, 63, s));
-        GB_TRY(hipMemsetAsync(d_flag + 1, 0, sizeof(unsigned int), s));
-        hipLaunchKernelGGL(count_distinct_kernel, dim3(blocks_for(n)), dim3(kGB), 0, s, d_k64s, n, d_flag + 1);
+        LOCGPU_TRY(prim::sort_keys(d_sort_tmp, tb, d_k64.get(), d_k64s.get(), (int)n, 0, 63, s));
+        LOCGPU_TRY(hipMemsetAsync(d_flag.get() + 1, 0, sizeof(unsigned int), s));
+        hipLaunchKernelGGL(count_distinct_kernel, dim3(blocks_for(n)), dim3(kGB), 0, s, d_k64s, n, d_flag.get() + 1);
         unsigned int occ = 0;
-        GB_TRY(hipMemcpyAsync(&occ, d_flag + 1, sizeof(occ), hipMemcpyDeviceToHost, s));
-        GB_TRY(hipStreamSynchronize(s));
+        LOCGPU_TRY(hipMemcpyAsync(&occ, d_flag.get() + 1, sizeof(occ), hipMemcpyDeviceToHost, s));
+        LOCGPU_TRY(hipStreamSynchronize(s));
         cell = c;
         if (occ == 0 || (double)n / (double)occ >= target_occ) break;
     }
@@ -258,43 +234,42 @@ hipError_t grid_build_device(const uint2* d_tree, const uint32_t* d_leaf_slots, 
     }
 
     // ---- sort the leaves by (tile, cell inside the tile)
-    uint32_t *d_key = nullptr, *d_idx = nullptr, *d_key_s = nullptr, *d_idx_s = nullptr, *d_tile_of = nullptr, *d_utile = nullptr, *d_cnt = nullptr,
-             *d_start = nullptr, *d_nocc = nullptr;
-    GB_TRY(tmp.alloc(&d_key, n * 4)); GB_TRY(tmp.alloc(&d_idx, n * 4)); GB_TRY(tmp.alloc(&d_key_s, n * 4)); GB_TRY(tmp.alloc(&d_idx_s, n * 4));
-    GB_TRY(tmp.alloc(&d_tile_of, n * 4)); GB_TRY(tmp.alloc(&d_utile, n * 4)); GB_TRY(tmp.alloc(&d_cnt, n * 4)); GB_TRY(tmp.alloc(&d_start, n * 4));
-    GB_TRY(tmp.alloc(&d_nocc, 4));
+    DevBuf<uint32_t> d_key, d_idx, d_key_s, d_idx_s, d_tile_of, d_utile, d_cnt, d_start, d_nocc;
+    LOCGPU_TRY(d_key.alloc(n)); LOCGPU_TRY(d_idx.alloc(n)); LOCGPU_TRY(d_key_s.alloc(n)); LOCGPU_TRY(d_idx_s.alloc(n));
+    LOCGPU_TRY(d_tile_of.alloc(n)); LOCGPU_TRY(d_utile.alloc(n)); LOCGPU_TRY(d_cnt.alloc(n)); LOCGPU_TRY(d_start.alloc(n));
+    LOCGPU_TRY(d_nocc.alloc(1));
     hipLaunchKernelGGL(cell_key_kernel, dim3(blocks_for(n)), dim3(kGB), 0, s, d_leaves, n, lo[0], lo[1], lo[2], inv, dims[0], dims[1], dims[2], tdims[0],
                        tdims[1], d_key, d_idx);
     size_t tb = sort_bytes;
-    GB_TRY(prim::sort_pairs(d_sort_tmp, tb, d_key, d_key_s, d_idx, d_idx_s, (int)n, 0, 32, s));  // stable: tree order inside a cell
-    GB_TRY(hipMalloc((void**)&buf.pts, n * sizeof(float4)));
+    LOCGPU_TRY(prim::sort_pairs(d_sort_tmp, tb, d_key.get(), d_key_s.get(), d_idx.get(), d_idx_s.get(), (int)n, 0, 32, s));  // stable: tree order inside a cell
+    LOCGPU_TRY(buf.pts.alloc(n));
     hipLaunchKernelGGL(gather_sorted_kernel, dim3(blocks_for(n)), dim3(kGB), 0, s, d_leaves, d_idx_s, d_key_s, n, buf.pts, d_tile_of);
     tb = sort_bytes;
-    GB_TRY(prim::run_length_encode(d_sort_tmp, tb, d_tile_of, d_utile, d_cnt, d_nocc, (int)n, s));
+    LOCGPU_TRY(prim::run_length_encode(d_sort_tmp, tb, d_tile_of.get(), d_utile.get(), d_cnt.get(), d_nocc.get(), (int)n, s));
     uint32_t n_tocc = 0;
-    GB_TRY(hipMemcpyAsync(&n_tocc, d_nocc, 4, hipMemcpyDeviceToHost, s));
-    GB_TRY(hipStreamSynchronize(s));
+    LOCGPU_TRY(hipMemcpyAsync(&n_tocc, d_nocc, 4, hipMemcpyDeviceToHost, s));
+    LOCGPU_TRY(hipStreamSynchronize(s));
     tb = sort_bytes;
-    GB_TRY(prim::exclusive_sum(d_sort_tmp, tb, d_cnt, d_start, (int)n_tocc, s));
+    LOCGPU_TRY(prim::exclusive_sum(d_sort_tmp, tb, d_cnt.get(), d_start.get(), (int)n_tocc, s));
     uint32_t cap = 1024;
     while (cap < 2u * n_tocc) cap <<= 1;
-    GB_TRY(hipMalloc((void**)&buf.tile_hash, (size_t)cap * sizeof(uint2)));
-    GB_TRY(hipMemsetAsync(buf.tile_hash, 0xFF, (size_t)cap * sizeof(uint2), s));
-    GB_TRY(hipMalloc((void**)&buf.tiles, (size_t)n_tocc * sizeof(TileRec)));
-    GB_TRY(hipMemsetAsync(d_flag, 0, 2 * sizeof(unsigned int), s));
+    LOCGPU_TRY(buf.tile_hash.alloc(cap));
+    LOCGPU_TRY(hipMemsetAsync(buf.tile_hash, 0xFF, (size_t)cap * sizeof(uint2), s));
+    LOCGPU_TRY(buf.tiles.alloc(n_tocc));
+    LOCGPU_TRY(hipMemsetAsync(d_flag, 0, 2 * sizeof(unsigned int), s));
     hipLaunchKernelGGL(tile_record_kernel, dim3(n_tocc), dim3(64), 0, s, d_key_s, d_utile, d_start, d_cnt, n_tocc, buf.tiles, buf.tile_hash, cap - 1, d_flag);
-    GB_TRY(hipMemcpyAsync(flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, s));
-    GB_TRY(hipStreamSynchronize(s));
+    LOCGPU_TRY(hipMemcpyAsync(flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, s));
+    LOCGPU_TRY(hipStreamSynchronize(s));
     if (flag[0] & 2u) { msg = "a tile holds more than 65535 leaves (degenerate point distribution)"; return hipErrorInvalidValue; }
     const uint32_t n_occ = flag[1];
 
     // ---- per-iteration binning scratch: one counter per occupied tile
-    GB_TRY(hipMalloc((void**)&buf.tile_count, ((size_t)n_tocc + 2) * sizeof(uint32_t)));
+    LOCGPU_TRY(buf.tile_count.alloc((size_t)n_tocc + 2));
     size_t scan_bytes = 0;
-    GB_TRY(prim::exclusive_sum(nullptr, scan_bytes, buf.tile_count, buf.tile_count, (int)(n_tocc + 1), s));
-    GB_TRY(hipMalloc(&buf.scan_temp, scan_bytes ? scan_bytes : 1));
-    GB_TRY(hipGetLastError());
-    GB_TRY(hipStreamSynchronize(s));
+    LOCGPU_TRY(prim::exclusive_sum(nullptr, scan_bytes, buf.tile_count.get(), buf.tile_count.get(), (int)(n_tocc + 1), s));
+    LOCGPU_TRY(buf.scan_temp.alloc(scan_bytes ? scan_bytes : 1));
+    LOCGPU_TRY(hipGetLastError());
+    LOCGPU_TRY(hipStreamSynchronize(s));
 
     view.tile_hash = buf.tile_hash;
     view.tile_mask = cap - 1;

@@ -13,6 +13,7 @@
 
 #include <string>
 
+#include "device_buffer.hpp"
 #include "launch.hpp"
 
 namespace locgpu {
@@ -46,11 +47,11 @@ struct GridView {
 };
 
 struct GridBuffers {  // device allocations behind a GridView
-    uint2* tile_hash = nullptr;
-    TileRec* tiles = nullptr;
-    float4* pts = nullptr;
-    uint32_t* tile_count = nullptr;
-    void* scan_temp = nullptr;
+    DevBuf<uint2> tile_hash;
+    DevBuf<TileRec> tiles;
+    DevBuf<float4> pts;
+    DevBuf<uint32_t> tile_count;
+    DevBuf<unsigned char> scan_temp;
 };
 
 // Builds the grid from the packed tree's leaves (d_tree, d_leaf_slots). Returns hipSuccess or the failing call's error;

@@ -88,18 +88,8 @@ static int install_tree_meta(locgpu_ctx* ctx, const long long meta[6]) {
     for (hipStream_t st : ctx->slot_stream) LOCGPU_HIP(ctx, hipStreamSynchronize(st));  // nobody reads the old tree any more (a begun alignment must be finished first)
     free_grid(ctx);
     const size_t slots = (size_t)meta[0], leaves = (size_t)meta[1];
-    if (slots + 2 > ctx->tree_cap_slots) {  // + the sentinel leaf behind the tree (search_walk.hpp)
-        if (ctx->d_tree) { LOCGPU_HIP(ctx, hipFree(ctx->d_tree)); ctx->d_tree = nullptr; ctx->tree_cap_slots = 0; }
-        const size_t cap = slots + slots / 4 + 1024;
-        LOCGPU_HIP(ctx, hipMalloc((void**)&ctx->d_tree, cap * sizeof(uint64_t)));
-        ctx->tree_cap_slots = cap;
-    }
-    if (leaves > ctx->leaf_cap) {
-        if (ctx->d_leaf_slots) { LOCGPU_HIP(ctx, hipFree(ctx->d_leaf_slots)); ctx->d_leaf_slots = nullptr; ctx->leaf_cap = 0; }
-        const size_t cap = leaves + leaves / 4 + 1024;
-        LOCGPU_HIP(ctx, hipMalloc((void**)&ctx->d_leaf_slots, cap * sizeof(uint32_t)));
-        ctx->leaf_cap = cap;
-    }
+    if (slots + 2 > ctx->d_tree.cap()) LOCGPU_HIP(ctx, ctx->d_tree.alloc(with_headroom(slots)));  // + the sentinel leaf behind the tree (search_walk.hpp)
+    if (leaves > ctx->d_leaf_slots.cap()) LOCGPU_HIP(ctx, ctx->d_leaf_slots.alloc(with_headroom(leaves)));
     ctx->tree_slots = slots;
     ctx->num_leaves = leaves;
     ctx->num_nodes = (size_t)meta[2];
@@ -240,24 +230,23 @@ int locgpu_icp_set_target_bcast(locgpu_ctx* ctx, const void* pts, size_t n, size
         if (rc == LOCGPU_OK) { meta[0] = (long long)t.slots.size(); meta[1] = (long long)t.num_leaves; meta[2] = (long long)t.num_nodes; meta[3] = (long long)t.num_points; meta[4] = t.depth; meta[5] = t.bounded ? 1 : 0; }
         meta[6] = rc;
     }
-    long long* d_meta = nullptr;
-    LOCGPU_HIP(ctx, hipMalloc((void**)&d_meta, sizeof(meta)));
+    DevBuf<long long> d_meta;
+    LOCGPU_HIP(ctx, d_meta.alloc(8));
     bool ok = hip_ok(ctx, hipMemcpyAsync(d_meta, meta, sizeof(meta), hipMemcpyHostToDevice, s), "bcast meta H2D");
     ok = ok && comm_broadcast(ctx, d_meta, sizeof(meta), root, s);
     ok = ok && hip_ok(ctx, hipMemcpyAsync(meta, d_meta, sizeof(meta), hipMemcpyDeviceToHost, s), "bcast meta D2H") && hip_ok(ctx, hipStreamSynchronize(s), "sync");
-    (void)hipFree(d_meta);
+    d_meta.reset();
     if (!ok) return fail(ctx, LOCGPU_ERR_NO_DEVICE, "icp_set_target_bcast: broadcast of the tree header failed");
     if (meta[6] != LOCGPU_OK) return ctx->comm_rank == root ? (int)meta[6] : fail(ctx, (int)meta[6], "icp_set_target_bcast: the root rank could not build the tree");
     rc = install_tree_meta(ctx, meta);
     {
         // collective error exit: a rank that could not make room for the tree must not leave the others waiting in the broadcast
-        int* d_rc = nullptr;
+        DevBuf<int> d_rc;
         int all_rc = rc;
-        bool okc = hip_ok(ctx, hipMalloc((void**)&d_rc, sizeof(int)), "bcast status") &&
+        bool okc = hip_ok(ctx, d_rc.alloc(1), "bcast status") &&
                    hip_ok(ctx, hipMemcpyAsync(d_rc, &rc, sizeof(int), hipMemcpyHostToDevice, s), "bcast status H2D");
         okc = okc && comm_all_reduce_min_int(ctx, d_rc, s);  // status codes are <= 0
         okc = okc && hip_ok(ctx, hipMemcpyAsync(&all_rc, d_rc, sizeof(int), hipMemcpyDeviceToHost, s), "bcast status D2H") && hip_ok(ctx, hipStreamSynchronize(s), "sync");
-        if (d_rc) (void)hipFree(d_rc);
         if (!okc) return fail(ctx, LOCGPU_ERR_NO_DEVICE, "icp_set_target_bcast: status exchange failed");
         if (rc != LOCGPU_OK) return rc;
         if (all_rc != LOCGPU_OK) return fail(ctx, all_rc, "icp_set_target_bcast: another rank could not allocate the tree buffers");

@@ -39,34 +39,29 @@ struct locgpu_loam {
     bool has_target[2] = {false, false};
     bool resident = false;  // the storage batches hold (or, after a _cloud call, point at) the scans of a single-scan call: locgpu_loam_fitness_resident
     hipStream_t stream = nullptr;  // the first enabled class's context stream: every launch of an alignment
-    hipEvent_t ev = nullptr;       // orders `stream` behind the other context's stream
-    // joint state, for cap_scans scans
-    int cap_scans = 0;
-    PoseState* d_state = nullptr;
-    PoseState* h_state = nullptr;  // pinned
-    double* d_hb = nullptr;
-    double* h_hb = nullptr;        // pinned
-    int* d_active = nullptr;
-    int* h_active = nullptr;       // pinned
-    double* d_fit = nullptr;       // [cap_scans][3][kFitW]: the joint score's sums — joint, surface, edge
-    double* h_fit = nullptr;       // pinned
+    Event ev;                      // orders `stream` behind the other context's stream
+    // joint state; h_fit, grown last, has the capacity of all eight
+    DevBuf<PoseState> d_state;
+    PinnedBuf<PoseState> h_state;
+    DevBuf<double> d_hb;
+    PinnedBuf<double> h_hb;
+    DevBuf<int> d_active;
+    PinnedBuf<int> h_active;
+    DevBuf<double> d_fit;          // [scans][3][kFitW]: the joint score's sums — joint, surface, edge
+    PinnedBuf<double> h_fit;
     // Shared-source form of the storage batches (share_scans): every entry of class c reads ONE region of n_shared[c] points — the
     // batch's own d_src, filled once through h_shared[c], or a caller's cloud through d_src_ext. src_of[c] / split_scans are what run()
     // hands to LocalStage::src_of / split_scans: nullptr / 0 in the two other forms (upload_scans, attach_scans).
-    int* d_src_of[2] = {nullptr, nullptr};      // a zero per entry
-    int cap_src_of[2] = {0, 0};
-    float4* h_shared[2] = {nullptr, nullptr};   // pinned staging of a host scan
-    size_t cap_shared[2] = {0, 0};
+    DevBuf<int> d_src_of[2];        // a zero per entry
+    PinnedBuf<float4> h_shared[2];  // pinned staging of a host scan
     size_t n_shared[2] = {0, 0};
     const int* src_of[2] = {nullptr, nullptr};
     int split_scans = 0;
     // output cloud of scan_match: packed x, y, z of edge then surface points; the points of a switched-off class pass through d_off
-    size_t cap_xyz = 0;
-    float* d_xyz = nullptr;
-    float* h_xyz = nullptr;        // pinned
-    size_t cap_off = 0;
-    float4* d_off = nullptr;
-    float4* h_off = nullptr;       // pinned
+    DevBuf<float> d_xyz;
+    PinnedBuf<float> h_xyz;
+    DevBuf<float4> d_off;
+    PinnedBuf<float4> h_off;
     std::string err;
 };
 
@@ -111,34 +106,17 @@ int check_opts(const locgpu_loam_opts* o) {
     return LOCGPU_OK;
 }
 
-void free_joint(locgpu_loam* l) {
-    if (l->d_state) (void)hipFree(l->d_state);
-    if (l->h_state) (void)hipHostFree(l->h_state);
-    if (l->d_hb) (void)hipFree(l->d_hb);
-    if (l->h_hb) (void)hipHostFree(l->h_hb);
-    if (l->d_active) (void)hipFree(l->d_active);
-    if (l->h_active) (void)hipHostFree(l->h_active);
-    if (l->d_fit) (void)hipFree(l->d_fit);
-    if (l->h_fit) (void)hipHostFree(l->h_fit);
-    l->d_fit = nullptr; l->h_fit = nullptr;
-    l->d_state = nullptr; l->h_state = nullptr; l->d_hb = nullptr; l->h_hb = nullptr; l->d_active = nullptr; l->h_active = nullptr;
-    l->cap_scans = 0;
-}
-
 int reserve_joint(locgpu_loam* l, int n) {
-    if (n <= l->cap_scans) return LOCGPU_OK;
-    free_joint(l);
-    const bool ok = lhip(l, hipMalloc((void**)&l->d_state, (size_t)n * sizeof(PoseState)), "hipMalloc state") &&
-                    lhip(l, hipHostMalloc((void**)&l->h_state, (size_t)n * sizeof(PoseState)), "hipHostMalloc state") &&
-                    lhip(l, hipMalloc((void**)&l->d_hb, (size_t)n * kLoamHbW * sizeof(double)), "hipMalloc hb") &&
-                    lhip(l, hipHostMalloc((void**)&l->h_hb, (size_t)n * kLoamHbW * sizeof(double)), "hipHostMalloc hb") &&
-                    lhip(l, hipMalloc((void**)&l->d_active, (size_t)n * sizeof(int)), "hipMalloc active") &&
-                    lhip(l, hipHostMalloc((void**)&l->h_active, (size_t)n * sizeof(int)), "hipHostMalloc active") &&
-                    lhip(l, hipMalloc((void**)&l->d_fit, (size_t)n * 3 * kFitW * sizeof(double)), "hipMalloc fit") &&
-                    lhip(l, hipHostMalloc((void**)&l->h_fit, (size_t)n * 3 * kFitW * sizeof(double)), "hipHostMalloc fit");
-    if (!ok) { free_joint(l); return LOCGPU_ERR_OOM; }
-    l->cap_scans = n;
-    return LOCGPU_OK;
+    if ((size_t)n * 3 * kFitW <= l->h_fit.cap()) return LOCGPU_OK;
+    const bool ok = lhip(l, l->d_state.alloc((size_t)n), "hipMalloc state") &&
+                    lhip(l, l->h_state.alloc((size_t)n), "hipHostMalloc state") &&
+                    lhip(l, l->d_hb.alloc((size_t)n * kLoamHbW), "hipMalloc hb") &&
+                    lhip(l, l->h_hb.alloc((size_t)n * kLoamHbW), "hipHostMalloc hb") &&
+                    lhip(l, l->d_active.alloc((size_t)n), "hipMalloc active") &&
+                    lhip(l, l->h_active.alloc((size_t)n), "hipHostMalloc active") &&
+                    lhip(l, l->d_fit.alloc((size_t)n * 3 * kFitW), "hipMalloc fit") &&
+                    lhip(l, l->h_fit.alloc((size_t)n * 3 * kFitW), "hipHostMalloc fit");
+    return ok ? LOCGPU_OK : LOCGPU_ERR_OOM;
 }
 
 // Class c's storage batch shaped as n_scans scans of at most max_n points: the one of the previous call when it has the room
@@ -151,7 +129,7 @@ int shape_batch(locgpu_loam* l, int c, int n_scans, size_t max_n) {
     if (!b || b->cap_scans < n_scans || b->cap_points < max_n) {
         const int cs = std::max(n_scans, b ? b->cap_scans : 0);
         size_t cp = std::max(max_n, b ? b->cap_points : (size_t)0);
-        if (cp == max_n && n_scans == 1) cp = max_n + max_n / 4 + 1024;
+        if (cp == max_n && n_scans == 1) cp = with_headroom(max_n);
         if (b) { (void)hipStreamSynchronize(l->stream); free_batch(b); l->batch[c] = nullptr; }
         const int slot = ctx->next_slot;
         int rc = from_ctx(l, c, alloc_batch(ctx, cs, cp, &l->batch[c]));
@@ -161,12 +139,12 @@ int shape_batch(locgpu_loam* l, int c, int n_scans, size_t max_n) {
         b->slot = 0;
         b->stream = ctx->stream;
         // the uploader's pinned counts are sized by the batch's scans at its first upload: give it the capacity's worth now
-        if (!lhip(l, hipHostMalloc((void**)&b->upl.h_counts, (size_t)cs * sizeof(int)), "hipHostMalloc counts")) return LOCGPU_ERR_OOM;
+        if (!lhip(l, b->upl.h_counts.alloc((size_t)cs), "hipHostMalloc counts")) return LOCGPU_ERR_OOM;
     }
     if (b->n_scans != n_scans || (size_t)b->max_n != max_n) {
         if ((size_t)n_scans * max_n > b->pitch) {  // the grid search's lists were sized by the old pitch (ensure_grid_lists)
-            if (b->d_grid_qkey) { (void)hipFree(b->d_grid_qkey); b->d_grid_qkey = nullptr; }
-            if (b->d_grid_sorted) { (void)hipFree(b->d_grid_sorted); b->d_grid_sorted = nullptr; }
+            b->d_grid_qkey.reset();
+            b->d_grid_sorted.reset();
         }
         b->n_scans = b->n_total = n_scans;
         b->max_n = (int)max_n;
@@ -316,24 +294,15 @@ int share_scans(locgpu_loam* l, const char* who, const void* const host[2], cons
         const int jrc = from_ctx(l, c, upload_join_batch(b));  // a failed earlier upload stays with the batch until one replaces it: say so
         if (jrc != LOCGPU_OK) return jrc;
         LOAM_HIP(l, upload_order_after(b, l->stream));
-        if (l->cap_src_of[c] < b->cap_scans) {
-            if (l->d_src_of[c]) (void)hipFree(l->d_src_of[c]);
-            l->d_src_of[c] = nullptr; l->cap_src_of[c] = 0;
-            if (!lhip(l, hipMalloc((void**)&l->d_src_of[c], (size_t)b->cap_scans * sizeof(int)), "hipMalloc src_of")) return LOCGPU_ERR_OOM;
-            l->cap_src_of[c] = b->cap_scans;
+        if (l->d_src_of[c].cap() < (size_t)b->cap_scans) {
+            if (!lhip(l, l->d_src_of[c].alloc((size_t)b->cap_scans), "hipMalloc src_of")) return LOCGPU_ERR_OOM;
             LOAM_HIP(l, hipMemsetAsync(l->d_src_of[c], 0, (size_t)b->cap_scans * sizeof(int), l->stream));
         }
         b->d_src_ext = nullptr;
         if (clouds) {
             if (n[c]) b->d_src_ext = clouds[c]->d;
         } else if (n[c]) {
-            if (l->cap_shared[c] < n[c]) {
-                if (l->h_shared[c]) (void)hipHostFree(l->h_shared[c]);
-                l->h_shared[c] = nullptr; l->cap_shared[c] = 0;
-                const size_t cap = n[c] + n[c] / 4 + 1024;
-                if (!lhip(l, hipHostMalloc((void**)&l->h_shared[c], cap * sizeof(float4)), "hipHostMalloc shared scan")) return LOCGPU_ERR_OOM;
-                l->cap_shared[c] = cap;
-            }
+            if (l->h_shared[c].cap() < n[c] && !lhip(l, l->h_shared[c].alloc(with_headroom(n[c])), "hipHostMalloc shared scan")) return LOCGPU_ERR_OOM;
             pack_points((const char*)host[c], stride, n[c], l->h_shared[c]);  // the deep copy of SetSource (icp_registration.cpp:252-265), once
             LOAM_HIP(l, hipMemcpyAsync(b->d_src, l->h_shared[c], n[c] * sizeof(float4), hipMemcpyHostToDevice, l->stream));
         }
@@ -600,15 +569,9 @@ int write_output(locgpu_loam* l, const void* src[2], const size_t n_pts[2], size
     const size_t n_all = n_pts[kEdge] + n_pts[kSurf];
     if (n_all == 0) return LOCGPU_OK;
     hipStream_t s = l->stream;
-    if (n_all > l->cap_xyz) {
-        if (l->d_xyz) (void)hipFree(l->d_xyz);
-        if (l->h_xyz) (void)hipHostFree(l->h_xyz);
-        l->d_xyz = nullptr; l->h_xyz = nullptr; l->cap_xyz = 0;
-        const size_t cap = n_all + n_all / 4 + 1024;
-        if (!lhip(l, hipMalloc((void**)&l->d_xyz, cap * 3 * sizeof(float)), "hipMalloc output cloud") ||
-            !lhip(l, hipHostMalloc((void**)&l->h_xyz, cap * 3 * sizeof(float)), "hipHostMalloc output cloud"))
-            return LOCGPU_ERR_OOM;
-        l->cap_xyz = cap;
+    if (3 * n_all > l->h_xyz.cap()) {  // h_xyz is grown last
+        const size_t cap = with_headroom(n_all);
+        if (!lhip(l, l->d_xyz.alloc(cap * 3), "hipMalloc output cloud") || !lhip(l, l->h_xyz.alloc(cap * 3), "hipHostMalloc output cloud")) return LOCGPU_ERR_OOM;
     }
     double R[9];
     quat_to_R(pose, R);
@@ -627,15 +590,9 @@ int write_output(locgpu_loam* l, const void* src[2], const size_t n_pts[2], size
         if (l->use[c]) {
             d_pts = l->batch[c]->d_src;  // scan 0 of the one-scan shape
         } else {
-            if (n > l->cap_off) {
-                if (l->d_off) (void)hipFree(l->d_off);
-                if (l->h_off) (void)hipHostFree(l->h_off);
-                l->d_off = nullptr; l->h_off = nullptr; l->cap_off = 0;
-                const size_t cap = n + n / 4 + 1024;
-                if (!lhip(l, hipMalloc((void**)&l->d_off, cap * sizeof(float4)), "hipMalloc output cloud") ||
-                    !lhip(l, hipHostMalloc((void**)&l->h_off, cap * sizeof(float4)), "hipHostMalloc output cloud"))
-                    return LOCGPU_ERR_OOM;
-                l->cap_off = cap;
+            if (n > l->h_off.cap()) {  // h_off is grown last
+                const size_t cap = with_headroom(n);
+                if (!lhip(l, l->d_off.alloc(cap), "hipMalloc output cloud") || !lhip(l, l->h_off.alloc(cap), "hipHostMalloc output cloud")) return LOCGPU_ERR_OOM;
             }
             pack_points((const char*)src[c], stride, n, l->h_off);
             LOAM_HIP(l, hipMemcpyAsync(l->d_off, l->h_off, n * sizeof(float4), hipMemcpyHostToDevice, s));
@@ -684,7 +641,7 @@ int locgpu_loam_create(int device_id, const locgpu_loam_opts* opts, locgpu_loam*
         if (rc != LOCGPU_OK) g_loam_create_err = locgpu_last_error(nullptr);
         else if (!l->stream) l->stream = l->ctx[c]->stream;
     }
-    if (rc == LOCGPU_OK && hipEventCreateWithFlags(&l->ev, hipEventDisableTiming) != hipSuccess) rc = lfail(nullptr, LOCGPU_ERR_NO_DEVICE, "loam_create: hipEventCreate");
+    if (rc == LOCGPU_OK && l->ev.ensure() != hipSuccess) rc = lfail(nullptr, LOCGPU_ERR_NO_DEVICE, "loam_create: hipEventCreate");
     if (rc != LOCGPU_OK) { locgpu_loam_destroy(l); return rc; }
     *out = l;
     return LOCGPU_OK;
@@ -711,7 +668,7 @@ int locgpu_loam_create_on(locgpu_ctx* surf_ctx, locgpu_ctx* edge_ctx, const locg
         l->ctx[c] = ctx[c];
         if (!l->stream) { l->stream = ctx[c]->stream; l->device = ctx[c]->device; }
     }
-    if (hipSetDevice(l->device) != hipSuccess || hipEventCreateWithFlags(&l->ev, hipEventDisableTiming) != hipSuccess) {
+    if (hipSetDevice(l->device) != hipSuccess || l->ev.ensure() != hipSuccess) {
         locgpu_loam_destroy(l);
         return lfail(nullptr, LOCGPU_ERR_NO_DEVICE, "loam_create_on: hipEventCreate");
     }
@@ -727,17 +684,8 @@ void locgpu_loam_destroy(locgpu_loam* l) {
         if (l->batch[c]) free_batch(l->batch[c]);
         l->batch[c] = nullptr;
     }
-    free_joint(l);
-    if (l->d_xyz) (void)hipFree(l->d_xyz);
-    if (l->h_xyz) (void)hipHostFree(l->h_xyz);
-    if (l->d_off) (void)hipFree(l->d_off);
-    if (l->h_off) (void)hipHostFree(l->h_off);
-    if (l->ev) (void)hipEventDestroy(l->ev);
-    for (int c = 0; c < 2; ++c) {
-        if (l->d_src_of[c]) (void)hipFree(l->d_src_of[c]);
-        if (l->h_shared[c]) (void)hipHostFree(l->h_shared[c]);
-        if (!l->borrowed) locgpu_destroy(l->ctx[c]);  // borrowed contexts stay alive, with their targets
-    }
+    if (!l->borrowed)
+        for (int c = 0; c < 2; ++c) locgpu_destroy(l->ctx[c]);  // borrowed contexts stay alive, with their targets
     delete l;
 }
 

@@ -101,75 +101,52 @@ __global__ __launch_bounds__(kLB) void sector_scatter_kernel(const float4* __res
     for (uint32_t s = threadIdx.x; s < ns; s += kLB) surf_out[surf_off[task] + s] = surf_slot[src + s];
 }
 
+}  // namespace
+
 struct LoamScratch {
-    size_t cap = 0;
-    int tasks_cap = 0;
-    unsigned char* d_ring = nullptr;
-    uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr};
-    float4 *ring_pts = nullptr, *surf_slot = nullptr, *edge_slot = nullptr;
-    double* curv = nullptr;
-    uint32_t *ring_start = nullptr, *edge_cnt = nullptr, *surf_cnt = nullptr, *edge_off = nullptr, *surf_off = nullptr;
-    void* temp = nullptr;
-    size_t temp_bytes = 0;
-    LoamParams *d_params = nullptr, *h_params = nullptr;
+    size_t cap = 0;  // points the group {d_ring … curv, temp} has room for
+    DevBuf<unsigned char> d_ring;
+    DevBuf<uint32_t> keys[2], vals[2];
+    DevBuf<float4> ring_pts, surf_slot;
+    DevBuf<double> curv;
+    DevBuf<unsigned char> temp;  // scratch of the sort at `cap` points
+    // per (ring, sector) task; edge_slot, grown last, has the capacity of the group
+    DevBuf<uint32_t> ring_start, edge_cnt, surf_cnt, edge_off, surf_off;
+    DevBuf<float4> edge_slot;
+    DevBuf<LoamParams> d_params;
+    PinnedBuf<LoamParams> h_params;
 };
 
-#define LOCGPU_TRY(expr)                   \
-    do {                                   \
-        const hipError_t e__ = (expr);     \
-        if (e__ != hipSuccess) return e__; \
-    } while (0)
-
-void free_scratch(LoamScratch* S) {
-    if (!S) return;
-    void* ptrs[] = {S->d_ring, S->keys[0], S->keys[1], S->vals[0], S->vals[1], S->ring_pts, S->surf_slot, S->edge_slot, S->curv, S->ring_start,
-                    S->edge_cnt, S->surf_cnt, S->edge_off, S->surf_off, S->temp, S->d_params};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (S->h_params) (void)hipHostFree(S->h_params);
-    delete S;
-}
+namespace {
 
 hipError_t ensure(locgpu_ctx* ctx, size_t n, int num_scan) {
     if (!ctx->loam) ctx->loam = new LoamScratch();
-    LoamScratch* S = (LoamScratch*)ctx->loam;
-    if (!S->d_params) {
-        LOCGPU_TRY(hipMalloc((void**)&S->d_params, sizeof(LoamParams)));
-        LOCGPU_TRY(hipHostMalloc((void**)&S->h_params, sizeof(LoamParams)));
-    }
-    const int tasks = num_scan * 6;
-    if (tasks > S->tasks_cap) {
-        void* ptrs[] = {S->ring_start, S->edge_cnt, S->surf_cnt, S->edge_off, S->surf_off, S->edge_slot};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-        S->ring_start = S->edge_cnt = S->surf_cnt = S->edge_off = S->surf_off = nullptr; S->edge_slot = nullptr; S->tasks_cap = 0;
-        LOCGPU_TRY(hipMalloc((void**)&S->ring_start, (num_scan + 1) * sizeof(uint32_t)));
-        LOCGPU_TRY(hipMalloc((void**)&S->edge_cnt, tasks * sizeof(uint32_t)));
-        LOCGPU_TRY(hipMalloc((void**)&S->surf_cnt, tasks * sizeof(uint32_t)));
-        LOCGPU_TRY(hipMalloc((void**)&S->edge_off, tasks * sizeof(uint32_t)));
-        LOCGPU_TRY(hipMalloc((void**)&S->surf_off, tasks * sizeof(uint32_t)));
-        LOCGPU_TRY(hipMalloc((void**)&S->edge_slot, (size_t)tasks * kMaxEdges * sizeof(float4)));
-        S->tasks_cap = tasks;
+    LoamScratch* S = ctx->loam;
+    LOCGPU_TRY(S->d_params.reserve(1));
+    LOCGPU_TRY(S->h_params.reserve(1));
+    const size_t tasks = (size_t)num_scan * 6;
+    if (tasks * kMaxEdges > S->edge_slot.cap()) {
+        LOCGPU_TRY(S->ring_start.alloc((size_t)num_scan + 1));
+        LOCGPU_TRY(S->edge_cnt.alloc(tasks));
+        LOCGPU_TRY(S->surf_cnt.alloc(tasks));
+        LOCGPU_TRY(S->edge_off.alloc(tasks));
+        LOCGPU_TRY(S->surf_off.alloc(tasks));
+        LOCGPU_TRY(S->edge_slot.alloc(tasks * kMaxEdges));
     }
     if (n > S->cap) {
-        void* ptrs[] = {S->d_ring, S->keys[0], S->keys[1], S->vals[0], S->vals[1], S->ring_pts, S->surf_slot, S->curv, S->temp};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-        S->d_ring = nullptr; S->keys[0] = S->keys[1] = S->vals[0] = S->vals[1] = nullptr; S->ring_pts = S->surf_slot = nullptr; S->curv = nullptr;
-        S->temp = nullptr; S->cap = 0;
-        const size_t cap = n + n / 4 + 1024;
-        LOCGPU_TRY(hipMalloc((void**)&S->d_ring, cap));
+        S->cap = 0;
+        const size_t cap = with_headroom(n);
+        LOCGPU_TRY(S->d_ring.alloc(cap));
         for (int j = 0; j < 2; ++j) {
-            LOCGPU_TRY(hipMalloc((void**)&S->keys[j], cap * sizeof(uint32_t)));
-            LOCGPU_TRY(hipMalloc((void**)&S->vals[j], cap * sizeof(uint32_t)));
+            LOCGPU_TRY(S->keys[j].alloc(cap));
+            LOCGPU_TRY(S->vals[j].alloc(cap));
         }
-        LOCGPU_TRY(hipMalloc((void**)&S->ring_pts, cap * sizeof(float4)));
-        LOCGPU_TRY(hipMalloc((void**)&S->surf_slot, cap * sizeof(float4)));
-        LOCGPU_TRY(hipMalloc((void**)&S->curv, cap * sizeof(double)));
+        LOCGPU_TRY(S->ring_pts.alloc(cap));
+        LOCGPU_TRY(S->surf_slot.alloc(cap));
+        LOCGPU_TRY(S->curv.alloc(cap));
         size_t tb = 0;
-        LOCGPU_TRY(prim::sort_pairs(nullptr, tb, S->keys[0], S->keys[1], S->vals[0], S->vals[1], (int)cap, 0, 8, ctx->stream));
-        S->temp_bytes = tb + 256;
-        LOCGPU_TRY(hipMalloc(&S->temp, S->temp_bytes));
+        LOCGPU_TRY(prim::sort_pairs(nullptr, tb, S->keys[0].get(), S->keys[1].get(), S->vals[0].get(), S->vals[1].get(), (int)cap, 0, 8, ctx->stream));
+        LOCGPU_TRY(S->temp.alloc(tb + 256));
         S->cap = cap;
     }
     return hipSuccess;
@@ -178,7 +155,7 @@ hipError_t ensure(locgpu_ctx* ctx, size_t n, int num_scan) {
 }  // namespace
 
 void loam_free(locgpu_ctx* ctx) {
-    free_scratch((LoamScratch*)ctx->loam);
+    delete ctx->loam;
     ctx->loam = nullptr;
     batch_loam_free(ctx);
 }
@@ -192,14 +169,14 @@ hipError_t loam_extract_dev(locgpu_ctx* ctx, const locgpu_cloud* in, const unsig
     surf->n = 0; surf->is_dense = 1;
     if (n == 0) return hipSuccess;
     LOCGPU_TRY(ensure(ctx, n, num_scan));
-    LoamScratch* S = (LoamScratch*)ctx->loam;
+    LoamScratch* S = ctx->loam;
     hipStream_t s = ctx->stream;
     const unsigned nb = (unsigned)((n + kLB - 1) / kLB);
     LOCGPU_TRY(hipMemcpyAsync(S->d_ring, ring, n, hipMemcpyHostToDevice, s));
     LOCGPU_TRY(hipMemsetAsync(S->d_params, 0, sizeof(LoamParams), s));
     hipLaunchKernelGGL(ring_key_kernel, dim3(nb), dim3(kLB), 0, s, S->d_ring, n, S->keys[0], S->vals[0]);
-    size_t tb = S->temp_bytes;
-    LOCGPU_TRY(prim::sort_pairs(S->temp, tb, S->keys[0], S->keys[1], S->vals[0], S->vals[1], (int)n, 0, 8, s));  // stable: input order per ring
+    size_t tb = S->temp.cap();
+    LOCGPU_TRY(prim::sort_pairs(S->temp, tb, S->keys[0].get(), S->keys[1].get(), S->vals[0].get(), S->vals[1].get(), (int)n, 0, 8, s));  // stable: input order per ring
     hipLaunchKernelGGL(ring_start_kernel, dim3((num_scan + 1 + 63) / 64), dim3(64), 0, s, S->keys[1], (uint32_t)n, num_scan, S->ring_start);
     hipLaunchKernelGGL(ring_gather_kernel, dim3(nb), dim3(kLB), 0, s, in->d, S->vals[1], n, S->ring_pts);
     hipLaunchKernelGGL(curvature_kernel, dim3(nb, num_scan), dim3(kLB), 0, s, S->ring_pts, S->ring_start, num_scan, S->curv);

@@ -49,35 +49,8 @@ static bool fill_now(locgpu_ctx* ctx, void* p, size_t bytes, const char* what) {
 void locgpu::free_batch(locgpu_batch* b) {
     if (!b) return;
     upload_free_batch(b);
-    for (hipEvent_t ev : b->stage_ev.ev) (void)hipEventDestroy(ev);
-    if (b->ev_ready) (void)hipEventDestroy(b->ev_ready);
-    if (b->ev_reduced) (void)hipEventDestroy(b->ev_reduced);
-    if (b->d_src) (void)hipFree(b->d_src);
-    if (b->d_src_of) (void)hipFree(b->d_src_of);
-    if (b->d_counts) (void)hipFree(b->d_counts);
-    if (b->d_state) (void)hipFree(b->d_state);
-    if (b->d_nn) (void)hipFree(b->d_nn);
-    if (b->d_partials) (void)hipFree(b->d_partials);
-    if (b->d_hb) (void)hipFree(b->d_hb);
-    if (b->d_acc) (void)hipFree(b->d_acc);
-    if (b->d_redo_list) (void)hipFree(b->d_redo_list);
-    if (b->d_redo_count) (void)hipFree(b->d_redo_count);
-    if (b->d_redo_list2) (void)hipFree(b->d_redo_list2);
-    if (b->d_grid_qkey) (void)hipFree(b->d_grid_qkey);
-    if (b->d_grid_sorted) (void)hipFree(b->d_grid_sorted);
-    if (b->d_grid_tile_count) (void)hipFree(b->d_grid_tile_count);
-    if (b->d_grid_scan_temp) (void)hipFree(b->d_grid_scan_temp);
     if (b->graph_exec) (void)hipGraphExecDestroy(b->graph_exec);
     if (b->graph_exec_next) (void)hipGraphExecDestroy(b->graph_exec_next);
-    if (b->h_src) (void)hipHostFree(b->h_src);
-    if (b->h_state) (void)hipHostFree(b->h_state);
-    if (b->h_post) (void)hipHostFree(b->h_post);
-    if (b->tail_ev) (void)hipEventDestroy(b->tail_ev);
-    for (hipEvent_t e : b->xyz_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (b->h_hb) (void)hipHostFree(b->h_hb);
-    if (b->h_active) (void)hipHostFree(b->h_active);
-    if (b->d_active) (void)hipFree(b->d_active);
     delete b;
 }
 
@@ -163,20 +136,11 @@ void locgpu_destroy(locgpu_ctx* ctx) {
     free_batch(ctx->single);
     free_batch(ctx->search);
     free_batch(ctx->planes_ws);
-    if (ctx->d_planes) (void)hipFree(ctx->d_planes);
-    if (ctx->d_planes_count) (void)hipFree(ctx->d_planes_count);
     upload_free_ctx(ctx);
     comm_destroy(ctx);
     if (ctx->comm_stream) (void)hipStreamDestroy(ctx->comm_stream);
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
-    if (ctx->foreign_ev) (void)hipEventDestroy(ctx->foreign_ev);
-    if (ctx->d_tree) (void)hipFree(ctx->d_tree);
-    if (ctx->d_leaf_slots) (void)hipFree(ctx->d_leaf_slots);
-    if (ctx->d_bfnn) (void)hipFree(ctx->d_bfnn);
     free_grid(ctx);
-    if (ctx->d_visits) (void)hipFree(ctx->d_visits);
-    if (ctx->d_touched) (void)hipFree(ctx->d_touched);
-    if (ctx->d_search_stats) (void)hipFree(ctx->d_search_stats);
     ndt_free(ctx);
     filters_free(ctx);
     loam_free(ctx);
@@ -203,17 +167,14 @@ int locgpu_knn(locgpu_ctx* ctx, const float* queries, size_t nq, int k, int appr
         const int grc = ensure_grid(ctx);
         if (grc != LOCGPU_OK) return grc;
     }
-    float* d_q = nullptr;
-    int32_t* d_out = nullptr;
-    uint32_t* d_vis = nullptr;
-    unsigned int* d_flag = nullptr;
+    DevBuf<float> d_q;
+    DevBuf<int32_t> d_out;
+    DevBuf<uint32_t> d_vis;
+    DevBuf<unsigned int> d_flag;
     int rc = LOCGPU_OK;
-    auto cleanup = [&]() { if (d_q) (void)hipFree(d_q); if (d_out) (void)hipFree(d_out); if (d_vis) (void)hipFree(d_vis); if (d_flag) (void)hipFree(d_flag); };
-    if (!hip_ok(ctx, hipMalloc((void**)&d_q, nq * 12), "hipMalloc") || !hip_ok(ctx, hipMalloc((void**)&d_out, nq * k * 4), "hipMalloc") ||
-        !hip_ok(ctx, hipMalloc((void**)&d_flag, 4), "hipMalloc") || (visits && !hip_ok(ctx, hipMalloc((void**)&d_vis, nq * 8), "hipMalloc"))) {
-        cleanup();
+    if (!hip_ok(ctx, d_q.alloc(nq * 3), "hipMalloc") || !hip_ok(ctx, d_out.alloc(nq * k), "hipMalloc") || !hip_ok(ctx, d_flag.alloc(1), "hipMalloc") ||
+        (visits && !hip_ok(ctx, d_vis.alloc(nq * 2), "hipMalloc")))
         return LOCGPU_ERR_OOM;
-    }
     hipStream_t s = ctx->stream;
     if (!hip_ok(ctx, hipMemcpyAsync(d_q, queries, nq * 12, hipMemcpyHostToDevice, s), "H2D")) rc = LOCGPU_ERR_NO_DEVICE;
     if (rc == LOCGPU_OK && grid) {
@@ -237,7 +198,6 @@ int locgpu_knn(locgpu_ctx* ctx, const float* queries, size_t nq, int k, int appr
                     if (out_idx[i * k] == -2)
                         for (int j = 0; j < k; ++j) out_idx[i * k + j] = tmp[i * k + j];
         }
-        cleanup();
         return rc;
     }
     if (rc == LOCGPU_OK && !launch_knn_query(ctx->d_tree, ctx->depth, d_q, nq, k, approximate ? alpha : 1.0f, d_out, d_vis, s))
@@ -246,7 +206,6 @@ int locgpu_knn(locgpu_ctx* ctx, const float* queries, size_t nq, int k, int appr
     if (rc == LOCGPU_OK && !hip_ok(ctx, hipMemcpyAsync(out_idx, d_out, nq * k * 4, hipMemcpyDeviceToHost, s), "D2H")) rc = LOCGPU_ERR_NO_DEVICE;
     if (rc == LOCGPU_OK && visits && !hip_ok(ctx, hipMemcpyAsync(visits, d_vis, nq * 8, hipMemcpyDeviceToHost, s), "D2H")) rc = LOCGPU_ERR_NO_DEVICE;
     if (!hip_ok(ctx, hipStreamSynchronize(s), "sync") && rc == LOCGPU_OK) rc = LOCGPU_ERR_NO_DEVICE;
-    cleanup();
     return rc;
 }
 
@@ -285,22 +244,22 @@ int locgpu::alloc_batch(locgpu_ctx* ctx, int n_scans, size_t max_n, locgpu_batch
     b->cap_scans = n_scans;
     b->cap_points = max_n;
     // a shared-source batch holds ONE region of points, whatever its number of entries, and a zero per entry that says so
-    bool ok = hip_ok(ctx, hipMalloc((void**)&b->d_src, std::max<size_t>(shared_src ? max_n : b->pitch, 1) * sizeof(float4)), "hipMalloc src") &&
-              (!shared_src || (hip_ok(ctx, hipMalloc((void**)&b->d_src_of, (size_t)n_scans * sizeof(int)), "hipMalloc src_of") &&
+    bool ok = hip_ok(ctx, b->d_src.alloc(std::max<size_t>(shared_src ? max_n : b->pitch, 1)), "hipMalloc src") &&
+              (!shared_src || (hip_ok(ctx, b->d_src_of.alloc((size_t)n_scans), "hipMalloc src_of") &&
                                fill_now(ctx, b->d_src_of, (size_t)n_scans * sizeof(int), "hipMemset src_of"))) &&
-              hip_ok(ctx, hipMalloc((void**)&b->d_counts, std::max(n_scans, 1) * sizeof(int)), "hipMalloc counts") &&
-              hip_ok(ctx, hipMalloc((void**)&b->d_state, n_total * sizeof(PoseState)), "hipMalloc state") &&
-              (!sharded || hip_ok(ctx, hipMalloc((void**)&b->d_acc, (size_t)kFirstChunk * n_total * kAccW * sizeof(double)), "hipMalloc acc")) &&  // one slot per iteration of a chunk
-              hip_ok(ctx, hipMalloc((void**)&b->d_nn, 5 * std::max<size_t>(b->pitch, 1) * sizeof(uint32_t)), "hipMalloc nn") &&
-              hip_ok(ctx, hipMalloc((void**)&b->d_partials, (size_t)std::max(n_scans, 1) * b->blocks_per_scan * kAccW * sizeof(double)), "hipMalloc partials") &&
-              hip_ok(ctx, hipMalloc((void**)&b->d_hb, (size_t)n_total * 44 * sizeof(double)), "hipMalloc hb") &&
-              hip_ok(ctx, hipMalloc((void**)&b->d_redo_list, (stamp_build() ? 2 : 1) * std::max<size_t>(b->pitch, 1) * sizeof(uint32_t)), "hipMalloc redo") &&  // diagnostic build: + per-query trip counts
-              hip_ok(ctx, hipMalloc((void**)&b->d_redo_list2, std::max<size_t>(b->pitch, 1) * sizeof(uint32_t)), "hipMalloc redo2") &&  // deep pass / grid search: second work list
-              hip_ok(ctx, hipMalloc((void**)&b->d_redo_count, 4 * sizeof(unsigned int)), "hipMalloc redo") &&  // [0] redo list, [1] deep list, [2..3] spare
-              hip_ok(ctx, hipHostMalloc((void**)&b->h_state, n_total * sizeof(PoseState)), "hipHostMalloc state") &&
-              hip_ok(ctx, hipHostMalloc((void**)&b->h_hb, (size_t)n_total * 44 * sizeof(double)), "hipHostMalloc hb") &&
-              hip_ok(ctx, hipHostMalloc((void**)&b->h_active, (size_t)std::max(n_scans, 1) * sizeof(int)), "hipHostMalloc active") &&
-              hip_ok(ctx, hipMalloc((void**)&b->d_active, (size_t)std::max(n_scans, 1) * sizeof(int)), "hipMalloc active") &&
+              hip_ok(ctx, b->d_counts.alloc(std::max(n_scans, 1)), "hipMalloc counts") &&
+              hip_ok(ctx, b->d_state.alloc(n_total), "hipMalloc state") &&
+              (!sharded || hip_ok(ctx, b->d_acc.alloc((size_t)kFirstChunk * n_total * kAccW), "hipMalloc acc")) &&  // one slot per iteration of a chunk
+              hip_ok(ctx, b->d_nn.alloc(5 * std::max<size_t>(b->pitch, 1)), "hipMalloc nn") &&
+              hip_ok(ctx, b->d_partials.alloc((size_t)std::max(n_scans, 1) * b->blocks_per_scan * kAccW), "hipMalloc partials") &&
+              hip_ok(ctx, b->d_hb.alloc((size_t)n_total * 44), "hipMalloc hb") &&
+              hip_ok(ctx, b->d_redo_list.alloc((stamp_build() ? 2 : 1) * std::max<size_t>(b->pitch, 1)), "hipMalloc redo") &&  // diagnostic build: + per-query trip counts
+              hip_ok(ctx, b->d_redo_list2.alloc(std::max<size_t>(b->pitch, 1)), "hipMalloc redo2") &&  // deep pass / grid search: second work list
+              hip_ok(ctx, b->d_redo_count.alloc(4), "hipMalloc redo") &&  // [0] redo list, [1] deep list, [2..3] spare
+              hip_ok(ctx, b->h_state.alloc(n_total), "hipHostMalloc state") &&
+              hip_ok(ctx, b->h_hb.alloc((size_t)n_total * 44), "hipHostMalloc hb") &&
+              hip_ok(ctx, b->h_active.alloc((size_t)std::max(n_scans, 1)), "hipHostMalloc active") &&
+              hip_ok(ctx, b->d_active.alloc((size_t)std::max(n_scans, 1)), "hipMalloc active") &&
               // hipMemset runs on the NULL stream and returns before it has run; the context's streams are non-blocking, i.e. NOT ordered
               // behind it — the first upload of the scan counts could be overtaken by this very fill (the first alignment of a fresh
               // batch then saw a scan of zero points and ran its 20 iterations on nothing; once in ≈1000 first calls, found by
@@ -367,8 +326,7 @@ int locgpu_batch_create_sharded(locgpu_ctx* ctx, const void* const* srcs, const 
     const int rc = make_batch(ctx, srcs, counts, stride_bytes, n_local, out, first_scan, n_total);
     if (rc != LOCGPU_OK) return rc;
     locgpu_batch* b = *out;
-    if (!hip_ok(ctx, hipEventCreateWithFlags(&b->ev_ready, hipEventDisableTiming), "batch_create_sharded: hipEventCreate") ||
-        !hip_ok(ctx, hipEventCreateWithFlags(&b->ev_reduced, hipEventDisableTiming), "batch_create_sharded: hipEventCreate")) {
+    if (!hip_ok(ctx, b->ev_ready.ensure(), "batch_create_sharded: hipEventCreate") || !hip_ok(ctx, b->ev_reduced.ensure(), "batch_create_sharded: hipEventCreate")) {
         free_batch(b);
         *out = nullptr;
         return LOCGPU_ERR_OOM;
@@ -435,13 +393,13 @@ static int single_reserve(locgpu_ctx* ctx, size_t n, locgpu_batch** out) {
     if (!b || (size_t)b->max_n < n || !b->h_src) {
         if (b) { free_batch(b); ctx->single = nullptr; }
         // device buffers with headroom, then pinned staging of the same capacity
-        const size_t cap = n + n / 4 + 1024;
+        const size_t cap = with_headroom(n);
         const int rc = alloc_batch(ctx, 1, cap, &ctx->single);
         if (rc != LOCGPU_OK) return rc;
         b = ctx->single;
         b->slot = 0;  // single-scan calls share the stream of the clouds and of the target ingest
         b->stream = ctx->stream;
-        if (!hip_ok(ctx, hipHostMalloc((void**)&b->h_src, cap * sizeof(float4)), "hipHostMalloc src")) { free_batch(b); ctx->single = nullptr; return LOCGPU_ERR_OOM; }
+        if (!hip_ok(ctx, b->h_src.alloc(cap), "hipHostMalloc src")) { free_batch(b); ctx->single = nullptr; return LOCGPU_ERR_OOM; }
     }
     *out = b;
     return LOCGPU_OK;
@@ -541,12 +499,11 @@ int locgpu_debug_batch_nn(locgpu_ctx* ctx, locgpu_batch* b, int k, int32_t* out)
     if (!ctx->d_tree) return fail(ctx, LOCGPU_ERR_NO_TARGET, "debug_batch_nn: no ICP target");
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nq = (size_t)b->n_scans * b->max_n;
-    int32_t* d_out = nullptr;
-    LOCGPU_HIP(ctx, hipMalloc((void**)&d_out, nq * k * sizeof(int32_t)));
+    DevBuf<int32_t> d_out;
+    LOCGPU_HIP(ctx, d_out.alloc(nq * k));
     launch_nn_to_index(ctx->d_tree, b->d_nn, b->pitch, nq, k, d_out, b->stream);
     const hipError_t e = hipMemcpyAsync(out, d_out, nq * k * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream);
     const hipError_t e2 = hipStreamSynchronize(b->stream);
-    (void)hipFree(d_out);
     LOCGPU_HIP(ctx, e);
     LOCGPU_HIP(ctx, e2);
     return LOCGPU_OK;
@@ -598,19 +555,16 @@ int locgpu_icp_map_planes_dump(locgpu_ctx* ctx, double* n4, uint8_t* valid, size
     if (n_out) *n_out = n;
     if (!n4 && !valid && cap == 0 && n_out) return LOCGPU_OK;  // size query
     if (!n4 || !valid || cap < n) return fail(ctx, LOCGPU_ERR_INVALID, "icp_map_planes_dump: NULL output or capacity below the number of target points");
-    double* d_n4 = nullptr;
-    unsigned char* d_valid = nullptr;
+    DevBuf<double> d_n4;
+    DevBuf<unsigned char> d_valid;
     hipStream_t s = ctx->stream;
-    bool ok = hip_ok(ctx, hipMalloc((void**)&d_n4, std::max<size_t>(n, 1) * 4 * sizeof(double)), "hipMalloc") &&
-              hip_ok(ctx, hipMalloc((void**)&d_valid, std::max<size_t>(n, 1)), "hipMalloc");
+    bool ok = hip_ok(ctx, d_n4.alloc(std::max<size_t>(n, 1) * 4), "hipMalloc") && hip_ok(ctx, d_valid.alloc(std::max<size_t>(n, 1)), "hipMalloc");
     if (!ok) rc = LOCGPU_ERR_OOM;
     ok = ok && hip_ok(ctx, hipMemsetAsync(d_n4, 0, n * 4 * sizeof(double), s), "hipMemset") && hip_ok(ctx, hipMemsetAsync(d_valid, 0, n, s), "hipMemset");
     if (ok && ctx->num_leaves > 0) launch_map_plane_dump(ctx->d_tree, ctx->d_leaf_slots, ctx->num_leaves, ctx->d_planes, n, d_n4, d_valid, s);
     ok = ok && hip_ok(ctx, hipGetLastError(), "map_planes_dump launch") && hip_ok(ctx, hipMemcpyAsync(n4, d_n4, n * 4 * sizeof(double), hipMemcpyDeviceToHost, s), "D2H") &&
          hip_ok(ctx, hipMemcpyAsync(valid, d_valid, n, hipMemcpyDeviceToHost, s), "D2H");
     if (!hip_ok(ctx, hipStreamSynchronize(s), "sync")) ok = false;
-    if (d_n4) (void)hipFree(d_n4);
-    if (d_valid) (void)hipFree(d_valid);
     return ok ? LOCGPU_OK : (rc != LOCGPU_OK ? rc : LOCGPU_ERR_NO_DEVICE);
 }
 
@@ -644,8 +598,8 @@ static int write_output_cloud(locgpu_ctx* ctx, locgpu_batch* b, const float4* d_
         for (int c = 0; c < 3; ++c) m.v[4 * r + c] = (float)R[3 * r + c];
         m.v[4 * r + 3] = (float)pose[4 + r];
     }
-    float* d_xyz = reinterpret_cast<float*>(b->d_nn);
-    float* h_xyz = reinterpret_cast<float*>(b->h_src);
+    float* d_xyz = reinterpret_cast<float*>(b->d_nn.get());
+    float* h_xyz = reinterpret_cast<float*>(b->h_src.get());
     launch_transform_cloud(d_points, n, m, d_xyz, b->stream);
     LOCGPU_HIP(ctx, hipGetLastError());
     // back in up to eight pieces, each with an event: the host writes piece i into the caller's points while the later ones cross PCIe —
@@ -655,7 +609,7 @@ static int write_output_cloud(locgpu_ctx* ctx, locgpu_batch* b, const float4* d_
     const size_t piece = std::max<size_t>(32 * 1024, (n + kMaxPieces - 1) / kMaxPieces);
     const int pieces = (int)((n + piece - 1) / piece);
     for (int p = 0; p < pieces; ++p) {
-        if (!b->xyz_ev[p]) LOCGPU_HIP(ctx, hipEventCreateWithFlags(&b->xyz_ev[p], hipEventDisableTiming));
+        LOCGPU_HIP(ctx, b->xyz_ev[p].ensure());
         const size_t lo = (size_t)p * piece, len = std::min(piece, n - lo);
         LOCGPU_HIP(ctx, hipMemcpyAsync(h_xyz + 3 * lo, d_xyz + 3 * lo, len * 3 * sizeof(float), hipMemcpyDeviceToHost, b->stream));
         LOCGPU_HIP(ctx, hipEventRecord(b->xyz_ev[p], b->stream));
@@ -778,8 +732,8 @@ int reshape_shared(locgpu_ctx* ctx, locgpu_batch* b, int n_scans, size_t n, int 
         LOCGPU_HIP(ctx, hipStreamSynchronize(b->stream));
         drop_graphs(b);  // captured launches carry the old shape
         if ((size_t)n_scans * n > b->pitch) {  // the grid search's lists were sized by the old pitch (ensure_grid_lists)
-            if (b->d_grid_qkey) { (void)hipFree(b->d_grid_qkey); b->d_grid_qkey = nullptr; }
-            if (b->d_grid_sorted) { (void)hipFree(b->d_grid_sorted); b->d_grid_sorted = nullptr; }
+            b->d_grid_qkey.reset();
+            b->d_grid_sorted.reset();
         }
         b->n_scans = b->n_total = n_scans;
         b->max_n = (int)n;
@@ -795,7 +749,7 @@ int reshape_shared(locgpu_ctx* ctx, locgpu_batch* b, int n_scans, size_t n, int 
 
 // The one upload of a shared-source batch: the deep copy of the source (SetSource, icp_registration.cpp:252-265), 16 B per point once.
 int upload_shared(locgpu_ctx* ctx, locgpu_batch* b, const void* src, size_t n, size_t stride_bytes) {
-    if (!b->h_src) LOCGPU_HIP(ctx, hipHostMalloc((void**)&b->h_src, b->cap_points * sizeof(float4)));
+    if (!b->h_src) LOCGPU_HIP(ctx, b->h_src.alloc(b->cap_points));
     pack_points((const char*)src, stride_bytes, n, b->h_src);
     LOCGPU_HIP(ctx, hipMemcpyAsync(b->d_src, b->h_src, n * sizeof(float4), hipMemcpyHostToDevice, b->stream));
     return LOCGPU_OK;
@@ -1064,7 +1018,7 @@ int locgpu_search_stats_read(locgpu_ctx* ctx, uint64_t out[4], int reset) {
     if (!ctx || !out) return LOCGPU_ERR_INVALID;
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->d_search_stats) {
-        LOCGPU_HIP(ctx, hipMalloc((void**)&ctx->d_search_stats, kSearchStatSlots * sizeof(unsigned long long)));
+        LOCGPU_HIP(ctx, ctx->d_search_stats.alloc(kSearchStatSlots));
         if (!fill_now(ctx, ctx->d_search_stats, kSearchStatSlots * sizeof(unsigned long long), "hipMemset search stats")) return LOCGPU_ERR_NO_DEVICE;
     }
     for (hipStream_t st : ctx->slot_stream) LOCGPU_HIP(ctx, hipStreamSynchronize(st));
@@ -1085,7 +1039,7 @@ int locgpu_visit_count_enable(locgpu_ctx* ctx, int on) {
     if (!ctx) return LOCGPU_ERR_INVALID;
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
     if (on && !ctx->d_visits) {
-        LOCGPU_HIP(ctx, hipMalloc((void**)&ctx->d_visits, 4 * sizeof(unsigned long long)));
+        LOCGPU_HIP(ctx, ctx->d_visits.alloc(4));
         if (!fill_now(ctx, ctx->d_visits, 4 * sizeof(unsigned long long), "hipMemset visits")) return LOCGPU_ERR_NO_DEVICE;
     }
     ctx->count_visits = on != 0;
@@ -1139,7 +1093,8 @@ extern "C" __attribute__((visibility("default"))) size_t locgpu_debug_grid_dump(
 // --------------------------------------------------------------------------------------------- NDT
 namespace locgpu {
 void ndt_free(locgpu_ctx* ctx) {
-    if (ctx->ndt) { ndt_table_free(*ctx->ndt); delete ctx->ndt; ctx->ndt = nullptr; }
+    delete ctx->ndt;
+    ctx->ndt = nullptr;
     if (ctx->inc) { inc_ndt_destroy(ctx->inc); ctx->inc = nullptr; }
 }
 int check_ndt(locgpu_ctx* ctx, AlignSpec& spec) {
@@ -1210,12 +1165,11 @@ int locgpu_ndt_set_target(locgpu_ctx* ctx, const void* pts, size_t n, size_t str
     std::vector<float4> host(n);
     const char* base = (const char*)pts;
     for (size_t i = 0; i < n; ++i) { host[i] = float4{0.f, 0.f, 0.f, 0.f}; std::memcpy(&host[i], base + i * stride_bytes, 12); }
-    float4* d_pts = nullptr;
-    LOCGPU_HIP(ctx, hipMalloc((void**)&d_pts, n * sizeof(float4)));
-    if (!hip_ok(ctx, hipMemcpy(d_pts, host.data(), n * sizeof(float4), hipMemcpyHostToDevice), "H2D map")) { (void)hipFree(d_pts); return LOCGPU_ERR_NO_DEVICE; }
+    DevBuf<float4> d_pts;
+    LOCGPU_HIP(ctx, d_pts.alloc(n));
+    if (!hip_ok(ctx, hipMemcpy(d_pts, host.data(), n * sizeof(float4), hipMemcpyHostToDevice), "H2D map")) return LOCGPU_ERR_NO_DEVICE;
     const int rc = ndt_set_target_dev(ctx, d_pts, host.data(), n, opts);
     (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_pts);
     return rc;
 }
 

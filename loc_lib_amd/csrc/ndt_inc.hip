@@ -31,6 +31,7 @@
 // align: AlignIncNdt differs from the direct variant: sums ARE info-weighted (H += Jᵀ·info·J, err += −Jᵀ·info·e, :345-346),
 // effective_num counts accepted (point, voxel) pairs (:343), too few ⇒ `return false` with result = current pose (:349-353), and
 // there is no det(H) test.
+#include "device_buffer.hpp"
 #include "device_prims.hpp"
 #include "env.hpp"
 
@@ -346,46 +347,29 @@ struct IncNdtState {
     int n_slots = 0;  // slots ever handed out: [0, n_slots)
     int n_live = 0;   // voxels alive
     int n_free = 0;   // entries on the free stack
-    // per slot
-    unsigned long long *d_slot_key = nullptr, *d_slot_stamp = nullptr;
-    double *d_mu = nullptr, *d_info = nullptr;
-    int* d_free = nullptr;
-    size_t slot_cap = 0;
+    // per slot; d_free, grown last, has the capacity of all five
+    DevBuf<unsigned long long> d_slot_key, d_slot_stamp;
+    DevBuf<double> d_mu, d_info;
+    DevBuf<int> d_free;
     // key → slot table for the align kernel
-    unsigned long long* d_keys = nullptr;
-    int* d_vid = nullptr;
+    DevBuf<unsigned long long> d_keys;
+    DevBuf<int> d_vid;
     size_t table_cap = 0;
     // per-call scratch, by points (pt_cap) — also holds the per-voxel arrays (a call has at most n voxels)
-    unsigned long long *d_pkey = nullptr, *d_skey = nullptr, *d_ukey = nullptr;
-    uint32_t *d_pidx = nullptr, *d_sidx = nullptr, *d_ustart = nullptr;
-    int *d_head = nullptr, *d_uid = nullptr, *d_uslot = nullptr, *d_unew = nullptr, *d_urank = nullptr;
-    float4* d_psorted = nullptr;
-    unsigned char* d_keep = nullptr;
+    DevBuf<unsigned long long> d_pkey, d_skey, d_ukey;
+    DevBuf<uint32_t> d_pidx, d_sidx, d_ustart;
+    DevBuf<int> d_head, d_uid, d_uslot, d_unew, d_urank;
+    DevBuf<float4> d_psorted;
+    DevBuf<unsigned char> d_keep;
     size_t pt_cap = 0;
     // eviction scratch, by slots (ev_cap)
-    unsigned long long *d_ev_stamp = nullptr, *d_ev_stamp_sorted = nullptr;
-    int *d_ev_slot = nullptr, *d_ev_slot_sorted = nullptr;
+    DevBuf<unsigned long long> d_ev_stamp, d_ev_stamp_sorted;
+    DevBuf<int> d_ev_slot, d_ev_slot_sorted;
     size_t ev_cap = 0;
-    void* d_temp = nullptr;  // scratch of the device-wide primitives
-    size_t temp_bytes = 0;
-    int *d_ctr = nullptr, *h_ctr = nullptr;  // kIncCtrs counters, device + pinned
+    DevBuf<unsigned char> d_temp;  // scratch of the device-wide primitives
+    DevBuf<int> d_ctr;  // kIncCtrs counters, device + pinned
+    PinnedBuf<int> h_ctr;
 };
-
-#define INC_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
-
-template <typename T>
-static hipError_t regrow(T*& p, size_t old_count, size_t new_count, bool keep, hipStream_t s) {
-    T* q = nullptr;
-    INC_TRY(hipMalloc((void**)&q, new_count * sizeof(T)));
-    if (keep && p && old_count) {
-        const hipError_t e = hipMemcpyAsync(q, p, old_count * sizeof(T), hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) { (void)hipFree(q); return e; }
-        INC_TRY(hipStreamSynchronize(s));
-    }
-    if (p) (void)hipFree(p);
-    p = q;
-    return hipSuccess;
-}
 
 static size_t grown(size_t have, size_t need, size_t floor_) {
     size_t cap = have ? have : floor_;
@@ -394,52 +378,44 @@ static size_t grown(size_t have, size_t need, size_t floor_) {
 }
 
 static hipError_t ensure_temp(IncNdtState& st, size_t bytes) {
-    if (bytes <= st.temp_bytes) return hipSuccess;
-    if (st.d_temp) (void)hipFree(st.d_temp);
-    st.d_temp = nullptr; st.temp_bytes = 0;
-    INC_TRY(hipMalloc(&st.d_temp, bytes + 256));
-    st.temp_bytes = bytes + 256;
-    return hipSuccess;
+    return bytes <= st.d_temp.cap() ? hipSuccess : st.d_temp.alloc(bytes + 256);
 }
 
 // room for `need` slots (μ/info/keys/stamps of the slots in use are kept)
 static hipError_t ensure_slots(IncNdtState& st, size_t need, hipStream_t s) {
-    if (need <= st.slot_cap) return hipSuccess;
-    const size_t cap = grown(st.slot_cap, need, 4096), old = (size_t)st.n_slots;
-    INC_TRY(regrow(st.d_slot_key, old, cap, true, s));
-    INC_TRY(regrow(st.d_slot_stamp, old, cap, true, s));
-    INC_TRY(regrow(st.d_mu, 3 * old, 3 * cap, true, s));
-    INC_TRY(regrow(st.d_info, 9 * old, 9 * cap, true, s));
-    INC_TRY(regrow(st.d_free, (size_t)st.n_free, cap, true, s));
-    st.slot_cap = cap;
+    if (need <= st.d_free.cap()) return hipSuccess;
+    const size_t cap = grown(st.d_free.cap(), need, 4096), old = (size_t)st.n_slots;
+    LOCGPU_TRY(st.d_slot_key.grow_keep(cap, old, s));
+    LOCGPU_TRY(st.d_slot_stamp.grow_keep(cap, old, s));
+    LOCGPU_TRY(st.d_mu.grow_keep(3 * cap, 3 * old, s));
+    LOCGPU_TRY(st.d_info.grow_keep(9 * cap, 9 * old, s));
+    LOCGPU_TRY(st.d_free.grow_keep(cap, (size_t)st.n_free, s));
     return hipSuccess;
 }
 
 static hipError_t ensure_points(IncNdtState& st, size_t n, hipStream_t s) {
-    if (!st.d_ctr) {
-        INC_TRY(hipMalloc((void**)&st.d_ctr, kIncCtrs * sizeof(int)));
-        INC_TRY(hipHostMalloc((void**)&st.h_ctr, kIncCtrs * sizeof(int)));
-    }
+    LOCGPU_TRY(st.d_ctr.reserve(kIncCtrs));
+    LOCGPU_TRY(st.h_ctr.reserve(kIncCtrs));
     if (!st.table_cap) {  // an empty table, so that the first call's look-ups run like every other call's
         const size_t cap = 1024;
-        INC_TRY(hipMalloc((void**)&st.d_keys, cap * sizeof(unsigned long long)));
-        INC_TRY(hipMalloc((void**)&st.d_vid, cap * sizeof(int)));
+        LOCGPU_TRY(st.d_keys.alloc(cap));
+        LOCGPU_TRY(st.d_vid.alloc(cap));
         st.table_cap = cap;
         hipLaunchKernelGGL(inc_fill_kernel, dim3((unsigned)(cap / kBlock)), dim3(kBlock), 0, s, st.d_keys, cap, kNdtEmpty);
-        INC_TRY(hipMemsetAsync(st.d_vid, 0xFF, cap * sizeof(int), s));
+        LOCGPU_TRY(hipMemsetAsync(st.d_vid, 0xFF, cap * sizeof(int), s));
     }
     if (n + 1 > st.pt_cap) {
         const size_t cap = grown(st.pt_cap, n + 1, 16384);
-        INC_TRY(regrow(st.d_pkey, 0, cap, false, s)); INC_TRY(regrow(st.d_skey, 0, cap, false, s)); INC_TRY(regrow(st.d_ukey, 0, cap, false, s));
-        INC_TRY(regrow(st.d_pidx, 0, cap, false, s)); INC_TRY(regrow(st.d_sidx, 0, cap, false, s)); INC_TRY(regrow(st.d_ustart, 0, cap, false, s));
-        INC_TRY(regrow(st.d_head, 0, cap, false, s)); INC_TRY(regrow(st.d_uid, 0, cap, false, s)); INC_TRY(regrow(st.d_uslot, 0, cap, false, s));
-        INC_TRY(regrow(st.d_unew, 0, cap, false, s)); INC_TRY(regrow(st.d_urank, 0, cap, false, s));
-        INC_TRY(regrow(st.d_psorted, 0, cap, false, s)); INC_TRY(regrow(st.d_keep, 0, cap, false, s));
+        LOCGPU_TRY(st.d_pkey.alloc(cap)); LOCGPU_TRY(st.d_skey.alloc(cap)); LOCGPU_TRY(st.d_ukey.alloc(cap));
+        LOCGPU_TRY(st.d_pidx.alloc(cap)); LOCGPU_TRY(st.d_sidx.alloc(cap)); LOCGPU_TRY(st.d_ustart.alloc(cap));
+        LOCGPU_TRY(st.d_head.alloc(cap)); LOCGPU_TRY(st.d_uid.alloc(cap)); LOCGPU_TRY(st.d_uslot.alloc(cap));
+        LOCGPU_TRY(st.d_unew.alloc(cap)); LOCGPU_TRY(st.d_urank.alloc(cap));
+        LOCGPU_TRY(st.d_psorted.alloc(cap)); LOCGPU_TRY(st.d_keep.alloc(cap));
         st.pt_cap = cap;
         size_t b1 = 0, b2 = 0;
-        INC_TRY(prim::sort_pairs(nullptr, b1, st.d_pkey, st.d_skey, st.d_pidx, st.d_sidx, (int)cap, 0, 64, s));
-        INC_TRY(prim::exclusive_sum(nullptr, b2, st.d_head, st.d_uid, (int)cap, s));
-        INC_TRY(ensure_temp(st, std::max(b1, b2)));
+        LOCGPU_TRY(prim::sort_pairs(nullptr, b1, st.d_pkey.get(), st.d_skey.get(), st.d_pidx.get(), st.d_sidx.get(), (int)cap, 0, 64, s));
+        LOCGPU_TRY(prim::exclusive_sum(nullptr, b2, st.d_head.get(), st.d_uid.get(), (int)cap, s));
+        LOCGPU_TRY(ensure_temp(st, std::max(b1, b2)));
     }
     return hipSuccess;
 }
@@ -447,12 +423,12 @@ static hipError_t ensure_points(IncNdtState& st, size_t n, hipStream_t s) {
 static hipError_t ensure_evict(IncNdtState& st, size_t n_live, hipStream_t s) {
     if (n_live > st.ev_cap) {
         const size_t cap = grown(st.ev_cap, n_live, 4096);
-        INC_TRY(regrow(st.d_ev_stamp, 0, cap, false, s)); INC_TRY(regrow(st.d_ev_stamp_sorted, 0, cap, false, s));
-        INC_TRY(regrow(st.d_ev_slot, 0, cap, false, s)); INC_TRY(regrow(st.d_ev_slot_sorted, 0, cap, false, s));
+        LOCGPU_TRY(st.d_ev_stamp.alloc(cap)); LOCGPU_TRY(st.d_ev_stamp_sorted.alloc(cap));
+        LOCGPU_TRY(st.d_ev_slot.alloc(cap)); LOCGPU_TRY(st.d_ev_slot_sorted.alloc(cap));
         st.ev_cap = cap;
         size_t b = 0;
-        INC_TRY(prim::sort_pairs(nullptr, b, st.d_ev_stamp, st.d_ev_stamp_sorted, st.d_ev_slot, st.d_ev_slot_sorted, (int)cap, 0, 64, s));
-        INC_TRY(ensure_temp(st, b));
+        LOCGPU_TRY(prim::sort_pairs(nullptr, b, st.d_ev_stamp.get(), st.d_ev_stamp_sorted.get(), st.d_ev_slot.get(), st.d_ev_slot_sorted.get(), (int)cap, 0, 64, s));
+        LOCGPU_TRY(ensure_temp(st, b));
     }
     return hipSuccess;
 }
@@ -464,15 +440,7 @@ IncNdtState* inc_ndt_create(size_t capacity, double voxel_size) {
     return st;
 }
 
-void inc_ndt_destroy(IncNdtState* st) {
-    if (!st) return;
-    void* dev[] = {st->d_slot_key, st->d_slot_stamp, st->d_mu, st->d_info, st->d_free, st->d_keys, st->d_vid, st->d_pkey, st->d_skey, st->d_ukey, st->d_pidx,
-                   st->d_sidx, st->d_ustart, st->d_head, st->d_uid, st->d_uslot, st->d_unew, st->d_urank, st->d_psorted, st->d_keep, st->d_ev_stamp,
-                   st->d_ev_stamp_sorted, st->d_ev_slot, st->d_ev_slot_sorted, st->d_temp, st->d_ctr};
-    for (void* p : dev) if (p) (void)hipFree(p);
-    if (st->h_ctr) (void)hipHostFree(st->h_ctr);
-    delete st;
-}
+void inc_ndt_destroy(IncNdtState* st) { delete st; }
 
 size_t inc_ndt_num_voxels(const IncNdtState* st) { return st ? (size_t)st->n_live : 0; }
 
@@ -480,18 +448,18 @@ static unsigned grid_for(size_t n) { return (unsigned)((std::max<size_t>(n, 1) +
 
 // keys → sort → runs → look-ups; returns with h_ctr read back (one synchronisation)
 static hipError_t sort_and_look_up(IncNdtState& st, const float4* d_pts, size_t n, bool masked, hipStream_t s) {
-    INC_TRY(hipMemsetAsync(st.d_ctr, 0, kIncCtrs * sizeof(int), s));
+    LOCGPU_TRY(hipMemsetAsync(st.d_ctr, 0, kIncCtrs * sizeof(int), s));
     hipLaunchKernelGGL(inc_key_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, d_pts, n, st.inv_voxel, masked ? st.d_keep : nullptr, st.d_pkey, st.d_pidx, st.d_ctr);
-    size_t tb = st.temp_bytes;
-    INC_TRY(prim::sort_pairs(st.d_temp, tb, st.d_pkey, st.d_skey, st.d_pidx, st.d_sidx, (int)n, 0, 64, s));  // stable: a voxel's points keep their input order
+    size_t tb = st.d_temp.cap();
+    LOCGPU_TRY(prim::sort_pairs(st.d_temp, tb, st.d_pkey.get(), st.d_skey.get(), st.d_pidx.get(), st.d_sidx.get(), (int)n, 0, 64, s));  // stable: a voxel's points keep their input order
     hipLaunchKernelGGL(inc_head_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, st.d_skey, n, st.d_head);
-    tb = st.temp_bytes;
-    INC_TRY(prim::exclusive_sum(st.d_temp, tb, st.d_head, st.d_uid, (int)n, s));
+    tb = st.d_temp.cap();
+    LOCGPU_TRY(prim::exclusive_sum(st.d_temp, tb, st.d_head.get(), st.d_uid.get(), (int)n, s));
     hipLaunchKernelGGL(inc_runs_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, st.d_skey, st.d_sidx, st.d_head, st.d_uid, n, d_pts, st.d_ukey, st.d_ustart, st.d_psorted, st.d_ctr);
     hipLaunchKernelGGL(inc_lookup_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, st.d_ukey, st.d_ctr, st.d_keys, st.d_vid, st.table_cap - 1, st.d_uslot, st.d_unew, st.d_ctr);
-    INC_TRY(hipGetLastError());
-    INC_TRY(hipMemcpyAsync(st.h_ctr, st.d_ctr, kIncCtrs * sizeof(int), hipMemcpyDeviceToHost, s));
-    INC_TRY(hipStreamSynchronize(s));
+    LOCGPU_TRY(hipGetLastError());
+    LOCGPU_TRY(hipMemcpyAsync(st.h_ctr, st.d_ctr, kIncCtrs * sizeof(int), hipMemcpyDeviceToHost, s));
+    LOCGPU_TRY(hipStreamSynchronize(s));
     return hipSuccess;
 }
 
@@ -500,18 +468,16 @@ static hipError_t rebuild_table_and_stats(IncNdtState& st, int m, hipStream_t s)
     size_t cap = 1024;
     while (cap < 2 * (size_t)std::max(st.n_live, 1)) cap <<= 1;
     if (cap > st.table_cap) {  // grows only
-        if (st.d_keys) (void)hipFree(st.d_keys);
-        if (st.d_vid) (void)hipFree(st.d_vid);
-        st.d_keys = nullptr; st.d_vid = nullptr; st.table_cap = 0;
-        INC_TRY(hipMalloc((void**)&st.d_keys, cap * sizeof(unsigned long long)));
-        INC_TRY(hipMalloc((void**)&st.d_vid, cap * sizeof(int)));
+        st.d_keys.reset(); st.d_vid.reset(); st.table_cap = 0;
+        LOCGPU_TRY(st.d_keys.alloc(cap));
+        LOCGPU_TRY(st.d_vid.alloc(cap));
         st.table_cap = cap;
     }
     hipLaunchKernelGGL(inc_fill_kernel, dim3(grid_for(st.table_cap)), dim3(kBlock), 0, s, st.d_keys, st.table_cap, kNdtEmpty);
-    INC_TRY(hipMemsetAsync(st.d_vid, 0xFF, st.table_cap * sizeof(int), s));
+    LOCGPU_TRY(hipMemsetAsync(st.d_vid, 0xFF, st.table_cap * sizeof(int), s));
     hipLaunchKernelGGL(inc_table_kernel, dim3(grid_for((size_t)st.n_slots)), dim3(kBlock), 0, s, st.d_slot_key, st.n_slots, st.d_keys, st.d_vid, st.table_cap - 1);
     if (m > 0) hipLaunchKernelGGL(inc_stats_kernel, dim3(grid_for((size_t)m)), dim3(kBlock), 0, s, st.d_psorted, st.d_ustart, st.d_uslot, m, st.d_mu, st.d_info);
-    INC_TRY(hipGetLastError());
+    LOCGPU_TRY(hipGetLastError());
     return hipStreamSynchronize(s);
 }
 
@@ -520,19 +486,19 @@ static hipError_t ingest_replayed(IncNdtState& st, const float4* host_pts, const
     std::vector<float4> fetched;
     if (!host_pts) {
         fetched.resize(n);
-        INC_TRY(hipMemcpyAsync(fetched.data(), d_pts, n * sizeof(float4), hipMemcpyDeviceToHost, s));
-        INC_TRY(hipStreamSynchronize(s));
+        LOCGPU_TRY(hipMemcpyAsync(fetched.data(), d_pts, n * sizeof(float4), hipMemcpyDeviceToHost, s));
+        LOCGPU_TRY(hipStreamSynchronize(s));
         host_pts = fetched.data();
     }
     const size_t ns = (size_t)st.n_slots;
     std::vector<unsigned long long> h_key(ns), h_stamp(ns);
     std::vector<int> free_slots((size_t)st.n_free);
     if (ns) {
-        INC_TRY(hipMemcpyAsync(h_key.data(), st.d_slot_key, ns * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-        INC_TRY(hipMemcpyAsync(h_stamp.data(), st.d_slot_stamp, ns * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        LOCGPU_TRY(hipMemcpyAsync(h_key.data(), st.d_slot_key, ns * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        LOCGPU_TRY(hipMemcpyAsync(h_stamp.data(), st.d_slot_stamp, ns * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     }
-    if (st.n_free) INC_TRY(hipMemcpyAsync(free_slots.data(), st.d_free, (size_t)st.n_free * sizeof(int), hipMemcpyDeviceToHost, s));
-    INC_TRY(hipStreamSynchronize(s));
+    if (st.n_free) LOCGPU_TRY(hipMemcpyAsync(free_slots.data(), st.d_free, (size_t)st.n_free * sizeof(int), hipMemcpyDeviceToHost, s));
+    LOCGPU_TRY(hipStreamSynchronize(s));
     std::vector<IncLive> live;
     live.reserve((size_t)st.n_live);
     for (size_t sl = 0; sl < ns; ++sl)
@@ -548,7 +514,7 @@ static hipError_t ingest_replayed(IncNdtState& st, const float4* host_pts, const
     std::vector<unsigned char> keep;
     int n_slots = st.n_slots;
     inc_lru_replay(live, free_slots, n_slots, st.capacity, st.epoch, keys.data(), n, keep);
-    INC_TRY(ensure_slots(st, (size_t)std::max(n_slots, 1), s));
+    LOCGPU_TRY(ensure_slots(st, (size_t)std::max(n_slots, 1), s));
     st.n_slots = n_slots;
     st.n_live = (int)live.size();
     st.n_free = (int)free_slots.size();
@@ -556,19 +522,19 @@ static hipError_t ingest_replayed(IncNdtState& st, const float4* host_pts, const
     h_stamp.assign((size_t)n_slots, 0ull);
     for (const IncLive& v : live) { h_key[(size_t)v.slot] = v.key; h_stamp[(size_t)v.slot] = v.stamp; }
     if (n_slots) {
-        INC_TRY(hipMemcpyAsync(st.d_slot_key, h_key.data(), (size_t)n_slots * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
-        INC_TRY(hipMemcpyAsync(st.d_slot_stamp, h_stamp.data(), (size_t)n_slots * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+        LOCGPU_TRY(hipMemcpyAsync(st.d_slot_key, h_key.data(), (size_t)n_slots * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+        LOCGPU_TRY(hipMemcpyAsync(st.d_slot_stamp, h_stamp.data(), (size_t)n_slots * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
     }
-    if (st.n_free) INC_TRY(hipMemcpyAsync(st.d_free, free_slots.data(), (size_t)st.n_free * sizeof(int), hipMemcpyHostToDevice, s));
-    INC_TRY(hipMemcpyAsync(st.d_keep, keep.data(), n, hipMemcpyHostToDevice, s));
-    INC_TRY(hipStreamSynchronize(s));  // the vectors above are pageable: nothing may still be reading them when they go out of scope
+    if (st.n_free) LOCGPU_TRY(hipMemcpyAsync(st.d_free, free_slots.data(), (size_t)st.n_free * sizeof(int), hipMemcpyHostToDevice, s));
+    LOCGPU_TRY(hipMemcpyAsync(st.d_keep, keep.data(), n, hipMemcpyHostToDevice, s));
+    LOCGPU_TRY(hipStreamSynchronize(s));  // the vectors above are pageable: nothing may still be reading them when they go out of scope
     // the device finishes from the replayed state: table of the new voxel set, then the surviving points by voxel
-    INC_TRY(rebuild_table_and_stats(st, 0, s));
-    INC_TRY(sort_and_look_up(st, d_pts, n, true, s));
+    LOCGPU_TRY(rebuild_table_and_stats(st, 0, s));
+    LOCGPU_TRY(sort_and_look_up(st, d_pts, n, true, s));
     const int m = st.h_ctr[0] - st.h_ctr[3];
     if (st.h_ctr[2] != 0) return hipErrorUnknown;  // every surviving point's voxel is in the replayed set
     if (m > 0) hipLaunchKernelGGL(inc_stats_kernel, dim3(grid_for((size_t)m)), dim3(kBlock), 0, s, st.d_psorted, st.d_ustart, st.d_uslot, m, st.d_mu, st.d_info);
-    INC_TRY(hipGetLastError());
+    LOCGPU_TRY(hipGetLastError());
     return hipStreamSynchronize(s);
 }
 
@@ -579,8 +545,8 @@ hipError_t inc_ndt_ingest(IncNdtState& st, const float4* host_pts, const float4*
     if (n > 0x7FFFFFF0ull) return hipErrorInvalidValue;
     st.epoch++;
     const unsigned long long epoch_hi = (unsigned long long)st.epoch << 32;
-    INC_TRY(ensure_points(st, n, s));
-    INC_TRY(sort_and_look_up(st, d_pts, n, false, s));
+    LOCGPU_TRY(ensure_points(st, n, s));
+    LOCGPU_TRY(sort_and_look_up(st, d_pts, n, false, s));
     *bad_key = st.h_ctr[1] != 0;
     const int m = st.h_ctr[0] - st.h_ctr[3];                   // distinct voxels the cloud touches
     const int m_new = st.h_ctr[2];                             // … of which not alive yet
@@ -593,22 +559,22 @@ hipError_t inc_ndt_ingest(IncNdtState& st, const float4* host_pts, const float4*
     if (n_evict < 0) return ingest_replayed(st, host_pts, d_pts, n, s);
     const int n_free_after_evict = st.n_free + n_evict;
     const int n_fresh = std::max(0, m_new - n_free_after_evict);
-    INC_TRY(ensure_slots(st, (size_t)(st.n_slots + n_fresh), s));
+    LOCGPU_TRY(ensure_slots(st, (size_t)(st.n_slots + n_fresh), s));
     hipLaunchKernelGGL(inc_touch_kernel, dim3(grid_for((size_t)m)), dim3(kBlock), 0, s, st.d_uslot, st.d_ustart, st.d_sidx, m, epoch_hi, st.d_slot_stamp);
     if (n_evict > 0) {
-        INC_TRY(ensure_evict(st, (size_t)st.n_live, s));
+        LOCGPU_TRY(ensure_evict(st, (size_t)st.n_live, s));
         hipLaunchKernelGGL(inc_collect_kernel, dim3(grid_for((size_t)st.n_slots)), dim3(kBlock), 0, s, st.d_slot_key, st.d_slot_stamp, st.n_slots, st.d_ev_stamp, st.d_ev_slot, st.d_ctr);
-        size_t tb = st.temp_bytes;
-        INC_TRY(prim::sort_pairs(st.d_temp, tb, st.d_ev_stamp, st.d_ev_stamp_sorted, st.d_ev_slot, st.d_ev_slot_sorted, st.n_live, 0, 64, s));
+        size_t tb = st.d_temp.cap();
+        LOCGPU_TRY(prim::sort_pairs(st.d_temp, tb, st.d_ev_stamp.get(), st.d_ev_stamp_sorted.get(), st.d_ev_slot.get(), st.d_ev_slot_sorted.get(), st.n_live, 0, 64, s));
         hipLaunchKernelGGL(inc_evict_kernel, dim3(grid_for((size_t)n_evict)), dim3(kBlock), 0, s, st.d_ev_slot_sorted, n_evict, st.n_free, st.d_slot_key, st.d_free);
     }
     if (m_new > 0) {
-        size_t tb = st.temp_bytes;
-        INC_TRY(prim::exclusive_sum(st.d_temp, tb, st.d_unew, st.d_urank, m, s));
+        size_t tb = st.d_temp.cap();
+        LOCGPU_TRY(prim::exclusive_sum(st.d_temp, tb, st.d_unew.get(), st.d_urank.get(), m, s));
         hipLaunchKernelGGL(inc_assign_kernel, dim3(grid_for((size_t)m)), dim3(kBlock), 0, s, st.d_ukey, st.d_unew, st.d_urank, st.d_ustart, st.d_sidx, m, st.d_free,
                            n_free_after_evict, st.n_slots, epoch_hi, st.d_slot_key, st.d_slot_stamp, st.d_uslot);
     }
-    INC_TRY(hipGetLastError());
+    LOCGPU_TRY(hipGetLastError());
     st.n_free = std::max(0, n_free_after_evict - m_new);
     st.n_slots += n_fresh;
     st.n_live += m_new - n_evict;

@@ -145,54 +145,42 @@ __global__ __launch_bounds__(kBlock) void ndt_dump_kernel(const NdtRecord* __res
     for (int k = 0; k < 9; ++k) info[9 * o + k] = R.info[k];
 }
 
-void ndt_table_free(NdtTable& t) {
-    if (t.d_slots) (void)hipFree(t.d_slots);
-    if (t.d_rec) (void)hipFree(t.d_rec);
-    t = NdtTable();
-}
-
-#define NDT_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return e_; } } while (0)
-
 hipError_t ndt_build(NdtTable& t, const float4* d_pts, size_t n, double voxel_size, int min_pts_in_voxel, hipStream_t s, bool* bad_key) {
-    ndt_table_free(t);
+    t = NdtTable();
     *bad_key = false;
     t.inv_voxel = 1.0 / voxel_size;  // the reference's constructors recompute it (ndt cpp:15,25)
-    unsigned long long *d_pkey = nullptr, *d_skey = nullptr;
-    uint32_t *d_pidx = nullptr, *d_sidx = nullptr, *d_ustart = nullptr;
-    int *d_head = nullptr, *d_uid = nullptr, *d_scalar = nullptr;  // scalars: [0] runs, [1] bad key, [2] voxels kept
-    float4* d_psorted = nullptr;
-    void* d_temp = nullptr;
-    auto cleanup = [&]() {
-        for (void* p : {(void*)d_pkey, (void*)d_skey, (void*)d_pidx, (void*)d_sidx, (void*)d_ustart, (void*)d_head, (void*)d_uid, (void*)d_scalar, (void*)d_psorted, d_temp})
-            if (p) (void)hipFree(p);
-    };
+    DevBuf<unsigned long long> d_pkey, d_skey;
+    DevBuf<uint32_t> d_pidx, d_sidx, d_ustart;
+    DevBuf<int> d_head, d_uid, d_scalar;  // scalars: [0] runs, [1] bad key, [2] voxels kept
+    DevBuf<float4> d_psorted;
+    DevBuf<unsigned char> d_temp;
     if (n > 0xFFFFFFF0ull) return hipErrorInvalidValue;
-    NDT_TRY(hipMalloc((void**)&d_pkey, n * sizeof(unsigned long long)));
-    NDT_TRY(hipMalloc((void**)&d_skey, n * sizeof(unsigned long long)));
-    NDT_TRY(hipMalloc((void**)&d_pidx, n * sizeof(uint32_t)));
-    NDT_TRY(hipMalloc((void**)&d_sidx, n * sizeof(uint32_t)));
-    NDT_TRY(hipMalloc((void**)&d_ustart, (n + 1) * sizeof(uint32_t)));
-    NDT_TRY(hipMalloc((void**)&d_head, n * sizeof(int)));
-    NDT_TRY(hipMalloc((void**)&d_uid, n * sizeof(int)));
-    NDT_TRY(hipMalloc((void**)&d_psorted, n * sizeof(float4)));
-    NDT_TRY(hipMalloc((void**)&d_scalar, 4 * sizeof(int)));
-    NDT_TRY(hipMemsetAsync(d_scalar, 0, 4 * sizeof(int), s));
+    LOCGPU_TRY(d_pkey.alloc(n));
+    LOCGPU_TRY(d_skey.alloc(n));
+    LOCGPU_TRY(d_pidx.alloc(n));
+    LOCGPU_TRY(d_sidx.alloc(n));
+    LOCGPU_TRY(d_ustart.alloc((n + 1)));
+    LOCGPU_TRY(d_head.alloc(n));
+    LOCGPU_TRY(d_uid.alloc(n));
+    LOCGPU_TRY(d_psorted.alloc(n));
+    LOCGPU_TRY(d_scalar.alloc(4));
+    LOCGPU_TRY(hipMemsetAsync(d_scalar, 0, 4 * sizeof(int), s));
     size_t b1 = 0, b2 = 0;
-    NDT_TRY(prim::sort_pairs(nullptr, b1, d_pkey, d_skey, d_pidx, d_sidx, n, 0, 64, s));
-    NDT_TRY(prim::exclusive_sum(nullptr, b2, d_head, d_uid, n, s));
+    LOCGPU_TRY(prim::sort_pairs(nullptr, b1, d_pkey.get(), d_skey.get(), d_pidx.get(), d_sidx.get(), n, 0, 64, s));
+    LOCGPU_TRY(prim::exclusive_sum(nullptr, b2, d_head.get(), d_uid.get(), n, s));
     size_t tb = std::max(b1, b2);
-    NDT_TRY(hipMalloc(&d_temp, std::max<size_t>(tb, 16)));
+    LOCGPU_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
     const unsigned gn = (unsigned)((n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(ndt_key_kernel, dim3(gn), dim3(kBlock), 0, s, d_pts, n, t.inv_voxel, d_pkey, d_pidx, d_scalar + 1);
+    hipLaunchKernelGGL(ndt_key_kernel, dim3(gn), dim3(kBlock), 0, s, d_pts, n, t.inv_voxel, d_pkey, d_pidx, d_scalar.get() + 1);
     tb = b1;
-    NDT_TRY(prim::sort_pairs(d_temp, tb, d_pkey, d_skey, d_pidx, d_sidx, n, 0, 64, s));  // stable: a voxel's points keep their input order
+    LOCGPU_TRY(prim::sort_pairs(d_temp, tb, d_pkey.get(), d_skey.get(), d_pidx.get(), d_sidx.get(), n, 0, 64, s));  // stable: a voxel's points keep their input order
     hipLaunchKernelGGL(ndt_head_kernel, dim3(gn), dim3(kBlock), 0, s, d_skey, n, d_head);
     tb = b2;
-    NDT_TRY(prim::exclusive_sum(d_temp, tb, d_head, d_uid, n, s));
+    LOCGPU_TRY(prim::exclusive_sum(d_temp, tb, d_head.get(), d_uid.get(), n, s));
     hipLaunchKernelGGL(ndt_runs_kernel, dim3(gn), dim3(kBlock), 0, s, d_sidx, d_head, d_uid, n, d_pts, d_ustart, d_psorted, d_scalar);
     int h_scalar[4] = {0, 0, 0, 0};
-    NDT_TRY(hipMemcpyAsync(h_scalar, d_scalar, sizeof(h_scalar), hipMemcpyDeviceToHost, s));
-    NDT_TRY(hipStreamSynchronize(s));
+    LOCGPU_TRY(hipMemcpyAsync(h_scalar, d_scalar, sizeof(h_scalar), hipMemcpyDeviceToHost, s));
+    LOCGPU_TRY(hipStreamSynchronize(s));
     *bad_key = h_scalar[1] != 0;
     const size_t runs = (size_t)h_scalar[0];
     // A SPARSE table: at load 0.03 nearly every look-up — hit or miss — ends at its first probe, and a collision walk is what costs
@@ -201,37 +189,34 @@ hipError_t ndt_build(NdtTable& t, const float4* d_pts, size_t n, double voxel_si
     size_t cap = 1024;
     while (cap < 32 * runs && cap < ((size_t)1 << 26)) cap <<= 1;  // at most 1 GB of slots ...
     while (cap < 2 * runs) cap <<= 1;                              // ... but never above load 0.5
-    NDT_TRY(hipMalloc((void**)&t.d_slots, cap * sizeof(NdtSlot)));
-    NDT_TRY(hipMalloc((void**)&t.d_rec, std::max<size_t>(runs, 1) * sizeof(NdtRecord)));  // room for every run; the kept voxels fill a prefix
+    LOCGPU_TRY(t.d_slots.alloc(cap));
+    LOCGPU_TRY(t.d_rec.alloc(std::max<size_t>(runs, 1)));  // room for every run; the kept voxels fill a prefix
     t.cap = cap;
     hipLaunchKernelGGL(ndt_clear_kernel, dim3((unsigned)((cap + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, t.d_slots, cap);
-    NDT_TRY(hipMemsetAsync(t.d_rec, 0, std::max<size_t>(runs, 1) * sizeof(NdtRecord), s));  // record 0 is read for voxels that are not there: finite numbers, never accepted
+    LOCGPU_TRY(hipMemsetAsync(t.d_rec, 0, std::max<size_t>(runs, 1) * sizeof(NdtRecord), s));  // record 0 is read for voxels that are not there: finite numbers, never accepted
     if (runs > 0 && !*bad_key)
         hipLaunchKernelGGL(ndt_voxel_kernel, dim3((unsigned)((runs + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, d_skey, d_psorted, d_ustart, d_scalar, min_pts_in_voxel, t.d_slots,
-                           t.d_rec, cap - 1, d_scalar + 2);
-    NDT_TRY(hipGetLastError());
-    NDT_TRY(hipMemcpyAsync(h_scalar, d_scalar, sizeof(h_scalar), hipMemcpyDeviceToHost, s));
-    NDT_TRY(hipStreamSynchronize(s));
+                           t.d_rec, cap - 1, d_scalar.get() + 2);
+    LOCGPU_TRY(hipGetLastError());
+    LOCGPU_TRY(hipMemcpyAsync(h_scalar, d_scalar, sizeof(h_scalar), hipMemcpyDeviceToHost, s));
+    LOCGPU_TRY(hipStreamSynchronize(s));
     t.n_vox = (size_t)h_scalar[2];
-    cleanup();
     return hipSuccess;
 }
 
 hipError_t ndt_dump(const NdtTable& t, int* keys, double* mu, double* info, size_t out_cap, hipStream_t s) {
     const size_t n = std::min(out_cap, t.n_vox);
     if (!t.d_rec || n == 0) return hipSuccess;
-    int* d_keys = nullptr;
-    double *d_mu = nullptr, *d_info = nullptr;
-    auto cleanup = [&]() { for (void* p : {(void*)d_keys, (void*)d_mu, (void*)d_info}) if (p) (void)hipFree(p); };
-    NDT_TRY(hipMalloc((void**)&d_keys, n * 3 * sizeof(int)));
-    NDT_TRY(hipMalloc((void**)&d_mu, n * 3 * sizeof(double)));
-    NDT_TRY(hipMalloc((void**)&d_info, n * 9 * sizeof(double)));
+    DevBuf<int> d_keys;
+    DevBuf<double> d_mu, d_info;
+    LOCGPU_TRY(d_keys.alloc(n * 3));
+    LOCGPU_TRY(d_mu.alloc(n * 3));
+    LOCGPU_TRY(d_info.alloc(n * 9));
     hipLaunchKernelGGL(ndt_dump_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, t.d_rec, n, d_keys, d_mu, d_info);
-    if (keys) NDT_TRY(hipMemcpyAsync(keys, d_keys, n * 3 * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (mu) NDT_TRY(hipMemcpyAsync(mu, d_mu, n * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (info) NDT_TRY(hipMemcpyAsync(info, d_info, n * 9 * sizeof(double), hipMemcpyDeviceToHost, s));
-    NDT_TRY(hipStreamSynchronize(s));
-    cleanup();
+    if (keys) LOCGPU_TRY(hipMemcpyAsync(keys, d_keys, n * 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (mu) LOCGPU_TRY(hipMemcpyAsync(mu, d_mu, n * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (info) LOCGPU_TRY(hipMemcpyAsync(info, d_info, n * 9 * sizeof(double), hipMemcpyDeviceToHost, s));
+    LOCGPU_TRY(hipStreamSynchronize(s));
     return hipSuccess;
 }
 

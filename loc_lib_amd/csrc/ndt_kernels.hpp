@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "device_buffer.hpp"
 #include "device_math.hpp"
 
 struct alignas(128) NdtRecord {
@@ -26,8 +27,8 @@ struct alignas(16) NdtSlot {
 };
 
 struct NdtTable {
-    NdtSlot* d_slots = nullptr;  // [cap]
-    NdtRecord* d_rec = nullptr;  // [n_vox (allocated: runs)], dense
+    locgpu::DevBuf<NdtSlot> d_slots;  // [cap]
+    locgpu::DevBuf<NdtRecord> d_rec;  // [n_vox (allocated: runs)], dense
     size_t cap = 0, n_vox = 0;
     double inv_voxel = 1.0;
     double res_outlier_th = 20.0;
@@ -70,7 +71,6 @@ __device__ __forceinline__ void ndt_key_of(const D3& p, double inv, int& kx, int
 // Build (SetDirectNdtTargetCloud, ndt_registration.cpp:87-148). Returns hipError; *bad_key is set when a point falls
 // outside the ±2^20-voxel key range.
 hipError_t ndt_build(NdtTable& t, const float4* d_pts, size_t n, double voxel_size, int min_pts_in_voxel, hipStream_t s, bool* bad_key);
-void ndt_table_free(NdtTable& t);
 // Test read-back: up to out_cap voxels as dense arrays (keys n×3 int32, mu n×3, info n×9), in table order.
 hipError_t ndt_dump(const NdtTable& t, int* keys, double* mu, double* info, size_t out_cap, hipStream_t s);
 

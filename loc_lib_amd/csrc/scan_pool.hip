@@ -77,27 +77,27 @@ struct locgpu_pool {
     bool multi_rank = false;  // ... of more than one rank: nothing may depend on this rank's timing
     bool decoupled = false;   // the owner of a slot solves it ahead of the exchange, which runs on the communication stream
     int regions = 0;                      // source regions in the arena (>= slots)
-    float4* d_arena = nullptr;            // [regions][max_n]
+    DevBuf<float4> d_arena;               // [regions][max_n]
     std::unique_ptr<PoolSched> sched;     // pool_sched.hpp: free slots and regions, which scan sits where, who waits (pure host logic)
-    int* h_src_of = nullptr;              // pinned [slots]: region of the slot's points
-    int* d_src_of = nullptr;
+    PinnedBuf<int> h_src_of;              // pinned [slots]: region of the slot's points
+    DevBuf<int> d_src_of;
     std::map<int64_t, PoolJob*> jobs;     // every job not yet handed back through locgpu_pool_wait
     int64_t next_ticket = 1;
     bool in_flight = false;               // a chunk (and the read-back of the states behind it) is enqueued
     int n_open = 0;                       // admitted scans not finished, as of the last look at the flags
     long long iterations = 0;             // pooled iterations launched so far
     long long scan_iterations = 0;        // Σ over them of the open scans this rank held
-    int* h_list = nullptr;                // pinned [2][slots]: open slots this rank holds | open slots it does not
-    int* d_list = nullptr;
-    int* h_counts = nullptr;              // pinned [slots]
-    unsigned char* h_owned = nullptr;     // pinned [slots]
-    unsigned char* d_owned = nullptr;
-    double* d_acc = nullptr;              // [kAccRing][slots][kAccW] (with a communicator)
-    hipEvent_t ev_ready = nullptr, ev_reduced = nullptr;
+    PinnedBuf<int> h_list;                // pinned [2][slots]: open slots this rank holds | open slots it does not
+    DevBuf<int> d_list;
+    PinnedBuf<int> h_counts;              // pinned [slots]
+    PinnedBuf<unsigned char> h_owned;     // pinned [slots]
+    DevBuf<unsigned char> d_owned;
+    DevBuf<double> d_acc;                 // [kAccRing][slots][kAccW] (with a communicator)
+    Event ev_ready, ev_reduced;
     int n_mine = 0, n_theirs = 0;         // lengths of the two lists of the chunk in flight
     int acc_slot = 0;
     // measurement (locgpu_profile_enable on the context): device time of the chunks, HIP events on the pool's stream
-    hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
+    Event ev_t0, ev_t1;
     bool timed = false;
     double chunk_ms = 0.0;
     long long chunks = 0;
@@ -113,7 +113,6 @@ void job_free(PoolJob* j) {
     if (!j) return;
     for (auto& u : j->upl) {
         if (u->done_valid && u->done) (void)hipEventSynchronize(u->done);
-        if (u->done) (void)hipEventDestroy(u->done);
     }
     delete j;
 }
@@ -324,21 +323,21 @@ int locgpu_pool_create(locgpu_ctx* ctx, const locgpu_pool_opts* o, locgpu_pool**
     if (rc != LOCGPU_OK) { delete P; return rc; }
     const size_t S = (size_t)P->slots;
     // the points live in the arena, not in the storage batch's own source array
-    if (P->b->d_src) { (void)hipFree(P->b->d_src); P->b->d_src = nullptr; }
+    P->b->d_src.reset();
     P->regions = P->slots + (o->prefetch >= 0 ? o->prefetch : P->slots);
-    if (!hip_ok(ctx, hipMalloc((void**)&P->d_arena, (size_t)P->regions * P->b->max_n * sizeof(float4)), "pool: hipMalloc source arena")) { locgpu_pool_destroy(P); return LOCGPU_ERR_OOM; }
-    bool ok = hip_ok(ctx, hipHostMalloc((void**)&P->h_list, 2 * S * sizeof(int)), "pool: hipHostMalloc") &&
-              hip_ok(ctx, hipMalloc((void**)&P->d_list, 2 * S * sizeof(int)), "pool: hipMalloc") &&
-              hip_ok(ctx, hipHostMalloc((void**)&P->h_counts, S * sizeof(int)), "pool: hipHostMalloc") &&
-              hip_ok(ctx, hipHostMalloc((void**)&P->h_owned, S), "pool: hipHostMalloc") &&
-              hip_ok(ctx, hipHostMalloc((void**)&P->h_src_of, S * sizeof(int)), "pool: hipHostMalloc") &&
-              hip_ok(ctx, hipMalloc((void**)&P->d_src_of, S * sizeof(int)), "pool: hipMalloc") &&
-              hip_ok(ctx, hipEventCreate(&P->ev_t0), "pool: hipEventCreate") && hip_ok(ctx, hipEventCreate(&P->ev_t1), "pool: hipEventCreate");
+    if (!hip_ok(ctx, P->d_arena.alloc((size_t)P->regions * P->b->max_n), "pool: hipMalloc source arena")) { locgpu_pool_destroy(P); return LOCGPU_ERR_OOM; }
+    bool ok = hip_ok(ctx, P->h_list.alloc(2 * S), "pool: hipHostMalloc") &&
+              hip_ok(ctx, P->d_list.alloc(2 * S), "pool: hipMalloc") &&
+              hip_ok(ctx, P->h_counts.alloc(S), "pool: hipHostMalloc") &&
+              hip_ok(ctx, P->h_owned.alloc(S), "pool: hipHostMalloc") &&
+              hip_ok(ctx, P->h_src_of.alloc(S), "pool: hipHostMalloc") &&
+              hip_ok(ctx, P->d_src_of.alloc(S), "pool: hipMalloc") &&
+              hip_ok(ctx, P->ev_t0.ensure(hipEventDefault), "pool: hipEventCreate") && hip_ok(ctx, P->ev_t1.ensure(hipEventDefault), "pool: hipEventCreate");
     if (ok && P->with_comm)
-        ok = hip_ok(ctx, hipMalloc((void**)&P->d_owned, S), "pool: hipMalloc") &&
-             hip_ok(ctx, hipMalloc((void**)&P->d_acc, (size_t)kAccRing * S * kAccW * sizeof(double)), "pool: hipMalloc") &&
-             hip_ok(ctx, hipEventCreateWithFlags(&P->ev_ready, hipEventDisableTiming), "pool: hipEventCreate") &&
-             hip_ok(ctx, hipEventCreateWithFlags(&P->ev_reduced, hipEventDisableTiming), "pool: hipEventCreate");
+        ok = hip_ok(ctx, P->d_owned.alloc(S), "pool: hipMalloc") &&
+             hip_ok(ctx, P->d_acc.alloc((size_t)kAccRing * S * kAccW), "pool: hipMalloc") &&
+             hip_ok(ctx, P->ev_ready.ensure(), "pool: hipEventCreate") &&
+             hip_ok(ctx, P->ev_reduced.ensure(), "pool: hipEventCreate");
     if (!ok) { locgpu_pool_destroy(P); return LOCGPU_ERR_OOM; }
     std::memset(P->h_counts, 0, S * sizeof(int));
     std::memset(P->h_owned, 0, S);
@@ -358,19 +357,6 @@ void locgpu_pool_destroy(locgpu_pool* P) {
     if (P->b) (void)hipStreamSynchronize(P->b->stream);
     if (P->with_comm && ctx->comm_stream) (void)hipStreamSynchronize(ctx->comm_stream);
     for (auto& kv : P->jobs) job_free(kv.second);
-    if (P->h_list) (void)hipHostFree(P->h_list);
-    if (P->d_list) (void)hipFree(P->d_list);
-    if (P->h_counts) (void)hipHostFree(P->h_counts);
-    if (P->h_owned) (void)hipHostFree(P->h_owned);
-    if (P->h_src_of) (void)hipHostFree(P->h_src_of);
-    if (P->d_src_of) (void)hipFree(P->d_src_of);
-    if (P->d_arena) (void)hipFree(P->d_arena);
-    if (P->d_owned) (void)hipFree(P->d_owned);
-    if (P->d_acc) (void)hipFree(P->d_acc);
-    if (P->ev_t0) (void)hipEventDestroy(P->ev_t0);
-    if (P->ev_t1) (void)hipEventDestroy(P->ev_t1);
-    if (P->ev_ready) (void)hipEventDestroy(P->ev_ready);
-    if (P->ev_reduced) (void)hipEventDestroy(P->ev_reduced);
     if (P->b) free_batch(P->b);
     delete P;
 }

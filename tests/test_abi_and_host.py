@@ -391,6 +391,29 @@ def test_finished_scan_post_rejects_torn_reads(tmp_path):
     assert r.returncode == 0 and "accepted early 0, wrong content 0, missed 0" in r.stdout and "20000 taken, 0 wrong" in r.stdout, r.stdout[-1000:] + r.stderr[-3000:]
 
 
+def test_owning_buffers_free_once_and_survive_failed_growth(tmp_path):
+    """The types every handle and workspace holds its device memory, pinned memory and events in (csrc/device_buffer.hpp) against a
+    malloc-backed stand-in for the HIP runtime that counts live blocks and events and can fail the k-th allocation or the copy
+    (tests/cpp/device_buffer_sanitize.cpp, not linked against HIP): alloc / reserve / reset / destructor, moves and swap, grow_keep with
+    the allocation and then the copy failing (old block, contents and capacity untouched), a group of five buffers whose third growth
+    fails and is retried, the headroom rule, events created once and destroyed once. ASan (with leak detection) + UBSan on."""
+    import shutil
+    import subprocess
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    if not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
+        pytest.skip("no ROCm headers")
+    exe = str(tmp_path / "device_buffer_sanitize")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+           "-I", os.path.join(ROOT, "loc_lib_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "device_buffer_sanitize.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    if r.returncode != 0 and ("libasan" in r.stderr or "libubsan" in r.stderr):
+        pytest.skip("sanitizer runtime not installed")
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert r.returncode == 0 and "device_buffer ok" in r.stdout, r.stdout[-1000:] + r.stderr[-3000:]
+
+
 def test_context_helper_thread_under_tsan(tmp_path):
     """The context's helper thread (csrc/host_worker.hpp: the output cloud of locgpu_*_scan_match is sized, field-copied and half of
     its coordinates written there, beside the caller's thread) under ThreadSanitizer: results handed back through wait(), a run() behind

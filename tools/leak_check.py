@@ -42,6 +42,14 @@ def main():
     scan = full[::4].copy()
     xyzi = np.concatenate([full[:, :3], np.zeros((len(full), 1), np.float32)], axis=1).astype(np.float32)
     _, init = synth.make_pose(3)
+    # small inputs for the owners that only need to exist, be used once and go: a few hundred to a few thousand points each
+    tiny = [np.ascontiguousarray(scan[i::12, :3]) for i in range(2)]
+    rings = [(np.arange(len(t)) // 200).astype(np.uint8) for t in tiny]
+    edge_map, surf_map = np.ascontiguousarray(m[::20]), np.ascontiguousarray(m[::10])
+    edge_pts, surf_pts = np.ascontiguousarray(scan[::30]), np.ascontiguousarray(scan[::10])
+    cands = np.stack([init] * 3)
+    cands[1, 4] += 0.2
+    cands[2, 5] -= 0.2
 
     def once():
         ctx = api.Context(0)
@@ -67,6 +75,37 @@ def main():
             ctx.icp_align_cloud(f, init, api.icp_opts(method=api.P2PLANE))
             sub.close()
         f.close(); c.close()
+        # the batch front-end and the batched feature picker, the uploader's cloud path
+        raw = ctx.batch(tiny)
+        kept = ctx.batch_empty(2, raw.max_points)
+        raw.preprocess(0.5, out=kept)
+        raw.preprocess(0.5)
+        raw.close(); kept.close()
+        raw = ctx.batch(tiny)
+        eb, sb = ctx.batch_empty(2, raw.max_points), ctx.batch_empty(2, raw.max_points)
+        raw.loam_extract(rings, 16, eb, sb)
+        clouds = [api.Cloud(ctx, np.concatenate([t, np.zeros((len(t), 1), np.float32)], axis=1)) for t in tiny]
+        raw.upload_clouds(clouds)
+        for x in clouds + [raw, eb, sb]:
+            x.close()
+        # a LOAM handle: two contexts of its own, storage batches, joint state
+        lo = api.Loam()
+        lo.set_target(edge_map, surf_map)
+        lo.scan_match(edge_pts, surf_pts, init)
+        lo.align_batch([edge_pts, edge_pts[::2].copy()], [surf_pts, surf_pts[::2].copy()], np.stack([init] * 2))
+        lo.close()
+        # a scan pool with one job
+        pool = api.Pool(ctx, 2, len(edge_pts), opts=api.icp_opts(method=api.P2PLANE))
+        pool.wait(pool.submit([edge_pts, edge_pts[::2].copy()], np.stack([init] * 2)))
+        pool.close()
+        # shared-source batches, the candidate search, the brute-force matcher's target, the map planes, the incremental voxel set
+        shared = ctx.batch_shared(edge_pts, 3)
+        shared.close()
+        ctx.icp_init_search(edge_pts, cands, api.icp_opts(method=api.P2PLANE))
+        ctx.bfnn_set_target(edge_map)
+        ctx.bfnn_knn(edge_pts[:200], 5)
+        ctx.icp_build_map_planes()
+        ctx.ndt_set_target(surf_map, api.ndt_opts(method=2))
         ctx.close()
 
     for _ in range(5):
