@@ -812,6 +812,49 @@ LOCGPU_API int locgpu_loam_submap_add_keyframe(locgpu_loam_submap* m, const locg
 LOCGPU_API int locgpu_loam_submap_clouds(locgpu_loam_submap* m, locgpu_cloud** edge_map, locgpu_cloud** surf_map); /* borrowed */
 LOCGPU_API int locgpu_loam_submap_info(const locgpu_loam_submap* m, int* n_keyframes, size_t* edge_points, size_t* surf_points);
 
+/* ---- The global map (csrc/cloud_merge.hip): Lio::GetGlobalMap (lio.cpp:550-614: the cloud form :550-580, the LOAM edge / surface pair
+ * :582-614), which SaveGlobalMap (:131-207) calls — the product of a mapping run. The reference takes every saved keyframe (the RAW
+ * scan: lio.cpp:254, :275) through pcl::transformPointCloud(kf, kf, estimated_poses_[i].matrix()) (:571, the DOUBLE 4x4), joins them
+ * with `*global_map += *kf` and runs ONE VoxelFilter::Filter (voxel_filter.cpp:19-25) over the sum. locgpu_clouds_merge does that for n
+ * resident clouds with one transform-and-join launch, whatever n is, and the existing filter: `out` is, byte for byte — x, y, z, the
+ * intensity lane, the count, is_dense and *passthrough — what
+ *     acc = a fresh cloud;  for i in 0..n-1: locgpu_cloud_append(acc, locgpu_cloud_transform(clouds[i], poses + 7 i));
+ *     locgpu_cloud_voxel_filter(acc, leaf, out, passthrough)
+ * leaves, without the n temporaries, the n launches and the n copies. The arithmetic is locgpu_cloud_transform's (one device function
+ * serves both): per row (float)(((m0 x + m1 y) + m2 z) + m3) in double, a non-finite point of a cloud that is not flagged dense left
+ * as it is, the intensity lane carried through — and then averaged per voxel by the filter, as PCL does.
+ *   poses == NULL: the clouds are already in the world frame; no arithmetic touches them, the bits are carried through.
+ *   leaf == 0: join only — `out` is the joined cloud (non-finite points kept, is_dense = the AND of the inputs' flags) and
+ *     *passthrough = 0. SaveGlobalMap builds its LOAM edge-plus-surface cloud this way before it filters.
+ * Clouds of any context on ctx's GPU are accepted (the rule of locgpu_batch_upload_clouds: ctx's stream is ordered behind what their
+ * contexts have enqueued; the call is blocking and the clouds are free again when it returns). Empty clouds may stand anywhere in the
+ * list. `out` belongs to ctx and is none of the inputs. The call returns when out's count is known on the host.
+ * LOCGPU_ERR_INVALID, with a text and with `out` exactly as it was (points, count and flag), for a NULL ctx, clouds, out or clouds[i],
+ * n < 1, leaf < 0 or not finite, out among the inputs or of another context, a cloud on another GPU, and more than 0x7FFFFF00 points
+ * in total (a cloud's limit); all of these are checked before any device is touched. Scratch is grow-only on the context: the joined
+ * cloud (16 B per point) and 124 B per cloud, beside the filter's own. */
+LOCGPU_API int locgpu_clouds_merge(locgpu_ctx* ctx, const locgpu_cloud* const* clouds, const double* poses /* n x 7 or NULL */, int n, float leaf,
+                                   locgpu_cloud* out, int* passthrough /* optional */);
+/* The same for the scans of a batch — what closes the batched loop: scans registered against a prior map with locgpu_icp_align_batch,
+ * locgpu_ndt_align_batch or locgpu_loam_align_batches are folded, under the poses that came out, into the next target
+ * (locgpu_icp_set_target_cloud, locgpu_ndt_set_target_cloud, locgpu_loam_set_target_cloud) without a trip through host memory. The
+ * result equals locgpu_clouds_merge on the clouds locgpu_batch_export_cloud makes of the scans, in scan order: scan s is a cloud of its
+ * count points {x, y, z, 0} that is NOT flagged dense (a batch carries no flag — the rule of locgpu_batch_preprocess), so a batch
+ * scan's intensity is 0: batches do not carry one, whereas a map built from clouds keeps and averages intensity as PCL does.
+ * poses: n_scans x 7 (indexed by scan, whatever `use` says) or NULL. use (n_scans bytes or NULL): a scan with use[s] == 0 contributes
+ * nothing — alignments that locgpu_icp_fitness_batch / locgpu_ndt_fitness_batch rejected stay out of the map; with no scan in use
+ * `out` comes out empty and dense. `out` belongs to the batch's context. The batch is not modified; a pending upload is waited for.
+ * Refusals (LOCGPU_ERR_INVALID, `out` as it was): those of locgpu_batch_download_scan (shared-source batch, alignment begun and not
+ * ended), a sharded batch, a NULL batch or out, and the leaf and size rules above. */
+LOCGPU_API int locgpu_batch_merge(locgpu_batch* b, const double* poses /* n_scans x 7 or NULL */, const uint8_t* use /* n_scans or NULL */, float leaf,
+                                  locgpu_cloud* out, int* passthrough /* optional */);
+/* Scan `scan` of a batch as a resident cloud: the device-to-device inverse of locgpu_batch_upload_clouds. `cloud`, of any context on the
+ * batch's GPU, receives the scan's points {x, y, z, 0} with is_dense = 0; locgpu_batch_upload_clouds of the exported clouds reproduces
+ * the scans' bytes and counts. It makes a batch scan usable as a keyframe of locgpu_submap_add_keyframe. Blocking. Refusals: those of
+ * locgpu_batch_download_scan (scan index out of range, shared-source batch, alignment begun and not ended), a NULL batch or cloud, a
+ * cloud on another GPU. */
+LOCGPU_API int locgpu_batch_export_cloud(locgpu_batch* b, int scan, locgpu_cloud* cloud);
+
 #ifdef __cplusplus
 }
 #endif

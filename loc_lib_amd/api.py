@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "locgpu_loam_create_on", "locgpu_loam_fitness", "locgpu_loam_fitness_cloud", "locgpu_loam_init_search", "locgpu_loam_init_search_cloud",
     "locgpu_batch_preprocess", "locgpu_batch_upload_clouds", "locgpu_batch_download_scan",
     "locgpu_batch_loam_extract", "locgpu_loam_align_batches",
+    "locgpu_clouds_merge", "locgpu_batch_merge", "locgpu_batch_export_cloud",
 ]
 COMM_ID_BYTES = 128
 NO_INTENSITY = ctypes.c_size_t(-1).value
@@ -197,6 +198,8 @@ def lib():
             "locgpu_batch_preprocess": (i32, [vp, f32, vp, vp, vp]), "locgpu_batch_upload_clouds": (i32, [vp, vp, i32]),
             "locgpu_batch_download_scan": (i32, [vp, i32, vp, sz, sz, vp]),
             "locgpu_batch_loam_extract": (i32, [vp, vp, i32, vp, vp, vp, vp, vp]), "locgpu_loam_align_batches": (i32, [vp, vp, vp, vp, vp, vp]),
+            "locgpu_clouds_merge": (i32, [vp, vp, vp, i32, f32, vp, vp]), "locgpu_batch_merge": (i32, [vp, vp, vp, f32, vp, vp]),
+            "locgpu_batch_export_cloud": (i32, [vp, i32, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -470,6 +473,20 @@ class Context:
         st = AlignStats()
         self._check(lib().locgpu_ndt_align_cloud(self._h, cloud._h, _pose(init_pose).ctypes.data, out.ctypes.data, ctypes.byref(st)))
         return out, _stats_dict(st)
+
+    def clouds_merge(self, clouds, poses, leaf, out=None, with_passthrough=False):
+        """Lio::GetGlobalMap on resident clouds (locgpu_clouds_merge): every cloud under its pose (``poses`` [n, 7], or None for clouds
+        already in the world frame), joined in list order, one voxel filter (``leaf`` 0: join only). Clouds of other contexts on the
+        GPU are accepted; ``out`` (a cloud of this context, none of the inputs; None = a new one) receives the map."""
+        clouds = list(clouds)
+        arr = (ctypes.c_void_p * max(len(clouds), 1))(*[c._h for c in clouds])
+        p = None
+        if poses is not None:
+            p = _pose(poses).reshape(len(clouds), 7)
+        out = out if out is not None else Cloud(self)
+        pt = ctypes.c_int(0)
+        self._check(lib().locgpu_clouds_merge(self._h, arr, p.ctypes.data if p is not None else None, len(clouds), float(leaf), out._h, ctypes.byref(pt)))
+        return (out, bool(pt.value)) if with_passthrough else out
 
     # ---- several GPUs of one node: RCCL communicator + sharded batches
     def comm_init(self, rank, world, uid):
@@ -978,6 +995,31 @@ class Batch:
         clouds = list(clouds)
         arr = (ctypes.c_void_p * max(len(clouds), 1))(*[c._h for c in clouds])
         self.ctx._check(lib().locgpu_batch_upload_clouds(self._h, arr, len(clouds)))
+
+    def merge(self, poses, leaf, use=None, out=None, with_passthrough=False):
+        """The scans of the batch as one map (locgpu_batch_merge): scan s under ``poses[s]`` ([n_scans, 7], or None), joined in scan
+        order, one voxel filter (``leaf`` 0: join only). ``use`` (n_scans booleans or None): scans to leave out. Equals
+        Context.clouds_merge of the clouds export_cloud makes; the batch is not modified."""
+        self.upload_wait()
+        p = _pose(poses).reshape(self.n_local, 7) if poses is not None else None
+        u = None
+        if use is not None:
+            u = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.uint8)
+            if u.shape != (self.n_local,):
+                raise ValueError("use needs %d entries" % self.n_local)
+        out = out if out is not None else Cloud(self.ctx)
+        pt = ctypes.c_int(0)
+        self.ctx._check(lib().locgpu_batch_merge(self._h, p.ctypes.data if p is not None else None, u.ctypes.data if u is not None else None, float(leaf),
+                                                 out._h, ctypes.byref(pt)))
+        return (out, bool(pt.value)) if with_passthrough else out
+
+    def export_cloud(self, scan, cloud=None):
+        """Scan ``scan`` as a resident cloud {x, y, z, 0}, not flagged dense (locgpu_batch_export_cloud); ``cloud`` may belong to any
+        context on the GPU (None = a new cloud of the batch's context)."""
+        self.upload_wait()
+        cloud = cloud if cloud is not None else Cloud(self.ctx)
+        self.ctx._check(lib().locgpu_batch_export_cloud(self._h, int(scan), cloud._h))
+        return cloud
 
     def download_scan(self, s):
         """Scan ``s`` of the batch as an [n, 4] float32 array: x, y, z and the fourth lane as the batch holds it."""

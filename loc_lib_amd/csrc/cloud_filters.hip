@@ -260,20 +260,10 @@ __global__ __launch_bounds__(kFB) void compact_scatter_kernel(const float4* __re
     if (blockIdx.x == n_tiles - 1 && threadIdx.x == 0) P->n_out = tile_base + tile_count[blockIdx.x];
 }
 
-struct M34 { double v[12]; };  // row-major 3×4, passed by value
-
 __global__ __launch_bounds__(kFB) void transform_cloud_f64_kernel(const float4* __restrict__ src, size_t n, int dense, M34 m, float4* __restrict__ dst) {
     const size_t i = (size_t)blockIdx.x * kFB + threadIdx.x;
     if (i >= n) return;
-    const float4 p = src[i];
-    float4 o = p;
-    if (dense || finite3(p)) {
-        const double x = p.x, y = p.y, z = p.z;
-        o.x = (float)(((m.v[0] * x + m.v[1] * y) + m.v[2] * z) + m.v[3]);
-        o.y = (float)(((m.v[4] * x + m.v[5] * y) + m.v[6] * z) + m.v[7]);
-        o.z = (float)(((m.v[8] * x + m.v[9] * y) + m.v[10] * z) + m.v[11]);
-    }
-    dst[i] = o;
+    dst[i] = transform_point_f64(src[i], m.v, dense != 0);
 }
 
 inline unsigned blocks_for(size_t n) { return (unsigned)((n + kFB - 1) / kFB); }
@@ -338,6 +328,7 @@ hipError_t copy_through(locgpu_ctx* ctx, const locgpu_cloud* in, locgpu_cloud* o
 
 void filters_free(locgpu_ctx* ctx) {
     batch_filters_free(ctx);
+    merge_free(ctx);
     FilterScratch* S = ctx->filt;
     if (!S) return;
     if (S->stage_ev) (void)hipEventSynchronize(S->stage_ev);
@@ -492,13 +483,8 @@ hipError_t transform_dev(locgpu_ctx* ctx, const locgpu_cloud* in, const double p
     // float overload instead — pose.matrix().cast<float>(), icp cpp:241 — that one is transform_cloud_kernel.)
     LOCGPU_TRY(ensure_scratch(ctx, 1));
     FilterScratch* S = scratch(ctx);
-    double R[9];
-    quat_to_R(pose, R);
     M34 m;
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) m.v[4 * r + c] = R[3 * r + c];
-        m.v[4 * r + 3] = pose[4 + r];
-    }
+    pose_to_m34(pose, m);
     const size_t n = in->n;
     if (in == out) {
         LOCGPU_TRY(ensure_tmp(ctx, n));

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "device_buffer.hpp"
+#include "device_math.hpp"
 
 struct locgpu_ctx;
 struct locgpu_batch;
@@ -53,6 +54,7 @@ hipError_t cloud_input_ready(locgpu_ctx* ctx, const locgpu_cloud* c);
 hipError_t cloud_mark_ready(locgpu_cloud* c);
 void filters_free(locgpu_ctx* ctx);
 void batch_filters_free(locgpu_ctx* ctx);  // batch_filters.hip: the batch front-end's workspaces (called by filters_free)
+void merge_free(locgpu_ctx* ctx);          // cloud_merge.hip: the global-map pass's workspaces (called by filters_free)
 // batch_filters.hip, for every pass over a batch's points on its context's stream (batch_loam.hip too). order_behind_batch: the stream
 // goes behind everything that may still touch b's points — its pending upload (the host side is waited for) and the idle launches a
 // paced one-scan alignment may have left queued; returns a locgpu_status. set_host_counts: the batch's three copies of its counts
@@ -70,6 +72,30 @@ hipError_t crop_box_dev(locgpu_ctx* ctx, const locgpu_cloud* in, const float mn[
 hipError_t remove_nan_dev(locgpu_ctx* ctx, const locgpu_cloud* in, locgpu_cloud* out);
 hipError_t transform_dev(locgpu_ctx* ctx, const locgpu_cloud* in, const double pose[7], locgpu_cloud* out);
 hipError_t append_dev(locgpu_ctx* ctx, locgpu_cloud* dst, const locgpu_cloud* src);
+
+// pcl::transformPointCloud with a DOUBLE 4x4 (lio.cpp:244,279,571), the one copy of its arithmetic: transform_cloud_f64_kernel
+// (cloud_filters.hip) and merge_kernel (cloud_merge.hip) both call it. Per row (float)(((m0·x + m1·y) + m2·z) + m3) in double — PCL 1.8's
+// templated overload, left to right; a non-finite point of a cloud that is not flagged dense is left as it is; the w lane is carried.
+struct M34 { double v[12]; };  // row-major 3×4
+__device__ __forceinline__ float4 transform_point_f64(const float4& p, const double* __restrict__ m, bool dense) {
+    float4 o = p;
+    if (dense || (isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) {
+        const double x = p.x, y = p.y, z = p.z;
+        o.x = (float)(((m[0] * x + m[1] * y) + m[2] * z) + m[3]);
+        o.y = (float)(((m[4] * x + m[5] * y) + m[6] * z) + m[7]);
+        o.z = (float)(((m[8] * x + m[9] * y) + m[10] * z) + m[11]);
+    }
+    return o;
+}
+// pose.matrix() of a 7-double pose (quaternion xyzw + translation): Eigen's toRotationMatrix (quat_to_R) beside the translation.
+inline void pose_to_m34(const double pose[7], M34& m) {
+    double R[9];
+    quat_to_R(pose, R);
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) m.v[4 * r + c] = R[3 * r + c];
+        m.v[4 * r + 3] = pose[4 + r];
+    }
+}
 
 // loam_features.hip
 void loam_free(locgpu_ctx* ctx);

@@ -21,6 +21,7 @@ struct FilterScratch;       // cloud_filters.hpp
 struct LoamScratch;         // loam_features.hip
 struct BatchFilterScratch;  // batch_filters.hip
 struct BatchLoamScratch;    // batch_loam.hip
+struct MergeScratch;        // cloud_merge.hip
 }  // namespace locgpu
 
 namespace locgpu {
@@ -103,6 +104,7 @@ struct locgpu_ctx {
     locgpu::LoamScratch* loam = nullptr;    // workspaces of the LOAM feature picker (loam_features.hip)
     locgpu::BatchFilterScratch* bfilt = nullptr;  // workspaces of the batch front-end (batch_filters.hip)
     locgpu::BatchLoamScratch* bloam = nullptr;    // workspaces of the batched LOAM feature picker (batch_loam.hip)
+    locgpu::MergeScratch* merge = nullptr;        // table and joined cloud of the global-map pass (cloud_merge.hip)
 
     // reusable one-scan batch for the single-scan entry points
     locgpu_batch* single = nullptr;
