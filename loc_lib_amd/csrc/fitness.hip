@@ -5,12 +5,13 @@
 // Shape: the existing search stage (launch_icp_search, k = 1, alpha_eff = 1: the exact walk of search_walk.hpp, with its deep pass and
 // its tie redo — no new instantiation of the walk) leaves one leaf slot per point in the batch's neighbour list; the accumulate kernel
 // below re-forms the float32 query and the float32 squared distance exactly as the walk evaluates it, and reduces {Σd², inliers,
-// finite points} in FP64 per block; a last small kernel adds the block rows of a scan in a fixed order. Same skeleton and same
-// determinism rule as icp_point_accum_kernel + gn_solve_kernel: no atomics on the sums, two runs give the same bits. A fused
+// finite points} in FP64 per block — the accumulators' scheme, spelled out in the kernel (it says why); a last small kernel
+// adds the block rows of a scan in a fixed order (fixed_order_row_sum below, also the joint LOAM score's). No atomics on the sums,
+// two runs give the same bits. A fused
 // walk + reduce kernel was not built: the walk retires lanes to the deep pass and the redo kernel, so a fused reduction would have
 // to live in three kernels; the separate pass costs one 4-byte load per point.
 //
-// The split of the sums is FIXED (kFitPts points per thread, rows added in the order of fitness_sum_kernel) and does not depend on
+// The split of the sums is FIXED (kFitPts points per thread, rows added in the order of fixed_order_row_sum) and does not depend on
 // the batch: a scan scores the same bits alone, in a batch of any size and in any chunk of a candidate search.
 #include "icp_kernels.hpp"
 #include "launch.hpp"
@@ -47,6 +48,8 @@ __global__ __launch_bounds__(kBlock) void icp_fitness_accum_kernel(const uint2* 
             }
         }
     }
+    // block_reduce_store's scheme (icp_kernels.hpp) with the three butterflies side by side and one guarded store: through the shared
+    // function, which finishes and stores one value before the next, the score call measured 0.7 % slower (profiles/ndt_shared_front.md)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     sum = wave_sum(sum); inl = wave_sum(inl); fin = wave_sum(fin);
     if (lane == 0) { s_part[wave][0] = sum; s_part[wave][1] = inl; s_part[wave][2] = fin; }
@@ -59,15 +62,11 @@ __global__ __launch_bounds__(kBlock) void icp_fitness_accum_kernel(const uint2* 
     }
 }
 
-// One wave per scan: lane l adds rows l, l + 64, … in order, then lane 0 adds the 64 lane sums in order. Rows that do not exist count
-// as zeros, so the result does not depend on how many rows the batch's longest scan needs. out[scan] = {Σd², inliers, finite points, 0}.
-// list_counts: the search stage's work-list counters, consumed by now — zeroed for the next search (as gn_solve_kernel does).
-__global__ __launch_bounds__(64) void icp_fitness_sum_kernel(const double* __restrict__ partials, int rows, double* __restrict__ out,
-                                                             unsigned int* __restrict__ list_counts) {
-    __shared__ double s_lane[3][64];
-    const int scan = blockIdx.x, lane = threadIdx.x;
-    if (list_counts && blockIdx.x == 0 && lane < 4) list_counts[lane] = 0u;
-    const double* p = partials + (size_t)scan * rows * kFitW;
+// The fixed-order sum of the block rows p[rows][kFitW] by one wave: lane l adds rows l, l + 64, … in order, then lane c < 3 adds the 64
+// lane sums of column c in order and returns the total (other lanes: 0). Rows that do not exist count as zeros, so the result does not
+// depend on how many rows the batch's longest scan needs. Every lane of the wave must call it (barrier inside); a second call needs a
+// barrier in front of it: s_lane is still being read.
+__device__ __forceinline__ double fixed_order_row_sum(const double* __restrict__ p, int rows, int lane, double (&s_lane)[3][64]) {
     double a = 0.0, b = 0.0, c = 0.0;
     for (int r = lane; r < rows; r += 64) {
         a += p[(size_t)r * kFitW + 0];
@@ -76,20 +75,31 @@ __global__ __launch_bounds__(64) void icp_fitness_sum_kernel(const double* __res
     }
     s_lane[0][lane] = a; s_lane[1][lane] = b; s_lane[2][lane] = c;
     __syncthreads();
+    double t = 0.0;
     if (lane < 3) {
-        double t = s_lane[lane][0];
+        t = s_lane[lane][0];
         for (int l = 1; l < 64; ++l) t += s_lane[lane][l];
-        out[(size_t)scan * kFitW + lane] = t;
     }
-    if (lane == 3) out[(size_t)scan * kFitW + 3] = 0.0;
+    return t;
+}
+
+// One wave per scan: out[scan] = {Σd², inliers, finite points, 0}, the block rows added by fixed_order_row_sum.
+// list_counts: the search stage's work-list counters, consumed by now — zeroed for the next search (as gn_solve_kernel does).
+__global__ __launch_bounds__(64) void icp_fitness_sum_kernel(const double* __restrict__ partials, int rows, double* __restrict__ out,
+                                                             unsigned int* __restrict__ list_counts) {
+    __shared__ double s_lane[3][64];
+    const int scan = blockIdx.x, lane = threadIdx.x;
+    if (list_counts && blockIdx.x == 0 && lane < 4) list_counts[lane] = 0u;
+    const double t = fixed_order_row_sum(partials + (size_t)scan * rows * kFitW, rows, lane, s_lane);
+    if (lane < 4) out[(size_t)scan * kFitW + lane] = t;  // lane 3: 0
 }
 
 // The joint score of the LOAM matcher (loam_align.hip): one wave per candidate adds the surface batch's rows, then the edge batch's —
-// each class exactly as icp_fitness_sum_kernel adds them (lane l rows l, l + 64, …, then lane 0..2 the 64 lane sums in order), with its
-// own rows per scan — so out[cand][1 + c] holds the bits locgpu_icp_fitness gives for class c, and out[cand][0] = surface + edge formed
-// from those UN-ROUNDED class sums (surface first), not from two means. partials[c] == nullptr: the class is switched off and adds
-// zeros. out[cand][3][kFitW] = {Σd², inliers, finite points, 0} of joint, surface, edge. list_counts[c]: the class batch's search
-// work-list counters, consumed by now — zeroed for the next search (as loam_solve_kernel does). No atomics.
+// each class with fixed_order_row_sum, the sum icp_fitness_sum_kernel is, with its own rows per scan — so out[cand][1 + c] holds the
+// bits locgpu_icp_fitness gives for class c, and out[cand][0] = surface + edge formed from those UN-ROUNDED class sums (surface first),
+// not from two means. partials[c] == nullptr: the class is switched off and adds zeros. out[cand][3][kFitW] = {Σd², inliers, finite
+// points, 0} of joint, surface, edge. list_counts[c]: the class batch's search work-list counters, consumed by now — zeroed for the
+// next search (as loam_solve_kernel does). No atomics.
 __global__ __launch_bounds__(64) void loam_fitness_sum_kernel(const double* __restrict__ part_surf, int rows_surf, const double* __restrict__ part_edge,
                                                               int rows_edge, double* __restrict__ out, unsigned int* __restrict__ counts_surf,
                                                               unsigned int* __restrict__ counts_edge) {
@@ -105,26 +115,12 @@ __global__ __launch_bounds__(64) void loam_fitness_sum_kernel(const double* __re
     for (int c = 0; c < 2; ++c) {
         const double* part = c == 0 ? part_surf : part_edge;
         const int rows = part ? (c == 0 ? rows_surf : rows_edge) : 0;
-        const double* p = part + (size_t)cand * rows * kFitW;  // not read when rows == 0
-        double a = 0.0, b = 0.0, d = 0.0;
-        for (int r = lane; r < rows; r += 64) {
-            a += p[(size_t)r * kFitW + 0];
-            b += p[(size_t)r * kFitW + 1];
-            d += p[(size_t)r * kFitW + 2];
-        }
         if (c == 1) __syncthreads();  // the surface class's lane sums have been read
-        s_lane[0][lane] = a; s_lane[1][lane] = b; s_lane[2][lane] = d;
-        __syncthreads();
-        if (lane < 3) {
-            double t = s_lane[lane][0];
-            for (int l = 1; l < 64; ++l) t += s_lane[lane][l];
-            o[(1 + c) * kFitW + lane] = t;
-            joint += t;
-        }
-        if (lane == 3) o[(1 + c) * kFitW + 3] = 0.0;
+        const double t = fixed_order_row_sum(part + (size_t)cand * rows * kFitW, rows, lane, s_lane);  // part is not read when rows == 0
+        if (lane < 4) o[(1 + c) * kFitW + lane] = t;
+        joint += t;
     }
-    if (lane < 3) o[lane] = joint;
-    if (lane == 3) o[3] = 0.0;
+    if (lane < 4) o[lane] = joint;
 }
 
 int icp_fitness_rows(int max_n) { return (max_n + kFitPts * kBlock - 1) / (kFitPts * kBlock); }

@@ -6,26 +6,6 @@
 
 namespace locgpu {
 
-// ---------------------------------------------------------------------------------------------
-// Block reduction of `acc[0..NV)` → partials[block][0..NV). Wave butterfly, then LDS across the 4 waves.
-template <int NV>
-__device__ __forceinline__ void block_reduce_store(double (&acc)[NV], double* __restrict__ dst) {
-    __shared__ double s_part[kBlock / 64][kAccW];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const double s = wave_sum(acc[v]);
-        if (lane == 0) s_part[wave][v] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < NV) {
-        double s = s_part[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < kBlock / 64; ++w) s += s_part[w][threadIdx.x];
-        dst[threadIdx.x] = s;
-    }
-}
-
 // acc layout: [0..20] upper triangle of H row by row (00 01 .. 05 11 12 .. 55), [21..26] B, [27] effective_num.
 template <int ROWS>
 __device__ __forceinline__ void add_rows(double (&acc)[28], const double (&J)[ROWS][6], const double (&e)[ROWS]) {
@@ -231,7 +211,7 @@ __global__ __launch_bounds__(kBlock) void icp_point_accum_kernel(const uint2* __
         }
     }
     }
-    block_reduce_store<28>(acc, partials + ((size_t)scan * gridDim.x + blockIdx.x) * kAccW);
+    block_reduce_store<28, kAccW>(acc, partials + ((size_t)scan * gridDim.x + blockIdx.x) * kAccW);
 }
 
 // K2'', LOCGPU_P2PLANE_MAP: CaculateMatrixHAndBP2Plane (icp_registration.cpp:161-213) with the per-query math::FitPlane
@@ -274,7 +254,7 @@ __global__ __launch_bounds__(kBlock) void icp_mapplane_accum_kernel(const double
             }
         }
     }
-    block_reduce_store<28>(acc, partials + ((size_t)scan * gridDim.x + blockIdx.x) * kAccW);
+    block_reduce_store<28, kAccW>(acc, partials + ((size_t)scan * gridDim.x + blockIdx.x) * kAccW);
 }
 
 // K2', P2Line: CaculateMatrixHAndBP2Line (icp_registration.cpp:105-159) + math::FitLine (math_utils.h:138-163).

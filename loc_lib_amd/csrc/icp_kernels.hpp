@@ -53,6 +53,29 @@ __device__ __forceinline__ size_t src_index(const int* __restrict__ src_of, int 
     return (size_t)(src_of ? src_of[scan] : scan) * max_n + i;
 }
 
+// Block reduction of acc[0..NV) → dst[0..NV), for the 28-value accumulate kernels (ICP, direct and incremental NDT): W = doubles per
+// LDS row. This is the determinism rule's text — no atomics: one wave butterfly per value, lane 0 of each wave stores, thread v adds
+// waves 0, 1, 2, 3 in that order. Every thread of the block must call it (barrier inside). The two three-value score kernels
+// (fitness.hip, ndt_fitness.hip) spell the same scheme out with their butterflies interleaved.
+template <int NV, int W>
+__device__ __forceinline__ void block_reduce_store(double (&acc)[NV], double* __restrict__ dst) {
+    static_assert(NV <= W, "a value per LDS column");
+    __shared__ double s_part[kBlock / 64][W];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        const double s = wave_sum(acc[v]);
+        if (lane == 0) s_part[wave][v] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < NV) {
+        double s = s_part[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < kBlock / 64; ++w) s += s_part[w][threadIdx.x];
+        dst[threadIdx.x] = s;
+    }
+}
+
 // list[(*count)++] = value for every lane with `pred`, one atomic per wave (same-address atomics cost ≈10 ns each on gfx950: a
 // per-lane append from millions of queries serialises for milliseconds). Every active lane of the wave must reach the call.
 __device__ __forceinline__ void wave_append(uint32_t* __restrict__ list, unsigned int* __restrict__ count, bool pred, uint32_t value) {

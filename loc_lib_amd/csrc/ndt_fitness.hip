@@ -2,10 +2,10 @@
 // locgpu_ndt_fitness): the mean over the inlier points of the smallest accepted χ² residual eᵀ·info·e among the voxels AlignNdt probes
 // for the point (ndt_registration.cpp:399-433). AlignNdt forms that residual for its gate (:416-421) and drops it; here it is kept.
 //
-// Shape: one kernel probes the voxel table exactly as ndt_accum_kernel does — the key by truncation toward zero, the seven (or one)
-// voxels of nearby_grids_ (:57-58), all first-probe slot loads issued together, the few collisions one by one, then the records, one
-// 128-byte line each, the gate as a select — and reduces {Σ min res, inliers, finite points} in FP64 per block; the row format is the
-// ICP score's (fitness.hip), so its last small kernel adds the block rows of a scan in its fixed order. No atomics on the sums.
+// Shape: one kernel probes the voxel table with ndt_accum_kernel's look-up (ndt_kernels.hip, where it says why this is a copy) and
+// reduces {Σ min res, inliers, finite points} in FP64 per block — the accumulators' scheme, spelled out in the kernel (it says
+// why); the row format is the ICP score's (fitness.hip), so its last small kernel adds the block rows of a scan in its
+// fixed order. No atomics on the sums.
 //
 // The split of the sums is FIXED (kFitPts points per thread, a block covers 1024 consecutive points of its scan) and does not depend
 // on the batch: a scan scores the same bits alone, in a batch of any size, from a shared-source batch and in any chunk of a search.
@@ -90,6 +90,8 @@ __global__ __launch_bounds__(kBlock) void ndt_fitness_accum_kernel(const NdtSlot
         sum = any ? sum + best : sum;
         inl = any ? inl + 1.0 : inl;
     }
+    // block_reduce_store's scheme (icp_kernels.hpp) with the three butterflies side by side and one guarded store: through the shared
+    // function, which finishes and stores one value before the next, the score call measured 0.7 % slower (profiles/ndt_shared_front.md)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     sum = wave_sum(sum); inl = wave_sum(inl); fin = wave_sum(fin);
     if (lane == 0) { s_part[wave][0] = sum; s_part[wave][1] = inl; s_part[wave][2] = fin; }

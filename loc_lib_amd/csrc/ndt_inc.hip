@@ -16,11 +16,11 @@
 //     forced true at the end of every SetIncNdtTargetCloud, :181, so UpdateVoxel always takes its first branch, :186-198: more
 //     than one point ⇒ mean, (n−1)-covariance, info = (Σ + 1e-3·I)⁻¹; a single point ⇒ μ = the point, info = 100·I), untouched
 //     voxels keep theirs.
-// That is a sort, a scan and a few per-voxel kernels: keys → stable radix sort (a voxel's points stay in input order) → segment
-// heads → table look-ups → ONE read-back of three counters → stamps, evictions (a sort of the live stamps, only when E > 0), slots
-// for the new voxels, table rebuild, per-voxel statistics by one thread per voxel summing its points sequentially in input order —
-// the reference's own summation order (math_utils.h:55-72), so μ and info carry the oracle's bits, not just its digits, and are
-// the same bits run after run (the round-3 kernels summed with FP64 atomics).
+// That is a sort, a scan and a few per-voxel kernels: the ingest front shared with the direct table (ndt_ingest.hpp: the runs of
+// equal keys, a voxel's points in input order) → table look-ups → ONE read-back of the counters → stamps, evictions (a sort of the
+// live stamps, only when E > 0), slots for the new voxels, table rebuild, per-voxel statistics by one thread per voxel from the
+// front's sums — the reference's own summation order, so μ and info carry the oracle's bits, not just its digits, and are the
+// same bits run after run (the round-3 kernels summed with FP64 atomics).
 // A cloud whose own working set exceeds the capacity (m > capacity − 1: test-sized capacities only — the reference default is
 // 100 000 voxels) needs the order of its points: the live {key, stamp, slot} records come back to the host, inc_lru_replay()
 // walks the points exactly like the reference, and the device finishes from the replayed state with the lost points masked out.
@@ -43,6 +43,7 @@
 #include "icp_kernels.hpp"
 #include "inc_ndt_lru.hpp"
 #include "ndt_inc.hpp"
+#include "ndt_ingest.hpp"
 #include "ndt_kernels.hpp"
 
 namespace locgpu {
@@ -50,57 +51,17 @@ namespace locgpu {
 static_assert(kIncNoKey == kNdtEmpty, "inc_ndt_lru.hpp and ndt_kernels.hpp disagree on the empty key");
 
 // ---------------------------------------------------------------------------------------------- ingest kernels
-// counters (device, mirrored in pinned host memory): [0] distinct keys of the call incl. the run of skipped points, [1] a point lay
-// outside the key range, [2] distinct keys that are not in the table (new voxels), [3] the last run is the skipped points' (key = kNdtEmpty),
-// [4] live slots collected for the eviction sort
-constexpr int kIncCtrs = 8;
-
-// key of every point ((pt * inv_voxel_size_).cast<int>(), ndt cpp:154: truncation toward zero); kNdtEmpty for a point outside the
-// ±2^20-voxel range (reported) or masked out by the host replay (keep[i] == 0)
-__global__ __launch_bounds__(kBlock) void inc_key_kernel(const float4* __restrict__ pts, size_t n, double inv_voxel, const unsigned char* __restrict__ keep,
-                                                         unsigned long long* __restrict__ pkey, uint32_t* __restrict__ pidx, int* __restrict__ ctr) {
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const float4 p = pts[i];
-    const int kx = (int)((double)p.x * inv_voxel), ky = (int)((double)p.y * inv_voxel), kz = (int)((double)p.z * inv_voxel);
-    unsigned long long key = kNdtEmpty;
-    if (!ndt_key_in_range(kx, ky, kz)) ctr[1] = 1;
-    else if (!keep || keep[i]) key = ndt_pack(kx, ky, kz);
-    pkey[i] = key;
-    pidx[i] = (uint32_t)i;
-}
-
-// sorted keys → 1 at the first point of every run
-__global__ __launch_bounds__(kBlock) void inc_head_kernel(const unsigned long long* __restrict__ skey, size_t n, int* __restrict__ head) {
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    head[i] = (i == 0 || skey[i] != skey[i - 1]) ? 1 : 0;
-}
-
-// run u: key, first sorted position; ustart[runs] = n; ctr[0] = runs; the points in voxel order (a voxel's points consecutive, in
-// input order — what the statistics kernel sums over)
-__global__ __launch_bounds__(kBlock) void inc_runs_kernel(const unsigned long long* __restrict__ skey, const uint32_t* __restrict__ sidx, const int* __restrict__ head,
-                                                          const int* __restrict__ uid, size_t n, const float4* __restrict__ pts,
-                                                          unsigned long long* __restrict__ ukey, uint32_t* __restrict__ ustart, float4* __restrict__ psorted,
-                                                          int* __restrict__ ctr) {
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    psorted[i] = pts[sidx[i]];
-    if (head[i]) { ukey[uid[i]] = skey[i]; ustart[uid[i]] = (uint32_t)i; }
-    if (i == n - 1) {
-        const int runs = uid[i] + head[i];
-        ustart[runs] = (uint32_t)n;
-        ctr[0] = runs;
-        ctr[3] = skey[i] == kNdtEmpty ? 1 : 0;
-    }
-}
+// the front's counter block (ndt_ingest.hpp), mirrored in pinned host memory; this file's two: distinct keys of the call that are not
+// in the table (new voxels), live slots collected for the eviction sort
+enum { kIncNew = kIngUser, kIncCollected = kIngUser + 1 };
+static_assert(kIncCollected < kIngCtrs, "the counter block is too small");
 
 // run u → its voxel's slot (−1: not in the table, −2: the run of skipped points); counts the new voxels
 __global__ __launch_bounds__(kBlock) void inc_lookup_kernel(const unsigned long long* __restrict__ ukey, const int* __restrict__ ctr_in,
                                                             const unsigned long long* __restrict__ tkeys, const int* __restrict__ tvid, size_t cap_mask,
                                                             int* __restrict__ uslot, int* __restrict__ unew, int* __restrict__ ctr) {
     const int u = blockIdx.x * kBlock + threadIdx.x;
-    if (u >= ctr_in[0]) return;
+    if (u >= ctr_in[kIngRuns]) return;
     const unsigned long long key = ukey[u];
     int slot = -2, is_new = 0;
     if (key != kNdtEmpty) {
@@ -113,7 +74,7 @@ __global__ __launch_bounds__(kBlock) void inc_lookup_kernel(const unsigned long 
             h = (h + 1) & cap_mask;
         }
         is_new = slot < 0 ? 1 : 0;
-        if (is_new) atomicAdd(&ctr[2], 1);
+        if (is_new) atomicAdd(&ctr[kIncNew], 1);
     }
     uslot[u] = slot;
     unew[u] = is_new;
@@ -133,7 +94,7 @@ __global__ __launch_bounds__(kBlock) void inc_collect_kernel(const unsigned long
                                                              unsigned long long* __restrict__ ev_stamp, int* __restrict__ ev_slot, int* __restrict__ ctr) {
     const int sl = blockIdx.x * kBlock + threadIdx.x;
     if (sl >= n_slots || slot_key[sl] == kNdtEmpty) return;
-    const int pos = atomicAdd(&ctr[4], 1);  // the order is settled by the sort (stamps are unique)
+    const int pos = atomicAdd(&ctr[kIncCollected], 1);  // the order is settled by the sort (stamps are unique)
     ev_stamp[pos] = slot_stamp[sl];
     ev_slot[pos] = sl;
 }
@@ -162,11 +123,6 @@ __global__ __launch_bounds__(kBlock) void inc_assign_kernel(const unsigned long 
     uslot[u] = slot;
 }
 
-__global__ void inc_fill_kernel(unsigned long long* p, size_t n, unsigned long long v) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
-}
-
 // key → slot table of the live slots (refilled on every call)
 __global__ __launch_bounds__(kBlock) void inc_table_kernel(const unsigned long long* __restrict__ slot_key, int n_slots, unsigned long long* keys, int* vid,
                                                            size_t cap_mask) {
@@ -183,9 +139,9 @@ __global__ __launch_bounds__(kBlock) void inc_table_kernel(const unsigned long l
     vid[h] = sl;
 }
 
-// UpdateVoxel, first-scan branch (ndt cpp:186-198) with math::ComputeMeanAndCov (math_utils.h:55-72): one thread per touched
-// voxel, its points consecutive in psorted and in input order — sums run in the reference's order, products are not fused
-// (the library is built with -ffp-contract=off), the 3×3 inverse is the cofactor form of Eigen's fixed-size inverse.
+// UpdateVoxel, first-scan branch (ndt cpp:186-198): one thread per touched voxel; math::ComputeMeanAndCov's sums are the front's
+// (ndt_mean_scatter: no contraction — this kernel must not get an fp contract pragma), the 3×3 inverse is the cofactor form of
+// Eigen's fixed-size inverse.
 __global__ __launch_bounds__(kBlock) void inc_stats_kernel(const float4* __restrict__ psorted, const uint32_t* __restrict__ ustart, const int* __restrict__ uslot, int m,
                                                            double* __restrict__ mu, double* __restrict__ info) {
     const int u = blockIdx.x * kBlock + threadIdx.x;
@@ -197,24 +153,17 @@ __global__ __launch_bounds__(kBlock) void inc_stats_kernel(const float4* __restr
     double* M = mu + 3 * (size_t)slot;
     double* I = info + 9 * (size_t)slot;
     if (len > 1) {
-        double sx = 0.0, sy = 0.0, sz = 0.0;
-        for (uint32_t j = b; j < e; ++j) { const float4 p = psorted[j]; sx = sx + (double)p.x; sy = sy + (double)p.y; sz = sz + (double)p.z; }
-        const double mx = sx / (double)len, my = sy / (double)len, mz = sz / (double)len;
-        double c00 = 0.0, c01 = 0.0, c02 = 0.0, c11 = 0.0, c12 = 0.0, c22 = 0.0;
-        for (uint32_t j = b; j < e; ++j) {
-            const float4 p = psorted[j];
-            const double dx = (double)p.x - mx, dy = (double)p.y - my, dz = (double)p.z - mz;
-            c00 += dx * dx; c01 += dx * dy; c02 += dx * dz; c11 += dy * dy; c12 += dy * dz; c22 += dz * dz;
-        }
+        double mean[3], sc[6];
+        ndt_mean_scatter(psorted, b, e, mean, sc);
         const double l1 = (double)(len - 1);
-        const double a = c00 / l1 + 1e-3, bq = c01 / l1, c = c02 / l1, e4 = c11 / l1 + 1e-3, f = c12 / l1, i8 = c22 / l1 + 1e-3;
+        const double a = sc[0] / l1 + 1e-3, bq = sc[1] / l1, c = sc[2] / l1, e4 = sc[3] / l1 + 1e-3, f = sc[4] / l1, i8 = sc[5] / l1 + 1e-3;
         const double d = bq, g = c, h = f;  // the matrix is symmetric: (row 1, col 0) = (0, 1) etc. — the same numbers, so the same bits
         const double det = a * (e4 * i8 - f * h) - bq * (d * i8 - f * g) + c * (d * h - e4 * g);
         const double id = 1.0 / det;
         I[0] = (e4 * i8 - f * h) * id; I[1] = (c * h - bq * i8) * id; I[2] = (bq * f - c * e4) * id;
         I[3] = (f * g - d * i8) * id;  I[4] = (a * i8 - c * g) * id;  I[5] = (c * d - a * f) * id;
         I[6] = (d * h - e4 * g) * id;  I[7] = (bq * g - a * h) * id;  I[8] = (a * e4 - bq * d) * id;
-        M[0] = mx; M[1] = my; M[2] = mz;
+        M[0] = mean[0]; M[1] = mean[1]; M[2] = mean[2];
     } else {
         const float4 p = psorted[b];
         M[0] = (double)p.x; M[1] = (double)p.y; M[2] = (double)p.z;
@@ -244,7 +193,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         const int kx = (int)(qs.x * inv_voxel), ky = (int)(qs.y * inv_voxel), kz = (int)(qs.z * inv_voxel);
         const int ox[7] = {0, -1, 1, 0, 0, 0, 0}, oy[7] = {0, 0, 0, 1, -1, 0, 0}, oz[7] = {0, 0, 0, 0, 0, -1, 1};
         double Is[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, Ie[3] = {0, 0, 0}, n_acc = 0.0;
-        // the seven look-ups level by level instead of one chain of dependent gathers after the other (see ndt_accum_kernel); the sums
+        // the seven look-ups level by level instead of one chain of dependent gathers after the other; the sums
         // are formed in the order j = 0..6 from the same numbers
         unsigned long long key[7], kk[7];
         size_t hs[7];
@@ -322,20 +271,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
             for (int a = 0; a < 6; ++a) acc[21 + a] = -((J[0][a] * Ie[0] + J[1][a] * Ie[1]) + J[2][a] * Ie[2]);
         }
     }
-    __shared__ double s_part[kBlock / 64][kAccW];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int v = 0; v < 28; ++v) {
-        const double s = wave_sum(acc[v]);
-        if (lane == 0) s_part[wave][v] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < 28) {
-        double s = s_part[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < kBlock / 64; ++w) s += s_part[w][threadIdx.x];
-        partials[((size_t)scan * gridDim.x + blockIdx.x) * kAccW + threadIdx.x] = s;
-    }
+    block_reduce_store<28, kAccW>(acc, partials + ((size_t)scan * gridDim.x + blockIdx.x) * kAccW);
 }
 
 // ---------------------------------------------------------------------------------------------- state
@@ -355,30 +291,20 @@ struct IncNdtState {
     DevBuf<unsigned long long> d_keys;
     DevBuf<int> d_vid;
     size_t table_cap = 0;
-    // per-call scratch, by points (pt_cap) — also holds the per-voxel arrays (a call has at most n voxels)
-    DevBuf<unsigned long long> d_pkey, d_skey, d_ukey;
-    DevBuf<uint32_t> d_pidx, d_sidx, d_ustart;
-    DevBuf<int> d_head, d_uid, d_uslot, d_unew, d_urank;
-    DevBuf<float4> d_psorted;
-    DevBuf<unsigned char> d_keep;
-    size_t pt_cap = 0;
+    NdtIngest ing;  // the front's per-call scratch, by points; grows with the rule of ensure_points
+    // per run of the call, as long as the front's arrays (a call has at most n voxels)
+    DevBuf<int> d_uslot, d_unew, d_urank;
     // eviction scratch, by slots (ev_cap)
     DevBuf<unsigned long long> d_ev_stamp, d_ev_stamp_sorted;
     DevBuf<int> d_ev_slot, d_ev_slot_sorted;
     size_t ev_cap = 0;
-    DevBuf<unsigned char> d_temp;  // scratch of the device-wide primitives
-    DevBuf<int> d_ctr;  // kIncCtrs counters, device + pinned
-    PinnedBuf<int> h_ctr;
+    PinnedBuf<int> h_ctr;  // the front's kIngCtrs counters, read back
 };
 
 static size_t grown(size_t have, size_t need, size_t floor_) {
     size_t cap = have ? have : floor_;
     while (cap < need) cap *= 2;
     return cap;
-}
-
-static hipError_t ensure_temp(IncNdtState& st, size_t bytes) {
-    return bytes <= st.d_temp.cap() ? hipSuccess : st.d_temp.alloc(bytes + 256);
 }
 
 // room for `need` slots (μ/info/keys/stamps of the slots in use are kept)
@@ -394,30 +320,19 @@ static hipError_t ensure_slots(IncNdtState& st, size_t need, hipStream_t s) {
 }
 
 static hipError_t ensure_points(IncNdtState& st, size_t n, hipStream_t s) {
-    LOCGPU_TRY(st.d_ctr.reserve(kIncCtrs));
-    LOCGPU_TRY(st.h_ctr.reserve(kIncCtrs));
+    LOCGPU_TRY(st.h_ctr.reserve(kIngCtrs));
     if (!st.table_cap) {  // an empty table, so that the first call's look-ups run like every other call's
         const size_t cap = 1024;
         LOCGPU_TRY(st.d_keys.alloc(cap));
         LOCGPU_TRY(st.d_vid.alloc(cap));
         st.table_cap = cap;
-        hipLaunchKernelGGL(inc_fill_kernel, dim3((unsigned)(cap / kBlock)), dim3(kBlock), 0, s, st.d_keys, cap, kNdtEmpty);
+        hipLaunchKernelGGL(ndt_fill_kernel<unsigned long long>, dim3((unsigned)(cap / kBlock)), dim3(kBlock), 0, s, st.d_keys.get(), cap, kNdtEmpty);
         LOCGPU_TRY(hipMemsetAsync(st.d_vid, 0xFF, cap * sizeof(int), s));
     }
-    if (n + 1 > st.pt_cap) {
-        const size_t cap = grown(st.pt_cap, n + 1, 16384);
-        LOCGPU_TRY(st.d_pkey.alloc(cap)); LOCGPU_TRY(st.d_skey.alloc(cap)); LOCGPU_TRY(st.d_ukey.alloc(cap));
-        LOCGPU_TRY(st.d_pidx.alloc(cap)); LOCGPU_TRY(st.d_sidx.alloc(cap)); LOCGPU_TRY(st.d_ustart.alloc(cap));
-        LOCGPU_TRY(st.d_head.alloc(cap)); LOCGPU_TRY(st.d_uid.alloc(cap)); LOCGPU_TRY(st.d_uslot.alloc(cap));
-        LOCGPU_TRY(st.d_unew.alloc(cap)); LOCGPU_TRY(st.d_urank.alloc(cap));
-        LOCGPU_TRY(st.d_psorted.alloc(cap)); LOCGPU_TRY(st.d_keep.alloc(cap));
-        st.pt_cap = cap;
-        size_t b1 = 0, b2 = 0;
-        LOCGPU_TRY(prim::sort_pairs(nullptr, b1, st.d_pkey.get(), st.d_skey.get(), st.d_pidx.get(), st.d_sidx.get(), (int)cap, 0, 64, s));
-        LOCGPU_TRY(prim::exclusive_sum(nullptr, b2, st.d_head.get(), st.d_uid.get(), (int)cap, s));
-        LOCGPU_TRY(ensure_temp(st, std::max(b1, b2)));
-    }
-    return hipSuccess;
+    // every call, so that an allocation that failed is tried again; nothing happens when all of it is there
+    const size_t cap = n + 1 > st.ing.cap() ? grown(st.ing.cap(), n + 1, 16384) : st.ing.cap();
+    LOCGPU_TRY(st.d_uslot.reserve(cap)); LOCGPU_TRY(st.d_unew.reserve(cap)); LOCGPU_TRY(st.d_urank.reserve(cap));
+    return st.ing.reserve(cap, true);
 }
 
 static hipError_t ensure_evict(IncNdtState& st, size_t n_live, hipStream_t s) {
@@ -428,7 +343,7 @@ static hipError_t ensure_evict(IncNdtState& st, size_t n_live, hipStream_t s) {
         st.ev_cap = cap;
         size_t b = 0;
         LOCGPU_TRY(prim::sort_pairs(nullptr, b, st.d_ev_stamp.get(), st.d_ev_stamp_sorted.get(), st.d_ev_slot.get(), st.d_ev_slot_sorted.get(), (int)cap, 0, 64, s));
-        LOCGPU_TRY(ensure_temp(st, b));
+        LOCGPU_TRY(st.ing.ensure_temp(b));
     }
     return hipSuccess;
 }
@@ -446,19 +361,13 @@ size_t inc_ndt_num_voxels(const IncNdtState* st) { return st ? (size_t)st->n_liv
 
 static unsigned grid_for(size_t n) { return (unsigned)((std::max<size_t>(n, 1) + kBlock - 1) / kBlock); }
 
-// keys → sort → runs → look-ups; returns with h_ctr read back (one synchronisation)
+// the front, then the look-ups; returns with h_ctr read back (one synchronisation)
 static hipError_t sort_and_look_up(IncNdtState& st, const float4* d_pts, size_t n, bool masked, hipStream_t s) {
-    LOCGPU_TRY(hipMemsetAsync(st.d_ctr, 0, kIncCtrs * sizeof(int), s));
-    hipLaunchKernelGGL(inc_key_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, d_pts, n, st.inv_voxel, masked ? st.d_keep : nullptr, st.d_pkey, st.d_pidx, st.d_ctr);
-    size_t tb = st.d_temp.cap();
-    LOCGPU_TRY(prim::sort_pairs(st.d_temp, tb, st.d_pkey.get(), st.d_skey.get(), st.d_pidx.get(), st.d_sidx.get(), (int)n, 0, 64, s));  // stable: a voxel's points keep their input order
-    hipLaunchKernelGGL(inc_head_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, st.d_skey, n, st.d_head);
-    tb = st.d_temp.cap();
-    LOCGPU_TRY(prim::exclusive_sum(st.d_temp, tb, st.d_head.get(), st.d_uid.get(), (int)n, s));
-    hipLaunchKernelGGL(inc_runs_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, st.d_skey, st.d_sidx, st.d_head, st.d_uid, n, d_pts, st.d_ukey, st.d_ustart, st.d_psorted, st.d_ctr);
-    hipLaunchKernelGGL(inc_lookup_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, st.d_ukey, st.d_ctr, st.d_keys, st.d_vid, st.table_cap - 1, st.d_uslot, st.d_unew, st.d_ctr);
+    NdtIngest& g = st.ing;
+    LOCGPU_TRY(g.run(d_pts, n, st.inv_voxel, masked, s));
+    hipLaunchKernelGGL(inc_lookup_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, g.ukey, g.ctr, st.d_keys, st.d_vid, st.table_cap - 1, st.d_uslot, st.d_unew, g.ctr);
     LOCGPU_TRY(hipGetLastError());
-    LOCGPU_TRY(hipMemcpyAsync(st.h_ctr, st.d_ctr, kIncCtrs * sizeof(int), hipMemcpyDeviceToHost, s));
+    LOCGPU_TRY(hipMemcpyAsync(st.h_ctr, g.ctr, kIngCtrs * sizeof(int), hipMemcpyDeviceToHost, s));
     LOCGPU_TRY(hipStreamSynchronize(s));
     return hipSuccess;
 }
@@ -473,10 +382,10 @@ static hipError_t rebuild_table_and_stats(IncNdtState& st, int m, hipStream_t s)
         LOCGPU_TRY(st.d_vid.alloc(cap));
         st.table_cap = cap;
     }
-    hipLaunchKernelGGL(inc_fill_kernel, dim3(grid_for(st.table_cap)), dim3(kBlock), 0, s, st.d_keys, st.table_cap, kNdtEmpty);
+    hipLaunchKernelGGL(ndt_fill_kernel<unsigned long long>, dim3(grid_for(st.table_cap)), dim3(kBlock), 0, s, st.d_keys.get(), st.table_cap, kNdtEmpty);
     LOCGPU_TRY(hipMemsetAsync(st.d_vid, 0xFF, st.table_cap * sizeof(int), s));
     hipLaunchKernelGGL(inc_table_kernel, dim3(grid_for((size_t)st.n_slots)), dim3(kBlock), 0, s, st.d_slot_key, st.n_slots, st.d_keys, st.d_vid, st.table_cap - 1);
-    if (m > 0) hipLaunchKernelGGL(inc_stats_kernel, dim3(grid_for((size_t)m)), dim3(kBlock), 0, s, st.d_psorted, st.d_ustart, st.d_uslot, m, st.d_mu, st.d_info);
+    if (m > 0) hipLaunchKernelGGL(inc_stats_kernel, dim3(grid_for((size_t)m)), dim3(kBlock), 0, s, st.ing.psorted, st.ing.ustart, st.d_uslot, m, st.d_mu, st.d_info);
     LOCGPU_TRY(hipGetLastError());
     return hipStreamSynchronize(s);
 }
@@ -505,7 +414,7 @@ static hipError_t ingest_replayed(IncNdtState& st, const float4* host_pts, const
         if (h_key[sl] != kNdtEmpty) live.push_back(IncLive{h_key[sl], h_stamp[sl], (int)sl});
     std::vector<uint64_t> keys(n);
     for (size_t i = 0; i < n; ++i) {
-        // the conversion the device's inc_key_kernel performs (v_cvt_i32_f64: NaN → 0, saturating) — `(int)` of such a value is
+        // the conversion the device's ndt_key_kernel performs (v_cvt_i32_f64: NaN → 0, saturating) — `(int)` of such a value is
         // undefined on the host, and the two paths must key a point alike
         auto cvt = [](double v) { return v != v ? 0 : (v >= 2147483647.0 ? 2147483647 : (v <= -2147483648.0 ? (-2147483647 - 1) : (int)v)); };
         const int kx = cvt((double)host_pts[i].x * st.inv_voxel), ky = cvt((double)host_pts[i].y * st.inv_voxel), kz = cvt((double)host_pts[i].z * st.inv_voxel);
@@ -526,14 +435,14 @@ static hipError_t ingest_replayed(IncNdtState& st, const float4* host_pts, const
         LOCGPU_TRY(hipMemcpyAsync(st.d_slot_stamp, h_stamp.data(), (size_t)n_slots * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
     }
     if (st.n_free) LOCGPU_TRY(hipMemcpyAsync(st.d_free, free_slots.data(), (size_t)st.n_free * sizeof(int), hipMemcpyHostToDevice, s));
-    LOCGPU_TRY(hipMemcpyAsync(st.d_keep, keep.data(), n, hipMemcpyHostToDevice, s));
+    LOCGPU_TRY(hipMemcpyAsync(st.ing.keep, keep.data(), n, hipMemcpyHostToDevice, s));
     LOCGPU_TRY(hipStreamSynchronize(s));  // the vectors above are pageable: nothing may still be reading them when they go out of scope
     // the device finishes from the replayed state: table of the new voxel set, then the surviving points by voxel
     LOCGPU_TRY(rebuild_table_and_stats(st, 0, s));
     LOCGPU_TRY(sort_and_look_up(st, d_pts, n, true, s));
-    const int m = st.h_ctr[0] - st.h_ctr[3];
-    if (st.h_ctr[2] != 0) return hipErrorUnknown;  // every surviving point's voxel is in the replayed set
-    if (m > 0) hipLaunchKernelGGL(inc_stats_kernel, dim3(grid_for((size_t)m)), dim3(kBlock), 0, s, st.d_psorted, st.d_ustart, st.d_uslot, m, st.d_mu, st.d_info);
+    const int m = st.h_ctr[kIngRuns] - st.h_ctr[kIngLastEmpty];
+    if (st.h_ctr[kIncNew] != 0) return hipErrorUnknown;  // every surviving point's voxel is in the replayed set
+    if (m > 0) hipLaunchKernelGGL(inc_stats_kernel, dim3(grid_for((size_t)m)), dim3(kBlock), 0, s, st.ing.psorted, st.ing.ustart, st.d_uslot, m, st.d_mu, st.d_info);
     LOCGPU_TRY(hipGetLastError());
     return hipStreamSynchronize(s);
 }
@@ -547,9 +456,9 @@ hipError_t inc_ndt_ingest(IncNdtState& st, const float4* host_pts, const float4*
     const unsigned long long epoch_hi = (unsigned long long)st.epoch << 32;
     LOCGPU_TRY(ensure_points(st, n, s));
     LOCGPU_TRY(sort_and_look_up(st, d_pts, n, false, s));
-    *bad_key = st.h_ctr[1] != 0;
-    const int m = st.h_ctr[0] - st.h_ctr[3];                   // distinct voxels the cloud touches
-    const int m_new = st.h_ctr[2];                             // … of which not alive yet
+    *bad_key = st.h_ctr[kIngBadKey] != 0;
+    const int m = st.h_ctr[kIngRuns] - st.h_ctr[kIngLastEmpty];  // distinct voxels the cloud touches
+    const int m_new = st.h_ctr[kIncNew];                       // … of which not alive yet
     const long long M = (long long)st.capacity - 1;            // voxels the reference's list holds after every point (ndt cpp:161-165)
     if (m == 0) return hipSuccess;                             // every point skipped: nothing changes
     const int n_evict = (long long)m > M ? -1 : (int)std::max<long long>(0, (long long)st.n_live + m_new - M);
@@ -560,18 +469,18 @@ hipError_t inc_ndt_ingest(IncNdtState& st, const float4* host_pts, const float4*
     const int n_free_after_evict = st.n_free + n_evict;
     const int n_fresh = std::max(0, m_new - n_free_after_evict);
     LOCGPU_TRY(ensure_slots(st, (size_t)(st.n_slots + n_fresh), s));
-    hipLaunchKernelGGL(inc_touch_kernel, dim3(grid_for((size_t)m)), dim3(kBlock), 0, s, st.d_uslot, st.d_ustart, st.d_sidx, m, epoch_hi, st.d_slot_stamp);
+    hipLaunchKernelGGL(inc_touch_kernel, dim3(grid_for((size_t)m)), dim3(kBlock), 0, s, st.d_uslot, st.ing.ustart, st.ing.sidx, m, epoch_hi, st.d_slot_stamp);
     if (n_evict > 0) {
         LOCGPU_TRY(ensure_evict(st, (size_t)st.n_live, s));
-        hipLaunchKernelGGL(inc_collect_kernel, dim3(grid_for((size_t)st.n_slots)), dim3(kBlock), 0, s, st.d_slot_key, st.d_slot_stamp, st.n_slots, st.d_ev_stamp, st.d_ev_slot, st.d_ctr);
-        size_t tb = st.d_temp.cap();
-        LOCGPU_TRY(prim::sort_pairs(st.d_temp, tb, st.d_ev_stamp.get(), st.d_ev_stamp_sorted.get(), st.d_ev_slot.get(), st.d_ev_slot_sorted.get(), st.n_live, 0, 64, s));
+        hipLaunchKernelGGL(inc_collect_kernel, dim3(grid_for((size_t)st.n_slots)), dim3(kBlock), 0, s, st.d_slot_key, st.d_slot_stamp, st.n_slots, st.d_ev_stamp, st.d_ev_slot, st.ing.ctr);
+        size_t tb = st.ing.temp.cap();
+        LOCGPU_TRY(prim::sort_pairs(st.ing.temp, tb, st.d_ev_stamp.get(), st.d_ev_stamp_sorted.get(), st.d_ev_slot.get(), st.d_ev_slot_sorted.get(), st.n_live, 0, 64, s));
         hipLaunchKernelGGL(inc_evict_kernel, dim3(grid_for((size_t)n_evict)), dim3(kBlock), 0, s, st.d_ev_slot_sorted, n_evict, st.n_free, st.d_slot_key, st.d_free);
     }
     if (m_new > 0) {
-        size_t tb = st.d_temp.cap();
-        LOCGPU_TRY(prim::exclusive_sum(st.d_temp, tb, st.d_unew.get(), st.d_urank.get(), m, s));
-        hipLaunchKernelGGL(inc_assign_kernel, dim3(grid_for((size_t)m)), dim3(kBlock), 0, s, st.d_ukey, st.d_unew, st.d_urank, st.d_ustart, st.d_sidx, m, st.d_free,
+        size_t tb = st.ing.temp.cap();
+        LOCGPU_TRY(prim::exclusive_sum(st.ing.temp, tb, st.d_unew.get(), st.d_urank.get(), m, s));
+        hipLaunchKernelGGL(inc_assign_kernel, dim3(grid_for((size_t)m)), dim3(kBlock), 0, s, st.ing.ukey, st.d_unew, st.d_urank, st.ing.ustart, st.ing.sidx, m, st.d_free,
                            n_free_after_evict, st.n_slots, epoch_hi, st.d_slot_key, st.d_slot_stamp, st.d_uslot);
     }
     LOCGPU_TRY(hipGetLastError());

@@ -3,15 +3,17 @@
 // K4 follows NdtRegistration::SetDirectNdtTargetCloud (ndt_registration.cpp:87-148): key = trunc-toward-zero of
 // pt/voxel (`(pt * inv_voxel_size_).cast<int>()`, :100), per voxel with more than min_pts_in_voxel points the mean and
 // the (n−1)-normalised covariance (math_utils.h:55-72), SVD, λ1,λ2 clamped to ≥ 1e-3·λ0, info = V·diag(1/λ)·Uᵀ (:118-130).
-// Round 5: the sums are the REFERENCE's sums — keys → stable radix sort (a voxel's points consecutive, in input order) → one
-// thread per voxel adding sequentially, products not fused — so μ and Σ equal the reference's bit for bit and two ingests of one
+// The sums are the REFERENCE's sums — the shared ingest front (ndt_ingest.hpp) puts a voxel's points side by side in input order and one
+// thread per voxel adds them sequentially, products not fused — so μ and Σ equal the reference's bit for bit and two ingests of one
 // map give the same bits (rounds 1-4 summed with FP64 atomics: 1e-10 / 1e-7 from the oracle, different last bits run to run).
 // The table is open addressing over 16-byte {key, voxel index} slots plus a dense array of 128-byte records {μ, info}
 // (ndt_kernels.hpp): two dependent gathers per voxel instead of three. Voxels the reference drops (:136-142) are simply not inserted.
 // K5 follows AlignNdt's inner loop (:399-433): 7 probes in the reference's offset order (:57-58), χ² gate with info,
 // sums NOT weighted by info, effective_num once per source point.
-#include "device_prims.hpp"
+#include <algorithm>
+
 #include "icp_kernels.hpp"
+#include "ndt_ingest.hpp"
 #include "ndt_kernels.hpp"
 
 #ifndef LOCGPU_NDT_WAVES
@@ -19,50 +21,8 @@
 #endif
 namespace locgpu {
 
-// key of every point; a point outside the ±2^20-voxel range raises *bad (the ingest is refused)
-__global__ __launch_bounds__(kBlock) void ndt_key_kernel(const float4* __restrict__ pts, size_t n, double inv, unsigned long long* __restrict__ pkey,
-                                                         uint32_t* __restrict__ pidx, int* __restrict__ bad) {
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const float4 p = pts[i];
-    int kx, ky, kz;
-    ndt_key_of(D3{(double)p.x, (double)p.y, (double)p.z}, inv, kx, ky, kz);
-    unsigned long long key = kNdtEmpty;
-    if (!ndt_key_in_range(kx, ky, kz)) *bad = 1;
-    else key = ndt_pack(kx, ky, kz);
-    pkey[i] = key;
-    pidx[i] = (uint32_t)i;
-}
-
-// sorted keys → 1 at the first point of every run
-__global__ __launch_bounds__(kBlock) void ndt_head_kernel(const unsigned long long* __restrict__ skey, size_t n, int* __restrict__ head) {
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    head[i] = (i == 0 || skey[i] != skey[i - 1]) ? 1 : 0;
-}
-
-// run u: first sorted position; ustart[runs] = n; *n_runs = runs; the points in voxel order (a voxel's points consecutive, in
-// input order — the order the reference's per-voxel index list has, ndt cpp:97-103)
-__global__ __launch_bounds__(kBlock) void ndt_runs_kernel(const uint32_t* __restrict__ sidx, const int* __restrict__ head, const int* __restrict__ uid, size_t n,
-                                                          const float4* __restrict__ pts, uint32_t* __restrict__ ustart, float4* __restrict__ psorted, int* __restrict__ n_runs) {
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    psorted[i] = pts[sidx[i]];
-    if (head[i]) ustart[uid[i]] = (uint32_t)i;
-    if (i == n - 1) {
-        const int runs = uid[i] + head[i];
-        ustart[runs] = (uint32_t)n;
-        *n_runs = runs;
-    }
-}
-
-__global__ void ndt_clear_kernel(NdtSlot* slots, size_t cap) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < cap) slots[i] = NdtSlot{kNdtEmpty, 0u, 0u};
-}
-
-// One thread per voxel (run of the sorted keys) with more than min_pts points: math::ComputeMeanAndCov (math_utils.h:55-72) summing
-// in input order, Σ/(n−1), one-sided Jacobi SVD, clamp, info = V diag(1/λ) Uᵀ (ndt cpp:111-130) — then the record goes into the table.
+// One thread per voxel (run of the sorted keys) with more than min_pts points: math::ComputeMeanAndCov's sums (ndt_mean_scatter),
+// Σ/(n−1), one-sided Jacobi SVD, clamp, info = V diag(1/λ) Uᵀ (ndt cpp:111-130) — then the record goes into the table.
 __global__ __launch_bounds__(kBlock) void ndt_voxel_kernel(const unsigned long long* __restrict__ skey, const float4* __restrict__ psorted, const uint32_t* __restrict__ ustart,
                                                            const int* __restrict__ n_runs, int min_pts, NdtSlot* __restrict__ slots, NdtRecord* __restrict__ rec, size_t cap_mask,
                                                            int* __restrict__ n_vox) {
@@ -72,17 +32,11 @@ __global__ __launch_bounds__(kBlock) void ndt_voxel_kernel(const unsigned long l
     const uint32_t len = e - b;
     const unsigned long long key = skey[b];
     if (key == kNdtEmpty || (int)len <= min_pts) return;  // count > min_pts_in_voxel_ (ndt cpp:111,137)
-    double sx = 0.0, sy = 0.0, sz = 0.0;
-    for (uint32_t j = b; j < e; ++j) { const float4 p = psorted[j]; sx = sx + (double)p.x; sy = sy + (double)p.y; sz = sz + (double)p.z; }
-    const double mx = sx / (double)len, my = sy / (double)len, mz = sz / (double)len;
-    double c00 = 0.0, c01 = 0.0, c02 = 0.0, c11 = 0.0, c12 = 0.0, c22 = 0.0;
-    for (uint32_t j = b; j < e; ++j) {
-        const float4 p = psorted[j];
-        const double dx = (double)p.x - mx, dy = (double)p.y - my, dz = (double)p.z - mz;
-        c00 += dx * dx; c01 += dx * dy; c02 += dx * dz; c11 += dy * dy; c12 += dy * dz; c22 += dz * dz;  // -ffp-contract=off: product, then sum
-    }
+    double mu[3], c[6];
+    ndt_mean_scatter(psorted, b, e, mu, c);
+    const double mx = mu[0], my = mu[1], mz = mu[2];
     const double len1 = (double)(len - 1);
-    const double sxx = c00 / len1, sxy = c01 / len1, sxz = c02 / len1, syy = c11 / len1, syz = c12 / len1, szz = c22 / len1;
+    const double sxx = c[0] / len1, sxy = c[1] / len1, sxz = c[2] / len1, syy = c[3] / len1, syz = c[4] / len1, szz = c[5] / len1;
     double a[3][3] = {{sxx, sxy, sxz}, {sxy, syy, syz}, {sxz, syz, szz}};  // columns of the symmetric Σ
     double vv[3][3];
     jacobi_svd_onesided<3, 3>(a, vv);
@@ -149,40 +103,16 @@ hipError_t ndt_build(NdtTable& t, const float4* d_pts, size_t n, double voxel_si
     t = NdtTable();
     *bad_key = false;
     t.inv_voxel = 1.0 / voxel_size;  // the reference's constructors recompute it (ndt cpp:15,25)
-    DevBuf<unsigned long long> d_pkey, d_skey;
-    DevBuf<uint32_t> d_pidx, d_sidx, d_ustart;
-    DevBuf<int> d_head, d_uid, d_scalar;  // scalars: [0] runs, [1] bad key, [2] voxels kept
-    DevBuf<float4> d_psorted;
-    DevBuf<unsigned char> d_temp;
     if (n > 0xFFFFFFF0ull) return hipErrorInvalidValue;
-    LOCGPU_TRY(d_pkey.alloc(n));
-    LOCGPU_TRY(d_skey.alloc(n));
-    LOCGPU_TRY(d_pidx.alloc(n));
-    LOCGPU_TRY(d_sidx.alloc(n));
-    LOCGPU_TRY(d_ustart.alloc((n + 1)));
-    LOCGPU_TRY(d_head.alloc(n));
-    LOCGPU_TRY(d_uid.alloc(n));
-    LOCGPU_TRY(d_psorted.alloc(n));
-    LOCGPU_TRY(d_scalar.alloc(4));
-    LOCGPU_TRY(hipMemsetAsync(d_scalar, 0, 4 * sizeof(int), s));
-    size_t b1 = 0, b2 = 0;
-    LOCGPU_TRY(prim::sort_pairs(nullptr, b1, d_pkey.get(), d_skey.get(), d_pidx.get(), d_sidx.get(), n, 0, 64, s));
-    LOCGPU_TRY(prim::exclusive_sum(nullptr, b2, d_head.get(), d_uid.get(), n, s));
-    size_t tb = std::max(b1, b2);
-    LOCGPU_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
-    const unsigned gn = (unsigned)((n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(ndt_key_kernel, dim3(gn), dim3(kBlock), 0, s, d_pts, n, t.inv_voxel, d_pkey, d_pidx, d_scalar.get() + 1);
-    tb = b1;
-    LOCGPU_TRY(prim::sort_pairs(d_temp, tb, d_pkey.get(), d_skey.get(), d_pidx.get(), d_sidx.get(), n, 0, 64, s));  // stable: a voxel's points keep their input order
-    hipLaunchKernelGGL(ndt_head_kernel, dim3(gn), dim3(kBlock), 0, s, d_skey, n, d_head);
-    tb = b2;
-    LOCGPU_TRY(prim::exclusive_sum(d_temp, tb, d_head.get(), d_uid.get(), n, s));
-    hipLaunchKernelGGL(ndt_runs_kernel, dim3(gn), dim3(kBlock), 0, s, d_sidx, d_head, d_uid, n, d_pts, d_ustart, d_psorted, d_scalar);
-    int h_scalar[4] = {0, 0, 0, 0};
-    LOCGPU_TRY(hipMemcpyAsync(h_scalar, d_scalar, sizeof(h_scalar), hipMemcpyDeviceToHost, s));
+    NdtIngest ing;  // local: allocated per build, freed on return
+    LOCGPU_TRY(ing.reserve(n + 1, false));
+    LOCGPU_TRY(ing.run(d_pts, n, t.inv_voxel, false, s));
+    int* const d_n_vox = ing.ctr.get() + kIngUser;  // voxels kept
+    int h_ctr[kIngCtrs] = {};
+    LOCGPU_TRY(hipMemcpyAsync(h_ctr, ing.ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, s));
     LOCGPU_TRY(hipStreamSynchronize(s));
-    *bad_key = h_scalar[1] != 0;
-    const size_t runs = (size_t)h_scalar[0];
+    *bad_key = h_ctr[kIngBadKey] != 0;
+    const size_t runs = (size_t)h_ctr[kIngRuns];
     // A SPARSE table: at load 0.03 nearly every look-up — hit or miss — ends at its first probe, and a collision walk is what costs
     // (a wave walks as long as its unluckiest lane, seven times per point); the lines a launch touches are as many as the voxels it
     // looks up, whatever the table's size (measured: load <= 0.5, 15.7 ms per 256-scan step; load <= 0.03, see profiles/experiments.md).
@@ -192,15 +122,15 @@ hipError_t ndt_build(NdtTable& t, const float4* d_pts, size_t n, double voxel_si
     LOCGPU_TRY(t.d_slots.alloc(cap));
     LOCGPU_TRY(t.d_rec.alloc(std::max<size_t>(runs, 1)));  // room for every run; the kept voxels fill a prefix
     t.cap = cap;
-    hipLaunchKernelGGL(ndt_clear_kernel, dim3((unsigned)((cap + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, t.d_slots, cap);
+    hipLaunchKernelGGL(ndt_fill_kernel<NdtSlot>, dim3((unsigned)((cap + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, t.d_slots.get(), cap, NdtSlot{kNdtEmpty, 0u, 0u});
     LOCGPU_TRY(hipMemsetAsync(t.d_rec, 0, std::max<size_t>(runs, 1) * sizeof(NdtRecord), s));  // record 0 is read for voxels that are not there: finite numbers, never accepted
     if (runs > 0 && !*bad_key)
-        hipLaunchKernelGGL(ndt_voxel_kernel, dim3((unsigned)((runs + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, d_skey, d_psorted, d_ustart, d_scalar, min_pts_in_voxel, t.d_slots,
-                           t.d_rec, cap - 1, d_scalar.get() + 2);
+        hipLaunchKernelGGL(ndt_voxel_kernel, dim3((unsigned)((runs + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, ing.skey, ing.psorted, ing.ustart, ing.ctr, min_pts_in_voxel,
+                           t.d_slots, t.d_rec, cap - 1, d_n_vox);
     LOCGPU_TRY(hipGetLastError());
-    LOCGPU_TRY(hipMemcpyAsync(h_scalar, d_scalar, sizeof(h_scalar), hipMemcpyDeviceToHost, s));
+    LOCGPU_TRY(hipMemcpyAsync(h_ctr, ing.ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, s));
     LOCGPU_TRY(hipStreamSynchronize(s));
-    t.n_vox = (size_t)h_scalar[2];
+    t.n_vox = (size_t)h_ctr[kIngUser];
     return hipSuccess;
 }
 
@@ -222,6 +152,12 @@ hipError_t ndt_dump(const NdtTable& t, int* keys, double* mu, double* info, size
 
 // ---------------------------------------------------------------------------------------------
 // K5. Grid (ceil(max_n/256), n_scans).
+// The seven-voxel look-up below is written out in the kernel, and again in ndt_fitness_accum_kernel (ndt_fitness.hip: the same table
+// and hash) and in inc_accum_kernel (ndt_inc.hip: another table and hash). It is not a shared function on purpose: this kernel sits
+// at 126 VGPRs under the 128 that amdgpu_waves_per_eu(4,4) allows, with no scratch, and every shape of a shared __forceinline__
+// look-up that was tried (arrays by reference, a returned struct, a visitor, the slot look-up alone without the residual, an
+// always_inline lambda around the unchanged text) put 240-440 bytes per lane of scratch into it. Sharing the fitness kernel's copy
+// alone would leave two of three, so it stays too.
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LOCGPU_NDT_WAVES, LOCGPU_NDT_WAVES))) void ndt_accum_kernel(const NdtSlot* __restrict__ slots, const NdtRecord* __restrict__ rec, size_t cap_mask,
                                                            double inv_voxel, double res_th, int n_nearby, const float4* __restrict__ src,
                                                            const int* __restrict__ counts, const PoseState* __restrict__ st, int max_n,
@@ -348,21 +284,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LOCGPU_N
         }
     }
     }
-    // block reduce (same scheme as the ICP accumulators)
-    __shared__ double s_part[kBlock / 64][kAccW];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int v = 0; v < 28; ++v) {
-        const double s = wave_sum(acc[v]);
-        if (lane == 0) s_part[wave][v] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < 28) {
-        double s = s_part[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < kBlock / 64; ++w) s += s_part[w][threadIdx.x];
-        partials[((size_t)scan * gridDim.x + blockIdx.x) * kAccW + threadIdx.x] = s;
-    }
+    block_reduce_store<28, kAccW>(acc, partials + ((size_t)scan * gridDim.x + blockIdx.x) * kAccW);
 }
 
 int launch_ndt_accum(const NdtTable* t, const float4* src, const int* counts, const PoseState* st, int max_n, int n_scans, double* partials,
