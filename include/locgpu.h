@@ -225,8 +225,9 @@ LOCGPU_API int locgpu_icp_align_batch(locgpu_ctx* ctx, locgpu_batch* b, const do
 LOCGPU_API int locgpu_ndt_align_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, double* out_poses,
                                       locgpu_align_stats* stats);
 /* The same alignments in two halves, for a caller that keeps several batches in flight — up to three pay — (no reference counterpart: the reference
- * matches one scan at a time). The batches of a context are dealt to three compute streams in turn; *_begin copies the poses,
- * enqueues the first eight Gauss–Newton iterations on the batch's stream and returns, locgpu_align_batch_end waits for them,
+ * matches one scan at a time). A context has three compute streams; *_begin gives the alignment one of its own — the batch's while no
+ * other alignment in flight is on it, else the least-loaded one, so a caller may rotate more batches than streams — copies the poses,
+ * enqueues the first eight Gauss–Newton iterations on that stream and returns, locgpu_align_batch_end waits for them,
  * enqueues further iterations while scans are still open and writes the results. Begun on batch B while batch A is not yet
  * ended, B's first iterations fill the chip under A's last ones (which hold a handful of unconverged scans):
  *     begin(A); loop { begin(B); end(A); swap(A, B); }
@@ -579,6 +580,12 @@ LOCGPU_API int locgpu_search_stats_read(locgpu_ctx* ctx, uint64_t out[4], int re
  * KdTree::GetClosestPoint returns (kdtree.cpp:160-165). out[(scan * max_points + i) * k + j]; -1 where there is none
  * (points beyond a scan's count hold stale values). This is how the tests compare the HOT search kernel's lists with the oracle's. */
 LOCGPU_API int locgpu_debug_batch_nn(locgpu_ctx* ctx, locgpu_batch* batch, int k, int32_t* out);
+/* Test hook: which of the context's compute streams (0, 1 or 2) the batch's current — begun and not ended — or last alignment runs on.
+ * A stream is leased per alignment: locgpu_*_align_batch_begin keeps the batch on its stream while no other alignment in flight uses
+ * it and otherwise moves it to the least-loaded one, so that a caller who rotates more batches than there are streams (three in flight
+ * over four batches) still has every alignment in flight on a stream of its own. Before the first alignment: the stream the batch was
+ * dealt when it was created. -1 for NULL. */
+LOCGPU_API int locgpu_debug_batch_slot(const locgpu_batch* batch);
 
 /* =====================================================================================================================
  * Clouds resident in HBM and the filters either side of the matcher.

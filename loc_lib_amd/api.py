@@ -29,7 +29,7 @@ ABI_SYMBOLS = [
     "locgpu_transform_cloud", "locgpu_batch_create", "locgpu_batch_destroy", "locgpu_icp_align_batch", "locgpu_ndt_align_batch",
     "locgpu_icp_hb_batch", "locgpu_gn_update", "locgpu_ndt_set_target", "locgpu_ndt_target_info", "locgpu_ndt_dump",
     "locgpu_ndt_align", "locgpu_profile_enable", "locgpu_profile_read", "locgpu_visit_count_enable", "locgpu_visit_count_read",
-    "locgpu_search_stats_read", "locgpu_debug_batch_nn", "locgpu_graph_enable",
+    "locgpu_search_stats_read", "locgpu_debug_batch_nn", "locgpu_debug_batch_slot", "locgpu_graph_enable",
     "locgpu_cloud_create", "locgpu_cloud_destroy", "locgpu_cloud_upload", "locgpu_cloud_info", "locgpu_cloud_download", "locgpu_cloud_copy",
     "locgpu_cloud_remove_nan", "locgpu_cloud_voxel_filter", "locgpu_cloud_crop_box", "locgpu_cloud_transform", "locgpu_cloud_append",
     "locgpu_icp_set_target_cloud", "locgpu_icp_set_target_cloud_async", "locgpu_ndt_set_target_cloud", "locgpu_icp_align_cloud", "locgpu_ndt_align_cloud",
@@ -140,7 +140,7 @@ def lib():
             "locgpu_ndt_dump": (i32, [vp, vp, vp, vp, sz, vp]), "locgpu_ndt_align": (i32, [vp, vp, sz, sz, vp, vp, vp]),
             "locgpu_profile_enable": (i32, [vp, i32]), "locgpu_profile_read": (i32, [vp, vp, i32]),
             "locgpu_visit_count_enable": (i32, [vp, i32]), "locgpu_visit_count_read": (i32, [vp, vp, i32]),
-            "locgpu_search_stats_read": (i32, [vp, vp, i32]), "locgpu_debug_batch_nn": (i32, [vp, vp, i32, vp]), "locgpu_graph_enable": (i32, [vp, i32]),
+            "locgpu_search_stats_read": (i32, [vp, vp, i32]), "locgpu_debug_batch_nn": (i32, [vp, vp, i32, vp]), "locgpu_debug_batch_slot": (i32, [vp]), "locgpu_graph_enable": (i32, [vp, i32]),
             "locgpu_cloud_create": (i32, [vp, vp]), "locgpu_cloud_destroy": (None, [vp]),
             "locgpu_cloud_upload": (i32, [vp, vp, sz, sz, sz, i32]), "locgpu_cloud_info": (i32, [vp, vp, vp]),
             "locgpu_cloud_download": (i32, [vp, vp, sz, sz, sz]), "locgpu_cloud_copy": (i32, [vp, vp]),
@@ -947,6 +947,10 @@ class Batch:
             raise ValueError("upload_async needs %d scans" % self.n_local)
         self._keep = (scans, ptrs, cnts)
         self.ctx._check(lib().locgpu_batch_upload_async(self._h, ptrs, cnts, stride))
+
+    def debug_slot(self):
+        """Index of the compute stream the batch's current or last alignment uses (locgpu_debug_batch_slot)."""
+        return int(lib().locgpu_debug_batch_slot(self._h))
 
     def upload_wait(self):
         if self._keep is not None:

@@ -211,10 +211,11 @@ int upload_start(locgpu_batch* b, const void* const* srcs, const size_t* counts,
     // One alignment per batch at a time, and no upload into a batch whose alignment has been begun and not ended: the
     // chunks locgpu_align_batch_end enqueues later read d_src / d_counts / b->counts, which this upload would replace under them.
     // A caller with several alignments in flight rotates depth + 1 batches (bench.py) — the copy always goes to an idle one.
-    // No ordering behind the batch's compute stream is needed beyond that: an ended alignment leaves its stream synchronised
-    // (align_finish synchronises it on its error paths as well) — or, a paced one-scan alignment, with at most a few launches
-    // queued that return on the scan's `done` flag before they read the counts or the points (and the copies are ordered behind
-    // them all the same, below).
+    // No ordering behind the batch's compute stream is needed beyond that: when an alignment has ended, NOTHING OF THIS BATCH IS STILL
+    // QUEUED — align_finish has waited for the event behind the last chunk's read-back (on its error paths for the whole stream). The
+    // stream itself may be busy: with more alignments in flight than streams another batch's chunks run there, and they touch nothing
+    // of this batch. A paced one-scan alignment leaves at most a few launches queued that return on the scan's `done` flag before
+    // they read the counts or the points (and the copies are ordered behind them all the same, below).
     if (b->pending.active) return fail(ctx, LOCGPU_ERR_INVALID, "batch upload: an alignment of this batch has been begun and not finished");
     if (b->paced_tail) {
         // belt and braces for the idle launches a paced alignment may have left queued: the copies go behind them

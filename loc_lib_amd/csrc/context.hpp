@@ -54,13 +54,19 @@ struct StageEvents {
 struct locgpu_ctx {
     int device = 0;
     hipStream_t stream = nullptr;  // = slot_stream[0]: target ingest, clouds, single-scan calls
-    // Batches are dealt to kSlots compute streams in turn, so that an alignment begun on one batch (locgpu_*_align_batch_begin)
-    // runs under the tail of the one begun before it: late Gauss–Newton iterations hold a handful of scans and leave most of the
-    // chip idle. Three, because that is what pays (32 / 64 scans per batch: +14 % scans/s over two, nothing more with four) and
-    // because three compute streams + the copy stream are the four hardware queues the runtime deals streams to in creation order.
+    // kSlots compute streams, so that an alignment begun on one batch (locgpu_*_align_batch_begin) runs under the tail of the one begun
+    // before it: late Gauss–Newton iterations hold a handful of scans and leave most of the chip idle. Three, because that is what
+    // pays (32 / 64 scans per batch: +14 % scans/s over two, nothing more with four) and because three compute streams + the copy
+    // stream are the four hardware queues the runtime deals streams to in creation order.
+    // Batches are dealt to them in turn when they are created, but a stream is LEASED PER ALIGNMENT (stream_lease.hpp; align_begin /
+    // align_finish, gn_driver.hip): a batch keeps its stream while no other alignment in flight is on it and otherwise moves to the
+    // least-loaded one. A streaming caller with three alignments in flight rotates four batches — two of them were dealt the same
+    // stream and are in flight together in two steps of every four. slot_load[i]: alignments begun and not ended on slot_stream[i].
+    // One caller thread per context (locgpu.h) is what guards these counters, as it guards next_slot.
     static constexpr int kSlots = 3;
     hipStream_t slot_stream[kSlots] = {};
     int next_slot = 0;
+    int slot_load[kSlots] = {};
     hipStream_t copy_stream = nullptr;  // host → HBM copies of the batch uploader
     locgpu::Event foreign_ev;           // ordering behind another context's stream when one of ITS clouds is an input here (cloud_input_ready)
     hipStream_t comm_stream = nullptr;  // every collective of the context, in host order (one communicator, one stream: no two at once)
@@ -133,7 +139,10 @@ struct locgpu_ctx {
 struct locgpu_batch {
     locgpu_ctx* ctx = nullptr;
     int slot = 0;
-    hipStream_t stream = nullptr;  // ctx->slot_stream[slot]: everything the batch's alignments enqueue
+    hipStream_t stream = nullptr;  // ctx->slot_stream[slot]: everything the batch's current (or last) alignment enqueues; align_begin may move it
+    bool pinned = false;           // one-scan and workspace batches of the context: they stay on ctx->stream, where the clouds and the target ingest are ordered with them — never leased
+    bool leased = false;           // an alignment begun on this batch counts in ctx->slot_load[slot]
+    locgpu::Event chunk_ev;        // behind the read-back of the last chunk enqueued: what align_finish waits for (NOT the stream: another batch's alignment may be queued behind)
     int n_scans = 0, max_n = 0, blocks_per_scan = 0;  // n_scans: the scans whose points THIS rank holds
     // Sharded batch (locgpu_batch_create_sharded): the batch has n_total scans, this rank holds the points of scans
     // [first, first + n_scans) — or, point-sharded, a slice of the points of every scan (first = 0, n_scans = n_total). Poses, flags

@@ -16,6 +16,7 @@
 #include "gn_driver.hpp"
 #include "ndt_inc.hpp"
 #include "ndt_kernels.hpp"
+#include "stream_lease.hpp"
 
 namespace locgpu {
 
@@ -287,15 +288,16 @@ static int ensure_graphs(locgpu_ctx* ctx, locgpu_batch* b, const AlignSpec& spec
     return LOCGPU_OK;
 }
 
-// One chunk of iterations + the read-back of the per-scan states behind it, on the batch's stream.
+// One chunk of iterations + the read-back of the per-scan states behind it, on the batch's stream, and the batch's event behind that.
 static int enqueue_chunk(locgpu_ctx* ctx, locgpu_batch* b, bool first_chunk) {
     locgpu_batch::Pending& P = b->pending;
     const GnParams& prm = P.spec.prm;
     hipStream_t s = b->stream;
     if (P.graph) {
         // kernels of a finished scan return at once and the solve kernel stops at max_iteration, so a whole chunk is always safe
-        LOCGPU_HIP(ctx, hipGraphLaunch(first_chunk ? b->graph_exec : b->graph_exec_next, s));
+        LOCGPU_HIP(ctx, hipGraphLaunch(first_chunk ? b->graph_exec : b->graph_exec_next, s));  // on whatever stream the batch holds now: a graph's nodes keep nothing of the capture stream
         P.launched += first_chunk ? std::min(kFirstChunk, prm.max_iteration) : next_chunk(b);
+        LOCGPU_HIP(ctx, hipEventRecord(b->chunk_ev, s));
         return LOCGPU_OK;
     }
     if (first_chunk) LOCGPU_HIP(ctx, hipMemcpyAsync(b->d_state, b->h_state, b->n_total * sizeof(PoseState), hipMemcpyHostToDevice, s));
@@ -323,6 +325,7 @@ static int enqueue_chunk(locgpu_ctx* ctx, locgpu_batch* b, bool first_chunk) {
         LOCGPU_HIP(ctx, hipStreamWaitEvent(s, b->ev_reduced, 0));
     }
     LOCGPU_HIP(ctx, hipMemcpyAsync(b->h_state, b->d_state, b->n_total * sizeof(PoseState), hipMemcpyDeviceToHost, s));
+    LOCGPU_HIP(ctx, hipEventRecord(b->chunk_ev, s));  // what align_finish waits for
     return LOCGPU_OK;
 }
 
@@ -398,12 +401,39 @@ static int paced_wait(locgpu_ctx* ctx, locgpu_batch* b, int seen, unsigned long 
     }
 }
 
-int align_begin(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const AlignSpec& spec, bool blocking) {
+// The compute stream of the alignment about to begin on `b` (stream_lease.hpp): the batch's own while no other alignment in flight
+// is on it, else the least-loaded one — b->slot and b->stream follow. Nothing of the batch is queued on the stream it leaves: every
+// entry point that works on a batch waits for that work on the host before it returns, an ended alignment included (align_finish)
+// — except the idle launches of a paced one-scan alignment (paced_tail), behind which the new stream is ordered. (NOT behind the old
+// stream as a whole: the alignment in flight there is the reason for the move, and waiting for it is what the move avoids.)
+static int lease_take(locgpu_ctx* ctx, locgpu_batch* b) {
+    if (b->pinned) return LOCGPU_OK;
+    const int to = lease_choose(ctx->slot_load, locgpu_ctx::kSlots, b->slot);
+    if (to != b->slot) {
+        if (b->paced_tail) {
+            LOCGPU_HIP(ctx, b->tail_ev.ensure());
+            LOCGPU_HIP(ctx, hipEventRecord(b->tail_ev, b->stream));
+            LOCGPU_HIP(ctx, hipStreamWaitEvent(ctx->slot_stream[to], b->tail_ev, 0));
+        }
+        b->slot = to;
+        b->stream = ctx->slot_stream[to];
+    }
+    ctx->slot_load[to]++;
+    b->leased = true;
+    return LOCGPU_OK;
+}
+
+static void lease_release(locgpu_ctx* ctx, locgpu_batch* b) {
+    if (!b->leased) return;
+    ctx->slot_load[b->slot]--;
+    b->leased = false;
+}
+
+static int begin_on_stream(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const AlignSpec& spec, bool blocking) {
     const GnParams& prm = spec.prm;
     const bool ndt = spec.ndt();
-    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
     locgpu_batch::Pending& P = b->pending;
-    if (P.active) return fail(ctx, LOCGPU_ERR_INVALID, "align: an alignment of this batch has been begun and not finished");
+    LOCGPU_HIP(ctx, b->chunk_ev.ensure());
     if (!ndt) { const int grc = ensure_grid_lists(ctx, b, spec); if (grc != LOCGPU_OK) return grc; }
     { const int urc = batch_ready(ctx, b); if (urc != LOCGPU_OK) return urc; }
     P.spec = spec;
@@ -436,12 +466,23 @@ int align_begin(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, cons
     return LOCGPU_OK;
 }
 
-int align_finish(locgpu_ctx* ctx, locgpu_batch* b, double* out_poses, locgpu_align_stats* stats) {
+int align_begin(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const AlignSpec& spec, bool blocking) {
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+    if (b->pending.active) return fail(ctx, LOCGPU_ERR_INVALID, "align: an alignment of this batch has been begun and not finished");
+    // the stream first: batch_ready orders it behind the batch's upload
+    { const int lrc = lease_take(ctx, b); if (lrc != LOCGPU_OK) return lrc; }
+    const int rc = begin_on_stream(ctx, b, init_poses, spec, blocking);
+    if (rc != LOCGPU_OK) {
+        // nothing of a failed begin may run on under the batch's next upload, or on a stream the batch no longer holds
+        (void)hipStreamSynchronize(b->stream);
+        lease_release(ctx, b);
+    }
+    return rc;
+}
+
+static int finish_on_stream(locgpu_ctx* ctx, locgpu_batch* b, double* out_poses, locgpu_align_stats* stats) {
     locgpu_batch::Pending& P = b->pending;
-    if (!P.active) return fail(ctx, LOCGPU_ERR_INVALID, "align: no alignment of this batch has been begun");
     const int max_iteration = P.spec.prm.max_iteration;
-    P.active = false;
     if (P.paced) {
         int seen = 0;
         for (;;) {
@@ -457,7 +498,17 @@ int align_finish(locgpu_ctx* ctx, locgpu_batch* b, double* out_poses, locgpu_ali
         b->paced_tail = true;
     }
     while (!P.paced && max_iteration > 0) {
-        LOCGPU_HIP(ctx, hipStreamSynchronize(b->stream));
+        // the batch's own event where the stream carries another alignment as well (more in flight than streams, or a one-scan call
+        // beside a batch on the context's stream): that one's chunks may be queued behind this one's, and ending this alignment must
+        // not wait for them. Alone on its stream, the stream's own wait is the same thing and returns sooner: with two alignments in
+        // flight the host's wake-up is on the critical path, and waiting for the event there cost 0.2-1.7 ms per 256-scan step
+        // (profiles/stream_lease.md).
+        const bool shared = ctx->slot_load[b->slot] > (b->leased ? 1 : 0);
+        if (const hipError_t e = shared ? hipEventSynchronize(b->chunk_ev) : hipStreamSynchronize(b->stream); e != hipSuccess) {
+            (void)hipStreamSynchronize(b->stream);
+            hip_ok(ctx, e, "align: waiting for the chunk");
+            return LOCGPU_ERR_NO_DEVICE;
+        }
         b->stage_ev.collect(ctx, P.spec.ndt());
         bool all_done = true;
         for (int i = 0; i < b->n_total; ++i)
@@ -466,7 +517,7 @@ int align_finish(locgpu_ctx* ctx, locgpu_batch* b, double* out_poses, locgpu_ali
         const int rc = enqueue_chunk(ctx, b, false);
         if (rc != LOCGPU_OK) {
             // whatever of the chunk was enqueued must not run on under the batch's next upload (which relies on an ended alignment
-            // leaving its stream idle, batch_upload.hip)
+            // leaving nothing of the batch queued, batch_upload.hip)
             (void)hipStreamSynchronize(b->stream);
             return rc;
         }
@@ -475,6 +526,15 @@ int align_finish(locgpu_ctx* ctx, locgpu_batch* b, double* out_poses, locgpu_ali
     b->counters_clean = !P.spec.ndt() && !ctx->count_visits && !P.spec.grid && !b->sharded;  // every search was followed by its solve kernel, which zeroes them (a one-scan front-end saves a fill launch per call)
     if (b->n_total == 1 && max_iteration > 0) b->last_iterations = b->h_state[0].iterations;
     return LOCGPU_OK;
+}
+
+int align_finish(locgpu_ctx* ctx, locgpu_batch* b, double* out_poses, locgpu_align_stats* stats) {
+    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+    if (!b->pending.active) return fail(ctx, LOCGPU_ERR_INVALID, "align: no alignment of this batch has been begun");
+    b->pending.active = false;
+    const int rc = finish_on_stream(ctx, b, out_poses, stats);
+    lease_release(ctx, b);  // on every way out
+    return rc;
 }
 
 int run_align(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const AlignSpec& spec, double* out_poses, locgpu_align_stats* stats) {
@@ -511,6 +571,7 @@ int ensure_map_planes(locgpu_ctx* ctx) {
             w = ctx->planes_ws;
             w->slot = 0;
             w->stream = s;
+            w->pinned = true;
         }
         const double identity[7] = {0, 0, 0, 1, 0, 0, 0};
         init_states(w, identity);

@@ -138,6 +138,7 @@ int shape_batch(locgpu_loam* l, int c, int n_scans, size_t max_n) {
         b = l->batch[c];
         b->slot = 0;
         b->stream = ctx->stream;
+        b->pinned = true;
         // the uploader's pinned counts are sized by the batch's scans at its first upload: give it the capacity's worth now
         if (!lhip(l, b->upl.h_counts.alloc((size_t)cs), "hipHostMalloc counts")) return LOCGPU_ERR_OOM;
     }

@@ -49,6 +49,7 @@ static bool fill_now(locgpu_ctx* ctx, void* p, size_t bytes, const char* what) {
 void locgpu::free_batch(locgpu_batch* b) {
     if (!b) return;
     upload_free_batch(b);
+    if (b->leased) b->ctx->slot_load[b->slot]--;  // destroyed with an alignment begun and not ended: its stream is free again
     if (b->graph_exec) (void)hipGraphExecDestroy(b->graph_exec);
     if (b->graph_exec_next) (void)hipGraphExecDestroy(b->graph_exec_next);
     delete b;
@@ -399,6 +400,7 @@ static int single_reserve(locgpu_ctx* ctx, size_t n, locgpu_batch** out) {
         b = ctx->single;
         b->slot = 0;  // single-scan calls share the stream of the clouds and of the target ingest
         b->stream = ctx->stream;
+        b->pinned = true;
         if (!hip_ok(ctx, b->h_src.alloc(cap), "hipHostMalloc src")) { free_batch(b); ctx->single = nullptr; return LOCGPU_ERR_OOM; }
     }
     *out = b;
@@ -773,6 +775,7 @@ int search_batch(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes
         b = ctx->search;
         b->slot = 0;
         b->stream = ctx->stream;
+        b->pinned = true;
     }
     const int rc = upload_shared(ctx, b, src, n, stride_bytes);
     if (rc != LOCGPU_OK) return rc;
@@ -989,6 +992,8 @@ int locgpu_pose_grid(const double centre[7], double xy_half, double xy_step, dou
     }
     return LOCGPU_OK;
 }
+
+int locgpu_debug_batch_slot(const locgpu_batch* b) { return b ? b->slot : -1; }
 
 // --------------------------------------------------------------------------------------------- measurement
 int locgpu_graph_enable(locgpu_ctx* ctx, int on) {
