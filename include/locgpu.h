@@ -744,6 +744,82 @@ LOCGPU_API int locgpu_batch_loam_extract(locgpu_batch* src, const uint8_t* const
 LOCGPU_API int locgpu_loam_align_batches(locgpu_loam* l, locgpu_batch* edge, locgpu_batch* surf, const double* init_poses, double* out_poses,
                                          locgpu_align_stats* stats);
 
+/* ---- Range-image ingest (csrc/range_ingest.hip): sensor-native scans decoded in HBM. The reference's step from the driver's cloud to
+ * the library's cloud is CloudConver::Conver (LocUtils/src/subscriber/cloud_subscriber.cpp:7-29): it drops non-finite points, drops
+ * points with PointDistance(p) < 4.0 (LocUtils/include/LocUtils/common/point_cloud_utils.h:41-44) and keeps the survivors in input
+ * order. A spinning LiDAR delivers that cloud as a RANGE IMAGE — 2 B per cell instead of 16 B per point over PCIe — and these entry
+ * points take the images on the host, decode them on the device and apply Conver's two rules there.
+ *
+ * Sensor model: n_rings (1..256), n_cols (1..12 288, the LOAM picker's ring limit of 6 x 2048), range_scale (float32, finite, > 0,
+ * metres per count), min_range (float32, finite, >= 0; the reference's value is 4.0f, 0 keeps everything) and caller-supplied float32
+ * tables cos_el[n_rings], sin_el[n_rings], cos_az / sin_az with n_cols entries (az_per_ring = 0) or n_rings * n_cols entries, ring-major
+ * (az_per_ring = 1: per-laser azimuth offsets). The library computes no trigonometry; locgpu_sensor_create copies the tables into HBM once.
+ * Image: one per scan, uint16_t[n_rings * n_cols], ring-major, columns in acquisition order.
+ * Decode of cell (ring g, column c) with count k, a = c (or g * n_cols + c with az_per_ring): k == 0 is "no return" and yields no
+ * point; otherwise, each line ONE IEEE float32 operation, round to nearest, nothing fused:
+ *   r = (float)k * range_scale;  h = r * cos_el[g];  x = h * cos_az[a];  y = h * sin_az[a];  z = r * sin_el[g]
+ * Conver's rules: the point is dropped if x, y or z is not finite, and if sqrtf((x*x + y*y) + z*z) < min_range (products and sums each
+ * rounded to float32, the comparison as the reference's float < 4.0).
+ * Output of a scan: its survivors in ring-ascending, then column-ascending order as {x, y, z, +0.0f}, with one ring byte g per
+ * survivor — byte for byte what the rules above, restated in numpy float32 (tests/range_image_ref.py), give. Counts, order and bits
+ * do not depend on n_scans, on a scan's position in the batch or on the run; no atomics decide an output position.
+ * Out of scope: an asynchronous, double-buffered form (every call here is blocking); intensity or reflectivity images (a batch's
+ * fourth lane stays 0); sharded and shared-source batches; the C++ façade (the reference's Conver lives in its ROS subscriber, which
+ * is not shadowed); bench.py. */
+typedef struct locgpu_sensor locgpu_sensor;
+typedef struct locgpu_sensor_model {
+    int32_t n_rings, n_cols;
+    float range_scale, min_range;
+    int32_t az_per_ring, reserved;
+    const float* cos_el;
+    const float* sin_el;
+    const float* cos_az;
+    const float* sin_az;
+} locgpu_sensor_model;
+/* The resident form of a sensor model (Conver's constants, cloud_subscriber.cpp:7-29, point_cloud_utils.h:41-44, beside the tables).
+ * The tables are read before the call returns. The sensor belongs to ctx, which frees the sensors that are still alive when it is
+ * destroyed (do not destroy a sensor after its context). LOCGPU_ERR_INVALID, with a text, for out-of-range sizes, a non-finite or
+ * non-positive range_scale, a negative or NaN min_range, an az_per_ring other than 0 or 1, NULL tables, a NULL model or out. */
+LOCGPU_API int locgpu_sensor_create(locgpu_ctx* ctx, const locgpu_sensor_model* model, locgpu_sensor** out);
+LOCGPU_API void locgpu_sensor_destroy(locgpu_sensor* s);
+/* Decodes n_scans images into the batch and applies Conver's rules (cloud_subscriber.cpp:7-29, point_cloud_utils.h:41-44): scan i
+ * becomes the output defined above for images[i], and the ring bytes stay resident with the batch. Blocking, like
+ * locgpu_batch_upload_clouds: the images are free again when it returns. One pass for all scans: the images go through pinned staging
+ * to HBM on the context's copy stream, then count, exclusive sum, verdict and scatter kernels and one read-back of n_scans counts.
+ * It replaces the batch's scans; counts are left as locgpu_batch_upload_async + locgpu_batch_upload_wait leave them (device counts,
+ * locgpu_batch_download_scan and the next upload agree). out_counts (n_scans entries or NULL) = the survivors per scan.
+ * Capacity: when a scan has more survivors than the batch's max_points_per_scan the call returns LOCGPU_ERR_INVALID, out_counts holds
+ * the needed counts, locgpu_last_error names the largest, and the batch is exactly as it was: points, counts and rings.
+ * Refusals (LOCGPU_ERR_INVALID, with a text): those of locgpu_batch_upload_async — sharded and shared-source batches, an alignment
+ * begun and not ended — a sensor of another context, a NULL sensor, NULL images or a NULL images[i].
+ * The resident rings are dropped by any later upload into the batch (locgpu_batch_upload_async, locgpu_batch_upload_clouds), by a
+ * locgpu_batch_preprocess with this batch as dst and by a locgpu_batch_loam_extract* that writes it as edge or surf. */
+LOCGPU_API int locgpu_batch_upload_ranges(locgpu_batch* b, const locgpu_sensor* s, const uint16_t* const* images /* n_scans */,
+                                          int32_t* out_counts /* n_scans or NULL */);
+/* The resident ring bytes of scan `scan` (Conver's survivors, cloud_subscriber.cpp:7-29, point_cloud_utils.h:41-44): *n (optional) =
+ * the scan's count, out == NULL returns the count only. LOCGPU_ERR_INVALID when the batch holds no resident rings, for a scan index
+ * out of range, capacity < the count, or an alignment begun and not ended. */
+LOCGPU_API int locgpu_batch_download_rings(locgpu_batch* b, int scan, uint8_t* out, size_t capacity, size_t* n);
+/* locgpu_batch_loam_extract reading the rings that locgpu_batch_upload_ranges left in src (Conver's survivors, cloud_subscriber.cpp:7-29,
+ * point_cloud_utils.h:41-44) instead of host arrays: the same pass, so results are byte for byte those of locgpu_batch_loam_extract
+ * given the same rings from the host, and every limit, refusal and "destinations untouched" rule of that call holds.
+ * LOCGPU_ERR_INVALID also when src has no resident rings. */
+LOCGPU_API int locgpu_batch_loam_extract_resident(locgpu_batch* src, int num_scan, locgpu_batch* edge, locgpu_batch* surf,
+                                                  int32_t* out_edge_counts, int32_t* out_surf_counts, int32_t* out_status /* each n_scans or NULL */);
+/* The same decode pass (cloud_subscriber.cpp:7-29, point_cloud_utils.h:41-44) for ONE image into a resident cloud — the streaming Lio
+ * case: the cloud becomes the scan's survivors with intensity 0 and is_dense = 1, equal to the batch form's scan byte for byte; *n
+ * (optional) = their number. ring_out (n_rings * n_cols bytes of room, or NULL) receives the survivors' ring bytes, which
+ * locgpu_cloud_loam_extract takes unchanged. Blocking. LOCGPU_ERR_INVALID for a NULL cloud, sensor or image and a sensor of another
+ * context. */
+LOCGPU_API int locgpu_cloud_upload_ranges(locgpu_cloud* c, const locgpu_sensor* s, const uint16_t* image, uint8_t* ring_out /* n_rings * n_cols or NULL */,
+                                          size_t* n);
+
+/* Measurement (tools/range_ingest_time.py): with locgpu_profile_enable on, out_ms[0] = the time on the copy stream from the first to
+ * the last H2D of the images of the most recent locgpu_*_upload_ranges (host staging included: it runs under the copies), out_ms[1] =
+ * the time of its four kernels — the decode of cloud_subscriber.cpp:7-29 / point_cloud_utils.h:41-44 alone. Zeros before the first
+ * profiled call. */
+LOCGPU_API int locgpu_range_ingest_times(locgpu_ctx* ctx, double out_ms[2]);
+
 /* The local map of Lio::AddCloud's keyframe branch (lio.cpp:268-306), kept in HBM: a queue of at most num_kfs world-frame
  * keyframe clouds (scans_in_local_map_) and the voxel-filtered local map (local_map_) that is the next matching target.
  * add_keyframe(scan, pose): key_frame_scan = transform(scan, pose) (pose NULL: scan is already in the world frame); push;

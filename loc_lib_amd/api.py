@@ -55,6 +55,8 @@ ABI_SYMBOLS = [
     "locgpu_batch_preprocess", "locgpu_batch_upload_clouds", "locgpu_batch_download_scan",
     "locgpu_batch_loam_extract", "locgpu_loam_align_batches",
     "locgpu_clouds_merge", "locgpu_batch_merge", "locgpu_batch_export_cloud",
+    "locgpu_sensor_create", "locgpu_sensor_destroy", "locgpu_batch_upload_ranges", "locgpu_batch_download_rings",
+    "locgpu_batch_loam_extract_resident", "locgpu_cloud_upload_ranges", "locgpu_range_ingest_times",
 ]
 COMM_ID_BYTES = 128
 NO_INTENSITY = ctypes.c_size_t(-1).value
@@ -94,6 +96,13 @@ class Fitness(ctypes.Structure):
 
 class InitSearchOpts(ctypes.Structure):
     _fields_ = [("max_range", ctypes.c_double), ("min_inlier_ratio", ctypes.c_double)]
+
+
+class SensorModelC(ctypes.Structure):
+    """locgpu_sensor_model."""
+    _fields_ = [("n_rings", ctypes.c_int32), ("n_cols", ctypes.c_int32), ("range_scale", ctypes.c_float), ("min_range", ctypes.c_float),
+                ("az_per_ring", ctypes.c_int32), ("reserved", ctypes.c_int32), ("cos_el", ctypes.c_void_p), ("sin_el", ctypes.c_void_p),
+                ("cos_az", ctypes.c_void_p), ("sin_az", ctypes.c_void_p)]
 
 
 class AlignStats(ctypes.Structure):
@@ -200,6 +209,10 @@ def lib():
             "locgpu_batch_loam_extract": (i32, [vp, vp, i32, vp, vp, vp, vp, vp]), "locgpu_loam_align_batches": (i32, [vp, vp, vp, vp, vp, vp]),
             "locgpu_clouds_merge": (i32, [vp, vp, vp, i32, f32, vp, vp]), "locgpu_batch_merge": (i32, [vp, vp, vp, f32, vp, vp]),
             "locgpu_batch_export_cloud": (i32, [vp, i32, vp]),
+            "locgpu_sensor_create": (i32, [vp, vp, vp]), "locgpu_sensor_destroy": (None, [vp]),
+            "locgpu_batch_upload_ranges": (i32, [vp, vp, vp, vp]), "locgpu_batch_download_rings": (i32, [vp, i32, vp, sz, vp]),
+            "locgpu_batch_loam_extract_resident": (i32, [vp, i32, vp, vp, vp, vp, vp]),
+            "locgpu_cloud_upload_ranges": (i32, [vp, vp, vp, vp, vp]), "locgpu_range_ingest_times": (i32, [vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -693,6 +706,12 @@ class Context:
         self._check(lib().locgpu_profile_read(self._h, out.ctypes.data, int(reset)))
         return dict(search_ms=out[0], accum_ms=out[1], solve_ms=out[2], search_n=int(out[3]), accum_n=int(out[4]), solve_n=int(out[5]))
 
+    def range_ingest_times(self):
+        """(copy-stream ms, kernel ms) of the most recent upload_ranges while profile_enable is on (locgpu_range_ingest_times)."""
+        out = np.zeros(2)
+        self._check(lib().locgpu_range_ingest_times(self._h, out.ctypes.data))
+        return float(out[0]), float(out[1])
+
     def visit_count_enable(self, on=True):
         self._check(lib().locgpu_visit_count_enable(self._h, int(on)))
 
@@ -793,6 +812,15 @@ class Cloud:
         self.ctx._check(lib().locgpu_cloud_append(self._h, other._h))
         return self
 
+    def upload_ranges(self, sensor, image, with_rings=True):
+        """Decode one range image into the cloud (locgpu_cloud_upload_ranges: CloudConver::Conver's rules on the device, intensity 0,
+        is_dense). Returns the survivors' ring bytes (uint8, one per point) — what loam_extract takes — or None."""
+        img = sensor.model.image(image)
+        rings = np.zeros(sensor.model.cells, np.uint8) if with_rings else None
+        n = ctypes.c_size_t(0)
+        self.ctx._check(lib().locgpu_cloud_upload_ranges(self._h, sensor._h, img.ctypes.data, rings.ctypes.data if with_rings else None, ctypes.byref(n)))
+        return np.ascontiguousarray(rings[:int(n.value)]) if with_rings else None
+
     def loam_extract(self, ring, num_scan=16):
         """LoamFeatureExtract::Extract on a resident cloud: returns (edge, surf) resident clouds."""
         ring = np.ascontiguousarray(ring, dtype=np.uint8)
@@ -805,6 +833,52 @@ class Cloud:
     def close(self):
         if self._owned and getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
             lib().locgpu_cloud_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+class SensorModel:
+    """A range-image sensor on the host (locgpu_sensor_model): sizes, range_scale, min_range and the caller's float32 tables —
+    cos_el / sin_el [n_rings]; cos_az / sin_az [n_cols], or [n_rings, n_cols] for per-laser azimuth offsets (az_per_ring)."""
+
+    def __init__(self, n_rings, n_cols, range_scale, min_range, cos_el, sin_el, cos_az, sin_az):
+        self.n_rings, self.n_cols = int(n_rings), int(n_cols)
+        self.range_scale, self.min_range = np.float32(range_scale), np.float32(min_range)
+        self.cos_el, self.sin_el, self.cos_az, self.sin_az = (np.ascontiguousarray(t, dtype=np.float32) for t in (cos_el, sin_el, cos_az, sin_az))
+        self.az_per_ring = int(self.cos_az.ndim == 2)
+        want_az = (self.n_rings, self.n_cols) if self.az_per_ring else (self.n_cols,)
+        if self.cos_el.shape != (self.n_rings,) or self.sin_el.shape != (self.n_rings,) or self.cos_az.shape != want_az or self.sin_az.shape != want_az:
+            raise ValueError("sensor tables do not match n_rings / n_cols")
+
+    @property
+    def cells(self):
+        return self.n_rings * self.n_cols
+
+    def c_struct(self):
+        return SensorModelC(self.n_rings, self.n_cols, float(self.range_scale), float(self.min_range), self.az_per_ring, 0, self.cos_el.ctypes.data,
+                            self.sin_el.ctypes.data, self.cos_az.ctypes.data, self.sin_az.ctypes.data)
+
+    def image(self, a):
+        a = np.ascontiguousarray(a, dtype=np.uint16)
+        if a.size != self.cells:
+            raise ValueError("a range image of this sensor has %d x %d cells" % (self.n_rings, self.n_cols))
+        return a
+
+
+class Sensor:
+    """A sensor model resident in HBM (locgpu_sensor): what Batch.upload_ranges and Cloud.upload_ranges decode with."""
+
+    def __init__(self, ctx, model):
+        self.ctx, self.model = ctx, model
+        self._h = ctypes.c_void_p()
+        m = model.c_struct()
+        ctx._check(lib().locgpu_sensor_create(ctx._h, ctypes.byref(m), ctypes.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            lib().locgpu_sensor_destroy(self._h)
         self._h = None
 
     def __del__(self):
@@ -987,6 +1061,46 @@ class Batch:
         ptrs = (ctypes.c_void_p * max(len(rings), 1))(*[(r.ctypes.data if r is not None and r.size else None) for r in rings])
         ne, ns, status = (np.zeros(self.n_local, np.int32) for _ in range(3))
         rc = lib().locgpu_batch_loam_extract(self._h, ptrs, int(num_scan), edge._h, surf._h, ne.ctypes.data, ns.ctypes.data, status.ctypes.data)
+        if rc != 0:
+            err = LocGpuError(rc, lib().locgpu_last_error(self.ctx._h).decode())
+            err.edge_counts, err.surf_counts, err.status = ne, ns, status
+            raise err
+        return ne, ns, status
+
+    def upload_ranges(self, sensor, images):
+        """Replace the batch's scans by the decoded range images (locgpu_batch_upload_ranges: one uint16 image of the sensor's
+        n_rings x n_cols cells per scan; CloudConver::Conver's rules on the device) and leave their ring bytes resident. Blocking.
+        Returns the counts; when a scan does not fit the batch the LocGpuError carries the needed counts as ``.counts``."""
+        self.upload_wait()
+        images = [sensor.model.image(a) for a in images]
+        if len(images) != self.n_local:
+            raise ValueError("upload_ranges needs %d images" % self.n_local)
+        ptrs = (ctypes.c_void_p * max(len(images), 1))(*[a.ctypes.data for a in images])
+        counts = np.zeros(self.n_local, np.int32)
+        rc = lib().locgpu_batch_upload_ranges(self._h, sensor._h, ptrs, counts.ctypes.data)
+        if rc != 0:
+            err = LocGpuError(rc, lib().locgpu_last_error(self.ctx._h).decode())
+            err.counts = counts
+            raise err
+        return counts
+
+    def download_rings(self, s):
+        """The resident ring bytes of scan ``s`` (uint8, one per point); refused when the batch holds none."""
+        self.upload_wait()
+        n = ctypes.c_size_t(0)
+        self.ctx._check(lib().locgpu_batch_download_rings(self._h, int(s), None, 0, ctypes.byref(n)))
+        out = np.zeros(int(n.value), np.uint8)
+        if n.value:
+            self.ctx._check(lib().locgpu_batch_download_rings(self._h, int(s), out.ctypes.data, int(n.value), ctypes.byref(n)))
+        return out
+
+    def loam_extract_resident(self, num_scan, edge, surf):
+        """loam_extract with the ring bytes upload_ranges left in the batch (locgpu_batch_loam_extract_resident); same returns and errors."""
+        self.upload_wait()
+        edge.upload_wait()
+        surf.upload_wait()
+        ne, ns, status = (np.zeros(self.n_local, np.int32) for _ in range(3))
+        rc = lib().locgpu_batch_loam_extract_resident(self._h, int(num_scan), edge._h, surf._h, ne.ctypes.data, ns.ctypes.data, status.ctypes.data)
         if rc != 0:
             err = LocGpuError(rc, lib().locgpu_last_error(self.ctx._h).decode())
             err.edge_counts, err.surf_counts, err.status = ne, ns, status

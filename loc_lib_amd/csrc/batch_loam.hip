@@ -244,7 +244,8 @@ hipError_t ensure(locgpu_ctx* ctx, size_t n, size_t n_rings, int n_scans, unsign
 
 inline unsigned blocks_for(size_t n) { return (unsigned)((n + kLB - 1) / kLB); }
 
-// The launches of one pass; the result rows are on their way to S->h_res when it returns.
+// The launches of one pass; the result rows are on their way to S->h_res when it returns. The ring bytes come from the host arrays
+// `rings`, or — rings == nullptr — are the ones locgpu_batch_upload_ranges left in src->d_rings, in the same [n_scans][max_n] layout.
 hipError_t extract_dev(locgpu_ctx* ctx, locgpu_batch* src, const uint8_t* const* rings, int num_scan, locgpu_batch* edge, locgpu_batch* surf) {
     hipStream_t s = ctx->stream;
     const int n_scans = src->n_scans;
@@ -255,11 +256,15 @@ hipError_t extract_dev(locgpu_ctx* ctx, locgpu_batch* src, const uint8_t* const*
     while ((1u << end_bit) <= n_rings) ++end_bit;
     LOCGPU_TRY(ensure(ctx, n, n_rings, n_scans, end_bit));
     BatchLoamScratch* S = ctx->bloam;
-    for (int i = 0; i < n_scans; ++i)
-        if (src->counts[i] > 0) std::memcpy(S->h_ring + (size_t)i * max_n, rings[i], (size_t)src->counts[i]);
-    LOCGPU_TRY(hipMemcpyAsync(S->d_ring, S->h_ring, n, hipMemcpyHostToDevice, s));
+    const unsigned char* d_ring = src->d_rings;
+    if (rings) {
+        for (int i = 0; i < n_scans; ++i)
+            if (src->counts[i] > 0) std::memcpy(S->h_ring + (size_t)i * max_n, rings[i], (size_t)src->counts[i]);
+        LOCGPU_TRY(hipMemcpyAsync(S->d_ring, S->h_ring, n, hipMemcpyHostToDevice, s));
+        d_ring = S->d_ring;
+    }
     LOCGPU_TRY(hipMemsetAsync(S->too_long, 0, (size_t)n_scans * sizeof(int32_t), s));
-    hipLaunchKernelGGL(bl_key_kernel, dim3(blocks_for(max_n), n_scans), dim3(kLB), 0, s, S->d_ring, src->d_counts, max_n, (uint32_t)num_scan, n_rings, S->keys[0],
+    hipLaunchKernelGGL(bl_key_kernel, dim3(blocks_for(max_n), n_scans), dim3(kLB), 0, s, d_ring, src->d_counts, max_n, (uint32_t)num_scan, n_rings, S->keys[0],
                        S->vals[0]);
     LOCGPU_TRY(hipGetLastError());
     size_t tb = S->temp.cap();
@@ -294,16 +299,19 @@ void batch_loam_free(locgpu_ctx* ctx) {
 
 using namespace locgpu;
 
-extern "C" {
-
-int locgpu_batch_loam_extract(locgpu_batch* src, const uint8_t* const* rings, int num_scan, locgpu_batch* edge, locgpu_batch* surf, int32_t* out_edge_counts,
-                              int32_t* out_surf_counts, int32_t* out_status) {
+// The one body of locgpu_batch_loam_extract (host ring arrays) and locgpu_batch_loam_extract_resident (resident = true: the ring bytes
+// that locgpu_batch_upload_ranges left in src).
+static int batch_loam_extract(locgpu_batch* src, const uint8_t* const* rings, bool resident, int num_scan, locgpu_batch* edge, locgpu_batch* surf,
+                              int32_t* out_edge_counts, int32_t* out_surf_counts, int32_t* out_status) {
     if (!src || !edge || !surf) {
         locgpu_batch* any = src ? src : (edge ? edge : surf);
         return fail(any ? any->ctx : nullptr, LOCGPU_ERR_INVALID, "batch_loam_extract: NULL batch");
     }
     locgpu_ctx* ctx = src->ctx;
-    if (!rings) return fail(ctx, LOCGPU_ERR_INVALID, "batch_loam_extract: rings is NULL");
+    if (resident) {
+        rings = nullptr;
+        if (!src->rings_valid) return fail(ctx, LOCGPU_ERR_INVALID, "batch_loam_extract_resident: src holds no resident rings (they are left by locgpu_batch_upload_ranges and dropped by every later upload or preprocess into the batch)");
+    } else if (!rings) return fail(ctx, LOCGPU_ERR_INVALID, "batch_loam_extract: rings is NULL");
     if (num_scan < 1 || num_scan > 256) return fail(ctx, LOCGPU_ERR_INVALID, "batch_loam_extract: num_scan must be in 1..256");
     if (src == edge || src == surf || edge == surf) return fail(ctx, LOCGPU_ERR_INVALID, "batch_loam_extract: src, edge and surf must be three distinct batches");
     if (edge->ctx != ctx || surf->ctx != ctx) return fail(ctx, LOCGPU_ERR_INVALID, "batch_loam_extract: the batches belong to different contexts");
@@ -321,7 +329,7 @@ int locgpu_batch_loam_extract(locgpu_batch* src, const uint8_t* const* rings, in
     if (rc == LOCGPU_OK) rc = order_behind_batch(ctx, surf, "batch_loam_extract: ordering behind surf");
     if (rc != LOCGPU_OK) return rc;
     for (int s = 0; s < n_scans; ++s)
-        if (src->counts[s] > 0 && !rings[s]) return fail(ctx, LOCGPU_ERR_INVALID, "batch_loam_extract: rings[" + std::to_string(s) + "] is NULL for a scan with points");
+        if (rings && src->counts[s] > 0 && !rings[s]) return fail(ctx, LOCGPU_ERR_INVALID, "batch_loam_extract: rings[" + std::to_string(s) + "] is NULL for a scan with points");
     if (n_scans == 0) return LOCGPU_OK;
     hipError_t e = extract_dev(ctx, src, rings, num_scan, edge, surf);
     // the one read-back: when it is there the whole pass has run, and whatever uses edge / surf next — on any stream — finds them complete
@@ -348,7 +356,20 @@ int locgpu_batch_loam_extract(locgpu_batch* src, const uint8_t* const* rings, in
                                                  std::to_string(surf->max_n) + " per scan (both are unchanged)");
     set_host_counts(edge, ne.data());
     set_host_counts(surf, ns.data());
+    edge->rings_valid = surf->rings_valid = false;  // features are written in picking order: whatever rings the destinations held are gone
     return LOCGPU_OK;
+}
+
+extern "C" {
+
+int locgpu_batch_loam_extract(locgpu_batch* src, const uint8_t* const* rings, int num_scan, locgpu_batch* edge, locgpu_batch* surf, int32_t* out_edge_counts,
+                              int32_t* out_surf_counts, int32_t* out_status) {
+    return batch_loam_extract(src, rings, false, num_scan, edge, surf, out_edge_counts, out_surf_counts, out_status);
+}
+
+int locgpu_batch_loam_extract_resident(locgpu_batch* src, int num_scan, locgpu_batch* edge, locgpu_batch* surf, int32_t* out_edge_counts, int32_t* out_surf_counts,
+                                       int32_t* out_status) {
+    return batch_loam_extract(src, nullptr, true, num_scan, edge, surf, out_edge_counts, out_surf_counts, out_status);
 }
 
 }  // extern "C"

@@ -22,7 +22,9 @@ struct LoamScratch;         // loam_features.hip
 struct BatchFilterScratch;  // batch_filters.hip
 struct BatchLoamScratch;    // batch_loam.hip
 struct MergeScratch;        // cloud_merge.hip
+struct RangeIngestScratch;  // range_ingest.hip
 }  // namespace locgpu
+struct locgpu_sensor;  // range_ingest.hpp
 
 namespace locgpu {
 struct PendingTarget;
@@ -111,6 +113,8 @@ struct locgpu_ctx {
     locgpu::BatchFilterScratch* bfilt = nullptr;  // workspaces of the batch front-end (batch_filters.hip)
     locgpu::BatchLoamScratch* bloam = nullptr;    // workspaces of the batched LOAM feature picker (batch_loam.hip)
     locgpu::MergeScratch* merge = nullptr;        // table and joined cloud of the global-map pass (cloud_merge.hip)
+    locgpu::RangeIngestScratch* ringest = nullptr;  // staging and workspaces of the range-image ingest (range_ingest.hip)
+    std::vector<locgpu_sensor*> sensors;          // the sensor models created on this context and not destroyed yet (range_ingest.hip)
 
     // reusable one-scan batch for the single-scan entry points
     locgpu_batch* single = nullptr;
@@ -153,6 +157,10 @@ struct locgpu_batch {
     size_t pitch = 0;  // n_scans * max_n
     locgpu::DevBuf<float4> d_src;
     locgpu::DevBuf<int> d_counts;
+    // One ring byte per point slot, [n_scans][max_n], left by locgpu_batch_upload_ranges (range_ingest.hip) and read by
+    // locgpu_batch_loam_extract_resident. Allocated on first use; rings_valid is dropped by everything else that writes d_src.
+    locgpu::DevBuf<unsigned char> d_rings;
+    bool rings_valid = false;
     locgpu::DevBuf<locgpu::PoseState> d_state;
     locgpu::DevBuf<uint32_t> d_nn;  // [5][pitch]
     // Shared-source batch (locgpu_batch_create_shared): ONE region of points in d_src, read by every entry — d_src_of holds a zero per

@@ -145,6 +145,7 @@ void locgpu_destroy(locgpu_ctx* ctx) {
     ndt_free(ctx);
     filters_free(ctx);
     loam_free(ctx);
+    range_ingest_free(ctx);
     for (hipStream_t st : ctx->slot_stream) if (st) (void)hipStreamDestroy(st);
     delete ctx;
 }

@@ -105,3 +105,39 @@ def make_pose(scan_id, trans_amp=0.3, rot_amp_deg=2.0, seed=PERTURB_SEED):
     i = np.zeros(7)
     _load().cityblock_pose(scan_id, seed, trans_amp, np.deg2rad(rot_amp_deg), t.ctypes.data, i.ctypes.data)
     return t, i
+
+
+def sensor_tables(n_rings=N_BEAMS, n_cols=N_AZ):
+    """(cos_el, sin_el, cos_az, sin_az) of the generator's beams as float32 tables: ring g at +2.0 … −24.8 deg, column c at 2π c / n_cols —
+    what a range-image sensor model of this LiDAR is made of."""
+    g = np.arange(n_rings, dtype=np.float64)
+    el = np.deg2rad(2.0 - (26.8 * g / (n_rings - 1) if n_rings > 1 else 0.0 * g))
+    az = 2.0 * np.pi * np.arange(n_cols, dtype=np.float64) / n_cols
+    return tuple(t.astype(np.float32) for t in (np.cos(el), np.sin(el), np.cos(az), np.sin(az)))
+
+
+def make_range_image(scan_id, model, **scan_args):
+    """Scan ``scan_id`` as the range image a spinning LiDAR delivers: uint16 [n_rings, n_cols], 0 = no return. Test and tool
+    infrastructure, numpy only: the points of ``make_scan(scan_id, n_beams=n_rings, n_az=n_cols)`` are binned into the model's cells by
+    elevation (nearest ring of the model's tables) and azimuth (nearest column), and the range is quantised with ``range_scale``
+    (counts clipped to 1..65535; of two returns in one cell the later one stays). ``model`` needs n_rings, n_cols, range_scale and the
+    four tables (api.SensorModel, or anything shaped like it)."""
+    n_rings, n_cols = int(model.n_rings), int(model.n_cols)
+    pts = make_scan(scan_id, n_beams=n_rings, n_az=n_cols, **scan_args)[:, :3].astype(np.float64)
+    image = np.zeros((n_rings, n_cols), np.uint16)
+    if len(pts) == 0:
+        return image
+    rng = np.sqrt((pts * pts).sum(1))
+    el = np.arcsin(np.clip(pts[:, 2] / np.maximum(rng, 1e-12), -1.0, 1.0))
+    az = np.arctan2(pts[:, 1], pts[:, 0])
+    ring_el = np.arctan2(np.asarray(model.sin_el, np.float64), np.asarray(model.cos_el, np.float64))
+    order = np.argsort(ring_el, kind="stable")
+    hi = np.clip(np.searchsorted(ring_el[order], el), 1, n_rings - 1) if n_rings > 1 else np.zeros(len(el), np.int64)
+    lo = np.maximum(hi - 1, 0)
+    ring = order[np.where(np.abs(el - ring_el[order][lo]) <= np.abs(el - ring_el[order][hi]), lo, hi)]
+    cos_az, sin_az = np.asarray(model.cos_az, np.float64), np.asarray(model.sin_az, np.float64)
+    az0 = np.arctan2(sin_az.reshape(-1, n_cols)[:, 0], cos_az.reshape(-1, n_cols)[:, 0])  # per ring with per-laser offsets, else one entry
+    az0 = az0[ring] if len(az0) == n_rings and cos_az.ndim == 2 else az0[0]
+    col = np.rint((az - az0) / (2.0 * np.pi) * n_cols).astype(np.int64) % n_cols
+    image[ring, col] = np.clip(np.rint(rng / float(model.range_scale)), 1, 65535).astype(np.uint16)
+    return image
