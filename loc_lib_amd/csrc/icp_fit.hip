@@ -1,4 +1,5 @@
 // loc_lib_amd/csrc/icp_fit.hip — K2/K3, the fit and solve stage of the ICP hot path: kernels + launchers (see icp_kernels.hpp).
+#include "env.hpp"
 #include "icp_kernels.hpp"
 #include "launch.hpp"
 
@@ -40,8 +41,14 @@ struct RowAccum {
     double sum;
     bool used;
     __device__ __forceinline__ void init() {
-        ent = threadIdx.x & 31;
-        slice = threadIdx.x >> 5;
+        index(threadIdx.x);
+        sum = 0.0;
+        used = false;
+    }
+    // the thread's entry and slice alone, from its thread index (a kernel short of registers may drop them over a phase and ask again)
+    __device__ __forceinline__ void index(int tid) {
+        ent = tid & 31;
+        slice = tid >> 5;
         ra = 7; rb = 7;
         int o = 0;
 #pragma unroll
@@ -52,8 +59,6 @@ struct RowAccum {
                 ++o;
             }
         if (ent >= 21 && ent < 27) { ra = ent - 21; rb = 6; }
-        sum = 0.0;
-        used = false;
     }
     template <int ROWS>
     __device__ __forceinline__ void add(double (&s_row)[8][kAccPad], const double (&J)[ROWS][6], const double (&neg_e)[ROWS], double fitted) {
@@ -111,10 +116,56 @@ __device__ __forceinline__ void plane_row(const D3& n3, const double* R, const D
     J[3] = n3.x; J[4] = n3.y; J[5] = n3.z;
 }
 
-// K2, P2Plane: IcpRegistration::CaculateMatrixHAndBP2Plane (icp_registration.cpp:161-213) + math::FitPlane (math_utils.h:112-136).
+// The five slots of a neighbour list in ascending order: a 9-comparator network in registers. The plane kernels fit the rows in this
+// order, so the plane is a function of the neighbour SET — the same bits whichever distance order the search found the five in.
+__device__ __forceinline__ void sort5(uint32_t (&s)[5]) {
+    auto cx = [&](int a, int b) {
+        const uint32_t lo = min(s[a], s[b]), hi = max(s[a], s[b]);
+        s[a] = lo; s[b] = hi;
+    };
+    cx(0, 1); cx(3, 4); cx(2, 4); cx(2, 3); cx(1, 4); cx(0, 3); cx(0, 2); cx(1, 3); cx(1, 2);
+}
+
+// math::FitPlane (math_utils.h:112-136) over the leaves at the five slots, in the order given, with the five residual checks of
+// icp_registration.cpp:176-182. Returns whether the plane n4 = {n, d} fits.
 // FIT: 0 = plane_null_vector (4-column one-sided Jacobi), 1 = plane_null_vector_secular with the former as its fall-back.
 template <int FIT>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void icp_plane_accum_kernel(const uint2* __restrict__ tree, const float4* __restrict__ src,
+__device__ __forceinline__ bool fit_plane(const uint2* __restrict__ tree, const uint32_t (&slot)[5], double (&n4)[4]) {
+    D3 nb[5];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) nb[j] = leaf_point(tree, slot[j]);
+    if constexpr (FIT == 1) {
+        if (!plane_null_vector_secular(nb, n4)) plane_null_vector(nb, n4);
+    } else {
+        plane_null_vector(nb, n4);
+    }
+    const D3 n3{n4[0], n4[1], n4[2]};
+    bool fit = true;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        const double err = dot3(n3, nb[j]) + n4[3];
+        if (err * err > 1e-2) fit = false;
+    }
+    return fit;
+}
+
+// The row of source point p against its fitted plane n4 (icp_registration.cpp:184-200): J and −e stay zero behind the residual gate.
+__device__ __forceinline__ void plane_point_row(const double (&n4)[4], const float4& p, const PoseState& ps, double max_plane_distance,
+                                                double (&J)[6], double& neg_e) {
+    const D3 n3{n4[0], n4[1], n4[2]};
+    const D3 q{(double)p.x, (double)p.y, (double)p.z};
+    const D3 qs = se3_apply(ps.q, ps.t, q);
+    const double dis = dot3(n3, qs) + n4[3];
+    if (!(fabs(dis) > max_plane_distance)) {
+        plane_row(n3, ps.R, q, J);
+        neg_e = -dis;
+    }
+}
+
+// K2, P2Plane: IcpRegistration::CaculateMatrixHAndBP2Plane (icp_registration.cpp:161-213) + math::FitPlane, a fit per point: the body
+// of icp_plane_accum_kernel<FIT, false> (LOCGPU_PLANE_DEDUP=0; the default is plane_accum_per_run below, which gives the same bits).
+template <int FIT>
+__device__ __forceinline__ void plane_accum_per_point(const uint2* __restrict__ tree, const float4* __restrict__ src,
                                                                  const int* __restrict__ counts, const PoseState* __restrict__ st,
                                                                  const uint32_t* __restrict__ nn, size_t nn_pitch, int max_n,
                                                                  double max_plane_distance, double* __restrict__ partials, int kPlanePts,
@@ -123,9 +174,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     __shared__ double s_slice[kBlock / 32][32];
     const int scan = active ? active[blockIdx.y] : (int)blockIdx.y;
     if (st[scan].done) return;  // uniform per block
-    const int tid = threadIdx.x;
     RowAccum ra;  // see there: the 28 sums are not kept per thread
     ra.init();
+    const int tid = threadIdx.x;
 #pragma unroll 1
     for (int pp = 0; pp < kPlanePts; ++pp) {
         const int i = (blockIdx.x * kPlanePts + pp) * kBlock + tid;
@@ -140,37 +191,178 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
             for (int j = 0; j < 5; ++j) slot[j] = __builtin_nontemporal_load(&nn[(size_t)j * nn_pitch + gi]);
             const float4 p = src[src_index(src_of, scan, max_n, i)];
             if (slot[4] != kInvalidSlot) {  // nn.size() > 3: k=5 yields 5 or (k > size_) none
-                D3 nb[5];
-#pragma unroll
-                for (int j = 0; j < 5; ++j) nb[j] = leaf_point(tree, slot[j]);
+                sort5(slot);
                 double n4[4];
-                if constexpr (FIT == 1) {
-                    if (!plane_null_vector_secular(nb, n4)) plane_null_vector(nb, n4);
-                } else {
-                    plane_null_vector(nb, n4);
-                }
-                const D3 n3{n4[0], n4[1], n4[2]};
-                bool fit = true;
-#pragma unroll
-                for (int j = 0; j < 5; ++j) {
-                    const double err = dot3(n3, nb[j]) + n4[3];
-                    if (err * err > 1e-2) fit = false;
-                }
-                if (fit) {
+                if (fit_plane<FIT>(tree, slot, n4)) {
                     fitted = 1.0;  // effective_num++ before the residual gate (icp cpp:184)
-                    const D3 q{(double)p.x, (double)p.y, (double)p.z};  // the transformed point is only needed from here on
-                    const D3 qs = se3_apply(st[scan].q, st[scan].t, q);
-                    const double dis = dot3(n3, qs) + n4[3];
-                    if (!(fabs(dis) > max_plane_distance)) {
-                        plane_row(n3, st[scan].R, q, J[0]);
-                        neg_e[0] = -dis;
-                    }
+                    plane_point_row(n4, p, st[scan], max_plane_distance, J[0], neg_e[0]);
                 }
             }
         }
         ra.add<1>(s_row, J, neg_e, fitted);
     }
     ra.store(s_slice, partials + ((size_t)scan * gridDim.x + blockIdx.x) * kAccW);
+}
+
+// K2, P2Plane, one fit per run of equal neighbour sets. Scans are ring-major: consecutive source points land centimetres apart on
+// the map and about half of them get the five map points of the point before them, mostly in another distance order. The plane depends
+// on the set alone (sort5), so a block fits once per run and deals the fits 64 to a wave; the rows, their LDS order, the block partials
+// and with them every bit of the sums are plane_accum_per_point's. Over the block's kPlanePts · 256 points (at most kDedupPts):
+//   leaders  a point with a full list whose sorted list differs from the previous lane's (by shuffle); lane 0 of a wave always is one,
+//            which costs 1.6 % more fits, needs no read across waves and keeps runs over wave, pp and block boundaries right by
+//            construction. A point without a list is neither a leader nor a follower, and the point behind it is a leader again.
+//   rank     the inclusive count of leader flags in point order over the block (ballot + popcount, wave totals through LDS): the
+//            1-based table row of a leader and of every follower of its run.
+//   fit      leader j by thread j % 256 in pass j / 256: its point from s_lead, the five slots once more (an L2 hit), fit_plane,
+//            n4 as it comes — NaNs of a non-finite leaf included — into s_plane[j], fit_plane's verdict into the top bit of
+//            s_lead[j]. A wave whose 64 indices lie past the block's leader count skips the pass on a scalar branch.
+//   rows     every thread takes the planes and verdicts of its points from row rank − 1 into registers; then, per point as before,
+//            the row.
+// LDS. The table (32 B per leader, 32 KB for 1024) does not fit beside s_row four times in 160 KB — it does not have to: the table
+// lives from the fit phase to the moment the planes are in registers, s_row from then on, so s_row is the table's first 16.5 KB.
+// Per block: table / s_row 32 768 + s_slice 2 048 + s_lead 2 048 + s_rank 2 048 + s_wcnt 64 = 38 976 B, four blocks in 160 KB.
+constexpr int kDedupPP = 4;                   // points per thread the table has room for: icp_accum_split's largest plane rung
+constexpr int kDedupPts = kDedupPP * kBlock;
+constexpr uint16_t kLeadFits = 0x8000;        // s_lead[j]: the leader's plane fits (set behind its fit)
+static_assert(8 * kAccPad <= 4 * kDedupPts && kDedupPts <= kLeadFits, "s_row inside the plane table; a leader's point in 15 bits");
+template <int FIT>
+__device__ __forceinline__ void plane_accum_per_run(const uint2* __restrict__ tree, const float4* __restrict__ src,
+                                                                 const int* __restrict__ counts, const PoseState* __restrict__ st,
+                                                                 const uint32_t* __restrict__ nn, size_t nn_pitch, int max_n,
+                                                                 double max_plane_distance, double* __restrict__ partials, int kPlanePts,
+                                                                 const int* __restrict__ active, const int* __restrict__ src_of) {
+    __shared__ double s_plane[kDedupPts][4];
+    __shared__ double s_slice[kBlock / 32][32];
+    __shared__ uint16_t s_lead[kDedupPts];         // leader j → its point of the block, h · 256 + tid; later | kLeadFits
+    __shared__ uint16_t s_rank[kDedupPP][kBlock];  // the ranks of a thread's points over the fit phase
+    __shared__ int s_wcnt[kDedupPP][kBlock / 64];
+    double (&s_row)[8][kAccPad] = *reinterpret_cast<double (*)[8][kAccPad]>(&s_plane[0][0]);
+    const int scan = active ? active[blockIdx.y] : (int)blockIdx.y;
+    if (st[scan].done) return;  // uniform per block
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int n = counts[scan];
+    const size_t region = (size_t)scan * max_n;
+    const int first = blockIdx.x * kPlanePts * kBlock;  // point (h, tid) of the block is first + h · 256 + tid
+    RowAccum ra;
+    ra.init();
+    // The fit phase has no register to spare (128 at four waves per SIMD), so nothing a later phase can work out again may stay live
+    // across it. The thread index is taken anew per phase, in a way the compiler cannot see through: the addresses made from it, and
+    // the accumulator's entry and slice, are then made where they are used; the ranks wait in LDS.
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    int rank[kDedupPP];  // the point's row of s_plane + 1; 0: no list
+    bool leader[kDedupPP];
+#pragma unroll
+    for (int h = 0; h < kDedupPP; ++h) {
+        const int i = first + h * kBlock + tid;
+        uint32_t slot[5];
+        bool has = false;
+        if (h < kPlanePts && i < n) {
+#pragma unroll
+            for (int j = 0; j < 5; ++j) slot[j] = nn[(size_t)j * nn_pitch + region + i];
+            has = slot[4] != kInvalidSlot;  // nn.size() > 3: k=5 yields 5 or (k > size_) none
+        }
+        if (has) {
+            sort5(slot);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 5; ++j) slot[j] = kInvalidSlot;  // differs from every full list
+        }
+        bool differs = lane == 0;
+#pragma unroll
+        for (int j = 0; j < 5; ++j) differs |= (uint32_t)__shfl_up((int)slot[j], 1, 64) != slot[j];
+        leader[h] = has && differs;
+        const unsigned long long mask = __ballot(leader[h]);
+        const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));  // leaders in the lanes before this one
+        rank[h] = has ? below + (leader[h] ? 1 : 0) : 0;  // within the wave so far
+        if (lane == 0) s_wcnt[h][wave] = __popcll(mask);
+    }
+    __syncthreads();
+    int n_lead = 0, before[kDedupPP];
+#pragma unroll
+    for (int h = 0; h < kDedupPP; ++h) {
+        before[h] = n_lead;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) {
+            const int c = s_wcnt[h][w];
+            before[h] += w < wave ? c : 0;
+            n_lead += c;
+        }
+    }
+    n_lead = __builtin_amdgcn_readfirstlane(n_lead);
+#pragma unroll
+    for (int h = 0; h < kDedupPP; ++h) {
+        if (rank[h] > 0) rank[h] += before[h];
+        if (leader[h]) s_lead[rank[h] - 1] = (uint16_t)(h * kBlock + tid);
+        s_rank[h][tid] = (uint16_t)rank[h];
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int base = 0; base < n_lead; base += kBlock) {
+        if (base + wave * 64 < n_lead) {  // scalar: the whole wave has a leader to fit, or none of it
+            const int j = base + tid;
+            if (j < n_lead) {
+                const uint16_t pt = s_lead[j];
+                const size_t gi = region + first + pt;
+                uint32_t slot[5];
+#pragma unroll
+                for (int k = 0; k < 5; ++k) slot[k] = __builtin_nontemporal_load(&nn[(size_t)k * nn_pitch + gi]);
+                sort5(slot);
+                double n4[4];
+                if (fit_plane<FIT>(tree, slot, n4)) s_lead[j] = pt | kLeadFits;  // read by this thread alone until the barrier
+#pragma unroll
+                for (int c = 0; c < 4; ++c) s_plane[j][c] = n4[c];
+            }
+        }
+    }
+    __syncthreads();
+    tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    ra.index(tid);
+    double n4[kDedupPP][4];
+    float4 p[kDedupPP];
+    bool fits[kDedupPP];
+#pragma unroll
+    for (int h = 0; h < kDedupPP; ++h) {
+        rank[h] = s_rank[h][tid];
+        fits[h] = false;
+        if (rank[h] > 0) {
+            fits[h] = (s_lead[rank[h] - 1] & kLeadFits) != 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) n4[h][c] = s_plane[rank[h] - 1][c];
+            p[h] = src[src_index(src_of, scan, max_n, first + h * kBlock + tid)];
+        }
+    }
+    __syncthreads();  // every plane is in registers: from here on the table's LDS is s_row
+#pragma unroll
+    for (int h = 0; h < kDedupPP; ++h) {
+        if (h < kPlanePts) {  // uniform per block
+            double J[1][6] = {{0.0, 0.0, 0.0, 0.0, 0.0, 0.0}};
+            double neg_e[1] = {0.0};
+            double fitted = 0.0;
+            if (fits[h]) {
+                fitted = 1.0;  // effective_num++ before the residual gate (icp cpp:184)
+                plane_point_row(n4[h], p[h], st[scan], max_plane_distance, J[0], neg_e[0]);
+            }
+            ra.add<1>(s_row, J, neg_e, fitted);
+        }
+    }
+    ra.store(s_slice, partials + ((size_t)scan * gridDim.x + blockIdx.x) * kAccW);
+}
+
+// The two bodies above under ONE kernel name — what the profiles, the benchmark's counters and the tools look for. DEDUP: a fit per
+// run of equal neighbour sets (true) or per point (false).
+template <int FIT, bool DEDUP>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void icp_plane_accum_kernel(const uint2* __restrict__ tree, const float4* __restrict__ src,
+                                                                 const int* __restrict__ counts, const PoseState* __restrict__ st,
+                                                                 const uint32_t* __restrict__ nn, size_t nn_pitch, int max_n,
+                                                                 double max_plane_distance, double* __restrict__ partials, int kPlanePts,
+                                                                 const int* __restrict__ active, const int* __restrict__ src_of) {
+    if constexpr (DEDUP)
+        plane_accum_per_run<FIT>(tree, src, counts, st, nn, nn_pitch, max_n, max_plane_distance, partials, kPlanePts, active, src_of);
+    else
+        plane_accum_per_point<FIT>(tree, src, counts, st, nn, nn_pitch, max_n, max_plane_distance, partials, kPlanePts, active, src_of);
 }
 
 // K2', P2P: CaculateMatrixHAndBP2P (icp_registration.cpp:57-103), including the /16 on the rotation block.
@@ -577,11 +769,18 @@ int plane_fit_mode() {
     static const int mode = [] { const char* e = getenv("LOCGPU_PLANE_FIT"); return e && *e ? atoi(e) : 1; }();  // not env_int: an empty value is the default too
     return mode;
 }
+// LOCGPU_PLANE_DEDUP (read once): 1 (default) = one plane fit per run of equal neighbour sets (plane_accum_per_run), 0 = a fit per
+// point (plane_accum_per_point). The two give the same bits.
+static bool plane_dedup() {
+    static const bool on = env_int("LOCGPU_PLANE_DEDUP", 1) != 0;
+    return on;
+}
 
 // Points per thread of the accumulate kernels for a batch of n_scans scans of at most max_n points: amortise the block reduction
 // when the batch already fills the chip; 1 for small launches (latency). The plane kernel's reduction is cheap (LDS rows, see
 // there): 4 is as good as 8 and leaves a finer tail; the line and point kernels still pay a 28-value wave reduction per block.
 int icp_accum_split(int method, int max_n, int n_scans) {
+    static_assert(kDedupPP >= 4, "the plane table of plane_accum_per_run has room for the largest plane rung below");
     const long total_blocks = (long)((max_n + kBlock - 1) / kBlock) * n_scans;
     return total_blocks >= 8192 ? (method == LOCGPU_P2PLANE ? 4 : 8) : (total_blocks >= 4096 ? 4 : (total_blocks >= 2048 ? 2 : 1));
 }
@@ -592,10 +791,12 @@ int launch_icp_accum(int method, const AccumArgs& a, hipStream_t s) {
     if (a.split_scans > 0) pts = icp_accum_split(method, a.max_n, a.split_scans);
     const dim3 grid((blocks + pts - 1) / pts, a.active ? a.n_active : a.n_scans);
     if (method == LOCGPU_P2PLANE) {
-        if (plane_fit_mode() == 1)
-            hipLaunchKernelGGL(icp_plane_accum_kernel<1>, grid, dim3(kBlock), 0, s, a.tree, a.src, a.counts, a.st, a.nn, a.nn_pitch, a.max_n, a.gate, a.partials, pts, a.active, a.src_of);
-        else
-            hipLaunchKernelGGL(icp_plane_accum_kernel<0>, grid, dim3(kBlock), 0, s, a.tree, a.src, a.counts, a.st, a.nn, a.nn_pitch, a.max_n, a.gate, a.partials, pts, a.active, a.src_of);
+        const bool secular = plane_fit_mode() == 1;
+        // pts <= kDedupPP always (the static_assert in icp_accum_split); were a larger rung added without the table growing, the launch
+        // would still be right, a fit per point
+        auto kernel = plane_dedup() && pts <= kDedupPP ? (secular ? icp_plane_accum_kernel<1, true> : icp_plane_accum_kernel<0, true>)
+                                    : (secular ? icp_plane_accum_kernel<1, false> : icp_plane_accum_kernel<0, false>);
+        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, a.tree, a.src, a.counts, a.st, a.nn, a.nn_pitch, a.max_n, a.gate, a.partials, pts, a.active, a.src_of);
     } else if (method == LOCGPU_P2PLANE_MAP)
         hipLaunchKernelGGL(icp_mapplane_accum_kernel, grid, dim3(kBlock), 0, s, reinterpret_cast<const double4*>(a.planes), a.src, a.counts, a.st, a.nn, a.max_n, a.gate, a.partials, pts, a.active, a.src_of);
     else if (method == LOCGPU_P2LINE)
