@@ -725,7 +725,7 @@ class Context:
         """Neighbour lists of the batch's most recent search stage as target point indices, [n_scans, max_points, k] (-1 = none)."""
         out = np.empty((batch.n_local, batch.max_points, k), dtype=np.int32)
         self._check(lib().locgpu_debug_batch_nn(self._h, batch._h, int(k), out.ctypes.data))
-        return out  # rows beyond a scan's point count are stale
+        return out  # rows beyond a scan's point count are -1: no search kernel writes them
 
     def search_stats_read(self, reset=True):
         out = np.zeros(4, dtype=np.uint64)

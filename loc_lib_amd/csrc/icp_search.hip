@@ -297,13 +297,17 @@ __global__ __launch_bounds__(kBlock) void count_touched_kernel(uint32_t* __restr
 }
 
 // Test hook: the search stage's slot lists as original point indices (what knn_query_kernel reports), out[(gi * k) + j].
-__global__ __launch_bounds__(kBlock) void nn_to_index_kernel(const uint2* __restrict__ tree, const uint32_t* __restrict__ nn, size_t nn_pitch, size_t n_queries,
-                                                             int k, int32_t* __restrict__ out) {
+// No search kernel writes the rows past a scan's count, and the batch's list buffer is not cleared when it is allocated: those rows
+// hold whatever the memory held, so they are reported as -1 without being read as slots (a ragged batch made this kernel read
+// tree[garbage]: an illegal memory access). A slot beyond the tree is reported as -1 as well instead of being followed.
+__global__ __launch_bounds__(kBlock) void nn_to_index_kernel(const uint2* __restrict__ tree, uint32_t tree_slots, const uint32_t* __restrict__ nn, size_t nn_pitch,
+                                                             const int* __restrict__ counts, int max_n, size_t n_queries, int k, int32_t* __restrict__ out) {
     const size_t gi = (size_t)blockIdx.x * kBlock + threadIdx.x;
     if (gi >= n_queries) return;
+    const bool live = (int)(gi % (size_t)max_n) < counts[gi / (size_t)max_n];
     for (int j = 0; j < k; ++j) {
-        const uint32_t slot = nn[(size_t)j * nn_pitch + gi];
-        out[gi * k + j] = slot == kInvalidSlot ? -1 : (int32_t)(tree[slot].y & 0x3FFFFFFFu);
+        const uint32_t slot = live ? nn[(size_t)j * nn_pitch + gi] : kInvalidSlot;
+        out[gi * k + j] = (slot == kInvalidSlot || slot >= tree_slots) ? -1 : (int32_t)(tree[slot].y & 0x3FFFFFFFu);
     }
 }
 
@@ -335,8 +339,11 @@ bool stamp_build() {
     return on;
 }
 
-void launch_nn_to_index(const uint2* tree, const uint32_t* nn, size_t nn_pitch, size_t n_queries, int k, int32_t* out, hipStream_t s) {
-    hipLaunchKernelGGL(nn_to_index_kernel, dim3((unsigned)((n_queries + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, tree, nn, nn_pitch, n_queries, k, out);
+void launch_nn_to_index(const uint2* tree, size_t tree_slots, const uint32_t* nn, size_t nn_pitch, const int* counts, int max_n, size_t n_queries, int k,
+                        int32_t* out, hipStream_t s) {
+    if (n_queries == 0 || max_n <= 0) return;
+    hipLaunchKernelGGL(nn_to_index_kernel, dim3((unsigned)((n_queries + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, tree, (uint32_t)tree_slots, nn, nn_pitch, counts, max_n,
+                       n_queries, k, out);
 }
 
 void launch_count_touched(uint32_t* touched, size_t n_words, unsigned long long* totals, hipStream_t s) {

@@ -147,7 +147,8 @@ bool search_kernels_lds_ok();
 bool stamp_build();
 // instrumented pass: totals[3] += number of set bits of touched[0..n_words), then touched := 0
 void launch_count_touched(uint32_t* touched, size_t n_words, unsigned long long* totals, hipStream_t s);
-// test hook: slot lists [k][pitch] → original point indices out[query * k + j] (-1 = none)
-void launch_nn_to_index(const uint2* tree, const uint32_t* nn, size_t nn_pitch, size_t n_queries, int k, int32_t* out, hipStream_t s);
+// test hook: slot lists [k][pitch] → original point indices out[query * k + j] (-1 = none, and every row past its scan's count)
+void launch_nn_to_index(const uint2* tree, size_t tree_slots, const uint32_t* nn, size_t nn_pitch, const int* counts, int max_n, size_t n_queries, int k,
+                        int32_t* out, hipStream_t s);
 
 }  // namespace locgpu

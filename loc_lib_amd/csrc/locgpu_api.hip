@@ -504,7 +504,7 @@ int locgpu_debug_batch_nn(locgpu_ctx* ctx, locgpu_batch* b, int k, int32_t* out)
     const size_t nq = (size_t)b->n_scans * b->max_n;
     DevBuf<int32_t> d_out;
     LOCGPU_HIP(ctx, d_out.alloc(nq * k));
-    launch_nn_to_index(ctx->d_tree, b->d_nn, b->pitch, nq, k, d_out, b->stream);
+    launch_nn_to_index(ctx->d_tree, ctx->tree_slots, b->d_nn, b->pitch, b->d_counts, b->max_n, nq, k, d_out, b->stream);
     const hipError_t e = hipMemcpyAsync(out, d_out, nq * k * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream);
     const hipError_t e2 = hipStreamSynchronize(b->stream);
     LOCGPU_HIP(ctx, e);

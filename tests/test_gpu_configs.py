@@ -452,7 +452,7 @@ def test_device_grid_invariants(api, locref, synth, case):
     """Grid ingest on the GPU (csrc/grid_build.hip): holds exactly the tree's leaves, sorted by (tile, cell inside the tile); every
     occupied tile has a record (first leaf, 65 prefix sums of its cells' counts) reachable through the tile hash; the cell edge
     is near the target occupancy."""
-    import ctypes
+    from grid_route_ref import grid_dump
     rng = np.random.RandomState(11)
     if case == "city":
         pts = synth.make_local_map(80000, 3, half=30.0)
@@ -462,21 +462,13 @@ def test_device_grid_invariants(api, locref, synth, case):
     ctx = api.Context(0)
     try:
         ctx.icp_set_target(pts)
-        L = api.lib()
-        L.locgpu_debug_grid_dump.restype = ctypes.c_size_t
-        L.locgpu_debug_grid_dump.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
-                                             ctypes.c_void_p, ctypes.c_size_t]
-        info = np.zeros(9, np.int64)
-        prm = np.zeros(6, np.float32)
-        n = L.locgpu_debug_grid_dump(ctx._h, info.ctypes.data, prm.ctypes.data, None, 0, None, 0, None, 0)
+        d = grid_dump(api, ctx)
+        n, dims, n_occ, n_tocc, cap, tdims = d["n"], d["dims"], d["n_occ"], d["n_tocc"], d["cap"], d["tdims"]
+        prm = np.concatenate([d["origin"], [d["cell"], d["inv_cell"], d["slack"]]]).astype(np.float32)
+        gp, rec, hsh = d["pts"], d["tiles"], d["hash"]
         tree = locref.KdTree(pts)
         assert n == tree.num_leaves
-        dims, n_occ, n_tocc, cap, tdims = info[:3], int(info[3]), int(info[4]), int(info[5]), info[6:9]
-        gp = np.zeros((n, 4), np.float32)
-        rec = np.zeros(n_tocc, dtype=np.dtype([("pt_start", "<u4"), ("tile_lin", "<u4"), ("cstart", "<u2", (66,))]))
         assert rec.dtype.itemsize == 140
-        hsh = np.zeros((cap, 2), np.uint32)
-        L.locgpu_debug_grid_dump(ctx._h, info.ctypes.data, prm.ctypes.data, gp.ctypes.data, gp.size, rec.ctypes.data, rec.nbytes, hsh.ctypes.data, hsh.size)
         c = np.floor((gp[:, :3] - prm[:3]) * prm[4]).astype(np.int64)
         assert np.all(c >= 0) and np.all(c < dims)
         t = c // 4

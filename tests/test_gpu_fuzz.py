@@ -27,6 +27,15 @@ def test_fuzz_search_short(rows):
     assert "mismatching runs 0" in out, out[-2000:]
 
 
+def test_fuzz_search_grid_short():
+    """18 cases = two of each map kind on maps of at most 10^4.5 points, with --grid: the lists of the exact grid stage (bin, scatter
+    and tile kernels, then the tree for what they hand on) against the oracle's exact k-NN as well. The seed is one at which the grid
+    build refuses no case, so all 18 run the stage. Refusals met while choosing it: none — seeds 201, 202 and 203 were tried, 18 cases
+    each, and the grid was built in all 54."""
+    out = _run("fuzz_search.py", "--cases", "18", "--seed", "201", "--grid", "--max-log10-map", "4.5")
+    assert "mismatching runs 0" in out and "grid refused in 0 cases" in out, out[-2000:]
+
+
 def test_fuzz_filters_short():
     assert "mismatches 0" in _run("fuzz_filters.py", "--cases", "400", "--seed", "7")
 

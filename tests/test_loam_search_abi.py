@@ -55,8 +55,11 @@ def test_create_on_refuses_by_argument_without_a_device(api):
 
 def test_facade_keeps_the_stub_and_reports_infinity_before_a_scan_match():
     """tests/cpp/facade_loam_search without arguments: GetFitnessScore() is 0.0f without EnableFitnessScore, +infinity (and a reason
-    in LastError) before the first ScanMatch with it, and InitialPoseSearch without targets is refused — no device is touched."""
+    in LastError) before the first ScanMatch with it, and InitialPoseSearch without targets is refused — no device is touched.
+    The driver is a build product under tests/: made here when it is absent or stale (as test_abi_and_host.py does with
+    facade_scanmatch), so the test does not depend on tests/cpp being left as build() left it."""
     exe = os.path.join(ROOT, "tests", "cpp", "facade_loam_search")
-    assert os.path.exists(exe), "run __graft_entry__.build() first"
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "loc_lib_amd", "host"), "../../tests/cpp/facade_loam_search"], stdout=subprocess.DEVNULL)
+    assert os.path.exists(exe)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, (r.returncode, r.stdout + r.stderr)

@@ -59,16 +59,18 @@ def main():
     ap.add_argument("--cases", type=int, default=200)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--grid", action="store_true", help="also run the exact grid search (search_mode = SEARCH_GRID_EXACT) against the exact oracle lists")
+    ap.add_argument("--max-log10-map", type=float, default=6.2, help="maps hold up to 10^this points (the draw itself is unchanged: one uniform per case)")
     ap.add_argument("--only", type=int, default=-1, help="run only this case of the sequence (the random stream is still consumed case by case)")
     ap.add_argument("--dump", type=str, default="", help="with --only: save the case (cloud, scan, pose) to this .npz")
     a = ap.parse_args()
     rng = np.random.default_rng(a.seed)
     kinds = ["uniform", "clusters", "sheets", "lines", "dups", "lattice", "geometric", "offset", "rings"]  # an odd number: every kind meets both kernels
     bad = 0
+    refused = set()  # --grid: cases in which the grid (or the target under it) was refused
     t0 = time.time()
     for case in range(a.cases):
         kind = kinds[case % len(kinds)]
-        n = int(10 ** rng.uniform(1.0, 6.2))
+        n = int(10 ** (1.0 + rng.uniform(0.0, 1.0) * (a.max_log10_map - 1.0)))
         cloud = make_map(rng, kind, n).astype(np.float32)
         if len(cloud) < 1:
             continue
@@ -84,6 +86,8 @@ def main():
             ctx.icp_set_target(cloud)
         except api.LocGpuError as e:  # depth > 64: refused by design
             print("case %d kind %s n %d: target refused (%s)" % (case, kind, n, str(e)[:80]), flush=True)
+            if a.grid:
+                refused.add(case)  # no target, no grid either
             rng.normal(size=4); rng.uniform(-3, 0.5); rng.normal(0, 1.0, size=3)  # what the case would have consumed (--only stays aligned)
             continue
         tree = locref.KdTree(cloud)
@@ -118,6 +122,7 @@ def main():
                             bad += 1
                             print("MISMATCH (grid) case %d kind %s n %d nq %d k %d: %d lists differ" % (case, kind, n, nq, k, int(np.sum(np.any(gg != want, axis=1)))), flush=True)
                     except api.LocGpuError as e:
+                        refused.add(case)
                         print("grid refused case %d kind %s: %s" % (case, kind, str(e)[:100]), flush=True)
                 if not np.array_equal(got, want):
                     bad += 1
@@ -125,7 +130,7 @@ def main():
                         case, kind, n, tree.num_leaves, tree.depth, nq, k, approximate, int(np.sum(np.any(got != want, axis=1)))), flush=True)
         b.close()
         del ctx
-    print("cases %d, mismatching runs %d, %.1f s" % (a.cases, bad, time.time() - t0))
+    print("cases %d, mismatching runs %d, grid refused in %d cases, %.1f s" % (a.cases, bad, len(refused), time.time() - t0))
     return 1 if bad else 0
 
 
