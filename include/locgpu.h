@@ -580,6 +580,13 @@ LOCGPU_API int locgpu_search_stats_read(locgpu_ctx* ctx, uint64_t out[4], int re
  * KdTree::GetClosestPoint returns (kdtree.cpp:160-165). out[(scan * max_points + i) * k + j]; -1 where there is none
  * (points beyond a scan's count hold stale values). This is how the tests compare the HOT search kernel's lists with the oracle's. */
 LOCGPU_API int locgpu_debug_batch_nn(locgpu_ctx* ctx, locgpu_batch* batch, int k, int32_t* out);
+/* Test hook: the run flags of the search stage of the batch's last Gauss-Newton iteration (an alignment or an H/B evaluation; a
+ * fitness score's search does not count) — out[n_scans * ceil(max_n / 64)], one 64-bit word per 64 points of a
+ * scan, bit j of word w set: point 64 w + j is a leader of the plane fit (its neighbour set is not known to equal the previous
+ * point's), clear: a follower. *written = 1 when that stage wrote flags (the 64-lane walk kernel of a P2Plane search with
+ * LOCGPU_PLANE_RUNFLAGS on), 0 when it did not (the words are then stale or undefined). Words of 64-point groups that lie wholly
+ * past a scan's count are never written. */
+LOCGPU_API int locgpu_debug_batch_run_flags(locgpu_ctx* ctx, locgpu_batch* batch, uint64_t* out, int* written);
 /* Test hook: which of the context's compute streams (0, 1 or 2) the batch's current — begun and not ended — or last alignment runs on.
  * A stream is leased per alignment: locgpu_*_align_batch_begin keeps the batch on its stream while no other alignment in flight uses
  * it and otherwise moves it to the least-loaded one, so that a caller who rotates more batches than there are streams (three in flight

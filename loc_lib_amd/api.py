@@ -29,7 +29,7 @@ ABI_SYMBOLS = [
     "locgpu_transform_cloud", "locgpu_batch_create", "locgpu_batch_destroy", "locgpu_icp_align_batch", "locgpu_ndt_align_batch",
     "locgpu_icp_hb_batch", "locgpu_gn_update", "locgpu_ndt_set_target", "locgpu_ndt_target_info", "locgpu_ndt_dump",
     "locgpu_ndt_align", "locgpu_profile_enable", "locgpu_profile_read", "locgpu_visit_count_enable", "locgpu_visit_count_read",
-    "locgpu_search_stats_read", "locgpu_debug_batch_nn", "locgpu_debug_batch_slot", "locgpu_graph_enable",
+    "locgpu_search_stats_read", "locgpu_debug_batch_nn", "locgpu_debug_batch_run_flags", "locgpu_debug_batch_slot", "locgpu_graph_enable",
     "locgpu_cloud_create", "locgpu_cloud_destroy", "locgpu_cloud_upload", "locgpu_cloud_info", "locgpu_cloud_download", "locgpu_cloud_copy",
     "locgpu_cloud_remove_nan", "locgpu_cloud_voxel_filter", "locgpu_cloud_crop_box", "locgpu_cloud_transform", "locgpu_cloud_append",
     "locgpu_icp_set_target_cloud", "locgpu_icp_set_target_cloud_async", "locgpu_ndt_set_target_cloud", "locgpu_icp_align_cloud", "locgpu_ndt_align_cloud",
@@ -149,7 +149,7 @@ def lib():
             "locgpu_ndt_dump": (i32, [vp, vp, vp, vp, sz, vp]), "locgpu_ndt_align": (i32, [vp, vp, sz, sz, vp, vp, vp]),
             "locgpu_profile_enable": (i32, [vp, i32]), "locgpu_profile_read": (i32, [vp, vp, i32]),
             "locgpu_visit_count_enable": (i32, [vp, i32]), "locgpu_visit_count_read": (i32, [vp, vp, i32]),
-            "locgpu_search_stats_read": (i32, [vp, vp, i32]), "locgpu_debug_batch_nn": (i32, [vp, vp, i32, vp]), "locgpu_debug_batch_slot": (i32, [vp]), "locgpu_graph_enable": (i32, [vp, i32]),
+            "locgpu_search_stats_read": (i32, [vp, vp, i32]), "locgpu_debug_batch_nn": (i32, [vp, vp, i32, vp]), "locgpu_debug_batch_run_flags": (i32, [vp, vp, vp, vp]), "locgpu_debug_batch_slot": (i32, [vp]), "locgpu_graph_enable": (i32, [vp, i32]),
             "locgpu_cloud_create": (i32, [vp, vp]), "locgpu_cloud_destroy": (None, [vp]),
             "locgpu_cloud_upload": (i32, [vp, vp, sz, sz, sz, i32]), "locgpu_cloud_info": (i32, [vp, vp, vp]),
             "locgpu_cloud_download": (i32, [vp, vp, sz, sz, sz]), "locgpu_cloud_copy": (i32, [vp, vp]),
@@ -726,6 +726,15 @@ class Context:
         out = np.empty((batch.n_local, batch.max_points, k), dtype=np.int32)
         self._check(lib().locgpu_debug_batch_nn(self._h, batch._h, int(k), out.ctypes.data))
         return out  # rows beyond a scan's point count are -1: no search kernel writes them
+
+    def debug_batch_run_flags(self, batch):
+        """Run flags of the batch's most recent search stage: (words [n_scans, ceil(max_points / 64)] uint64 — bit j of word w set:
+        point 64 w + j leads a run of equal neighbour sets, clear: it follows the point before it — and whether that stage wrote
+        any; words of 64-point groups wholly past a scan's count are never written)."""
+        out = np.zeros((batch.n_local, (batch.max_points + 63) // 64), dtype=np.uint64)
+        written = ctypes.c_int(0)
+        self._check(lib().locgpu_debug_batch_run_flags(self._h, batch._h, out.ctypes.data, ctypes.byref(written)))
+        return out, bool(written.value)
 
     def search_stats_read(self, reset=True):
         out = np.zeros(4, dtype=np.uint64)

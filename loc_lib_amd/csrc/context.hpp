@@ -163,6 +163,10 @@ struct locgpu_batch {
     bool rings_valid = false;
     locgpu::DevBuf<locgpu::PoseState> d_state;
     locgpu::DevBuf<uint32_t> d_nn;  // [5][pitch]
+    // [n_scans][ceil(max_n / 64)] run flags of the plane fit, written by the 64-lane walk kernel (SearchArgs::run_flags);
+    // run_flags_written: the search stage of the batch's last Gauss–Newton iteration wrote them (launch_local_stage)
+    locgpu::DevBuf<unsigned long long> d_run_flags;
+    bool run_flags_written = false;
     // Shared-source batch (locgpu_batch_create_shared): ONE region of points in d_src, read by every entry — d_src_of holds a zero per
     // entry and travels as SearchArgs / AccumArgs::src_of. The buffers are sized for cap_scans entries of cap_points points; n_scans
     // and max_n are what the current call uses of them (reshape_shared, locgpu_api.hip). split_scans > 0: the accumulate kernels

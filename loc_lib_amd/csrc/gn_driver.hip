@@ -46,6 +46,14 @@ SearchArgs make_search_args(const locgpu_ctx* ctx, const locgpu_batch* b, const 
     return sa;
 }
 
+// LOCGPU_PLANE_RUNFLAGS (read once): 1 (default) = the 64-lane walk kernel of a P2Plane search marks the runs of equal neighbour sets
+// for the plane kernel (SearchArgs::run_flags → AccumArgs::run_flags); 0 = it writes none and the plane kernel finds the runs itself
+// (measurement hook: the two give the same bits).
+static bool plane_run_flags() {
+    static const bool on = env_int("LOCGPU_PLANE_RUNFLAGS", 1) != 0;
+    return on;
+}
+
 void init_state(PoseState& ps, const double pose[7]) {
     std::memset(&ps, 0, sizeof(ps));
     for (int i = 0; i < 4; ++i) ps.q[i] = pose[i];
@@ -119,7 +127,11 @@ int launch_local_stage(locgpu_ctx* ctx, locgpu_batch* b, const LocalStage& w, hi
             }
             sa.touched = ctx->touched_words ? ctx->d_touched.get() : nullptr;
         }
-        const bool ok_search = (grid_mode && !sa.visit_totals) ? launch_icp_search_grid(ctx->grid, sa, *w.grid, s) : launch_icp_search(sa, s);
+        // only the plane kernel reads run flags (the line kernel's search has k = 5 too); the grid search writes none
+        if (prm.method == LOCGPU_P2PLANE && plane_run_flags()) sa.run_flags = b->d_run_flags;
+        bool wrote_flags = false;
+        const bool ok_search = (grid_mode && !sa.visit_totals) ? launch_icp_search_grid(ctx->grid, sa, *w.grid, s) : launch_icp_search(sa, s, &wrote_flags);
+        b->run_flags_written = wrote_flags;
         if (!ok_search) { fail(ctx, LOCGPU_ERR_DEPTH, std::string(w.who) + ": unsupported k/depth"); return -1; }
         if (sa.touched) launch_count_touched(sa.touched, (ctx->tree_slots + 2 + 31) / 32, sa.visit_totals, s);
         ev.mark(s, true);
@@ -128,6 +140,7 @@ int launch_local_stage(locgpu_ctx* ctx, locgpu_batch* b, const LocalStage& w, hi
         aa.active = w.active; aa.n_active = w.n_active;
         aa.src_of = w.src_of;
         aa.split_scans = w.split_scans;
+        if (wrote_flags && prm.method == LOCGPU_P2PLANE) aa.run_flags = b->d_run_flags;
         n_partial_blocks = launch_icp_accum(prm.method, aa, s);
     } else {
         ev.mark(s, true);  // NDT has no separate search kernel: the search slot stays empty

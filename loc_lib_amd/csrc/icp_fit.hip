@@ -116,16 +116,6 @@ __device__ __forceinline__ void plane_row(const D3& n3, const double* R, const D
     J[3] = n3.x; J[4] = n3.y; J[5] = n3.z;
 }
 
-// The five slots of a neighbour list in ascending order: a 9-comparator network in registers. The plane kernels fit the rows in this
-// order, so the plane is a function of the neighbour SET — the same bits whichever distance order the search found the five in.
-__device__ __forceinline__ void sort5(uint32_t (&s)[5]) {
-    auto cx = [&](int a, int b) {
-        const uint32_t lo = min(s[a], s[b]), hi = max(s[a], s[b]);
-        s[a] = lo; s[b] = hi;
-    };
-    cx(0, 1); cx(3, 4); cx(2, 4); cx(2, 3); cx(1, 4); cx(0, 3); cx(0, 2); cx(1, 3); cx(1, 2);
-}
-
 // math::FitPlane (math_utils.h:112-136) over the leaves at the five slots, in the order given, with the five residual checks of
 // icp_registration.cpp:176-182. Returns whether the plane n4 = {n, d} fits.
 // FIT: 0 = plane_null_vector (4-column one-sided Jacobi), 1 = plane_null_vector_secular with the former as its fall-back.
@@ -163,7 +153,7 @@ __device__ __forceinline__ void plane_point_row(const double (&n4)[4], const flo
 }
 
 // K2, P2Plane: IcpRegistration::CaculateMatrixHAndBP2Plane (icp_registration.cpp:161-213) + math::FitPlane, a fit per point: the body
-// of icp_plane_accum_kernel<FIT, false> (LOCGPU_PLANE_DEDUP=0; the default is plane_accum_per_run below, which gives the same bits).
+// of icp_plane_accum_kernel<FIT, 0> (LOCGPU_PLANE_DEDUP=0; the defaults are the per-run bodies below, which give the same bits).
 template <int FIT>
 __device__ __forceinline__ void plane_accum_per_point(const uint2* __restrict__ tree, const float4* __restrict__ src,
                                                                  const int* __restrict__ counts, const PoseState* __restrict__ st,
@@ -351,15 +341,159 @@ __device__ __forceinline__ void plane_accum_per_run(const uint2* __restrict__ tr
     ra.store(s_slice, partials + ((size_t)scan * gridDim.x + blockIdx.x) * kAccW);
 }
 
-// The two bodies above under ONE kernel name — what the profiles, the benchmark's counters and the tools look for. DEDUP: a fit per
-// run of equal neighbour sets (true) or per point (false).
-template <int FIT, bool DEDUP>
+// What the search stage's run flags (SearchArgs::run_flags) tell the threads of a block about their points: words[k] covers points
+// first + 64 k … of the scan (the block's first point is a multiple of 256, so its up to 4 · kDedupPP words are contiguous), `left` =
+// count − first. A bit counts only below the scan's count — a wave of the walk kernel that lies wholly past it wrote no word — and
+// below the block's kPlanePts · 256 points. leader[h]: the flag of point (h, tid); rank[h]: the inclusive count of leader bits in block
+// order up to that point, 0 for a point past the count; n_lead: the block's leaders (uniform). ONE trip to memory: lane k of every
+// wave loads word k, the counts before each word are a prefix sum over those 16 lanes, and a wave takes the word of its points and the
+// count before it from lane 4 h + wave.
+__device__ __forceinline__ void run_flag_ranks(const unsigned long long* __restrict__ words, int left, int kPlanePts, int wave, int lane,
+                                               int (&rank)[kDedupPP], bool (&leader)[kDedupPP], int& n_lead) {
+    static_assert(4 * kDedupPP <= 16, "a word per lane of a 16-lane row");
+    const int k = lane & 15;
+    const int valid = k < 4 * kPlanePts ? left - 64 * k : 0;  // points of word k that exist
+    unsigned long long word = 0ull;
+    if (valid > 0) {
+        word = words[k];
+        if (valid < 64) word &= (1ull << valid) - 1ull;
+    }
+    const int count = __popcll(word);
+    int upto = count;  // leaders in words 0..k
+#pragma unroll
+    for (int d = 1; d < 16; d <<= 1) {
+        const int t = __shfl_up(upto, d, 16);
+        if (k >= d) upto += t;
+    }
+    n_lead = __builtin_amdgcn_readlane(upto, 15);
+#pragma unroll
+    for (int h = 0; h < kDedupPP; ++h) {
+        const int from = 4 * h + wave;  // uniform: the lane that holds the word of this wave's points h
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)word, from), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(word >> 32), from);
+        const int before = __builtin_amdgcn_readlane(upto - count, from);
+        const int mine = h < kPlanePts ? left - 64 * from : 0;
+        const int below = (int)__builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u));  // leaders in the lanes before this one
+        const bool lead = (((lane < 32 ? lo : hi) >> (lane & 31)) & 1u) != 0u;
+        leader[h] = lead;
+        rank[h] = lane < mine ? before + below + (lead ? 1 : 0) : 0;
+    }
+}
+
+// K2, P2Plane, one fit per run of equal neighbour sets, the runs marked by the search stage: the 64-lane walk kernel ends with every
+// query's five slots in registers, its waves are the aligned groups of 64 points this kernel's waves are, and it answers "is my set
+// the set of the point before me?" for a sort and five shuffles behind its main loop (icp_search.hip). Against plane_accum_per_run
+// this body reads one 64-bit word per 64 points instead of 20 bytes per point, sorts nothing, has no s_wcnt and one barrier less in
+// front of the first fit; only the leaders load a list, once. (The ranks wait in LDS over the fit phase as before: working them out
+// again from the words would put one more trip to memory in front of the rows.)
+//   leaders  as the walk kernel flagged them: lane 0 of a wave, a point without a full list, a point whose list the deep pass, the
+//            in-wave exact walk or the redo kernel wrote after the walk (and the point behind it), a point whose set differs from the
+//            previous lane's. A follower therefore has a full list, its leader's set. Not every leader has a list: it gets the
+//            verdict "no fit" without a look at the tree, and with it the zero row.
+//   fit, rows, LDS order, partials: plane_accum_per_run's, so every bit of the sums is.
+// LDS per block: table / s_row 32 768 + s_slice 2 048 + s_lead 2 048 + s_rank 2 048 = 38 912 B, four blocks in 160 KB.
+template <int FIT>
+__device__ __forceinline__ void plane_accum_flagged(const uint2* __restrict__ tree, const float4* __restrict__ src,
+                                                                 const int* __restrict__ counts, const PoseState* __restrict__ st,
+                                                                 const uint32_t* __restrict__ nn, size_t nn_pitch, int max_n,
+                                                                 double max_plane_distance, double* __restrict__ partials, int kPlanePts,
+                                                                 const int* __restrict__ active, const int* __restrict__ src_of,
+                                                                 const unsigned long long* __restrict__ run_flags) {
+    __shared__ double s_plane[kDedupPts][4];
+    __shared__ double s_slice[kBlock / 32][32];
+    __shared__ uint16_t s_lead[kDedupPts];         // leader j → its point of the block, h · 256 + tid; later | kLeadFits
+    __shared__ uint16_t s_rank[kDedupPP][kBlock];  // the ranks of a thread's points over the fit phase
+    double (&s_row)[8][kAccPad] = *reinterpret_cast<double (*)[8][kAccPad]>(&s_plane[0][0]);
+    const int scan = active ? active[blockIdx.y] : (int)blockIdx.y;
+    if (st[scan].done) return;  // uniform per block
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const size_t region = (size_t)scan * max_n;
+    const int first = blockIdx.x * kPlanePts * kBlock;  // point (h, tid) of the block is first + h · 256 + tid
+    const int left = counts[scan] - first;
+    const unsigned long long* words = run_flags + (size_t)scan * ((max_n + 63) >> 6) + (first >> 6);
+    RowAccum ra;
+    ra.init();
+    // As in plane_accum_per_run nothing a later phase can work out again may stay live across the fit phase: the thread index is
+    // taken anew per phase, the ranks wait in LDS.
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    int rank[kDedupPP], n_lead;
+    bool leader[kDedupPP];
+    run_flag_ranks(words, left, kPlanePts, wave, lane, rank, leader, n_lead);
+    n_lead = __builtin_amdgcn_readfirstlane(n_lead);
+#pragma unroll
+    for (int h = 0; h < kDedupPP; ++h) {
+        if (leader[h]) s_lead[rank[h] - 1] = (uint16_t)(h * kBlock + tid);
+        s_rank[h][tid] = (uint16_t)rank[h];
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int base = 0; base < n_lead; base += kBlock) {
+        if (base + wave * 64 < n_lead) {  // scalar: the whole wave has a leader to fit, or none of it
+            const int j = base + tid;
+            if (j < n_lead) {
+                const uint16_t pt = s_lead[j];
+                const size_t gi = region + first + pt;
+                uint32_t slot[5];  // the list's only read
+#pragma unroll
+                for (int k = 0; k < 5; ++k) slot[k] = __builtin_nontemporal_load(&nn[(size_t)k * nn_pitch + gi]);
+                if (slot[4] != kInvalidSlot) {  // nn.size() > 3: k=5 yields 5 or (k > size_) none — no list, no fit
+                    sort5(slot);
+                    double n4[4];
+                    if (fit_plane<FIT>(tree, slot, n4)) s_lead[j] = pt | kLeadFits;  // read by this thread alone until the barrier
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) s_plane[j][c] = n4[c];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    ra.index(tid);
+    double n4[kDedupPP][4];
+    float4 p[kDedupPP];
+    bool fits[kDedupPP];
+#pragma unroll
+    for (int h = 0; h < kDedupPP; ++h) {
+        rank[h] = s_rank[h][tid];
+        fits[h] = false;
+        if (rank[h] > 0) {
+            fits[h] = (s_lead[rank[h] - 1] & kLeadFits) != 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) n4[h][c] = s_plane[rank[h] - 1][c];
+            p[h] = src[src_index(src_of, scan, max_n, first + h * kBlock + tid)];
+        }
+    }
+    __syncthreads();  // every plane is in registers: from here on the table's LDS is s_row
+#pragma unroll
+    for (int h = 0; h < kDedupPP; ++h) {
+        if (h < kPlanePts) {  // uniform per block
+            double J[1][6] = {{0.0, 0.0, 0.0, 0.0, 0.0, 0.0}};
+            double neg_e[1] = {0.0};
+            double fitted = 0.0;
+            if (fits[h]) {
+                fitted = 1.0;  // effective_num++ before the residual gate (icp cpp:184)
+                plane_point_row(n4[h], p[h], st[scan], max_plane_distance, J[0], neg_e[0]);
+            }
+            ra.add<1>(s_row, J, neg_e, fitted);
+        }
+    }
+    ra.store(s_slice, partials + ((size_t)scan * gridDim.x + blockIdx.x) * kAccW);
+}
+
+// The three bodies above under ONE kernel name — what the profiles, the benchmark's counters and the tools look for. RUNS: a fit per
+// point (0), per run of equal neighbour sets found from the lists (1), per run as the search stage flagged them (2; run_flags set).
+template <int FIT, int RUNS>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void icp_plane_accum_kernel(const uint2* __restrict__ tree, const float4* __restrict__ src,
                                                                  const int* __restrict__ counts, const PoseState* __restrict__ st,
                                                                  const uint32_t* __restrict__ nn, size_t nn_pitch, int max_n,
                                                                  double max_plane_distance, double* __restrict__ partials, int kPlanePts,
-                                                                 const int* __restrict__ active, const int* __restrict__ src_of) {
-    if constexpr (DEDUP)
+                                                                 const int* __restrict__ active, const int* __restrict__ src_of,
+                                                                 const unsigned long long* __restrict__ run_flags) {
+    if constexpr (RUNS == 2)
+        plane_accum_flagged<FIT>(tree, src, counts, st, nn, nn_pitch, max_n, max_plane_distance, partials, kPlanePts, active, src_of, run_flags);
+    else if constexpr (RUNS == 1)
         plane_accum_per_run<FIT>(tree, src, counts, st, nn, nn_pitch, max_n, max_plane_distance, partials, kPlanePts, active, src_of);
     else
         plane_accum_per_point<FIT>(tree, src, counts, st, nn, nn_pitch, max_n, max_plane_distance, partials, kPlanePts, active, src_of);
@@ -770,7 +904,8 @@ int plane_fit_mode() {
     return mode;
 }
 // LOCGPU_PLANE_DEDUP (read once): 1 (default) = one plane fit per run of equal neighbour sets (plane_accum_per_run), 0 = a fit per
-// point (plane_accum_per_point). The two give the same bits.
+// point (plane_accum_per_point). The two give the same bits. With 1, a launch whose search stage wrote run flags
+// (LOCGPU_PLANE_RUNFLAGS, gn_driver.hip) takes the runs from them (plane_accum_flagged) — the same bits again.
 static bool plane_dedup() {
     static const bool on = env_int("LOCGPU_PLANE_DEDUP", 1) != 0;
     return on;
@@ -794,9 +929,11 @@ int launch_icp_accum(int method, const AccumArgs& a, hipStream_t s) {
         const bool secular = plane_fit_mode() == 1;
         // pts <= kDedupPP always (the static_assert in icp_accum_split); were a larger rung added without the table growing, the launch
         // would still be right, a fit per point
-        auto kernel = plane_dedup() && pts <= kDedupPP ? (secular ? icp_plane_accum_kernel<1, true> : icp_plane_accum_kernel<0, true>)
-                                    : (secular ? icp_plane_accum_kernel<1, false> : icp_plane_accum_kernel<0, false>);
-        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, a.tree, a.src, a.counts, a.st, a.nn, a.nn_pitch, a.max_n, a.gate, a.partials, pts, a.active, a.src_of);
+        const bool runs = plane_dedup() && pts <= kDedupPP;
+        auto kernel = !runs ? (secular ? icp_plane_accum_kernel<1, 0> : icp_plane_accum_kernel<0, 0>)
+                      : !a.run_flags ? (secular ? icp_plane_accum_kernel<1, 1> : icp_plane_accum_kernel<0, 1>)
+                                     : (secular ? icp_plane_accum_kernel<1, 2> : icp_plane_accum_kernel<0, 2>);
+        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, a.tree, a.src, a.counts, a.st, a.nn, a.nn_pitch, a.max_n, a.gate, a.partials, pts, a.active, a.src_of, a.run_flags);
     } else if (method == LOCGPU_P2PLANE_MAP)
         hipLaunchKernelGGL(icp_mapplane_accum_kernel, grid, dim3(kBlock), 0, s, reinterpret_cast<const double4*>(a.planes), a.src, a.counts, a.st, a.nn, a.max_n, a.gate, a.partials, pts, a.active, a.src_of);
     else if (method == LOCGPU_P2LINE)

@@ -76,6 +76,17 @@ __device__ __forceinline__ void block_reduce_store(double (&acc)[NV], double* __
     }
 }
 
+// The five slots of a neighbour list in ascending order: a 9-comparator network in registers. The plane kernels fit the rows in this
+// order, so the plane is a function of the neighbour SET — the same bits whichever distance order the search found the five in. The
+// walk kernel compares neighbouring queries' sets in the same order (its run flags, icp_search.hip).
+__device__ __forceinline__ void sort5(uint32_t (&s)[5]) {
+    auto cx = [&](int a, int b) {
+        const uint32_t lo = min(s[a], s[b]), hi = max(s[a], s[b]);
+        s[a] = lo; s[b] = hi;
+    };
+    cx(0, 1); cx(3, 4); cx(2, 4); cx(2, 3); cx(1, 4); cx(0, 3); cx(0, 2); cx(1, 3); cx(1, 2);
+}
+
 // list[(*count)++] = value for every lane with `pred`, one atomic per wave (same-address atomics cost ≈10 ns each on gfx950: a
 // per-lane append from millions of queries serialises for milliseconds). Every active lane of the wave must reach the call.
 __device__ __forceinline__ void wave_append(uint32_t* __restrict__ list, unsigned int* __restrict__ count, bool pred, uint32_t value) {

@@ -126,7 +126,8 @@ __global__ __launch_bounds__(64) void icp_search_walk_kernel(const uint2* __rest
                                                              unsigned int tree_bytes, uint32_t dummy, int skip_nonfinite, uint32_t* __restrict__ redo_list,
                                                              unsigned int* __restrict__ redo_count, uint32_t* __restrict__ deep_list,
                                                              unsigned int* __restrict__ deep_count, unsigned long long* __restrict__ search_stats,
-                                                             const int* __restrict__ active, const int* __restrict__ src_of) {
+                                                             const int* __restrict__ active, const int* __restrict__ src_of,
+                                                             unsigned long long* __restrict__ run_flags) {
     extern __shared__ uint2 s_dyn[];
     constexpr int ROWB = LANES * 8;
     static_assert(DF * ROWB >= 64 * 2 * 8, "exact stack columns do not fit");
@@ -164,6 +165,25 @@ __global__ __launch_bounds__(64) void icp_search_walk_kernel(const uint2* __rest
     if (!deep && !slow) {
 #pragma unroll
         for (int j = 0; j < K; ++j) __builtin_nontemporal_store(w.id[j], &nn[(size_t)j * nn_pitch + gi]);
+    }
+    if constexpr (K == 5 && LANES == 64) {
+        // Run flags for the plane fit (icp_fit.hip, plane_accum_flagged): bit `lane` of the wave's word says that this query's
+        // neighbour SET is not known to be the previous lane's — a leader; 0 = a follower, whose plane is its leader's. The wave is the
+        // aligned group of 64 points a wave of the fit kernel takes, the five ids are in registers and the main loop's registers are
+        // free. A lane whose list is written later (deep pass, in-wave exact walk, redo kernel) is a leader and so is the lane behind
+        // it: its ids here mean nothing. Lanes past the scan's count have left and contribute 0; a wave wholly past it writes no word.
+        if (run_flags) {  // uniform; every surviving lane of the wave is here
+            uint32_t set5[5];
+#pragma unroll
+            for (int j = 0; j < 5; ++j) set5[j] = w.id[j];
+            sort5(set5);
+            bool lead = w.id[4] == kInvalidSlot;  // fewer than five found: no list
+#pragma unroll
+            for (int j = 0; j < 5; ++j) lead |= (uint32_t)__shfl_up((int)set5[j], 1, 64) != set5[j];
+            const unsigned long long unknown = __ballot(deep || slow);
+            const unsigned long long word = (__ballot(lead) | unknown | (unknown << 1) | 1ull) & __ballot(true);
+            if (tid == 0) run_flags[(size_t)scan * gridDim.x + blockIdx.x] = word;
+        }
     }
     wave_append(deep_list, deep_count, deep, (uint32_t)gi);
     if (LANES == 16) {
@@ -425,9 +445,9 @@ static void launch_walk_list(const SearchArgs& a, const uint32_t* list, const un
 
 // The search stage of one Gauss–Newton iteration: walk kernel → deep pass → exact redo (the last two over device-side lists that are
 // almost always short). a.redo_count / a.redo_count2 are zero here: the caller clears them before an alignment's first iteration,
-// gn_solve_kernel after every search.
+// gn_solve_kernel after every search. Returns whether the walk kernel wrote a.run_flags: the 64-lane route with k = 5 alone does.
 template <int K, int D, int DF, int WIN>
-static void launch_walk(const SearchArgs& a, hipStream_t s) {
+static bool launch_walk(const SearchArgs& a, hipStream_t s) {
     const bool stamp = stamp_build();
     const uint32_t dummy = (uint32_t)(a.tree_bytes / 8);  // the sentinel leaf behind the tree
     const unsigned int rsrc_bytes = (unsigned int)a.tree_bytes + 16u;
@@ -437,8 +457,8 @@ static void launch_walk(const SearchArgs& a, hipStream_t s) {
         // 16-lane kernel answers its ties itself: no redo launch on the latency path
         dim3 g1((a.max_n + 15) / 16, n_launch);
         hipLaunchKernelGGL((icp_search_walk_kernel<K, D + 2, 16>), g1, dim3(64), (D + 2) * 16 * 8, s, a.tree, a.src, a.counts, a.st, a.nn, a.nn_pitch, a.max_n,
-                           a.alpha_eff, 0, rsrc_bytes, dummy, a.skip_nonfinite, a.redo_list, a.redo_count, a.redo_list2, a.redo_count2, a.search_stats, a.active, a.src_of);
-        return;
+                           a.alpha_eff, 0, rsrc_bytes, dummy, a.skip_nonfinite, a.redo_list, a.redo_count, a.redo_list2, a.redo_count2, a.search_stats, a.active, a.src_of, nullptr);
+        return false;
     }
     // rows 0/1 of the DF stored rows hold the candidates of the un-stored levels, the other DF-2 rows one level each. Queries whose
     // un-stored levels need more than two candidates, or whose candidate descent outgrows the rows, go through a.redo_list2 to the
@@ -454,15 +474,17 @@ static void launch_walk(const SearchArgs& a, hipStream_t s) {
     if (lds_knob) lds_bytes = (unsigned)std::max(env_int("LOCGPU_K1_LDS_BYTES", 0), DF * 64 * 8);
     if (stamp)  // diagnostic build: counts rounds per lane and per wave (search_stats[4], [9], [12], [13]; per query at redo_list[pitch + gi]); timing meaningless
         hipLaunchKernelGGL((icp_search_walk_kernel<K, DF, 64, true, WIN>), g2, dim3(64), DF * 64 * 8, s, a.tree, a.src, a.counts, a.st, a.nn, a.nn_pitch, a.max_n,
-                           a.alpha_eff, Tw, rsrc_bytes, dummy, a.skip_nonfinite, a.redo_list, a.redo_count, a.redo_list2, a.redo_count2, a.search_stats, a.active, a.src_of);
+                           a.alpha_eff, Tw, rsrc_bytes, dummy, a.skip_nonfinite, a.redo_list, a.redo_count, a.redo_list2, a.redo_count2, a.search_stats, a.active, a.src_of, a.run_flags);
     else
         hipLaunchKernelGGL((icp_search_walk_kernel<K, DF, 64, false, WIN>), g2, dim3(64), lds_bytes, s, a.tree, a.src, a.counts, a.st, a.nn, a.nn_pitch, a.max_n,
-                           a.alpha_eff, Tw, rsrc_bytes, dummy, a.skip_nonfinite, a.redo_list, a.redo_count, a.redo_list2, a.redo_count2, a.search_stats, a.active, a.src_of);
+                           a.alpha_eff, Tw, rsrc_bytes, dummy, a.skip_nonfinite, a.redo_list, a.redo_count, a.redo_list2, a.redo_count2, a.search_stats, a.active, a.src_of, a.run_flags);
     launch_walk_list<K, D>(a, a.redo_list2, a.redo_count2, s);
     launch_redo<K, D>(a, s);
+    return K == 5 && a.run_flags != nullptr;
 }
 
-bool launch_icp_search(const SearchArgs& a, hipStream_t s) {
+bool launch_icp_search(const SearchArgs& a, hipStream_t s, bool* wrote_run_flags) {
+    if (wrote_run_flags) *wrote_run_flags = false;
     // Instrumented (visit-counting) runs and trees with non-finite / huge coordinates (no redo list) use the exact one-pass kernel.
     const bool exact_only = a.visit_totals != nullptr || !a.redo_list || !a.redo_list2;
     return with_k<false>(a.k, [&](auto Kc) {
@@ -471,7 +493,8 @@ bool launch_icp_search(const SearchArgs& a, hipStream_t s) {
             if (exact_only) return a.visit_totals ? launch_exact<K, D, true>(a, s) : launch_exact<K, D, false>(a, s);
             all_walk_shapes([&](auto DF, auto WIN) {  // stops at the selected one
                 if (DF() != fast_stack_depth()) return true;
-                launch_walk<K, D, DF(), WIN()>(a, s);
+                const bool wrote = launch_walk<K, D, DF(), WIN()>(a, s);
+                if (wrote_run_flags) *wrote_run_flags = wrote;
                 return false;
             });
         });

@@ -38,6 +38,9 @@ struct SearchArgs {
     // instrumented pass only: bitmap over the tree's 8-byte slots (one bit each, zeroed by the caller, counted and cleared again
     // by launch_count_touched) — which slots this search launch reads at all
     uint32_t* touched = nullptr;
+    // Optional, k = 5: [n_scans][ceil(max_n / 64)] words, one per 64-lane walk wave — bit `lane` set: the query's neighbour set is not
+    // known to be the previous lane's (a leader of the plane fit, AccumArgs::run_flags); nullptr = the walk kernel does nothing new.
+    unsigned long long* run_flags = nullptr;
 };
 
 struct AccumArgs {
@@ -58,9 +61,14 @@ struct AccumArgs {
     int split_scans = 0;
     // LOCGPU_P2PLANE_MAP: the plane table of the target (map_planes.hip), one 32-byte row of four doubles per slot >> 1
     const double* planes = nullptr;
+    // LOCGPU_P2PLANE, optional: the run flags the search launch just before this one on the same batch reported it wrote
+    // (SearchArgs::run_flags); nullptr = the plane kernel finds the runs itself from the lists.
+    const unsigned long long* run_flags = nullptr;
 };
 
-bool launch_icp_search(const SearchArgs& a, hipStream_t s);
+// wrote_run_flags (optional): whether the route taken wrote a.run_flags — the 64-lane walk kernel does; the 16-lane one-scan kernel,
+// the exact kernel and every other search launcher do not
+bool launch_icp_search(const SearchArgs& a, hipStream_t s, bool* wrote_run_flags = nullptr);
 // exact tree traversal over a.redo_list only (the list is filled by a preceding fast / grid kernel)
 bool launch_icp_search_redo(const SearchArgs& a, hipStream_t s);
 // the walk traversal with every level stored (a.alpha_eff) over the queries in `list`, then the exact redo kernel for its ties

@@ -253,6 +253,7 @@ int locgpu::alloc_batch(locgpu_ctx* ctx, int n_scans, size_t max_n, locgpu_batch
               hip_ok(ctx, b->d_state.alloc(n_total), "hipMalloc state") &&
               (!sharded || hip_ok(ctx, b->d_acc.alloc((size_t)kFirstChunk * n_total * kAccW), "hipMalloc acc")) &&  // one slot per iteration of a chunk
               hip_ok(ctx, b->d_nn.alloc(5 * std::max<size_t>(b->pitch, 1)), "hipMalloc nn") &&
+              hip_ok(ctx, b->d_run_flags.alloc(std::max<size_t>((size_t)n_scans * ((max_n + 63) / 64), 1)), "hipMalloc run flags") &&  // a smaller shape of a shared-source batch needs no more words
               hip_ok(ctx, b->d_partials.alloc((size_t)std::max(n_scans, 1) * b->blocks_per_scan * kAccW), "hipMalloc partials") &&
               hip_ok(ctx, b->d_hb.alloc((size_t)n_total * 44), "hipMalloc hb") &&
               hip_ok(ctx, b->d_redo_list.alloc((stamp_build() ? 2 : 1) * std::max<size_t>(b->pitch, 1)), "hipMalloc redo") &&  // diagnostic build: + per-query trip counts
@@ -509,6 +510,18 @@ int locgpu_debug_batch_nn(locgpu_ctx* ctx, locgpu_batch* b, int k, int32_t* out)
     const hipError_t e2 = hipStreamSynchronize(b->stream);
     LOCGPU_HIP(ctx, e);
     LOCGPU_HIP(ctx, e2);
+    return LOCGPU_OK;
+}
+
+int locgpu_debug_batch_run_flags(locgpu_ctx* ctx, locgpu_batch* b, uint64_t* out, int* written) {
+    if (!ctx || !b || b->ctx != ctx || !out || !written) return fail(ctx, LOCGPU_ERR_INVALID, "debug_batch_run_flags: bad arguments");
+    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t words = (size_t)b->n_scans * (((size_t)b->max_n + 63) / 64);
+    const hipError_t e = hipMemcpyAsync(out, b->d_run_flags, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream);
+    const hipError_t e2 = hipStreamSynchronize(b->stream);
+    LOCGPU_HIP(ctx, e);
+    LOCGPU_HIP(ctx, e2);
+    *written = b->run_flags_written ? 1 : 0;
     return LOCGPU_OK;
 }
 
