@@ -382,15 +382,29 @@ __device__ __forceinline__ void run_flag_ranks(const unsigned long long* __restr
 // K2, P2Plane, one fit per run of equal neighbour sets, the runs marked by the search stage: the 64-lane walk kernel ends with every
 // query's five slots in registers, its waves are the aligned groups of 64 points this kernel's waves are, and it answers "is my set
 // the set of the point before me?" for a sort and five shuffles behind its main loop (icp_search.hip). Against plane_accum_per_run
-// this body reads one 64-bit word per 64 points instead of 20 bytes per point, sorts nothing, has no s_wcnt and one barrier less in
-// front of the first fit; only the leaders load a list, once. (The ranks wait in LDS over the fit phase as before: working them out
-// again from the words would put one more trip to memory in front of the rows.)
+// this body reads one 64-bit word per 64 points instead of 20 bytes per point, has no s_wcnt and one barrier less in front of the
+// first fit; only the leaders load a list, once. (The ranks wait in LDS over the fit phase as before: working them out again from the
+// words would put one more trip to memory in front of the rows.) No fit pass starts with a trip for its lists, and the source points
+// are on their way while the block's slowest wave still fits (profiles/plane_trips.md):
 //   leaders  as the walk kernel flagged them: lane 0 of a wave, a point without a full list, a point whose list the deep pass, the
 //            in-wave exact walk or the redo kernel wrote after the walk (and the point behind it), a point whose set differs from the
 //            previous lane's. A follower therefore has a full list, its leader's set. Not every leader has a list: it gets the
 //            verdict "no fit" without a look at the tree, and with it the zero row.
-//   fit, rows, LDS order, partials: plane_accum_per_run's, so every bit of the sums is.
-// LDS per block: table / s_row 32 768 + s_slice 2 048 + s_lead 2 048 + s_rank 2 048 = 38 912 B, four blocks in 160 KB.
+//   lists    right behind the ranks thread (h, tid) loads the five words of every one of its points that leads — all of them in ONE
+//            trip, up to 20 loads in flight, where registers are still free — and parks them, unsorted, in the leader's own table
+//            row s_plane[rank − 1]: 32 B that nothing uses before that leader's fit. One 16-byte and one 4-byte store per list;
+//            rows 32 B apart put eight rows on the 64 banks, so the 16-byte store of 64 consecutive rows uses half the banks of each
+//            pass and the 4-byte one an eighth — a few dozen cycles per wave, nine waves' worth of stores per block.
+//   fit      leader j by thread j % 256 in pass j / 256: the five words from row j, the test for a full list, sort5, fit_plane, n4
+//            as it comes — NaNs of a non-finite leaf included — over the same row, the verdict into s_fits[j]. A row belongs to one
+//            thread from the barrier in front of the fit phase to the one behind it.
+//   points   a wave that has no pass left asks for the source points of its threads, all four in one trip, BEFORE it waits at the
+//            barrier behind the fit phase. A thread without a point asks for the scan's last one: one block of loads under a uniform
+//            branch (a branch per point makes four trips of them: the conversion to double sinks behind each load).
+//   rows, LDS order, partials: plane_accum_per_run's, so every bit of the sums is.
+// LDS per block: table / s_row 32 768 + s_slice 2 048 + s_fits 2 048 + s_rank 2 048 = 38 912 B, four blocks in 160 KB.
+typedef uint4 __attribute__((may_alias)) table_u4;  // a parked list in a row of the plane table
+typedef uint32_t __attribute__((may_alias)) table_u32;
 template <int FIT>
 __device__ __forceinline__ void plane_accum_flagged(const uint2* __restrict__ tree, const float4* __restrict__ src,
                                                                  const int* __restrict__ counts, const PoseState* __restrict__ st,
@@ -398,9 +412,9 @@ __device__ __forceinline__ void plane_accum_flagged(const uint2* __restrict__ tr
                                                                  double max_plane_distance, double* __restrict__ partials, int kPlanePts,
                                                                  const int* __restrict__ active, const int* __restrict__ src_of,
                                                                  const unsigned long long* __restrict__ run_flags) {
-    __shared__ double s_plane[kDedupPts][4];
+    __shared__ double s_plane[kDedupPts][4];       // row j: leader j's five slots until its fit, its plane from then on
     __shared__ double s_slice[kBlock / 32][32];
-    __shared__ uint16_t s_lead[kDedupPts];         // leader j → its point of the block, h · 256 + tid; later | kLeadFits
+    __shared__ uint16_t s_fits[kDedupPts];         // leader j → kLeadFits if its plane fits, else 0 (written by its fit)
     __shared__ uint16_t s_rank[kDedupPP][kBlock];  // the ranks of a thread's points over the fit phase
     double (&s_row)[8][kAccPad] = *reinterpret_cast<double (*)[8][kAccPad]>(&s_plane[0][0]);
     const int scan = active ? active[blockIdx.y] : (int)blockIdx.y;
@@ -421,10 +435,23 @@ __device__ __forceinline__ void plane_accum_flagged(const uint2* __restrict__ tr
     bool leader[kDedupPP];
     run_flag_ranks(words, left, kPlanePts, wave, lane, rank, leader, n_lead);
     n_lead = __builtin_amdgcn_readfirstlane(n_lead);
+    {
+        uint32_t list[kDedupPP][5];  // the lists' only read: a leader bit is set only for a point below the count
 #pragma unroll
-    for (int h = 0; h < kDedupPP; ++h) {
-        if (leader[h]) s_lead[rank[h] - 1] = (uint16_t)(h * kBlock + tid);
-        s_rank[h][tid] = (uint16_t)rank[h];
+        for (int h = 0; h < kDedupPP; ++h)
+            if (leader[h]) {
+#pragma unroll
+                for (int k = 0; k < 5; ++k) list[h][k] = __builtin_nontemporal_load(&nn[(size_t)k * nn_pitch + region + first + h * kBlock + tid]);
+            }
+#pragma unroll
+        for (int h = 0; h < kDedupPP; ++h) {
+            if (leader[h]) {
+                table_u4* row = reinterpret_cast<table_u4*>(&s_plane[rank[h] - 1][0]);
+                row[0] = make_uint4(list[h][0], list[h][1], list[h][2], list[h][3]);
+                reinterpret_cast<table_u32*>(row + 1)[0] = list[h][4];
+            }
+            s_rank[h][tid] = (uint16_t)rank[h];
+        }
     }
     __syncthreads();
 #pragma unroll 1
@@ -432,37 +459,49 @@ __device__ __forceinline__ void plane_accum_flagged(const uint2* __restrict__ tr
         if (base + wave * 64 < n_lead) {  // scalar: the whole wave has a leader to fit, or none of it
             const int j = base + tid;
             if (j < n_lead) {
-                const uint16_t pt = s_lead[j];
-                const size_t gi = region + first + pt;
-                uint32_t slot[5];  // the list's only read
-#pragma unroll
-                for (int k = 0; k < 5; ++k) slot[k] = __builtin_nontemporal_load(&nn[(size_t)k * nn_pitch + gi]);
+                const table_u4* row = reinterpret_cast<const table_u4*>(&s_plane[j][0]);
+                const uint4 head = row[0];
+                uint32_t slot[5] = {head.x, head.y, head.z, head.w, reinterpret_cast<const table_u32*>(row + 1)[0]};
+                uint16_t verdict = 0;
                 if (slot[4] != kInvalidSlot) {  // nn.size() > 3: k=5 yields 5 or (k > size_) none — no list, no fit
                     sort5(slot);
                     double n4[4];
-                    if (fit_plane<FIT>(tree, slot, n4)) s_lead[j] = pt | kLeadFits;  // read by this thread alone until the barrier
+                    if (fit_plane<FIT>(tree, slot, n4)) verdict = kLeadFits;
 #pragma unroll
                     for (int c = 0; c < 4; ++c) s_plane[j][c] = n4[c];
                 }
+                s_fits[j] = verdict;
             }
         }
     }
-    __syncthreads();
     tid = threadIdx.x;
     asm volatile("" : "+v"(tid));
-    ra.index(tid);
     double n4[kDedupPP][4];
     float4 p[kDedupPP];
     bool fits[kDedupPP];
+    if (left > 0) {  // uniform. A thread without a point asks for the scan's last one: ONE block of four loads, no branch per point
+        typedef float quad __attribute__((ext_vector_type(4)));
+        const quad* mine = reinterpret_cast<const quad*>(src + src_index(src_of, scan, max_n, first));
+        quad q[kDedupPP];
+#pragma unroll
+        for (int h = 0; h < kDedupPP; ++h) q[h] = mine[min(h * kBlock + tid, left - 1)];
+#pragma unroll
+        for (int h = 0; h < kDedupPP; ++h) {
+            asm volatile("" : "+v"(q[h]));  // all four asked for before the first conversion to double waits
+            p[h] = make_float4(q[h].x, q[h].y, q[h].z, q[h].w);
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < kDedupPP; ++h) rank[h] = s_rank[h][tid];  // the thread's own stores
+    __syncthreads();
+    ra.index(tid);
 #pragma unroll
     for (int h = 0; h < kDedupPP; ++h) {
-        rank[h] = s_rank[h][tid];
         fits[h] = false;
         if (rank[h] > 0) {
-            fits[h] = (s_lead[rank[h] - 1] & kLeadFits) != 0;
+            fits[h] = s_fits[rank[h] - 1] != 0;
 #pragma unroll
             for (int c = 0; c < 4; ++c) n4[h][c] = s_plane[rank[h] - 1][c];
-            p[h] = src[src_index(src_of, scan, max_n, first + h * kBlock + tid)];
         }
     }
     __syncthreads();  // every plane is in registers: from here on the table's LDS is s_row
