@@ -827,6 +827,74 @@ LOCGPU_API int locgpu_cloud_upload_ranges(locgpu_cloud* c, const locgpu_sensor* 
  * profiled call. */
 LOCGPU_API int locgpu_range_ingest_times(locgpu_ctx* ctx, double out_ms[2]);
 
+/* ---- Range-image ingest, motion-compensated (csrc/range_ingest.hip: rd_pose_kernel, rd_scatter_kernel). The entry points above treat a
+ * scan as if the sensor stood still while it turned. In a range image a column is a firing instant, so the decode can undo the
+ * sensor's motion per column at no extra pass over the points. The reference carries per-point firing times and has the poses at IMU
+ * rate (lio.cpp:428-433) and the interpolation helper math::PoseInterp (LocUtils/include/LocUtils/common/math_utils.h:470-517), but
+ * never applies the helper to a scan; this block does, with the caller's track.
+ *
+ * Sensor timing: col_time[n_cols], seconds from the scan's time origin, one per column, finite, in any order (a sensor may start
+ * mid-turn). Motion of a call: K = n_knots knots per scan (2 <= K <= 256, the same K for every scan of the call); knot_times
+ * [n_scans][K], seconds on the clock of col_time, finite and strictly increasing per scan; knot_poses [n_scans][K][7], the SENSOR's
+ * pose in any fixed frame at each knot, quaternion xyzw then translation, the quaternion taken as given (expected unit, not
+ * normalised); ref_times [n_scans], the instant whose sensor frame scan i is expressed in.
+ * Pose at time q of a scan with knot times t[0..K-1] (PoseInterp's rule, math_utils.h:470-517), everything FP64:
+ *   q > t[K-1]: knot K-1's pose as given. Otherwise j = the first index with t[j] < q <= t[j+1], or 0 when there is none (q == t[0]);
+ *   dt = t[j+1] - t[j]; fabs(dt) < 1e-6: knot j's pose as given (:505-508). Otherwise s = (q - t[j]) / dt, translation
+ *   t_j * (1 - s) + t_{j+1} * s, and the quaternion Eigen's slerp(s, .) (:513): d = a.b (summed left to right), ad = |d|;
+ *   ad >= 1 - DBL_EPSILON: s0 = 1 - s, s1 = s; otherwise th = acos(ad), s0 = sin((1 - s) * th) / sin(th), s1 = sin(s * th) / sin(th);
+ *   d < 0: s1 = -s1; the result s0 * a + s1 * b, not normalised.
+ * Matrix of column c of scan i: (q_r, t_r) = the pose at ref_times[i], (q_c, t_c) = the pose at col_time[c], R = Eigen's
+ * toRotationMatrix; M = [ R_r^T R_c | R_r^T (t_c - t_r) ], row-major 3 x 4 doubles, each dot product summed left to right.
+ * Output of a scan: Conver's two rules (cloud_subscriber.cpp:7-29, point_cloud_utils.h:41-44) and the decode are applied to the RAW
+ * cell exactly as by locgpu_batch_upload_ranges, so the survivors, their order, the counts and the ring bytes are those of the plain
+ * call; the survivor p of cell (g, c) is stored as locgpu_cloud_transform's arithmetic gives it with M[i][c] — per row
+ * (float)(((m0 * x + m1 * y) + m2 * z) + m3) in double — with the w lane +0. Only acos and sin may differ from a host restatement of
+ * the above (tests/range_deskew_ref.py); given the matrices, the points are byte for byte the restatement's.
+ * With every knot the pose (0,0,0,1, 0,0,0) the call leaves the bytes of locgpu_batch_upload_ranges (R of x = y = z = 0 is exactly I
+ * whatever w the slerp leaves). A constant track that is NOT the identity is not expected to: R_r^T R_c is then I only to rounding.
+ * Refusals, decided on the host before anything is written, so that the batch or cloud is exactly as it was (points, counts and rings):
+ * LOCGPU_ERR_INVALID with a text when a col_time[c] or ref_times[i] lies before t[i][0] (nothing is extrapolated the way the
+ * reference's loop would for an early query) or more than 0.5 s behind t[i][K-1] (PoseInterp's time_th) — compared through the
+ * minimum and maximum of col_time, O(n_scans) — for a sensor without column times, K out of range, knot times that are not finite or
+ * do not increase, a reference time that is not finite, a NULL motion or a NULL array inside it; and every refusal of the plain call,
+ * the capacity one included.
+ * Out of scope: clouds with per-point time fields (a per-point slerp kernel would be a later entry point on the same device
+ * function); per-laser time offsets inside a column; estimating the motion (the caller supplies it: ESKF states, or the matcher's
+ * previous two poses); re-compensating a batch that is already decoded; an asynchronous form; sharded and shared-source batches; the
+ * C++ facade; bench.py. */
+typedef struct locgpu_sweep_motion {
+    int32_t n_knots, reserved;
+    const double* knot_times;
+    const double* knot_poses;
+    const double* ref_times;
+} locgpu_sweep_motion;
+/* The firing time of every column, for the pose lookup of math_utils.h:470-517 at decode (cloud_subscriber.cpp:7-29): the table is
+ * copied into HBM before the call returns and replaces an earlier one. LOCGPU_ERR_INVALID, with a text, for a NULL sensor or table and
+ * an entry that is not finite (the sensor then keeps the table it had). */
+LOCGPU_API int locgpu_sensor_set_col_times(locgpu_sensor* s, const double* col_time /* n_cols */);
+/* locgpu_batch_upload_ranges (Conver's survivors, cloud_subscriber.cpp:7-29) with every survivor moved into the sensor frame of
+ * ref_times[i] by its column's matrix (PoseInterp, math_utils.h:470-517), as defined above. Everything the plain call promises holds:
+ * blocking, one pass for all scans, the rings stay resident, no atomics decide a position, and results do not depend on n_scans or on
+ * a scan's place in the batch. One more kernel ahead of the four: rd_pose_kernel writes n_scans * n_cols matrices (96 B each) into a
+ * grow-only table on the context; the scatter applies them to survivors only. */
+LOCGPU_API int locgpu_batch_upload_ranges_deskew(locgpu_batch* b, const locgpu_sensor* s, const uint16_t* const* images /* n_scans */,
+                                                 const locgpu_sweep_motion* motion, int32_t* out_counts /* n_scans or NULL */);
+/* The streaming Lio form: locgpu_cloud_upload_ranges (cloud_subscriber.cpp:7-29) with the motion of ONE scan (math_utils.h:470-517;
+ * knot_times [K], knot_poses [K][7], ref_times [1]); equal to the batch form's scan byte for byte, ring_out included. A refusal leaves
+ * the cloud as it was. */
+LOCGPU_API int locgpu_cloud_upload_ranges_deskew(locgpu_cloud* c, const locgpu_sensor* s, const uint16_t* image, const locgpu_sweep_motion* motion,
+                                                 uint8_t* ring_out /* n_rings * n_cols or NULL */, size_t* n);
+/* For tests and tools, as locgpu_ndt_dump: the matrices of scan `scan` (PoseInterp at every column, math_utils.h:470-517, for the decode
+ * of cloud_subscriber.cpp:7-29) as the context's most recent deskewed call computed them, n_cols * 12 doubles. *n_cols_out (optional) =
+ * the number of columns; out == NULL returns it alone. LOCGPU_ERR_INVALID before any such call, for a scan index out of range and
+ * capacity < n_cols * 12. */
+LOCGPU_API int locgpu_range_deskew_matrices(locgpu_ctx* ctx, int scan, double* out /* n_cols * 12 */, size_t capacity, size_t* n_cols_out);
+/* Measurement (tools/range_deskew_time.py): with locgpu_profile_enable on, the most recent deskewed call's out_ms[0] = copy stream,
+ * motion and images; out_ms[1] = rd_pose_kernel (math_utils.h:470-517); out_ms[2] = the four decode kernels (cloud_subscriber.cpp:7-29).
+ * Zeros before the first profiled call. locgpu_range_ingest_times keeps reporting the most recent plain call. */
+LOCGPU_API int locgpu_range_deskew_times(locgpu_ctx* ctx, double out_ms[3]);
+
 /* The local map of Lio::AddCloud's keyframe branch (lio.cpp:268-306), kept in HBM: a queue of at most num_kfs world-frame
  * keyframe clouds (scans_in_local_map_) and the voxel-filtered local map (local_map_) that is the next matching target.
  * add_keyframe(scan, pose): key_frame_scan = transform(scan, pose) (pose NULL: scan is already in the world frame); push;

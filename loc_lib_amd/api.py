@@ -57,6 +57,8 @@ ABI_SYMBOLS = [
     "locgpu_clouds_merge", "locgpu_batch_merge", "locgpu_batch_export_cloud",
     "locgpu_sensor_create", "locgpu_sensor_destroy", "locgpu_batch_upload_ranges", "locgpu_batch_download_rings",
     "locgpu_batch_loam_extract_resident", "locgpu_cloud_upload_ranges", "locgpu_range_ingest_times",
+    "locgpu_sensor_set_col_times", "locgpu_batch_upload_ranges_deskew", "locgpu_cloud_upload_ranges_deskew", "locgpu_range_deskew_matrices",
+    "locgpu_range_deskew_times",
 ]
 COMM_ID_BYTES = 128
 NO_INTENSITY = ctypes.c_size_t(-1).value
@@ -103,6 +105,12 @@ class SensorModelC(ctypes.Structure):
     _fields_ = [("n_rings", ctypes.c_int32), ("n_cols", ctypes.c_int32), ("range_scale", ctypes.c_float), ("min_range", ctypes.c_float),
                 ("az_per_ring", ctypes.c_int32), ("reserved", ctypes.c_int32), ("cos_el", ctypes.c_void_p), ("sin_el", ctypes.c_void_p),
                 ("cos_az", ctypes.c_void_p), ("sin_az", ctypes.c_void_p)]
+
+
+class SweepMotionC(ctypes.Structure):
+    """locgpu_sweep_motion."""
+    _fields_ = [("n_knots", ctypes.c_int32), ("reserved", ctypes.c_int32), ("knot_times", ctypes.c_void_p), ("knot_poses", ctypes.c_void_p),
+                ("ref_times", ctypes.c_void_p)]
 
 
 class AlignStats(ctypes.Structure):
@@ -213,6 +221,9 @@ def lib():
             "locgpu_batch_upload_ranges": (i32, [vp, vp, vp, vp]), "locgpu_batch_download_rings": (i32, [vp, i32, vp, sz, vp]),
             "locgpu_batch_loam_extract_resident": (i32, [vp, i32, vp, vp, vp, vp, vp]),
             "locgpu_cloud_upload_ranges": (i32, [vp, vp, vp, vp, vp]), "locgpu_range_ingest_times": (i32, [vp, vp]),
+            "locgpu_sensor_set_col_times": (i32, [vp, vp]), "locgpu_batch_upload_ranges_deskew": (i32, [vp, vp, vp, vp, vp]),
+            "locgpu_cloud_upload_ranges_deskew": (i32, [vp, vp, vp, vp, vp, vp]), "locgpu_range_deskew_matrices": (i32, [vp, i32, vp, sz, vp]),
+            "locgpu_range_deskew_times": (i32, [vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -712,6 +723,21 @@ class Context:
         self._check(lib().locgpu_range_ingest_times(self._h, out.ctypes.data))
         return float(out[0]), float(out[1])
 
+    def range_deskew_times(self):
+        """(copy-stream ms, matrix kernel ms, decode kernels ms) of the most recent upload_ranges_deskew while profile_enable is on
+        (locgpu_range_deskew_times)."""
+        out = np.zeros(3)
+        self._check(lib().locgpu_range_deskew_times(self._h, out.ctypes.data))
+        return float(out[0]), float(out[1]), float(out[2])
+
+    def range_deskew_matrices(self, scan):
+        """The [n_cols, 3, 4] float64 matrices of scan ``scan`` as the most recent deskewed ingest computed them (locgpu_range_deskew_matrices)."""
+        n = ctypes.c_size_t(0)
+        self._check(lib().locgpu_range_deskew_matrices(self._h, int(scan), None, 0, ctypes.byref(n)))
+        out = np.zeros((int(n.value), 3, 4))
+        self._check(lib().locgpu_range_deskew_matrices(self._h, int(scan), out.ctypes.data, out.size, ctypes.byref(n)))
+        return out
+
     def visit_count_enable(self, on=True):
         self._check(lib().locgpu_visit_count_enable(self._h, int(on)))
 
@@ -830,6 +856,17 @@ class Cloud:
         self.ctx._check(lib().locgpu_cloud_upload_ranges(self._h, sensor._h, img.ctypes.data, rings.ctypes.data if with_rings else None, ctypes.byref(n)))
         return np.ascontiguousarray(rings[:int(n.value)]) if with_rings else None
 
+    def upload_ranges_deskew(self, sensor, image, knot_times, knot_poses, ref_time, with_rings=True):
+        """upload_ranges with the scan motion-compensated per column (locgpu_cloud_upload_ranges_deskew): knot_times [K], knot_poses
+        [K, 7] (the sensor's pose, quaternion xyzw + translation), ref_time the instant whose sensor frame the cloud is expressed in."""
+        img = sensor.model.image(image)
+        motion, keep = sweep_motion(1, knot_times, knot_poses, [ref_time])
+        rings = np.zeros(sensor.model.cells, np.uint8) if with_rings else None
+        n = ctypes.c_size_t(0)
+        self.ctx._check(lib().locgpu_cloud_upload_ranges_deskew(self._h, sensor._h, img.ctypes.data, ctypes.byref(motion), rings.ctypes.data if with_rings else None,
+                                                                ctypes.byref(n)))
+        return np.ascontiguousarray(rings[:int(n.value)]) if with_rings else None
+
     def loam_extract(self, ring, num_scan=16):
         """LoamFeatureExtract::Extract on a resident cloud: returns (edge, surf) resident clouds."""
         ring = np.ascontiguousarray(ring, dtype=np.uint8)
@@ -876,6 +913,17 @@ class SensorModel:
         return a
 
 
+def sweep_motion(n_scans, knot_times, knot_poses, ref_times):
+    """(locgpu_sweep_motion, the arrays it points into) for n_scans scans: knot_times [n_scans, K], knot_poses [n_scans, K, 7], ref_times
+    [n_scans], all float64. Keep the second value alive while the struct is in use."""
+    t = np.ascontiguousarray(knot_times, dtype=np.float64).reshape(n_scans, -1)
+    p = np.ascontiguousarray(knot_poses, dtype=np.float64).reshape(n_scans, -1)
+    r = np.ascontiguousarray(ref_times, dtype=np.float64).reshape(-1)
+    if p.shape[1] != 7 * t.shape[1] or len(r) != n_scans:
+        raise ValueError("a sweep motion holds K times and K poses of 7 per scan, and one reference time per scan")
+    return SweepMotionC(t.shape[1], 0, t.ctypes.data, p.ctypes.data, r.ctypes.data), (t, p, r)
+
+
 class Sensor:
     """A sensor model resident in HBM (locgpu_sensor): what Batch.upload_ranges and Cloud.upload_ranges decode with."""
 
@@ -884,6 +932,14 @@ class Sensor:
         self._h = ctypes.c_void_p()
         m = model.c_struct()
         ctx._check(lib().locgpu_sensor_create(ctx._h, ctypes.byref(m), ctypes.byref(self._h)))
+
+    def set_col_times(self, col_time):
+        """The firing time of every column, seconds from the scan's time origin (locgpu_sensor_set_col_times); what the deskewed
+        ingests look the sensor's pose up with."""
+        t = np.ascontiguousarray(col_time, dtype=np.float64)
+        if t.shape != (self.model.n_cols,):
+            raise ValueError("one time per column: %d" % self.model.n_cols)
+        self.ctx._check(lib().locgpu_sensor_set_col_times(self._h, t.ctypes.data))
 
     def close(self):
         if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
@@ -1087,6 +1143,23 @@ class Batch:
         ptrs = (ctypes.c_void_p * max(len(images), 1))(*[a.ctypes.data for a in images])
         counts = np.zeros(self.n_local, np.int32)
         rc = lib().locgpu_batch_upload_ranges(self._h, sensor._h, ptrs, counts.ctypes.data)
+        if rc != 0:
+            err = LocGpuError(rc, lib().locgpu_last_error(self.ctx._h).decode())
+            err.counts = counts
+            raise err
+        return counts
+
+    def upload_ranges_deskew(self, sensor, images, knot_times, knot_poses, ref_times):
+        """upload_ranges with every scan motion-compensated per column (locgpu_batch_upload_ranges_deskew): knot_times [n, K],
+        knot_poses [n, K, 7] (the sensor's pose at each knot, quaternion xyzw + translation), ref_times [n]. Same returns and errors."""
+        self.upload_wait()
+        images = [sensor.model.image(a) for a in images]
+        if len(images) != self.n_local:
+            raise ValueError("upload_ranges_deskew needs %d images" % self.n_local)
+        motion, keep = sweep_motion(self.n_local, knot_times, knot_poses, ref_times)
+        ptrs = (ctypes.c_void_p * max(len(images), 1))(*[a.ctypes.data for a in images])
+        counts = np.zeros(self.n_local, np.int32)
+        rc = lib().locgpu_batch_upload_ranges_deskew(self._h, sensor._h, ptrs, ctypes.byref(motion), counts.ctypes.data)
         if rc != 0:
             err = LocGpuError(rc, lib().locgpu_last_error(self.ctx._h).decode())
             err.counts = counts

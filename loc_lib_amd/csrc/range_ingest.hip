@@ -24,10 +24,22 @@
 //
 // Scratch, grow-only on the context (freed by range_ingest_free): 2 B per cell pinned + 2 B per cell in HBM, 8 B per tile, 4 B per
 // scan (+ pinned), and for the cloud form 1 B per cell of ring bytes (+ pinned).
+//
+// Motion compensation at decode (include/locgpu.h, "Range-image ingest, motion-compensated"): the *_deskew entry points
+// run the same pass with one kernel ahead of it and another scatter —
+//
+//   matrices one block per scan: the knots staged in LDS, math::PoseInterp (math_utils.h:470-517) at the reference         rd_pose_kernel
+//            time once and at every column's time, M = [R_rᵀ·R_c | R_rᵀ·(t_c − t_r)] → 12 doubles per column
+//   scatter  ri_scatter_kernel with the survivor's column carried through the compaction; the final store loop applies     rd_scatter_kernel
+//            the column's matrix (transform_point_f64), so only survivors are transformed
+//
+// — so survivors, order, counts and ring bytes are the plain call's. Scratch: 96 B per column and scan for the matrices, 8 B per knot
+// value (+ pinned). The plain entry points launch the four kernels above and nothing else.
 #include "range_ingest.hpp"
 
 #include <algorithm>
 #include <atomic>
+#include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -146,12 +158,16 @@ __global__ __launch_bounds__(kRI) void ri_verdict_kernel(int32_t* __restrict__ r
     }
 }
 
-// Tile (blockIdx.x, scan blockIdx.y) → dst + s · dst_max_n + tile offset, {x, y, z, +0}, and the ring bytes beside it.
-__global__ __launch_bounds__(kRI) void ri_scatter_kernel(SensorView v, const uint16_t* __restrict__ img, uint32_t n_tiles, const uint32_t* __restrict__ tile_off,
-                                                         const int32_t* __restrict__ res, int n_scans, uint32_t dst_max_n, float4* __restrict__ dst,
-                                                         unsigned char* __restrict__ dst_ring, int* __restrict__ dst_counts) {
+// Tile (blockIdx.x, scan blockIdx.y) → dst + s · dst_max_n + tile offset, {x, y, z, +0}, and the ring bytes beside it: the body of both
+// scatter kernels. kDeskew: the survivor's column is carried through the compaction beside its ring byte and the final store loop
+// applies the column's matrix (mats [n_scans][n_cols][12], rd_pose_kernel), so only survivors are transformed.
+template <bool kDeskew>
+__device__ __forceinline__ void scatter_tile(const SensorView& v, const uint16_t* __restrict__ img, uint32_t n_tiles, const uint32_t* __restrict__ tile_off,
+                                             const int32_t* __restrict__ res, int n_scans, uint32_t dst_max_n, const double* __restrict__ mats, float4* __restrict__ dst,
+                                             unsigned char* __restrict__ dst_ring, int* __restrict__ dst_counts) {
     if (res[n_scans] == 0) return;  // the same for every thread of the grid
     __shared__ float4 s_pts[kTile];
+    __shared__ uint16_t s_col[kDeskew ? kTile : 1];  // n_cols <= 12 288
     __shared__ unsigned char s_ring[kTile];
     __shared__ uint32_t s_wave[kRI / 64];
     const uint32_t s = blockIdx.y, tile = blockIdx.x;
@@ -167,6 +183,7 @@ __global__ __launch_bounds__(kRI) void ri_scatter_kernel(SensorView v, const uin
     for (int j = 0; j < kCellsPerLane; ++j) {
         if (mask & (1u << j)) {
             s_pts[at] = pts[j];
+            if constexpr (kDeskew) s_col[at] = (uint16_t)(base + j - ring[j] * v.n_cols);  // cell = ring · n_cols + column
             s_ring[at] = (unsigned char)ring[j];
             ++at;
         }
@@ -175,9 +192,113 @@ __global__ __launch_bounds__(kRI) void ri_scatter_kernel(SensorView v, const uin
     // tile_off + total <= res[s] <= dst_max_n (the verdict): every store below is inside scan s's rows
     const size_t out = (size_t)s * dst_max_n + tile_off[(size_t)s * n_tiles + tile];
     for (uint32_t i = threadIdx.x; i < total; i += kRI) {
-        dst[out + i] = s_pts[i];
+        if constexpr (kDeskew)
+            dst[out + i] = transform_point_f64(s_pts[i], mats + ((size_t)s * v.n_cols + s_col[i]) * 12, true);  // every survivor is finite
+        else
+            dst[out + i] = s_pts[i];
         dst_ring[out + i] = s_ring[i];
     }
+}
+
+__global__ __launch_bounds__(kRI) void ri_scatter_kernel(SensorView v, const uint16_t* __restrict__ img, uint32_t n_tiles, const uint32_t* __restrict__ tile_off,
+                                                         const int32_t* __restrict__ res, int n_scans, uint32_t dst_max_n, float4* __restrict__ dst,
+                                                         unsigned char* __restrict__ dst_ring, int* __restrict__ dst_counts) {
+    scatter_tile<false>(v, img, n_tiles, tile_off, res, n_scans, dst_max_n, nullptr, dst, dst_ring, dst_counts);
+}
+
+// ---- Motion compensation at decode (include/locgpu.h, "Range-image ingest, motion-compensated") ------------------------------------
+constexpr int kMaxKnots = 256;
+constexpr double kInterpTimeTh = 0.5;  // PoseInterp's time_th, math_utils.h:471
+
+// math::PoseInterp (math_utils.h:470-517) on the K knots staged in LDS, t[K] and p[K][7] (quaternion xyzw, translation): the pose at
+// time q. The times increase strictly, so the first interval with t[j] < q <= t[j+1] is found by bisection. Everything but acos and
+// sin is one IEEE double operation per line of the header's definition (the build compiles with contraction off).
+__device__ __forceinline__ void rd_pose_at(const double* t, const double* p, int K, double q, double (&out)[7]) {
+    if (q > t[K - 1]) {  // :478-483, the caller has refused anything later than time_th behind the last knot
+#pragma unroll
+        for (int i = 0; i < 7; ++i) out[i] = p[7 * (K - 1) + i];
+        return;
+    }
+    int lo = 0, hi = K;  // the number of knots with t < q
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (t[mid] < q) lo = mid + 1; else hi = mid;
+    }
+    const int j = lo > 0 ? lo - 1 : 0;  // q <= t[K-1]: lo <= K - 1, so j + 1 <= K - 1
+    const double* a = p + 7 * j;
+    const double* b = a + 7;
+    const double dt = t[j + 1] - t[j];
+    if (fabs(dt) < 1e-6) {  // :505-508
+#pragma unroll
+        for (int i = 0; i < 7; ++i) out[i] = a[i];
+        return;
+    }
+    const double s = (q - t[j]) / dt;
+    // Eigen's QuaternionBase::slerp (:513)
+    const double d = ((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]) + a[3] * b[3];
+    const double ad = fabs(d);
+    double s0, s1;
+    if (ad >= 1.0 - DBL_EPSILON) {
+        s0 = 1.0 - s;
+        s1 = s;
+    } else {
+        const double th = acos(ad), st = sin(th);
+        s0 = sin((1.0 - s) * th) / st;
+        s1 = sin(s * th) / st;
+    }
+    if (d < 0.0) s1 = -s1;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) out[i] = s0 * a[i] + s1 * b[i];
+    const double u = 1.0 - s;
+#pragma unroll
+    for (int i = 4; i < 7; ++i) out[i] = a[i] * u + b[i] * s;  // :514
+}
+
+// Scan blockIdx.x: M[c] = [ R_rᵀ·R_c | R_rᵀ·(t_c − t_r) ] for each of its columns, row-major 3×4, every dot product summed left to
+// right. motion = times [n_scans][K] | poses [n_scans][K][7] | ref_times [n_scans]. One block per scan, so that the knots are staged
+// and the reference-time pose is computed once per scan; its threads walk the columns.
+__global__ __launch_bounds__(kRI) void rd_pose_kernel(const double* __restrict__ motion, int n_scans, int K, const double* __restrict__ col_time, uint32_t n_cols,
+                                                      double* __restrict__ mats) {
+    __shared__ double s_t[kMaxKnots];
+    __shared__ double s_p[kMaxKnots * 7];
+    __shared__ double s_ref[12];  // R_r, t_r
+    const uint32_t s = blockIdx.x;
+    const double* g_t = motion + (size_t)s * K;
+    const double* g_p = motion + (size_t)n_scans * K + (size_t)s * K * 7;
+    for (int i = threadIdx.x; i < K; i += kRI) s_t[i] = g_t[i];
+    for (int i = threadIdx.x; i < 7 * K; i += kRI) s_p[i] = g_p[i];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double pr[7];
+        rd_pose_at(s_t, s_p, K, motion[(size_t)n_scans * K * 8 + s], pr);
+        quat_to_R(pr, s_ref);
+        s_ref[9] = pr[4];
+        s_ref[10] = pr[5];
+        s_ref[11] = pr[6];
+    }
+    __syncthreads();
+    for (uint32_t c = threadIdx.x; c < n_cols; c += kRI) {
+        double pc[7], Rc[9];
+        rd_pose_at(s_t, s_p, K, col_time[c], pc);
+        quat_to_R(pc, Rc);
+        const double d0 = pc[4] - s_ref[9], d1 = pc[5] - s_ref[10], d2 = pc[6] - s_ref[11];
+        double* m = mats + ((size_t)s * n_cols + c) * 12;  // inside the table: ensure_deskew sized it for n_scans · n_cols matrices
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const double a0 = s_ref[r], a1 = s_ref[3 + r], a2 = s_ref[6 + r];  // column r of R_r = row r of R_rᵀ
+            m[4 * r + 0] = (a0 * Rc[0] + a1 * Rc[3]) + a2 * Rc[6];
+            m[4 * r + 1] = (a0 * Rc[1] + a1 * Rc[4]) + a2 * Rc[7];
+            m[4 * r + 2] = (a0 * Rc[2] + a1 * Rc[5]) + a2 * Rc[8];
+            m[4 * r + 3] = (a0 * d0 + a1 * d1) + a2 * d2;
+        }
+    }
+}
+
+// ri_scatter_kernel with every survivor moved by its column's matrix; positions, counts and ring bytes are ri_scatter_kernel's.
+__global__ __launch_bounds__(kRI) void rd_scatter_kernel(SensorView v, const uint16_t* __restrict__ img, uint32_t n_tiles, const uint32_t* __restrict__ tile_off,
+                                                         const int32_t* __restrict__ res, int n_scans, uint32_t dst_max_n, const double* __restrict__ mats,
+                                                         float4* __restrict__ dst, unsigned char* __restrict__ dst_ring, int* __restrict__ dst_counts) {
+    scatter_tile<true>(v, img, n_tiles, tile_off, res, n_scans, dst_max_n, mats, dst, dst_ring, dst_counts);
 }
 
 int hip_fail(locgpu_ctx* ctx, hipError_t e, const char* what) {
@@ -201,6 +322,17 @@ struct RangeIngestScratch {
     Event prof[4];
     bool prof_valid = false;
     double prof_ms[2] = {0, 0};
+    // The deskewed calls: the motion of a call, times [n_scans][K] | poses [n_scans][K][7] | ref_times [n_scans], and the matrices
+    // rd_pose_kernel made of it, [mats_scans][mats_cols][12], kept for locgpu_range_deskew_matrices. Events of their own, so that
+    // locgpu_range_ingest_times goes on reporting the most recent PLAIN call: copies [0,1] on the copy stream; the matrix kernel
+    // [2,3] and the four decode kernels [3,4] on the compute stream.
+    PinnedBuf<double> h_motion;
+    DevBuf<double> d_motion, d_mats;
+    int mats_scans = 0;
+    uint32_t mats_cols = 0;
+    Event dprof[5];
+    bool dprof_valid = false;
+    double dprof_ms[3] = {0, 0, 0};
 };
 
 namespace {
@@ -229,6 +361,31 @@ hipError_t ensure(locgpu_ctx* ctx, size_t n_scans, size_t cells_pad, size_t n_ti
         LOCGPU_TRY(S->h_res.alloc(cap));
     }
     return S->staged.ensure();
+}
+
+hipError_t ensure_deskew(locgpu_ctx* ctx, size_t n_scans, size_t K, size_t n_cols) {
+    RangeIngestScratch* S = scratch(ctx);
+    const size_t motion = n_scans * (8 * K + 1), mats = n_scans * n_cols * 12;
+    if (motion > S->d_motion.cap()) {
+        const size_t cap = with_headroom(motion);
+        LOCGPU_TRY(S->h_motion.alloc(cap));
+        LOCGPU_TRY(S->d_motion.alloc(cap));
+    }
+    if (mats > S->d_mats.cap()) {
+        S->mats_scans = 0;
+        LOCGPU_TRY(S->d_mats.alloc(with_headroom(mats)));
+    }
+    return hipSuccess;
+}
+
+// The call's knots and reference times → pinned staging → HBM on the copy stream, ahead of the images: `staged` covers them too.
+hipError_t stage_motion(locgpu_ctx* ctx, const locgpu_sweep_motion& m, int n_scans) {
+    RangeIngestScratch* S = ctx->ringest;
+    const size_t nk = (size_t)n_scans * m.n_knots;
+    std::memcpy(S->h_motion, m.knot_times, nk * sizeof(double));
+    std::memcpy(S->h_motion + nk, m.knot_poses, 7 * nk * sizeof(double));
+    std::memcpy(S->h_motion + 8 * nk, m.ref_times, (size_t)n_scans * sizeof(double));
+    return hipMemcpyAsync(S->d_motion, S->h_motion, (8 * nk + n_scans) * sizeof(double), hipMemcpyHostToDevice, ctx->copy_stream);
 }
 
 // The images → pinned staging → HBM on the context's copy stream, in groups of scans of about 4 MB: a few host threads copy groups
@@ -262,24 +419,38 @@ hipError_t stage_images(locgpu_ctx* ctx, const uint16_t* const* images, int n_sc
     return hipStreamWaitEvent(ctx->stream, S->staged, 0);
 }
 
+// dk: the checked motion of a deskewed call (check_motion), or NULL.
 // The pass for n_scans images into dst [n_scans][dst_max_n] (+ ring bytes, + device counts unless dst_counts is NULL), on
 // ctx->stream; the counts and the verdict are on their way to S->h_res when it returns.
 hipError_t ingest_dev(locgpu_ctx* ctx, const locgpu_sensor* sn, const uint16_t* const* images, int n_scans, float4* dst, unsigned char* dst_ring, int* dst_counts,
-                      uint32_t dst_max_n) {
+                      uint32_t dst_max_n, const locgpu_sweep_motion* dk = nullptr) {
     const size_t cells = sn->cells(), cells_pad = (cells + kCellsPerLane - 1) / kCellsPerLane * kCellsPerLane;
     const uint32_t n_tiles = (uint32_t)((cells + kTile - 1) / kTile);
     LOCGPU_TRY(ensure(ctx, (size_t)n_scans, cells_pad, n_tiles));
+    if (dk) LOCGPU_TRY(ensure_deskew(ctx, (size_t)n_scans, (size_t)dk->n_knots, sn->n_cols));
     RangeIngestScratch* S = ctx->ringest;
     const bool prof = ctx->profile != 0;
-    S->prof_valid = false;
+    // a deskewed call keeps its times apart: ev[0..1] round the copies, ev[2] ahead of the kernels, ev[3] behind them, and
+    // dprof[3] doubles as the mark between the matrix kernel and the decode
+    Event* ev[4] = {&S->prof[0], &S->prof[1], &S->prof[2], &S->prof[3]};
+    if (dk) {
+        ev[0] = &S->dprof[0], ev[1] = &S->dprof[1], ev[2] = &S->dprof[2], ev[3] = &S->dprof[4];
+        S->dprof_valid = false;
+        S->mats_scans = 0;
+    } else {
+        S->prof_valid = false;
+    }
     if (prof) {
         for (Event& e : S->prof) LOCGPU_TRY(e.ensure(hipEventDefault));
-        LOCGPU_TRY(hipEventRecord(S->prof[0], ctx->copy_stream));
+        if (dk)
+            for (Event& e : S->dprof) LOCGPU_TRY(e.ensure(hipEventDefault));
+        LOCGPU_TRY(hipEventRecord(*ev[0], ctx->copy_stream));
     }
+    if (dk) LOCGPU_TRY(stage_motion(ctx, *dk, n_scans));
     LOCGPU_TRY(stage_images(ctx, images, n_scans, cells, cells_pad));
     if (prof) {
-        LOCGPU_TRY(hipEventRecord(S->prof[1], ctx->copy_stream));
-        LOCGPU_TRY(hipEventRecord(S->prof[2], ctx->stream));
+        LOCGPU_TRY(hipEventRecord(*ev[1], ctx->copy_stream));
+        LOCGPU_TRY(hipEventRecord(*ev[2], ctx->stream));
     }
     const float* t = sn->d_tables;
     SensorView v;
@@ -294,15 +465,26 @@ hipError_t ingest_dev(locgpu_ctx* ctx, const locgpu_sensor* sn, const uint16_t* 
     v.range_scale = sn->range_scale;
     v.min_range = sn->min_range;
     hipStream_t s = ctx->stream;
+    if (dk) {
+        hipLaunchKernelGGL(rd_pose_kernel, dim3(n_scans), dim3(kRI), 0, s, S->d_motion.get(), n_scans, dk->n_knots, sn->d_col_time.get(), sn->n_cols, S->d_mats.get());
+        LOCGPU_TRY(hipGetLastError());
+        S->mats_scans = n_scans;
+        S->mats_cols = sn->n_cols;
+        if (prof) LOCGPU_TRY(hipEventRecord(S->dprof[3], s));
+    }
     hipLaunchKernelGGL(ri_count_kernel, dim3(n_tiles, n_scans), dim3(kRI), 0, s, v, S->d_img.get(), n_tiles, S->tile_cnt.get());
     hipLaunchKernelGGL(ri_offsets_kernel, dim3(n_scans), dim3(kRI), 0, s, S->tile_cnt.get(), n_tiles, S->tile_off.get(), S->res.get());
     hipLaunchKernelGGL(ri_verdict_kernel, dim3(1), dim3(kRI), 0, s, S->res.get(), n_scans, dst_max_n);
-    hipLaunchKernelGGL(ri_scatter_kernel, dim3(n_tiles, n_scans), dim3(kRI), 0, s, v, S->d_img.get(), n_tiles, S->tile_off.get(), S->res.get(), n_scans, dst_max_n, dst,
-                       dst_ring, dst_counts);
+    if (dk)
+        hipLaunchKernelGGL(rd_scatter_kernel, dim3(n_tiles, n_scans), dim3(kRI), 0, s, v, S->d_img.get(), n_tiles, S->tile_off.get(), S->res.get(), n_scans, dst_max_n,
+                           S->d_mats.get(), dst, dst_ring, dst_counts);
+    else
+        hipLaunchKernelGGL(ri_scatter_kernel, dim3(n_tiles, n_scans), dim3(kRI), 0, s, v, S->d_img.get(), n_tiles, S->tile_off.get(), S->res.get(), n_scans, dst_max_n, dst,
+                           dst_ring, dst_counts);
     LOCGPU_TRY(hipGetLastError());
     if (prof) {
-        LOCGPU_TRY(hipEventRecord(S->prof[3], s));
-        S->prof_valid = true;
+        LOCGPU_TRY(hipEventRecord(*ev[3], s));
+        (dk ? S->dprof_valid : S->prof_valid) = true;
     }
     return hipMemcpyAsync(S->h_res, S->res, ((size_t)n_scans + 2) * sizeof(int32_t), hipMemcpyDeviceToHost, s);
 }
@@ -317,6 +499,40 @@ void collect_times(locgpu_ctx* ctx) {
         S->prof_ms[0] = copy_ms;
         S->prof_ms[1] = kernel_ms;
     }
+}
+
+void collect_deskew_times(locgpu_ctx* ctx) {
+    RangeIngestScratch* S = ctx->ringest;
+    if (!S->dprof_valid) return;
+    float copy_ms = 0.f, pose_ms = 0.f, decode_ms = 0.f;
+    if (hipEventSynchronize(S->dprof[1]) == hipSuccess && hipEventElapsedTime(&copy_ms, S->dprof[0], S->dprof[1]) == hipSuccess &&
+        hipEventElapsedTime(&pose_ms, S->dprof[2], S->dprof[3]) == hipSuccess && hipEventElapsedTime(&decode_ms, S->dprof[3], S->dprof[4]) == hipSuccess) {
+        S->dprof_ms[0] = copy_ms;
+        S->dprof_ms[1] = pose_ms;
+        S->dprof_ms[2] = decode_ms;
+    }
+}
+
+// The refusals of a deskewed call that the host can decide, O(n_scans · K): LOCGPU_OK, or LOCGPU_ERR_INVALID with the text set.
+int check_motion(locgpu_ctx* ctx, const std::string& who, const locgpu_sensor* sn, const locgpu_sweep_motion* m, int n_scans) {
+    if (!sn->has_col_times) return fail(ctx, LOCGPU_ERR_INVALID, who + ": the sensor has no column times (locgpu_sensor_set_col_times)");
+    if (!m) return fail(ctx, LOCGPU_ERR_INVALID, who + ": motion is NULL");
+    if (!m->knot_times || !m->knot_poses || !m->ref_times) return fail(ctx, LOCGPU_ERR_INVALID, who + ": a NULL array in the motion");
+    const int K = m->n_knots;
+    if (K < 2 || K > kMaxKnots) return fail(ctx, LOCGPU_ERR_INVALID, who + ": n_knots must be in 2..256");
+    for (int i = 0; i < n_scans; ++i) {
+        const double* t = m->knot_times + (size_t)i * K;
+        const std::string scan = " (scan " + std::to_string(i) + ")";
+        for (int k = 0; k < K; ++k)
+            if (!std::isfinite(t[k]) || (k && !(t[k] > t[k - 1]))) return fail(ctx, LOCGPU_ERR_INVALID, who + ": knot times must be finite and strictly increasing" + scan);
+        const double r = m->ref_times[i];
+        if (!std::isfinite(r)) return fail(ctx, LOCGPU_ERR_INVALID, who + ": a reference time is not finite" + scan);
+        if (sn->col_time_min < t[0] || r < t[0])
+            return fail(ctx, LOCGPU_ERR_INVALID, who + ": a column time or the reference time lies before the first knot" + scan + "; nothing is extrapolated");
+        if (sn->col_time_max - t[K - 1] > kInterpTimeTh || r - t[K - 1] > kInterpTimeTh)
+            return fail(ctx, LOCGPU_ERR_INVALID, who + ": a column time or the reference time lies more than 0.5 s behind the last knot" + scan);
+    }
+    return LOCGPU_OK;
 }
 
 bool bad_scalar(float x, bool allow_zero) { return !std::isfinite(x) || x < 0.f || (!allow_zero && x == 0.f); }
@@ -382,41 +598,111 @@ void locgpu_sensor_destroy(locgpu_sensor* s) {
     delete s;
 }
 
-int locgpu_batch_upload_ranges(locgpu_batch* b, const locgpu_sensor* s, const uint16_t* const* images, int32_t* out_counts) {
-    if (!b) return fail(nullptr, LOCGPU_ERR_INVALID, "batch_upload_ranges: NULL batch");
+int locgpu_sensor_set_col_times(locgpu_sensor* s, const double* col_time) {
+    if (!s) return fail(nullptr, LOCGPU_ERR_INVALID, "sensor_set_col_times: NULL sensor");
+    locgpu_ctx* ctx = s->ctx;
+    if (!col_time) return fail(ctx, LOCGPU_ERR_INVALID, "sensor_set_col_times: col_time is NULL");
+    double lo = col_time[0], hi = col_time[0];
+    for (uint32_t c = 0; c < s->n_cols; ++c) {
+        if (!std::isfinite(col_time[c])) return fail(ctx, LOCGPU_ERR_INVALID, "sensor_set_col_times: col_time[" + std::to_string(c) + "] is not finite");
+        lo = std::min(lo, col_time[c]);
+        hi = std::max(hi, col_time[c]);
+    }
+    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+    // a call that reads the previous table has ended (every ingest is blocking); once per table, from pageable memory, as the model's tables
+    hipError_t e = s->d_col_time ? hipSuccess : s->d_col_time.alloc(s->n_cols);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_col_time, col_time, (size_t)s->n_cols * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        s->has_col_times = false;
+        return hip_fail(ctx, e, "sensor_set_col_times: table");
+    }
+    s->has_col_times = true;
+    s->col_time_min = lo;
+    s->col_time_max = hi;
+    return LOCGPU_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// locgpu_batch_upload_ranges (motion == NULL and !deskew) and locgpu_batch_upload_ranges_deskew: the same refusals in the same order,
+// then the motion's; nothing on the device is written before the last of them.
+int batch_upload_ranges(locgpu_batch* b, const locgpu_sensor* s, const uint16_t* const* images, bool deskew, const locgpu_sweep_motion* motion, int32_t* out_counts) {
+    const std::string who = deskew ? "batch_upload_ranges_deskew" : "batch_upload_ranges";
+    if (!b) return fail(nullptr, LOCGPU_ERR_INVALID, who + ": NULL batch");
     locgpu_ctx* ctx = b->ctx;
-    if (!s) return fail(ctx, LOCGPU_ERR_INVALID, "batch_upload_ranges: NULL sensor");
-    if (s->ctx != ctx) return fail(ctx, LOCGPU_ERR_INVALID, "batch_upload_ranges: the sensor belongs to another context");
+    if (!s) return fail(ctx, LOCGPU_ERR_INVALID, who + ": NULL sensor");
+    if (s->ctx != ctx) return fail(ctx, LOCGPU_ERR_INVALID, who + ": the sensor belongs to another context");
     if (b->shared_src) return fail(ctx, LOCGPU_ERR_INVALID, "batch upload: a shared-source batch takes its cloud when it is created");
-    if (b->sharded) return fail(ctx, LOCGPU_ERR_INVALID, "batch_upload_ranges: sharded batches are not supported");
+    if (b->sharded) return fail(ctx, LOCGPU_ERR_INVALID, who + ": sharded batches are not supported");
     if (b->pending.active) return fail(ctx, LOCGPU_ERR_INVALID, "batch upload: an alignment of this batch has been begun and not finished");
-    if (!images) return fail(ctx, LOCGPU_ERR_INVALID, "batch_upload_ranges: images is NULL");
+    if (!images) return fail(ctx, LOCGPU_ERR_INVALID, who + ": images is NULL");
     const int n_scans = b->n_scans;
     for (int i = 0; i < n_scans; ++i)
-        if (!images[i]) return fail(ctx, LOCGPU_ERR_INVALID, "batch_upload_ranges: images[" + std::to_string(i) + "] is NULL");
+        if (!images[i]) return fail(ctx, LOCGPU_ERR_INVALID, who + ": images[" + std::to_string(i) + "] is NULL");
+    if (deskew) {
+        const int rc = check_motion(ctx, who, s, motion, n_scans);
+        if (rc != LOCGPU_OK) return rc;
+    }
     if (n_scans == 0) return LOCGPU_OK;
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
-    const int rc = order_behind_batch(ctx, b, "batch_upload_ranges: ordering behind the batch");
+    const int rc = order_behind_batch(ctx, b, (who + ": ordering behind the batch").c_str());
     if (rc != LOCGPU_OK) return rc;
     hipError_t e = b->d_rings ? hipSuccess : b->d_rings.alloc(std::max<size_t>(b->pitch, 1));
-    if (e != hipSuccess) return hip_fail(ctx, e, "batch_upload_ranges: ring bytes");
-    e = ingest_dev(ctx, s, images, n_scans, b->d_src, b->d_rings, b->d_counts, (uint32_t)b->max_n);
+    if (e != hipSuccess) return hip_fail(ctx, e, (who + ": ring bytes").c_str());
+    e = ingest_dev(ctx, s, images, n_scans, b->d_src, b->d_rings, b->d_counts, (uint32_t)b->max_n, deskew ? motion : nullptr);
     // the one read-back: when it is there the whole pass has run, and whatever uses the batch next — on any stream — finds it complete
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(ctx->copy_stream);
         (void)hipStreamSynchronize(ctx->stream);
-        return hip_fail(ctx, e, "batch_upload_ranges");
+        return hip_fail(ctx, e, who.c_str());
     }
     b->paced_tail = false;
-    collect_times(ctx);
+    if (deskew) collect_deskew_times(ctx); else collect_times(ctx);
     const int32_t* res = ctx->ringest->h_res;
     if (out_counts) std::memcpy(out_counts, res, (size_t)n_scans * sizeof(int32_t));
     if (!res[n_scans])
-        return fail(ctx, LOCGPU_ERR_INVALID, "batch_upload_ranges: a decoded scan has " + std::to_string(res[n_scans + 1]) + " points, the batch was created for " +
+        return fail(ctx, LOCGPU_ERR_INVALID, who + ": a decoded scan has " + std::to_string(res[n_scans + 1]) + " points, the batch was created for " +
                                                  std::to_string(b->max_n) + " per scan (the batch is unchanged)");
     set_host_counts(b, res);
     b->rings_valid = true;
+    return LOCGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int locgpu_batch_upload_ranges(locgpu_batch* b, const locgpu_sensor* s, const uint16_t* const* images, int32_t* out_counts) {
+    return batch_upload_ranges(b, s, images, false, nullptr, out_counts);
+}
+
+int locgpu_batch_upload_ranges_deskew(locgpu_batch* b, const locgpu_sensor* s, const uint16_t* const* images, const locgpu_sweep_motion* motion, int32_t* out_counts) {
+    return batch_upload_ranges(b, s, images, true, motion, out_counts);
+}
+
+int locgpu_range_deskew_matrices(locgpu_ctx* ctx, int scan, double* out, size_t capacity, size_t* n_cols_out) {
+    if (!ctx) return fail(nullptr, LOCGPU_ERR_INVALID, "range_deskew_matrices: NULL context");
+    RangeIngestScratch* S = ctx->ringest;
+    if (!S || S->mats_scans == 0) return fail(ctx, LOCGPU_ERR_INVALID, "range_deskew_matrices: no deskewed ingest has run on this context");
+    if (scan < 0 || scan >= S->mats_scans) return fail(ctx, LOCGPU_ERR_INVALID, "range_deskew_matrices: scan index out of range");
+    if (n_cols_out) *n_cols_out = S->mats_cols;
+    if (!out) return LOCGPU_OK;
+    const size_t n = (size_t)S->mats_cols * 12;
+    if (capacity < n) return fail(ctx, LOCGPU_ERR_INVALID, "range_deskew_matrices: capacity < 12 doubles per column");
+    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+    hipError_t e = hipMemcpyAsync(out, S->d_mats + (size_t)scan * n, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "range_deskew_matrices: D2H");
+    return LOCGPU_OK;
+}
+
+int locgpu_range_deskew_times(locgpu_ctx* ctx, double out_ms[3]) {
+    if (!ctx || !out_ms) return fail(ctx, LOCGPU_ERR_INVALID, "range_deskew_times: NULL argument");
+    for (int i = 0; i < 3; ++i) out_ms[i] = ctx->ringest ? ctx->ringest->dprof_ms[i] : 0.0;
     return LOCGPU_OK;
 }
 
@@ -448,12 +734,22 @@ int locgpu_batch_download_rings(locgpu_batch* b, int scan, uint8_t* out, size_t 
     return LOCGPU_OK;
 }
 
-int locgpu_cloud_upload_ranges(locgpu_cloud* c, const locgpu_sensor* s, const uint16_t* image, uint8_t* ring_out, size_t* n) {
-    if (!c) return fail(nullptr, LOCGPU_ERR_INVALID, "cloud_upload_ranges: NULL cloud");
+}  // extern "C"
+
+namespace {
+
+// locgpu_cloud_upload_ranges and locgpu_cloud_upload_ranges_deskew: as batch_upload_ranges above, for one image into a resident cloud.
+int cloud_upload_ranges(locgpu_cloud* c, const locgpu_sensor* s, const uint16_t* image, bool deskew, const locgpu_sweep_motion* motion, uint8_t* ring_out, size_t* n) {
+    const std::string who = deskew ? "cloud_upload_ranges_deskew" : "cloud_upload_ranges";
+    if (!c) return fail(nullptr, LOCGPU_ERR_INVALID, who + ": NULL cloud");
     locgpu_ctx* ctx = c->ctx;
-    if (!s) return fail(ctx, LOCGPU_ERR_INVALID, "cloud_upload_ranges: NULL sensor");
-    if (s->ctx != ctx) return fail(ctx, LOCGPU_ERR_INVALID, "cloud_upload_ranges: the sensor belongs to another context");
-    if (!image) return fail(ctx, LOCGPU_ERR_INVALID, "cloud_upload_ranges: image is NULL");
+    if (!s) return fail(ctx, LOCGPU_ERR_INVALID, who + ": NULL sensor");
+    if (s->ctx != ctx) return fail(ctx, LOCGPU_ERR_INVALID, who + ": the sensor belongs to another context");
+    if (!image) return fail(ctx, LOCGPU_ERR_INVALID, who + ": image is NULL");
+    if (deskew) {  // before the cloud is touched: a refusal leaves it as it was
+        const int rc = check_motion(ctx, who, s, motion, 1);
+        if (rc != LOCGPU_OK) return rc;
+    }
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
     const size_t cells = s->cells();
     hipError_t e = cloud_reserve(c, cells, false);  // room for every cell: this form has no capacity refusal
@@ -463,21 +759,21 @@ int locgpu_cloud_upload_ranges(locgpu_cloud* c, const locgpu_sensor* s, const ui
         e = S->d_ring.alloc(cap);
     }
     if (e == hipSuccess && ring_out) e = S->h_ring.reserve(with_headroom(cells));
-    if (e != hipSuccess) return hip_fail(ctx, e, "cloud_upload_ranges: buffers");
-    e = ingest_dev(ctx, s, &image, 1, c->d, S->d_ring, nullptr, (uint32_t)cells);
+    if (e != hipSuccess) return hip_fail(ctx, e, (who + ": buffers").c_str());
+    e = ingest_dev(ctx, s, &image, 1, c->d, S->d_ring, nullptr, (uint32_t)cells, deskew ? motion : nullptr);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(ctx->copy_stream);
         (void)hipStreamSynchronize(ctx->stream);
         c->n = 0;
-        return hip_fail(ctx, e, "cloud_upload_ranges");
+        return hip_fail(ctx, e, who.c_str());
     }
-    collect_times(ctx);
+    if (deskew) collect_deskew_times(ctx); else collect_times(ctx);
     const size_t cnt = (size_t)S->h_res[0];
     if (ring_out && cnt) {
         e = hipMemcpyAsync(S->h_ring, S->d_ring, cnt, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return hip_fail(ctx, e, "cloud_upload_ranges: ring bytes");
+        if (e != hipSuccess) return hip_fail(ctx, e, (who + ": ring bytes").c_str());
         std::memcpy(ring_out, S->h_ring, cnt);
     }
     c->n = cnt;
@@ -485,6 +781,18 @@ int locgpu_cloud_upload_ranges(locgpu_cloud* c, const locgpu_sensor* s, const ui
     if (n) *n = cnt;
     (void)cloud_mark_ready(c);
     return LOCGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int locgpu_cloud_upload_ranges(locgpu_cloud* c, const locgpu_sensor* s, const uint16_t* image, uint8_t* ring_out, size_t* n) {
+    return cloud_upload_ranges(c, s, image, false, nullptr, ring_out, n);
+}
+
+int locgpu_cloud_upload_ranges_deskew(locgpu_cloud* c, const locgpu_sensor* s, const uint16_t* image, const locgpu_sweep_motion* motion, uint8_t* ring_out, size_t* n) {
+    return cloud_upload_ranges(c, s, image, true, motion, ring_out, n);
 }
 
 }  // extern "C"

@@ -15,6 +15,10 @@ struct locgpu_sensor {
     uint32_t n_rings = 0, n_cols = 0, az_per_ring = 0;
     float range_scale = 0.f, min_range = 0.f;
     locgpu::DevBuf<float> d_tables;  // cos_el[n_rings] | sin_el[n_rings] | cos_az[n_az] | sin_az[n_az], n_az = n_cols or n_rings · n_cols
+    // locgpu_sensor_set_col_times: one firing time per column, and the table's extremes for the host-side refusals of a deskewed ingest
+    locgpu::DevBuf<double> d_col_time;
+    bool has_col_times = false;
+    double col_time_min = 0.0, col_time_max = 0.0;
     size_t n_az() const { return az_per_ring ? (size_t)n_rings * n_cols : (size_t)n_cols; }
     size_t cells() const { return (size_t)n_rings * n_cols; }
 };
