@@ -895,6 +895,101 @@ LOCGPU_API int locgpu_range_deskew_matrices(locgpu_ctx* ctx, int scan, double* o
  * Zeros before the first profiled call. locgpu_range_ingest_times keeps reporting the most recent plain call. */
 LOCGPU_API int locgpu_range_deskew_times(locgpu_ctx* ctx, double out_ms[3]);
 
+/* ---- Point-record ingest (csrc/record_ingest.hip: rec_count_kernel, rec_scatter_kernel). The reference never sees a range image: its
+ * scans arrive as sensor_msgs::PointCloud2 blobs of driver-specific point records — velodyne_ros::Point (float time, uint16 ring),
+ * ouster_ros::Point (uint32 t, uint8 ring), rslidar_ros::Point (double timestamp, uint16 ring), LocUtils/include/LocUtils/common/
+ * point_types.h:99-169 — and CloudConver::Conver (LocUtils/src/subscriber/cloud_subscriber.cpp:7-29 and :31-58) turns them into the
+ * library's clouds: it drops non-finite points and points with PointDistance < 4.0, keeps the rest in input order and carries ring as
+ * one byte (:51). These entry points take the raw record blob as it is — the host copies it once and never touches a field — and do
+ * that on the device, for all scans of a batch in one pass; the *_deskew forms also move every survivor into the sensor frame of a
+ * reference instant by math::PoseInterp (LocUtils/include/LocUtils/common/math_utils.h:470-517) at THAT POINT's own time: the rule of
+ * the block above, per point instead of per column.
+ *
+ * Field reads. A layout says where the fields of a record are. A field may sit at any byte offset in a record of any stride (22-byte
+ * packed Velodyne records put a float32 at offset 18); it is read as memcpy would read it, little-endian. A U16 ring becomes
+ * (uint8_t)ring as cloud_subscriber.cpp:51 does, which keeps the low byte.
+ * Raw point: the three consecutive float32 at xyz_offset.
+ * Conver's rules (cloud_subscriber.cpp:7-29): a point is dropped if x, y or z is not finite, or if sqrtf((x*x + y*y) + z*z) < min_range,
+ * every product and sum rounded to float32 — the one device copy of the rule that the range-image decode uses.
+ * Output of a scan: its survivors IN INPUT ORDER as {x, y, z, +0.0f}. With ring_kind != LOCGPU_RING_NONE one ring byte per survivor
+ * stays resident with the batch under the contract of locgpu_batch_upload_ranges: locgpu_batch_download_rings and
+ * locgpu_batch_loam_extract_resident work on them and the same later calls drop them; with LOCGPU_RING_NONE the batch holds no rings.
+ * The cloud forms also carry intensity in the fourth lane (F32 as it is, U8 converted to float, NONE gives +0) and set is_dense = 1.
+ * A survivor's position is the number of survivors before it in input order — integer sums in a fixed order, no atomics — so counts,
+ * order and bits depend neither on n_scans, nor on a scan's place in the batch, nor on the run.
+ * Point time (deskew forms): tp = (double)field * time_scale + time_offsets[i], two IEEE double operations, not fused; that float64
+ * value IS the point's time. velodyne_ros::Point: F32, scale 1, offset = the scan's stamp on the knots' clock; ouster_ros::Point: U32,
+ * scale 1e-9; rslidar_ros::Point: F64, scale 1, offset 0 or minus an epoch.
+ * Pose and matrix: the pose at tp and at ref_times[i] is PoseInterp's rule as the block above states it (math_utils.h:470-517) with tp in
+ * place of a column time; M = [ R_r^T R_p | R_r^T (t_p - t_r) ] as there; the survivor is stored as locgpu_cloud_transform's arithmetic
+ * gives it with M. Conver's rules see the RAW point, so survivors, order, counts and ring bytes are those of the plain call on the same
+ * records. With every knot the pose (0,0,0,1, 0,0,0) the deskew call leaves the plain call's bytes.
+ * Time refusals: the host does not walk the points, so the count kernel decides. A SURVIVOR is bad if tp is not finite, if
+ * tp < t[i][0], or if tp - t[i][K-1] > 0.5 (PoseInterp's time_th); dropped points may hold any garbage in their time field. If a scan has
+ * a bad survivor, out_status[i] = 1, the call returns LOCGPU_ERR_INVALID, the text names the first such scan and how many of its
+ * survivors were bad, and the destination is exactly as it was (points, counts and rings): nothing is scattered when the verdict is 0,
+ * the mechanism of the capacity refusal. The reference-time bounds are decided on the host, as in the block above.
+ * Other refusals (LOCGPU_ERR_INVALID, with a text), all decided on the host before any launch: every refusal of
+ * locgpu_batch_upload_ranges (sharded and shared-source batches, an alignment begun and not ended, capacity — out_counts returned,
+ * batch untouched); a NULL layout; stride_bytes outside 12..64; a field with offset + size > stride_bytes; a field that overlaps xyz; an
+ * unknown kind; LOCGPU_TIME_NONE with a deskew call; a min_range that is not finite or negative; a time_scale that is not finite or 0;
+ * n_points[i] < 0 or above 16 x the batch's max_points_per_scan (a sanity bound before staging is sized, not the capacity rule); NULL
+ * records, or a NULL records[i] with n_points[i] > 0; a non-finite time_offsets[i]; and the motion's refusals (K out of 2..256, knot
+ * times not finite or not strictly increasing, a reference time that is not finite, before the first knot or more than 0.5 s behind
+ * the last, NULL members), decided by the host function the range-image path uses.
+ * Out of scope: an asynchronous form; sharded and shared-source batches; the C++ facade (Conver lives in the ROS subscriber,
+ * cloud_subscriber.cpp, which is not shadowed); bench.py; estimating the motion; re-compensating a batch that is already decoded;
+ * big-endian blobs; strides above 64. */
+enum { LOCGPU_TIME_NONE = 0, LOCGPU_TIME_F32 = 1, LOCGPU_TIME_F64 = 2, LOCGPU_TIME_U32 = 3 };
+enum { LOCGPU_RING_NONE = 0, LOCGPU_RING_U8 = 1, LOCGPU_RING_U16 = 2 };
+enum { LOCGPU_INTENSITY_NONE = 0, LOCGPU_INTENSITY_F32 = 1, LOCGPU_INTENSITY_U8 = 2 };
+typedef struct locgpu_point_layout {
+    uint32_t stride_bytes;                     /* 12..64, any value (PointCloud2::point_step) */
+    uint32_t xyz_offset;                       /* three consecutive little-endian float32 */
+    uint32_t time_offset, time_kind;
+    uint32_t ring_offset, ring_kind;
+    uint32_t intensity_offset, intensity_kind; /* cloud forms only; a batch's fourth lane stays +0 */
+    float    min_range;                        /* finite, >= 0; the reference's value is 4.0f */
+    uint32_t reserved;
+    double   time_scale;                       /* finite, != 0: seconds per unit of the time field */
+} locgpu_point_layout;
+/* Conver on the device for n_scans record blobs (cloud_subscriber.cpp:7-29 and :31-58; PoseInterp, math_utils.h:470-517, is not
+ * applied): scan i becomes the output defined above for the n_points[i] records at records[i]. Blocking: the blobs are free again when
+ * it returns. One pass for all scans — raw bytes through pinned staging to HBM on the context's copy stream, then count, exclusive sum,
+ * verdict and scatter kernels and one read-back. out_counts (n_scans entries or NULL) = the survivors per scan. */
+LOCGPU_API int locgpu_batch_upload_records(locgpu_batch* b, const locgpu_point_layout* layout, const void* const* records /* n_scans */,
+                                           const int64_t* n_points /* n_scans */, int32_t* out_counts /* n_scans or NULL */);
+/* locgpu_batch_upload_records (Conver's survivors, cloud_subscriber.cpp:7-29) with every survivor moved into the sensor frame of
+ * ref_times[i] by the pose at its own time (PoseInterp, math_utils.h:470-517), as defined above. time_offsets: n_scans doubles.
+ * out_status (n_scans entries or NULL): 1 for a scan with a refused survivor time, else 0. */
+LOCGPU_API int locgpu_batch_upload_records_deskew(locgpu_batch* b, const locgpu_point_layout* layout, const void* const* records /* n_scans */,
+                                                  const int64_t* n_points /* n_scans */, const double* time_offsets /* n_scans */,
+                                                  const locgpu_sweep_motion* motion, int32_t* out_counts /* n_scans or NULL */,
+                                                  int32_t* out_status /* n_scans or NULL */);
+/* The streaming Lio form (cloud_subscriber.cpp:7-29 and :31-58; no PoseInterp, math_utils.h:470-517): ONE blob of n records into a
+ * resident cloud, equal to the batch form's scan byte for byte in x, y, z, with the intensity in the fourth lane and is_dense = 1.
+ * ring_out (n bytes of room, or NULL) receives the survivors' ring bytes (it is not written with LOCGPU_RING_NONE); *n_out (optional) = their
+ * number. The cloud has room for every record: this form has no capacity refusal; n must not exceed 2^31 - 1. */
+LOCGPU_API int locgpu_cloud_upload_records(locgpu_cloud* c, const locgpu_point_layout* layout, const void* records, int64_t n, uint8_t* ring_out /* n or NULL */,
+                                           size_t* n_out);
+/* locgpu_cloud_upload_records (cloud_subscriber.cpp:7-29) with the motion of ONE scan (math_utils.h:470-517; knot_times [K], knot_poses
+ * [K][7], ref_times [1]); equal to the batch form's scan byte for byte. A refusal leaves the cloud as it was. */
+LOCGPU_API int locgpu_cloud_upload_records_deskew(locgpu_cloud* c, const locgpu_point_layout* layout, const void* records, int64_t n, double time_offset,
+                                                  const locgpu_sweep_motion* motion, uint8_t* ring_out /* n or NULL */, size_t* n_out);
+/* For tests and tools, as locgpu_range_deskew_matrices: with on != 0 the context's next locgpu_*_upload_records_deskew calls also store
+ * each survivor's matrix (PoseInterp at the point's time, math_utils.h:470-517, for Conver's survivors, cloud_subscriber.cpp:7-29), 12
+ * doubles = 96 B per point slot of the destination, in a grow-only table on the context. Off (the default): nothing is stored or
+ * allocated. */
+LOCGPU_API int locgpu_records_deskew_debug(locgpu_ctx* ctx, int on);
+/* The matrices of scan `scan` of the context's most recent deskewed record call that ran with the debug switch on (math_utils.h:470-517,
+ * cloud_subscriber.cpp:7-29), one per survivor in output order, n * 12 doubles. *n_out (optional) = n; out == NULL returns it alone.
+ * LOCGPU_ERR_INVALID before any such call, for a scan index out of range and capacity < n * 12. */
+LOCGPU_API int locgpu_records_deskew_matrices(locgpu_ctx* ctx, int scan, double* out /* n * 12 */, size_t capacity, size_t* n_out);
+/* Measurement (tools/record_ingest_time.py): with locgpu_profile_enable on, out_ms[0] = the copy stream's time and out_ms[1] = the
+ * kernels' time of the most recent locgpu_*_upload_records[_deskew] (Conver, cloud_subscriber.cpp:7-29; PoseInterp, math_utils.h:470-517).
+ * Zeros before the first profiled call. locgpu_range_ingest_times and locgpu_range_deskew_times are left alone. */
+LOCGPU_API int locgpu_records_ingest_times(locgpu_ctx* ctx, double out_ms[2]);
+
 /* The local map of Lio::AddCloud's keyframe branch (lio.cpp:268-306), kept in HBM: a queue of at most num_kfs world-frame
  * keyframe clouds (scans_in_local_map_) and the voxel-filtered local map (local_map_) that is the next matching target.
  * add_keyframe(scan, pose): key_frame_scan = transform(scan, pose) (pose NULL: scan is already in the world frame); push;

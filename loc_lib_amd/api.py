@@ -59,6 +59,8 @@ ABI_SYMBOLS = [
     "locgpu_batch_loam_extract_resident", "locgpu_cloud_upload_ranges", "locgpu_range_ingest_times",
     "locgpu_sensor_set_col_times", "locgpu_batch_upload_ranges_deskew", "locgpu_cloud_upload_ranges_deskew", "locgpu_range_deskew_matrices",
     "locgpu_range_deskew_times",
+    "locgpu_batch_upload_records", "locgpu_batch_upload_records_deskew", "locgpu_cloud_upload_records", "locgpu_cloud_upload_records_deskew",
+    "locgpu_records_deskew_debug", "locgpu_records_deskew_matrices", "locgpu_records_ingest_times",
 ]
 COMM_ID_BYTES = 128
 NO_INTENSITY = ctypes.c_size_t(-1).value
@@ -111,6 +113,55 @@ class SweepMotionC(ctypes.Structure):
     """locgpu_sweep_motion."""
     _fields_ = [("n_knots", ctypes.c_int32), ("reserved", ctypes.c_int32), ("knot_times", ctypes.c_void_p), ("knot_poses", ctypes.c_void_p),
                 ("ref_times", ctypes.c_void_p)]
+
+
+TIME_NONE, TIME_F32, TIME_F64, TIME_U32 = 0, 1, 2, 3
+RING_NONE, RING_U8, RING_U16 = 0, 1, 2
+INTENSITY_NONE, INTENSITY_F32, INTENSITY_U8 = 0, 1, 2
+
+
+class PointLayoutC(ctypes.Structure):
+    """locgpu_point_layout: where the fields of a driver's point record are (PointCloud2::point_step and field offsets)."""
+    _fields_ = [("stride_bytes", ctypes.c_uint32), ("xyz_offset", ctypes.c_uint32), ("time_offset", ctypes.c_uint32), ("time_kind", ctypes.c_uint32),
+                ("ring_offset", ctypes.c_uint32), ("ring_kind", ctypes.c_uint32), ("intensity_offset", ctypes.c_uint32), ("intensity_kind", ctypes.c_uint32),
+                ("min_range", ctypes.c_float), ("reserved", ctypes.c_uint32), ("time_scale", ctypes.c_double)]
+
+
+def point_layout(layout, **kw):
+    """A PointLayoutC from a layout given as plain data (a dict such as LAYOUT_VELODYNE, or a PointLayoutC), with fields overridden by
+    keyword: stride_bytes, xyz_offset, time_offset, time_kind, ring_offset, ring_kind, intensity_offset, intensity_kind, min_range,
+    time_scale. Missing fields: offsets 0, kinds NONE, min_range 4.0 (the reference's), time_scale 1."""
+    if isinstance(layout, PointLayoutC):
+        d = {name: getattr(layout, name) for name, _ in PointLayoutC._fields_}
+    else:
+        d = dict(min_range=4.0, time_scale=1.0)
+        d.update(layout)
+    d.update(kw)
+    out = PointLayoutC()
+    for k, v in d.items():
+        if not hasattr(out, k):
+            raise TypeError("unknown point layout field %r" % k)
+        setattr(out, k, v)
+    return out
+
+
+# The reference's record types (LocUtils/include/LocUtils/common/point_types.h:99-169) as PCL lays them out, and a packed Velodyne record.
+LAYOUT_VELODYNE = dict(stride_bytes=32, xyz_offset=0, intensity_offset=16, intensity_kind=INTENSITY_F32, time_offset=20, time_kind=TIME_F32, ring_offset=24,
+                       ring_kind=RING_U16)
+LAYOUT_RSLIDAR = dict(stride_bytes=32, xyz_offset=0, intensity_offset=16, intensity_kind=INTENSITY_F32, ring_offset=20, ring_kind=RING_U16, time_offset=24,
+                      time_kind=TIME_F64)
+LAYOUT_OUSTER = dict(stride_bytes=48, xyz_offset=0, intensity_offset=16, intensity_kind=INTENSITY_F32, time_offset=20, time_kind=TIME_U32, time_scale=1e-9,
+                     ring_offset=26, ring_kind=RING_U8)
+LAYOUT_VELODYNE_PACKED = dict(stride_bytes=22, xyz_offset=0, intensity_offset=12, intensity_kind=INTENSITY_F32, ring_offset=16, ring_kind=RING_U16, time_offset=18,
+                              time_kind=TIME_F32)
+
+
+def _records(layout, blob):
+    """(uint8 array, number of records) of one blob: bytes, or any array whose bytes are the records."""
+    a = np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else np.ascontiguousarray(blob).reshape(-1).view(np.uint8)
+    if a.size % layout.stride_bytes:
+        raise ValueError("a record blob holds whole records of %d bytes" % layout.stride_bytes)
+    return a, a.size // layout.stride_bytes
 
 
 class AlignStats(ctypes.Structure):
@@ -224,6 +275,11 @@ def lib():
             "locgpu_sensor_set_col_times": (i32, [vp, vp]), "locgpu_batch_upload_ranges_deskew": (i32, [vp, vp, vp, vp, vp]),
             "locgpu_cloud_upload_ranges_deskew": (i32, [vp, vp, vp, vp, vp, vp]), "locgpu_range_deskew_matrices": (i32, [vp, i32, vp, sz, vp]),
             "locgpu_range_deskew_times": (i32, [vp, vp]),
+            "locgpu_batch_upload_records": (i32, [vp, vp, vp, vp, vp]), "locgpu_batch_upload_records_deskew": (i32, [vp, vp, vp, vp, vp, vp, vp, vp]),
+            "locgpu_cloud_upload_records": (i32, [vp, vp, vp, ctypes.c_int64, vp, vp]),
+            "locgpu_cloud_upload_records_deskew": (i32, [vp, vp, vp, ctypes.c_int64, dbl, vp, vp, vp]),
+            "locgpu_records_deskew_debug": (i32, [vp, i32]), "locgpu_records_deskew_matrices": (i32, [vp, i32, vp, sz, vp]),
+            "locgpu_records_ingest_times": (i32, [vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -738,6 +794,25 @@ class Context:
         self._check(lib().locgpu_range_deskew_matrices(self._h, int(scan), out.ctypes.data, out.size, ctypes.byref(n)))
         return out
 
+    def records_deskew_debug(self, on=True):
+        """Make the next upload_records_deskew calls keep each survivor's matrix for records_deskew_matrices (locgpu_records_deskew_debug)."""
+        self._check(lib().locgpu_records_deskew_debug(self._h, int(on)))
+
+    def records_deskew_matrices(self, scan):
+        """The [n, 3, 4] float64 matrices of scan ``scan``'s survivors as the most recent deskewed record ingest with the debug switch on
+        computed them (locgpu_records_deskew_matrices)."""
+        n = ctypes.c_size_t(0)
+        self._check(lib().locgpu_records_deskew_matrices(self._h, int(scan), None, 0, ctypes.byref(n)))
+        out = np.zeros((int(n.value), 3, 4))
+        self._check(lib().locgpu_records_deskew_matrices(self._h, int(scan), out.ctypes.data if out.size else None, out.size, ctypes.byref(n)))
+        return out
+
+    def records_ingest_times(self):
+        """(copy-stream ms, kernel ms) of the most recent upload_records[_deskew] while profile_enable is on (locgpu_records_ingest_times)."""
+        out = np.zeros(2)
+        self._check(lib().locgpu_records_ingest_times(self._h, out.ctypes.data))
+        return float(out[0]), float(out[1])
+
     def visit_count_enable(self, on=True):
         self._check(lib().locgpu_visit_count_enable(self._h, int(on)))
 
@@ -865,6 +940,31 @@ class Cloud:
         n = ctypes.c_size_t(0)
         self.ctx._check(lib().locgpu_cloud_upload_ranges_deskew(self._h, sensor._h, img.ctypes.data, ctypes.byref(motion), rings.ctypes.data if with_rings else None,
                                                                 ctypes.byref(n)))
+        return np.ascontiguousarray(rings[:int(n.value)]) if with_rings else None
+
+    def upload_records(self, layout, blob, with_rings=True):
+        """Conver on the device for one blob of point records into the cloud (locgpu_cloud_upload_records: intensity kept, is_dense).
+        Returns the survivors' ring bytes (uint8, one per point), or None without them or for a layout without a ring field."""
+        L = point_layout(layout)
+        a, n_rec = _records(L, blob)
+        with_rings = with_rings and L.ring_kind != RING_NONE
+        rings = np.zeros(max(n_rec, 1), np.uint8) if with_rings else None
+        n = ctypes.c_size_t(0)
+        self.ctx._check(lib().locgpu_cloud_upload_records(self._h, ctypes.byref(L), a.ctypes.data if n_rec else None, n_rec, rings.ctypes.data if with_rings else None,
+                                                          ctypes.byref(n)))
+        return np.ascontiguousarray(rings[:int(n.value)]) if with_rings else None
+
+    def upload_records_deskew(self, layout, blob, time_offset, knot_times, knot_poses, ref_time, with_rings=True):
+        """upload_records with every survivor motion-compensated at its own time (locgpu_cloud_upload_records_deskew): the point's time is
+        field * layout.time_scale + time_offset on the clock of knot_times [K]; knot_poses [K, 7]; ref_time as in upload_ranges_deskew."""
+        L = point_layout(layout)
+        a, n_rec = _records(L, blob)
+        motion, keep = sweep_motion(1, knot_times, knot_poses, [ref_time])
+        with_rings = with_rings and L.ring_kind != RING_NONE
+        rings = np.zeros(max(n_rec, 1), np.uint8) if with_rings else None
+        n = ctypes.c_size_t(0)
+        self.ctx._check(lib().locgpu_cloud_upload_records_deskew(self._h, ctypes.byref(L), a.ctypes.data if n_rec else None, n_rec, float(time_offset), ctypes.byref(motion),
+                                                                 rings.ctypes.data if with_rings else None, ctypes.byref(n)))
         return np.ascontiguousarray(rings[:int(n.value)]) if with_rings else None
 
     def loam_extract(self, ring, num_scan=16):
@@ -1163,6 +1263,48 @@ class Batch:
         if rc != 0:
             err = LocGpuError(rc, lib().locgpu_last_error(self.ctx._h).decode())
             err.counts = counts
+            raise err
+        return counts
+
+    def _record_args(self, layout, blobs):
+        L = point_layout(layout)
+        blobs = [_records(L, x) for x in blobs]
+        if len(blobs) != self.n_local:
+            raise ValueError("a record upload needs %d blobs" % self.n_local)
+        ptrs = (ctypes.c_void_p * max(len(blobs), 1))(*[(a.ctypes.data if n else None) for a, n in blobs])
+        n_points = np.array([n for _, n in blobs], np.int64)
+        return L, blobs, ptrs, n_points
+
+    def upload_records(self, layout, blobs):
+        """Replace the batch's scans by Conver's survivors of one blob of point records per scan (locgpu_batch_upload_records; ``layout``
+        a dict such as LAYOUT_VELODYNE or a PointLayoutC) and leave their ring bytes resident when the layout has a ring field.
+        Blocking. Returns the counts; when a scan does not fit the batch the LocGpuError carries the needed counts as ``.counts``."""
+        self.upload_wait()
+        L, keep, ptrs, n_points = self._record_args(layout, blobs)
+        counts = np.zeros(self.n_local, np.int32)
+        rc = lib().locgpu_batch_upload_records(self._h, ctypes.byref(L), ptrs, n_points.ctypes.data, counts.ctypes.data)
+        if rc != 0:
+            err = LocGpuError(rc, lib().locgpu_last_error(self.ctx._h).decode())
+            err.counts = counts
+            raise err
+        return counts
+
+    def upload_records_deskew(self, layout, blobs, time_offsets, knot_times, knot_poses, ref_times):
+        """upload_records with every survivor motion-compensated at its own time (locgpu_batch_upload_records_deskew): time_offsets [n]
+        (a point's time is field * layout.time_scale + time_offsets[s]), knot_times [n, K], knot_poses [n, K, 7], ref_times [n]. A
+        refused call raises a LocGpuError that carries ``.counts`` and ``.status`` (1 for a scan with a refused survivor time)."""
+        self.upload_wait()
+        L, keep, ptrs, n_points = self._record_args(layout, blobs)
+        offs = np.ascontiguousarray(time_offsets, dtype=np.float64).reshape(-1)
+        if len(offs) != self.n_local:
+            raise ValueError("one time offset per scan")
+        motion, keep_m = sweep_motion(self.n_local, knot_times, knot_poses, ref_times)
+        counts, status = np.zeros(self.n_local, np.int32), np.zeros(self.n_local, np.int32)
+        rc = lib().locgpu_batch_upload_records_deskew(self._h, ctypes.byref(L), ptrs, n_points.ctypes.data, offs.ctypes.data, ctypes.byref(motion), counts.ctypes.data,
+                                                      status.ctypes.data)
+        if rc != 0:
+            err = LocGpuError(rc, lib().locgpu_last_error(self.ctx._h).decode())
+            err.counts, err.status = counts, status
             raise err
         return counts
 

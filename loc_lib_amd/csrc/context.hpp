@@ -23,6 +23,7 @@ struct BatchFilterScratch;  // batch_filters.hip
 struct BatchLoamScratch;    // batch_loam.hip
 struct MergeScratch;        // cloud_merge.hip
 struct RangeIngestScratch;  // range_ingest.hip
+struct RecordIngestScratch;  // record_ingest.hip
 }  // namespace locgpu
 struct locgpu_sensor;  // range_ingest.hpp
 
@@ -114,6 +115,7 @@ struct locgpu_ctx {
     locgpu::BatchLoamScratch* bloam = nullptr;    // workspaces of the batched LOAM feature picker (batch_loam.hip)
     locgpu::MergeScratch* merge = nullptr;        // table and joined cloud of the global-map pass (cloud_merge.hip)
     locgpu::RangeIngestScratch* ringest = nullptr;  // staging and workspaces of the range-image ingest (range_ingest.hip)
+    locgpu::RecordIngestScratch* recingest = nullptr;  // staging and workspaces of the point-record ingest (record_ingest.hip)
     std::vector<locgpu_sensor*> sensors;          // the sensor models created on this context and not destroyed yet (range_ingest.hip)
 
     // reusable one-scan batch for the single-scan entry points

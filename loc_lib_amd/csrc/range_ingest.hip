@@ -35,6 +35,10 @@
 //
 // — so survivors, order, counts and ring bytes are the plain call's. Scratch: 96 B per column and scan for the matrices, 8 B per knot
 // value (+ pinned). The plain entry points launch the four kernels above and nothing else.
+//
+// Shared with the point-record ingest (record_ingest.hip): Conver's keep rule and block_exclusive (range_ingest.hpp), rd_pose_at and the
+// matrix product (pose_interp.hpp), the offsets and verdict kernels (ingest_launch_*; a second row of sums that this file leaves
+// off) and the motion's host-side refusals (check_sweep_motion).
 #include "range_ingest.hpp"
 
 #include <algorithm>
@@ -49,12 +53,12 @@
 #include "batch_upload.hpp"
 #include "cloud_filters.hpp"
 #include "context.hpp"
+#include "pose_interp.hpp"
 
 namespace locgpu {
 
 namespace {
 
-constexpr int kRI = 256;                       // threads per block
 constexpr int kCellsPerLane = 8;               // one 16-byte load
 constexpr int kTile = kRI * kCellsPerLane;     // cells per block
 constexpr int kMaxRings = 256, kMaxCols = 12288;  // the LOAM picker's limits: a ring byte, rings of at most 6 × 2048 points
@@ -89,28 +93,6 @@ __device__ __forceinline__ uint32_t decode8(const SensorView& v, const uint16_t*
     return mask;
 }
 
-// Sum of `x` over the block in every thread's `total`; returns the exclusive prefix of the calling thread. One barrier pair.
-__device__ __forceinline__ uint32_t block_exclusive(uint32_t x, uint32_t* s_wave, uint32_t& total) {
-    static_assert(kRI == 256, "four waves");
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = x;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    __syncthreads();  // s_wave may still be read from the previous use
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < kRI / 64; ++w) {
-        before += w < wave ? s_wave[w] : 0u;
-        total += s_wave[w];
-    }
-    return before + inc - x;
-}
-
 __global__ __launch_bounds__(kRI) void ri_count_kernel(SensorView v, const uint16_t* __restrict__ img, uint32_t n_tiles, uint32_t* __restrict__ tile_cnt) {
     __shared__ uint32_t s_wave[kRI / 64];
     const uint32_t s = blockIdx.y, tile = blockIdx.x;
@@ -126,34 +108,44 @@ __global__ __launch_bounds__(kRI) void ri_count_kernel(SensorView v, const uint1
     if (threadIdx.x == 0) tile_cnt[(size_t)s * n_tiles + tile] = total;
 }
 
-// Scan blockIdx.x: tile_off = exclusive sums of its tile counts in tile order; res[s] = its survivors.
-__global__ __launch_bounds__(kRI) void ri_offsets_kernel(const uint32_t* __restrict__ tile_cnt, uint32_t n_tiles, uint32_t* __restrict__ tile_off, int32_t* __restrict__ res) {
+// Row blockIdx.y of scan blockIdx.x (range_ingest.hpp): row 0 — tile_off = exclusive sums of the scan's tile counts in tile order,
+// res[s] = its survivors; row 1 (the record ingest's refused times) — res[n_scans + 2 + s] = the sum alone.
+__global__ __launch_bounds__(kRI) void ri_offsets_kernel(const uint32_t* __restrict__ tile_cnt, uint32_t n_tiles, uint32_t* __restrict__ tile_off, int32_t* __restrict__ res,
+                                                         int n_scans) {
     __shared__ uint32_t s_wave[kRI / 64];
-    const uint32_t s = blockIdx.x;
+    const uint32_t s = blockIdx.x, r = blockIdx.y;
     const size_t row = (size_t)s * n_tiles;
+    const uint32_t* cnt = tile_cnt + (size_t)r * n_scans * n_tiles;
     uint32_t carry = 0;
     for (uint32_t t0 = 0; t0 < n_tiles; t0 += kRI) {  // n_tiles is the same for every thread: the barriers inside are uniform
         const uint32_t t = t0 + threadIdx.x;
-        const uint32_t x = t < n_tiles ? tile_cnt[row + t] : 0u;
+        const uint32_t x = t < n_tiles ? cnt[row + t] : 0u;
         uint32_t total;
         const uint32_t ex = block_exclusive(x, s_wave, total);
-        if (t < n_tiles) tile_off[row + t] = carry + ex;
+        if (r == 0 && t < n_tiles) tile_off[row + t] = carry + ex;
         carry += total;
     }
-    if (threadIdx.x == 0) res[s] = (int32_t)carry;
+    if (threadIdx.x == 0) res[r == 0 ? s : n_scans + 2 + s] = (int32_t)carry;
 }
 
-// res[n_scans] = 1 when every scan fits dst_max_n points, res[n_scans + 1] = the largest count.
-__global__ __launch_bounds__(kRI) void ri_verdict_kernel(int32_t* __restrict__ res, int n_scans, uint32_t dst_max_n) {
-    __shared__ int s_max[kRI / 64];
-    int m = 0;
-    for (int s = threadIdx.x; s < n_scans; s += kRI) m = max(m, res[s]);
-    for (int off = 32; off > 0; off >>= 1) m = max(m, __shfl_xor(m, off, 64));
-    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = m;
+// res[n_scans] = 1 when every scan fits dst_max_n points (and, rows == 2, no scan has a positive row-1 sum), res[n_scans + 1] = the
+// largest count.
+__global__ __launch_bounds__(kRI) void ri_verdict_kernel(int32_t* __restrict__ res, int n_scans, uint32_t dst_max_n, int rows) {
+    __shared__ int s_max[kRI / 64], s_bad[kRI / 64];
+    int m = 0, bad = 0;
+    for (int s = threadIdx.x; s < n_scans; s += kRI) {
+        m = max(m, res[s]);
+        if (rows == 2) bad = max(bad, res[n_scans + 2 + s]);
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        m = max(m, __shfl_xor(m, off, 64));
+        bad = max(bad, __shfl_xor(bad, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = m, s_bad[threadIdx.x >> 6] = bad;
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int w = 1; w < kRI / 64; ++w) m = max(m, s_max[w]);
-        res[n_scans] = (uint32_t)m <= dst_max_n ? 1 : 0;
+        for (int w = 1; w < kRI / 64; ++w) m = max(m, s_max[w]), bad = max(bad, s_bad[w]);
+        res[n_scans] = (uint32_t)m <= dst_max_n && bad == 0 ? 1 : 0;
         res[n_scans + 1] = m;
     }
 }
@@ -207,53 +199,6 @@ __global__ __launch_bounds__(kRI) void ri_scatter_kernel(SensorView v, const uin
 }
 
 // ---- Motion compensation at decode (include/locgpu.h, "Range-image ingest, motion-compensated") ------------------------------------
-constexpr int kMaxKnots = 256;
-constexpr double kInterpTimeTh = 0.5;  // PoseInterp's time_th, math_utils.h:471
-
-// math::PoseInterp (math_utils.h:470-517) on the K knots staged in LDS, t[K] and p[K][7] (quaternion xyzw, translation): the pose at
-// time q. The times increase strictly, so the first interval with t[j] < q <= t[j+1] is found by bisection. Everything but acos and
-// sin is one IEEE double operation per line of the header's definition (the build compiles with contraction off).
-__device__ __forceinline__ void rd_pose_at(const double* t, const double* p, int K, double q, double (&out)[7]) {
-    if (q > t[K - 1]) {  // :478-483, the caller has refused anything later than time_th behind the last knot
-#pragma unroll
-        for (int i = 0; i < 7; ++i) out[i] = p[7 * (K - 1) + i];
-        return;
-    }
-    int lo = 0, hi = K;  // the number of knots with t < q
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (t[mid] < q) lo = mid + 1; else hi = mid;
-    }
-    const int j = lo > 0 ? lo - 1 : 0;  // q <= t[K-1]: lo <= K - 1, so j + 1 <= K - 1
-    const double* a = p + 7 * j;
-    const double* b = a + 7;
-    const double dt = t[j + 1] - t[j];
-    if (fabs(dt) < 1e-6) {  // :505-508
-#pragma unroll
-        for (int i = 0; i < 7; ++i) out[i] = a[i];
-        return;
-    }
-    const double s = (q - t[j]) / dt;
-    // Eigen's QuaternionBase::slerp (:513)
-    const double d = ((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]) + a[3] * b[3];
-    const double ad = fabs(d);
-    double s0, s1;
-    if (ad >= 1.0 - DBL_EPSILON) {
-        s0 = 1.0 - s;
-        s1 = s;
-    } else {
-        const double th = acos(ad), st = sin(th);
-        s0 = sin((1.0 - s) * th) / st;
-        s1 = sin(s * th) / st;
-    }
-    if (d < 0.0) s1 = -s1;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) out[i] = s0 * a[i] + s1 * b[i];
-    const double u = 1.0 - s;
-#pragma unroll
-    for (int i = 4; i < 7; ++i) out[i] = a[i] * u + b[i] * s;  // :514
-}
-
 // Scan blockIdx.x: M[c] = [ R_rᵀ·R_c | R_rᵀ·(t_c − t_r) ] for each of its columns, row-major 3×4, every dot product summed left to
 // right. motion = times [n_scans][K] | poses [n_scans][K][7] | ref_times [n_scans]. One block per scan, so that the knots are staged
 // and the reference-time pose is computed once per scan; its threads walk the columns.
@@ -268,29 +213,12 @@ __global__ __launch_bounds__(kRI) void rd_pose_kernel(const double* __restrict__
     for (int i = threadIdx.x; i < K; i += kRI) s_t[i] = g_t[i];
     for (int i = threadIdx.x; i < 7 * K; i += kRI) s_p[i] = g_p[i];
     __syncthreads();
-    if (threadIdx.x == 0) {
-        double pr[7];
-        rd_pose_at(s_t, s_p, K, motion[(size_t)n_scans * K * 8 + s], pr);
-        quat_to_R(pr, s_ref);
-        s_ref[9] = pr[4];
-        s_ref[10] = pr[5];
-        s_ref[11] = pr[6];
-    }
+    if (threadIdx.x == 0) rd_ref_pose(s_t, s_p, K, motion[(size_t)n_scans * K * 8 + s], s_ref);
     __syncthreads();
     for (uint32_t c = threadIdx.x; c < n_cols; c += kRI) {
-        double pc[7], Rc[9];
+        double pc[7];
         rd_pose_at(s_t, s_p, K, col_time[c], pc);
-        quat_to_R(pc, Rc);
-        const double d0 = pc[4] - s_ref[9], d1 = pc[5] - s_ref[10], d2 = pc[6] - s_ref[11];
-        double* m = mats + ((size_t)s * n_cols + c) * 12;  // inside the table: ensure_deskew sized it for n_scans · n_cols matrices
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const double a0 = s_ref[r], a1 = s_ref[3 + r], a2 = s_ref[6 + r];  // column r of R_r = row r of R_rᵀ
-            m[4 * r + 0] = (a0 * Rc[0] + a1 * Rc[3]) + a2 * Rc[6];
-            m[4 * r + 1] = (a0 * Rc[1] + a1 * Rc[4]) + a2 * Rc[7];
-            m[4 * r + 2] = (a0 * Rc[2] + a1 * Rc[5]) + a2 * Rc[8];
-            m[4 * r + 3] = (a0 * d0 + a1 * d1) + a2 * d2;
-        }
+        rd_matrix(s_ref, pc, mats + ((size_t)s * n_cols + c) * 12);  // inside the table: ensure_deskew sized it for n_scans · n_cols matrices
     }
 }
 
@@ -419,7 +347,7 @@ hipError_t stage_images(locgpu_ctx* ctx, const uint16_t* const* images, int n_sc
     return hipStreamWaitEvent(ctx->stream, S->staged, 0);
 }
 
-// dk: the checked motion of a deskewed call (check_motion), or NULL.
+// dk: the checked motion of a deskewed call (check_sweep_motion), or NULL.
 // The pass for n_scans images into dst [n_scans][dst_max_n] (+ ring bytes, + device counts unless dst_counts is NULL), on
 // ctx->stream; the counts and the verdict are on their way to S->h_res when it returns.
 hipError_t ingest_dev(locgpu_ctx* ctx, const locgpu_sensor* sn, const uint16_t* const* images, int n_scans, float4* dst, unsigned char* dst_ring, int* dst_counts,
@@ -473,8 +401,8 @@ hipError_t ingest_dev(locgpu_ctx* ctx, const locgpu_sensor* sn, const uint16_t* 
         if (prof) LOCGPU_TRY(hipEventRecord(S->dprof[3], s));
     }
     hipLaunchKernelGGL(ri_count_kernel, dim3(n_tiles, n_scans), dim3(kRI), 0, s, v, S->d_img.get(), n_tiles, S->tile_cnt.get());
-    hipLaunchKernelGGL(ri_offsets_kernel, dim3(n_scans), dim3(kRI), 0, s, S->tile_cnt.get(), n_tiles, S->tile_off.get(), S->res.get());
-    hipLaunchKernelGGL(ri_verdict_kernel, dim3(1), dim3(kRI), 0, s, S->res.get(), n_scans, dst_max_n);
+    ingest_launch_offsets(s, S->tile_cnt.get(), n_tiles, S->tile_off.get(), S->res.get(), n_scans, 1);
+    ingest_launch_verdict(s, S->res.get(), n_scans, dst_max_n, 1);
     if (dk)
         hipLaunchKernelGGL(rd_scatter_kernel, dim3(n_tiles, n_scans), dim3(kRI), 0, s, v, S->d_img.get(), n_tiles, S->tile_off.get(), S->res.get(), n_scans, dst_max_n,
                            S->d_mats.get(), dst, dst_ring, dst_counts);
@@ -513,13 +441,24 @@ void collect_deskew_times(locgpu_ctx* ctx) {
     }
 }
 
-// The refusals of a deskewed call that the host can decide, O(n_scans · K): LOCGPU_OK, or LOCGPU_ERR_INVALID with the text set.
-int check_motion(locgpu_ctx* ctx, const std::string& who, const locgpu_sensor* sn, const locgpu_sweep_motion* m, int n_scans) {
-    if (!sn->has_col_times) return fail(ctx, LOCGPU_ERR_INVALID, who + ": the sensor has no column times (locgpu_sensor_set_col_times)");
+bool bad_scalar(float x, bool allow_zero) { return !std::isfinite(x) || x < 0.f || (!allow_zero && x == 0.f); }
+
+}  // namespace
+
+void ingest_launch_offsets(hipStream_t s, const uint32_t* tile_cnt, uint32_t n_tiles, uint32_t* tile_off, int32_t* res, int n_scans, int rows) {
+    hipLaunchKernelGGL(ri_offsets_kernel, dim3(n_scans, rows), dim3(kRI), 0, s, tile_cnt, n_tiles, tile_off, res, n_scans);
+}
+
+void ingest_launch_verdict(hipStream_t s, int32_t* res, int n_scans, uint32_t dst_max_n, int rows) {
+    hipLaunchKernelGGL(ri_verdict_kernel, dim3(1), dim3(kRI), 0, s, res, n_scans, dst_max_n, rows);
+}
+
+int check_sweep_motion(locgpu_ctx* ctx, const std::string& who, const locgpu_sweep_motion* m, int n_scans, bool cols, double q_min, double q_max) {
     if (!m) return fail(ctx, LOCGPU_ERR_INVALID, who + ": motion is NULL");
     if (!m->knot_times || !m->knot_poses || !m->ref_times) return fail(ctx, LOCGPU_ERR_INVALID, who + ": a NULL array in the motion");
     const int K = m->n_knots;
     if (K < 2 || K > kMaxKnots) return fail(ctx, LOCGPU_ERR_INVALID, who + ": n_knots must be in 2..256");
+    const std::string what = cols ? ": a column time or the reference time lies " : ": the reference time lies ";
     for (int i = 0; i < n_scans; ++i) {
         const double* t = m->knot_times + (size_t)i * K;
         const std::string scan = " (scan " + std::to_string(i) + ")";
@@ -527,17 +466,12 @@ int check_motion(locgpu_ctx* ctx, const std::string& who, const locgpu_sensor* s
             if (!std::isfinite(t[k]) || (k && !(t[k] > t[k - 1]))) return fail(ctx, LOCGPU_ERR_INVALID, who + ": knot times must be finite and strictly increasing" + scan);
         const double r = m->ref_times[i];
         if (!std::isfinite(r)) return fail(ctx, LOCGPU_ERR_INVALID, who + ": a reference time is not finite" + scan);
-        if (sn->col_time_min < t[0] || r < t[0])
-            return fail(ctx, LOCGPU_ERR_INVALID, who + ": a column time or the reference time lies before the first knot" + scan + "; nothing is extrapolated");
-        if (sn->col_time_max - t[K - 1] > kInterpTimeTh || r - t[K - 1] > kInterpTimeTh)
-            return fail(ctx, LOCGPU_ERR_INVALID, who + ": a column time or the reference time lies more than 0.5 s behind the last knot" + scan);
+        if ((cols && q_min < t[0]) || r < t[0]) return fail(ctx, LOCGPU_ERR_INVALID, who + what + "before the first knot" + scan + "; nothing is extrapolated");
+        if ((cols && q_max - t[K - 1] > kInterpTimeTh) || r - t[K - 1] > kInterpTimeTh)
+            return fail(ctx, LOCGPU_ERR_INVALID, who + what + "more than 0.5 s behind the last knot" + scan);
     }
     return LOCGPU_OK;
 }
-
-bool bad_scalar(float x, bool allow_zero) { return !std::isfinite(x) || x < 0.f || (!allow_zero && x == 0.f); }
-
-}  // namespace
 
 void range_ingest_free(locgpu_ctx* ctx) {
     delete ctx->ringest;
@@ -643,7 +577,8 @@ int batch_upload_ranges(locgpu_batch* b, const locgpu_sensor* s, const uint16_t*
     for (int i = 0; i < n_scans; ++i)
         if (!images[i]) return fail(ctx, LOCGPU_ERR_INVALID, who + ": images[" + std::to_string(i) + "] is NULL");
     if (deskew) {
-        const int rc = check_motion(ctx, who, s, motion, n_scans);
+        if (!s->has_col_times) return fail(ctx, LOCGPU_ERR_INVALID, who + ": the sensor has no column times (locgpu_sensor_set_col_times)");
+        const int rc = check_sweep_motion(ctx, who, motion, n_scans, true, s->col_time_min, s->col_time_max);
         if (rc != LOCGPU_OK) return rc;
     }
     if (n_scans == 0) return LOCGPU_OK;
@@ -725,7 +660,7 @@ int locgpu_batch_download_rings(locgpu_batch* b, int scan, uint8_t* out, size_t 
     if (cnt > capacity) return fail(ctx, LOCGPU_ERR_INVALID, "batch_download_rings: capacity < the scan's size");
     if (cnt == 0) return LOCGPU_OK;
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
-    RangeIngestScratch* S = ctx->ringest;  // rings_valid: an ingest has run on this context
+    RangeIngestScratch* S = scratch(ctx);  // rings_valid: an ingest has run on this context, the range-image or the point-record one
     hipError_t e = S->h_ring.reserve(cnt);
     if (e == hipSuccess) e = hipMemcpyAsync(S->h_ring, b->d_rings + (size_t)scan * b->max_n, cnt, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -747,7 +682,8 @@ int cloud_upload_ranges(locgpu_cloud* c, const locgpu_sensor* s, const uint16_t*
     if (s->ctx != ctx) return fail(ctx, LOCGPU_ERR_INVALID, who + ": the sensor belongs to another context");
     if (!image) return fail(ctx, LOCGPU_ERR_INVALID, who + ": image is NULL");
     if (deskew) {  // before the cloud is touched: a refusal leaves it as it was
-        const int rc = check_motion(ctx, who, s, motion, 1);
+        if (!s->has_col_times) return fail(ctx, LOCGPU_ERR_INVALID, who + ": the sensor has no column times (locgpu_sensor_set_col_times)");
+        const int rc = check_sweep_motion(ctx, who, motion, 1, true, s->col_time_min, s->col_time_max);
         if (rc != LOCGPU_OK) return rc;
     }
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
