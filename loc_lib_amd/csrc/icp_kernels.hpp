@@ -24,6 +24,9 @@ namespace locgpu {
 constexpr int kBlock = 256;
 constexpr int kAccW = 32;          // doubles per block partial: 21 H (upper) + 6 B + effective_num + 4 spare
 constexpr uint32_t kInvalidSlot = 0xFFFFFFFFu;
+// The walk kernels name a node by its byte offset in 32 bits (search_walk.hpp, NODE REFERENCES): a tree whose slots, with the two of
+// the sentinel leaf behind them, do not all lie below 2²⁹ is searched by the exact kernel alone (install_tree_meta, icp_target.hip).
+constexpr size_t kWalkMaxSlots = (size_t)1 << 29;
 constexpr int kSearchStatSlots = 16 + 2 * 64;  // [0..15] counters, then two 64-bin histograms of the LOCGPU_STAMP diagnostic build
 
 struct GnParams {

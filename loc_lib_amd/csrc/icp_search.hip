@@ -80,15 +80,18 @@ __device__ __forceinline__ void walk_query(__amdgpu_buffer_rsrc_t rsrc, const ui
     w.slow = 0;
     // finite-arithmetic precondition of the traversal (the tree is `bounded`): anything else goes to the exact kernel
     const bool sane = fabsf(w.qx) < 1e18f && fabsf(w.qy) < 1e18f && fabsf(w.qz) < 1e18f;
+    const uint32_t dummy_ref = node_ref(dummy);  // the traversal names nodes by reference (search_walk.hpp); scalar work
     if (valid && sane) {
         walk_descend<K, ROWB, WIN>(rsrc, tree, w, T, col_addr);
     } else {
-        w.cur = dummy; w.avail = 0; w.c3n = 0; w.slow = valid ? 1u : 0u;
+        w.cur = dummy_ref; w.avail = 0; w.c3n = 0; w.slow = valid ? 1u : 0u;
     }
 #ifndef LOCGPU_K1_C
 #define LOCGPU_K1_C 2  // internal steps per round (A/B builds: -DLOCGPU_K1_C=1|3)
 #endif
-    walk_rounds_capped<K, ROWB, LOCGPU_K1_C, STAMP>(rsrc, w, alpha_eff, dummy, col_addr, cap);
+    walk_rounds_capped<K, ROWB, LOCGPU_K1_C, STAMP>(rsrc, w, alpha_eff, dummy_ref, col_addr, cap);
+#pragma unroll
+    for (int j = 0; j < K; ++j) w.id[j] = node_slot(w.id[j]);  // back to slots once per query, behind the loop
 #pragma unroll
     for (int j = 0; j + 1 < K; ++j) w.slow |= w.d[j] == w.d[j + 1] ? 1u : 0u;  // equal distances in the final set: heap pop order is layout-dependent
 }

@@ -95,7 +95,7 @@ static int install_tree_meta(locgpu_ctx* ctx, const long long meta[6]) {
     ctx->num_nodes = (size_t)meta[2];
     ctx->num_points = (size_t)meta[3];
     ctx->depth = (int)meta[4];
-    ctx->tree_bounded = meta[5] != 0;
+    ctx->tree_bounded = meta[5] != 0 && slots + 2 <= kWalkMaxSlots;  // … and small enough for the walk kernels' 32-bit node references
     ctx->target_epoch++;
     ctx->planes_ready = false;  // the plane table belongs to the previous target (rebuilt on the next use of LOCGPU_P2PLANE_MAP)
     ctx->planes_rows = 0;

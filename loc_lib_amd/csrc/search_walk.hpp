@@ -6,7 +6,7 @@
 //
 //   * a lane that has nothing to visit (it is finished, or it sits out a stage) visits the SENTINEL LEAF behind the packed tree
 //     (coordinates 3e38: its squared distance overflows to +inf and is never inserted), so "leaf" is the only predicate of a stage;
-//   * the stack holds {far slot, −d²}. With the sign flipped, `d² < bound` is a SIGNED INTEGER compare of the raw bits against the
+//   * the stack holds {far node (as a reference: its byte offset, see NODE REFERENCES), −d²}. With the sign flipped, `d² < bound` is a SIGNED INTEGER compare of the raw bits against the
 //     bits of −bound (non-positive floats order like their magnitudes), a row below the stack's bottom reads as 0 from outside the
 //     workgroup's LDS allocation (never "less than" a non-positive bound) and INT_MIN (−0.0f) as the bound switches a test off:
 //     the `j < avail` and `is this lane popping` predicates cost nothing;
@@ -36,8 +36,8 @@ template <int K>
 struct Walk {
     float qx, qy, qz;
     float d[K];        // ascending; +inf = empty
-    uint32_t id[K];
-    uint32_t cur;      // slot to visit next (`dummy` = the sentinel leaf: nothing to visit)
+    uint32_t id[K];    // node references (below) inside the traversal; walk_query hands out slots
+    uint32_t cur;      // reference of the node to visit next (`dummy` = the sentinel leaf's: nothing to visit)
     int avail;         // rows on the stack
     uint32_t c3n;      // bits of −(third smallest d² of the un-stored levels); 0 = none; 1 = the query needs the deep pass
     uint32_t slow;
@@ -49,6 +49,21 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef u32x2 __attribute__((address_space(3))) lds_u32x2;
 
 __device__ __forceinline__ lds_u32* lds_ptr(uint32_t byte_addr) { return reinterpret_cast<lds_u32*>(byte_addr); }
+
+// NODE REFERENCES. The traversal names a node by its BYTE OFFSET in the packed tree (slot × 8), which is what the buffer load takes as
+// its offset: the right child of an internal node is `meta << 3` (the two axis bits fall off the top — no mask), the left child is
+// `ref + 8`, and no load is preceded by a shift. Precondition, stated here and checked where a tree is installed (kWalkMaxSlots,
+// icp_kernels.hpp): every slot, the sentinel leaf's two included, lies below 2²⁹, so that its byte offset fits the 32-bit offset.
+// References order like slots and kInvalidSlot (all ones, no multiple of 8) stands for itself in both forms.
+constexpr uint32_t kNodeStep = 8u;
+__device__ __forceinline__ uint32_t node_right(uint32_t meta) { return meta << 3; }
+__device__ __forceinline__ uint32_t node_ref(uint32_t slot) { return slot << 3; }
+__device__ __forceinline__ uint32_t node_slot(uint32_t ref) { return ref == kInvalidSlot ? kInvalidSlot : ref >> 3; }
+__device__ __forceinline__ u32x4 node_load(__amdgpu_buffer_rsrc_t rsrc, uint32_t ref) { return __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)ref, 0, 0); }
+__device__ __forceinline__ uint2 node_head(const uint2* __restrict__ tree, uint32_t ref) { return *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(tree) + ref); }
+// min(c, d2) for a d2 that is never NaN (`sane`): the select on the compare the insertion makes anyway — __builtin_fminf puts a
+// canonicalising v_max in front of its v_min
+__device__ __forceinline__ float min_lt(bool lt, float d2, float c) { return lt ? d2 : c; }
 
 // First descent (result set empty ⇒ every level pushes). Levels 0..T-1 are not stored: their two smallest d² become rows 0/1, the
 // third smallest goes to w.c3n. Levels ≥ T are stored from row 2 on. Leaves w.cur at the first leaf (not yet visited).
@@ -73,50 +88,59 @@ __device__ __forceinline__ void walk_descend(__amdgpu_buffer_rsrc_t rsrc, const 
     // The lanes of a wave are neighbours on a scan ring: they share the top ≈10–14 levels of the tree. While every lane takes the
     // same turn, the node is read ONCE with a scalar load and its axis, threshold and children are wave-uniform — per lane only
     // d² and the candidate update remain (the kernel is VALU-bound, the scalar unit idles).
-    {
+    // One 8-byte scalar fetch per level and ONE way out of the loop: threshold and meta word arrive together, the lanes vote on the
+    // loaded pair whatever it is (on a leaf the "threshold" is its x coordinate: a vote nobody reads), and a single scalar condition —
+    // internal node, unanimous lanes — decides whether the level is shared.
+    if (T > 0) {
         uint32_t cur_s = 0;
-        for (; l < T; ++l) {
-            const uint2 hd = tree[__builtin_amdgcn_readfirstlane(cur_s)];
+        const unsigned long long all = __ballot(true);
+        bool more;
+        do {
+            const uint2 hd = node_head(tree, __builtin_amdgcn_readfirstlane(cur_s));
             const uint32_t meta = __builtin_amdgcn_readfirstlane(hd.y);
-            if (meta >= 0xC0000000u) break;  // a leaf above level T: the per-lane loop below sees it
             const float th = as_f32(__builtin_amdgcn_readfirstlane(hd.x));
+            const uint32_t right = node_right(meta), cur1 = cur_s + kNodeStep;
             const float qa = meta < 0x40000000u ? qx : (meta < 0x80000000u ? qy : qz);
             const bool go_left = qa < th;
             const unsigned long long m = __ballot(go_left);
-            if (m != 0ull && m != __ballot(true)) break;  // the lanes part here: this level is handled per lane
-            const uint32_t right = meta & 0x3FFFFFFFu, cur1 = cur_s + 1u;
-            const uint32_t far_slot = m != 0ull ? right : cur1;
-            const float dd = qa - th;
-            const float d2 = dd * dd;
-            const bool lt1 = d2 < c1, lt2 = d2 < c2;
-            c3 = __builtin_amdgcn_fmed3f(c2, d2, c3);
-            c2 = __builtin_amdgcn_fmed3f(c1, d2, c2);
-            c1 = __builtin_fminf(c1, d2);
-            const uint32_t f2n = lt2 ? far_slot : f2;
-            f2 = lt1 ? f1 : f2n;
-            f1 = lt1 ? far_slot : f1;
-            const uint32_t yn = lt2 ? 0u : c1_younger;
-            c1_younger = lt1 ? 1u : yn;
-            cur_s = m != 0ull ? cur1 : right;
-        }
+            // a leaf above level T, or the lanes part here: the per-lane loop below takes this level
+            const bool shared = (meta < 0xC0000000u) & ((m == 0ull) | (m == all));
+            more = false;
+            if (shared) {
+                const uint32_t far_slot = m != 0ull ? right : cur1;
+                const float dd = qa - th;
+                const float d2 = dd * dd;
+                const bool lt1 = d2 < c1, lt2 = d2 < c2;
+                c3 = __builtin_amdgcn_fmed3f(c2, d2, c3);
+                c2 = __builtin_amdgcn_fmed3f(c1, d2, c2);
+                c1 = min_lt(lt1, d2, c1);
+                const uint32_t f2n = lt2 ? far_slot : f2;
+                f2 = lt1 ? f1 : f2n;
+                f1 = lt1 ? far_slot : f1;
+                const uint32_t yn = lt2 ? 0u : c1_younger;
+                c1_younger = lt1 ? 1u : yn;
+                cur_s = m != 0ull ? cur1 : right;
+                more = ++l < T;
+            }
+        } while (more);
         cur = cur_s;
     }
     for (; l < T; ++l) {  // un-stored levels: sorted insertion of d² into (c1 ≤ c2 ≤ c3), far slots of the first two
-        const u32x4 n = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(cur << 3), 0, 0);
+        const u32x4 n = node_load(rsrc, cur);
         const uint32_t meta = n.y;
         if (meta >= 0xC0000000u) { at_leaf = true; break; }
         const float th = as_f32(n.x);
         const float qa = meta < 0x40000000u ? qx : (meta < 0x80000000u ? qy : qz);
         const float dd = qa - th;
         const float d2 = dd * dd;
-        const uint32_t right = meta & 0x3FFFFFFFu;
+        const uint32_t right = node_right(meta);
         const bool go_left = qa < th;
-        const uint32_t cur1 = cur + 1u;
+        const uint32_t cur1 = cur + kNodeStep;
         const uint32_t far_slot = go_left ? right : cur1;
         const bool lt1 = d2 < c1, lt2 = d2 < c2;
         c3 = __builtin_amdgcn_fmed3f(c2, d2, c3);
         c2 = __builtin_amdgcn_fmed3f(c1, d2, c2);
-        c1 = __builtin_fminf(c1, d2);
+        c1 = min_lt(lt1, d2, c1);
         const uint32_t f2n = lt2 ? far_slot : f2;
         f2 = lt1 ? f1 : f2n;
         f1 = lt1 ? far_slot : f1;
@@ -136,22 +160,22 @@ __device__ __forceinline__ void walk_descend(__amdgpu_buffer_rsrc_t rsrc, const 
             for (;;) {
 #pragma unroll
                 for (int j = 0; j < WIN; ++j) {
-                    const u32x4 n = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(cur << 3), 0, 0);
+                    const u32x4 n = node_load(rsrc, cur);
                     const uint32_t meta = n.y;
                     if (meta >= 0xC0000000u) { found = true; break; }
                     const float th = as_f32(n.x);
                     const float qa = meta < 0x40000000u ? qx : (meta < 0x80000000u ? qy : qz);
                     const float dd = qa - th;
-                    const uint32_t right = meta & 0x3FFFFFFFu;
+                    const uint32_t right = node_right(meta);
                     const bool go_left = qa < th;
-                    const uint32_t cur1 = cur + 1u;
+                    const uint32_t cur1 = cur + kNodeStep;
                     if (pass > 0) {  // level T + n3 − WIN leaves the window: an un-stored level like those above T
                         const float d2 = -as_f32(wd[j]);
                         const uint32_t far_slot = wf[j];
                         const bool lt1 = d2 < c1, lt2 = d2 < c2;
                         c3 = __builtin_amdgcn_fmed3f(c2, d2, c3);
                         c2 = __builtin_amdgcn_fmed3f(c1, d2, c2);
-                        c1 = __builtin_fminf(c1, d2);
+                        c1 = min_lt(lt1, d2, c1);
                         const uint32_t f2n = lt2 ? far_slot : f2;
                         f2 = lt1 ? f1 : f2n;
                         f1 = lt1 ? far_slot : f1;
@@ -185,15 +209,15 @@ __device__ __forceinline__ void walk_descend(__amdgpu_buffer_rsrc_t rsrc, const 
     } else if (!at_leaf) {
         uint32_t row = col_addr + 2u * ROWB;
         for (;;) {  // stored levels
-            const u32x4 n = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(cur << 3), 0, 0);
+            const u32x4 n = node_load(rsrc, cur);
             const uint32_t meta = n.y;
             if (meta >= 0xC0000000u) break;
             const float th = as_f32(n.x);
             const float qa = meta < 0x40000000u ? qx : (meta < 0x80000000u ? qy : qz);
             const float dd = qa - th;
-            const uint32_t right = meta & 0x3FFFFFFFu;
+            const uint32_t right = node_right(meta);
             const bool go_left = qa < th;
-            const uint32_t cur1 = cur + 1u;
+            const uint32_t cur1 = cur + kNodeStep;
             *reinterpret_cast<lds_u32x2*>(row) = u32x2{go_left ? right : cur1, __float_as_uint(-(dd * dd))};
             row += ROWB;
             rows++;
@@ -234,7 +258,7 @@ __device__ __forceinline__ void walk_rounds_capped(__amdgpu_buffer_rsrc_t rsrc, 
 #pragma unroll
     for (int j = 0; j < K; ++j) { d[j] = w.d[j]; id[j] = w.id[j]; }
     uint32_t slow = w.slow, c3n = w.c3n;
-    u32x4 n = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(cur << 3), 0, 0);
+    u32x4 n = node_load(rsrc, cur);
     do {
         if (STAMP) { my_rounds += (cur != dummy || avail > 0) ? 1u : 0u; all_rounds++; }
         const bool is_leaf = n.y >= 0xC0000000u;
@@ -290,7 +314,7 @@ __device__ __forceinline__ void walk_rounds_capped(__amdgpu_buffer_rsrc_t rsrc, 
         cur = nxt;
         avail = deep ? 0 : avail - used;
         // a lane that popped loads its new node; one that was not on a leaf still holds its internal node in n
-        if (moved) n = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(cur << 3), 0, 0);
+        if (moved) n = node_load(rsrc, cur);
 #pragma unroll
         for (int step = 0; step < C; ++step) {
             if (n.y < 0xC0000000u) {
@@ -299,13 +323,13 @@ __device__ __forceinline__ void walk_rounds_capped(__amdgpu_buffer_rsrc_t rsrc, 
                 const float qa = meta < 0x40000000u ? qx : (meta < 0x80000000u ? qy : qz);
                 const float dd = qa - th;
                 const uint32_t nd2 = __float_as_uint(-(dd * dd));
-                const uint32_t right = meta & 0x3FFFFFFFu;
+                const uint32_t right = node_right(meta);
                 const bool go_left = qa < th;
-                const uint32_t cur1 = cur + 1u;
+                const uint32_t cur1 = cur + kNodeStep;
                 *reinterpret_cast<lds_u32x2*>(col_addr + (uint32_t)avail * ROWB) = u32x2{go_left ? right : cur1, nd2};
                 avail += (int)nd2 < nbound ? 1 : 0;
                 cur = go_left ? cur1 : right;
-                n = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(cur << 3), 0, 0);
+                n = node_load(rsrc, cur);
             }
         }
     } while (__ballot(cur != dummy || avail > 0) != 0ull);
