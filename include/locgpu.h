@@ -860,9 +860,9 @@ LOCGPU_API int locgpu_range_ingest_times(locgpu_ctx* ctx, double out_ms[2]);
  * do not increase, a reference time that is not finite, a NULL motion or a NULL array inside it; and every refusal of the plain call,
  * the capacity one included.
  * Out of scope: clouds with per-point time fields (a per-point slerp kernel would be a later entry point on the same device
- * function); per-laser time offsets inside a column; estimating the motion (the caller supplies it: ESKF states, or the matcher's
- * previous two poses); re-compensating a batch that is already decoded; an asynchronous form; sharded and shared-source batches; the
- * C++ facade; bench.py. */
+ * function); per-laser time offsets inside a column; for the cloud forms, estimating the motion and compensating a scan again once it
+ * is decoded (batches: locgpu_motion_from_poses and locgpu_batch_deskew, "Deskew of a resident batch" below); an asynchronous form;
+ * sharded and shared-source batches; the C++ facade; bench.py. */
 typedef struct locgpu_sweep_motion {
     int32_t n_knots, reserved;
     const double* knot_times;
@@ -938,8 +938,8 @@ LOCGPU_API int locgpu_range_deskew_times(locgpu_ctx* ctx, double out_ms[3]);
  * times not finite or not strictly increasing, a reference time that is not finite, before the first knot or more than 0.5 s behind
  * the last, NULL members), decided by the host function the range-image path uses.
  * Out of scope: an asynchronous form; sharded and shared-source batches; the C++ facade (Conver lives in the ROS subscriber,
- * cloud_subscriber.cpp, which is not shadowed); bench.py; estimating the motion; re-compensating a batch that is already decoded;
- * big-endian blobs; strides above 64. */
+ * cloud_subscriber.cpp, which is not shadowed); bench.py; for the cloud forms, estimating the motion and compensating a scan again once
+ * it is decoded (batches: "Deskew of a resident batch" below); big-endian blobs; strides above 64. */
 enum { LOCGPU_TIME_NONE = 0, LOCGPU_TIME_F32 = 1, LOCGPU_TIME_F64 = 2, LOCGPU_TIME_U32 = 3 };
 enum { LOCGPU_RING_NONE = 0, LOCGPU_RING_U8 = 1, LOCGPU_RING_U16 = 2 };
 enum { LOCGPU_INTENSITY_NONE = 0, LOCGPU_INTENSITY_F32 = 1, LOCGPU_INTENSITY_U8 = 2 };
@@ -989,6 +989,82 @@ LOCGPU_API int locgpu_records_deskew_matrices(locgpu_ctx* ctx, int scan, double*
  * kernels' time of the most recent locgpu_*_upload_records[_deskew] (Conver, cloud_subscriber.cpp:7-29; PoseInterp, math_utils.h:470-517).
  * Zeros before the first profiled call. locgpu_range_ingest_times and locgpu_range_deskew_times are left alone. */
 LOCGPU_API int locgpu_records_ingest_times(locgpu_ctx* ctx, double out_ms[2]);
+
+/* ---- Deskew of a resident batch (csrc/resident_deskew.hip: rsd_check_kernel, rsd_move_kernel). The two deskewed ingest blocks above
+ * need the sweep motion BEFORE the scan is uploaded, and the caller has it only afterwards: it is what the alignment of that same scan
+ * yields. The reference forms it from the last two results, predict_pos = result_pos * last_pose.inverse() * result_pos (loc.cpp:232,
+ * lio.cpp:465). So the standard two-pass — align the skewed scan, derive the motion, compensate, re-align or merge — had to send the
+ * raw bytes over PCIe twice, and that copy is the whole cost of an ingest call. The raw survivors are already resident; what a plain
+ * ingest throws away is 8 bytes per point, its time. This block keeps them on request, adds the pass that uses them and the host
+ * function that turns a pose sequence into a locgpu_sweep_motion: ingest once, align, compensate, re-align or locgpu_batch_merge,
+ * without a second host-to-device copy. A caller who does not opt in sees no change: nothing is allocated, every call leaves the
+ * bytes it left before.
+ *
+ * Resident times. locgpu_batch_keep_times(b, 1) turns time keeping on for a batch (off by default). With it on, the PLAIN ingest calls
+ * leave one float64 time KEY per survivor beside the ring bytes, [n_scans][max_points_per_scan], allocated on first use:
+ *   locgpu_batch_upload_records with time_kind != LOCGPU_TIME_NONE: key = (double)field * time_scale, the first of the two IEEE
+ *     operations of "Point time" above; the offset is added by the pass;
+ *   locgpu_batch_upload_ranges with a sensor that has column times (locgpu_sensor_set_col_times): key = col_time[c] of the survivor's
+ *     column c.
+ * A layout without a time field or a sensor without column times leaves no times (the ingest itself succeeds as before); the *_deskew
+ * ingest forms never leave times: their points are no longer raw. Everything that drops the resident rings drops the times too (any
+ * other upload, locgpu_batch_preprocess into the batch, the feature picker's destinations), and so does a later ingest that leaves none.
+ * The pass, for every survivor of every scan i of src: tp = key + time_offsets[i] (one IEEE double addition; time_offsets == NULL:
+ * tp = key and nothing is added); the pose at tp and at ref_times[i] by PoseInterp's rule (math_utils.h:470-517) as "Range-image ingest,
+ * motion-compensated" states it; M = [ R_r^T R_p | R_r^T (t_p - t_r) ] as there; the point stored as locgpu_cloud_transform's
+ * arithmetic gives it with M, the w lane +0 — through the SAME device function as the per-point deskew of the record ingest, so the
+ * bytes are those of locgpu_batch_upload_records_deskew (locgpu_batch_upload_ranges_deskew) for the same scans, offsets and motion. A
+ * point keeps its place: no atomics, and nothing depends on n_scans or on a scan's place in the batch.
+ * dst == src compensates in place. Otherwise dst must hold the same number of scans and have room for every count of src; it receives
+ * the counts and, when src holds them, the ring bytes of src, so locgpu_batch_loam_extract_resident(dst, ...) works, and src keeps its
+ * raw points and times: it can be compensated again with a better motion. After the call dst never holds times: compensating
+ * compensated points is refused.
+ * Time refusals follow the ingest's mechanism: a check kernel counts the bad survivors of every scan first — tp not finite,
+ * tp < t[i][0], or tp - t[i][K-1] > 0.5 (PoseInterp's time_th) — and if any scan has one, out_status[i] = 1 for each such scan, the call
+ * returns LOCGPU_ERR_INVALID, the text names the first such scan and its count, and dst is exactly as it was (points, counts and
+ * rings), also when dst == src.
+ * Other refusals (LOCGPU_ERR_INVALID, with a text), decided on the host before any launch: a NULL batch; batches of different
+ * contexts; sharded or shared-source batches; an alignment begun and not ended on either batch; no resident times in src; different
+ * numbers of scans; every motion refusal of locgpu_batch_upload_ranges_deskew (the same host function; the reference times are bounded
+ * there); a non-finite time_offsets[i]; a scan of src with more points than dst has room for (dst is unchanged).
+ * Out of scope: the locgpu_cloud_* forms; the C++ facade; bench.py; an asynchronous form; sharded batches; estimating the motion from
+ * anything but poses. */
+/* Time keeping of a batch on (on != 0) or off (the default), for the survivors Conver keeps (cloud_subscriber.cpp:7-29) and PoseInterp's
+ * later use of their times (math_utils.h:470-517). Off: the times the batch holds are freed. LOCGPU_ERR_INVALID for a NULL, sharded or
+ * shared-source batch and for one whose alignment has been begun and not ended. */
+LOCGPU_API int locgpu_batch_keep_times(locgpu_batch* b, int on);
+/* For tests and tools, as locgpu_batch_download_rings: the resident time keys of scan `scan` (the times PoseInterp is asked at,
+ * math_utils.h:470-517, of Conver's survivors, cloud_subscriber.cpp:7-29), one double per point. *n (optional) = the scan's size;
+ * out == NULL returns it alone. LOCGPU_ERR_INVALID when the batch holds no times, for a scan index out of range and capacity < n. */
+LOCGPU_API int locgpu_batch_download_times(locgpu_batch* b, int scan, double* out, size_t capacity, size_t* n);
+/* The pass defined above: every survivor of src (Conver's, cloud_subscriber.cpp:7-29) moved into the sensor frame of ref_times[i] by the
+ * pose at its own time (PoseInterp, math_utils.h:470-517), into dst (dst == src: in place). The motion is typically
+ * locgpu_motion_from_poses' (loc.cpp:232). Blocking. Two kernels of this file round the ingest's sum and verdict kernels: the check
+ * (8 B per point in) and the move (16 B + 8 B in, 16 B out per point; the scan's knots staged in LDS). */
+LOCGPU_API int locgpu_batch_deskew(locgpu_batch* src, locgpu_batch* dst, const double* time_offsets /* n_scans or NULL */,
+                                   const locgpu_sweep_motion* motion, int32_t* out_status /* n_scans or NULL */);
+/* Measurement (tools/resident_deskew_time.py): with locgpu_profile_enable on, out_ms[0] = the check kernel's time and out_ms[1] = the
+ * move kernel's time (PoseInterp, math_utils.h:470-517, on Conver's survivors, cloud_subscriber.cpp:7-29) of the most recent
+ * locgpu_batch_deskew. Zeros before the first profiled call. */
+LOCGPU_API int locgpu_batch_deskew_times(locgpu_ctx* ctx, double out_ms[2]);
+/* The motion of n consecutive scans from their poses — host only, no launch, FP64, nothing normalised. poses [n][7] (quaternion xyzw,
+ * then translation: the matcher's results) and stamps [n] (strictly increasing) in; knot_times [n][3] and knot_poses [n][3][7] out:
+ * scan i gets K = 3 knots, the poses and stamps of scans i-1, i, i+1, which cover start-stamped and end-stamped sensors alike
+ * (PoseInterp, math_utils.h:470-517, then interpolates between them; the points are Conver's, cloud_subscriber.cpp:7-29). A missing
+ * neighbour is extrapolated at constant velocity with the reference's own expression predict_pos = result_pos * last_pose.inverse() *
+ * result_pos (loc.cpp:232): after the last scan the pose (T[n-1] * inv(T[n-2])) * T[n-1] at time 2.0 * t[n-1] - t[n-2]; before the
+ * first the pose (T[0] * inv(T[1])) * T[0] at time 2.0 * t[0] - t[1]. The caller fills ref_times itself.
+ * Arithmetic, one IEEE double operation per written operation, in this order (q = x, y, z, w; R(q) = Eigen's toRotationMatrix:
+ *   tx = 2 x, ty = 2 y, tz = 2 z; twx = tx w, twy = ty w, twz = tz w; txx = tx x, txy = ty x, txz = tz x; tyy = ty y, tyz = tz y,
+ *   tzz = tz z; R = [1 - (tyy + tzz), txy - twz, txz + twy; txy + twz, 1 - (txx + tzz), tyz - twx; txz - twy, tyz + twx, 1 - (txx + tyy)]):
+ *   a (x) b:  w = ((aw bw - ax bx) - ay by) - az bz;  x = ((aw bx + ax bw) + ay bz) - az by;
+ *             y = ((aw by + ay bw) + az bx) - ax bz;  z = ((aw bz + az bw) + ax by) - ay bx;
+ *   R v:      row r = (R[r][0] v0 + R[r][1] v1) + R[r][2] v2;
+ *   inv(q, t) = (c, -(R(c) t)) with c = (-x, -y, -z, w);
+ *   (q1, t1) * (q2, t2) = (q1 (x) q2, t1 + R(q1) t2), each component t1[r] + (R(q1) t2)[r].
+ * LOCGPU_ERR_INVALID, with a text (locgpu_last_error(NULL)), for n < 2, a NULL array, or stamps that are not finite or not increasing. */
+LOCGPU_API int locgpu_motion_from_poses(const double* poses /* n * 7 */, const double* stamps /* n */, int n, double* knot_times /* n * 3 */,
+                                        double* knot_poses /* n * 3 * 7 */);
 
 /* The local map of Lio::AddCloud's keyframe branch (lio.cpp:268-306), kept in HBM: a queue of at most num_kfs world-frame
  * keyframe clouds (scans_in_local_map_) and the voxel-filtered local map (local_map_) that is the next matching target.

@@ -61,6 +61,7 @@ ABI_SYMBOLS = [
     "locgpu_range_deskew_times",
     "locgpu_batch_upload_records", "locgpu_batch_upload_records_deskew", "locgpu_cloud_upload_records", "locgpu_cloud_upload_records_deskew",
     "locgpu_records_deskew_debug", "locgpu_records_deskew_matrices", "locgpu_records_ingest_times",
+    "locgpu_batch_keep_times", "locgpu_batch_download_times", "locgpu_batch_deskew", "locgpu_batch_deskew_times", "locgpu_motion_from_poses",
 ]
 COMM_ID_BYTES = 128
 NO_INTENSITY = ctypes.c_size_t(-1).value
@@ -280,6 +281,9 @@ def lib():
             "locgpu_cloud_upload_records_deskew": (i32, [vp, vp, vp, ctypes.c_int64, dbl, vp, vp, vp]),
             "locgpu_records_deskew_debug": (i32, [vp, i32]), "locgpu_records_deskew_matrices": (i32, [vp, i32, vp, sz, vp]),
             "locgpu_records_ingest_times": (i32, [vp, vp]),
+            "locgpu_batch_keep_times": (i32, [vp, i32]), "locgpu_batch_download_times": (i32, [vp, i32, vp, sz, vp]),
+            "locgpu_batch_deskew": (i32, [vp, vp, vp, vp, vp]), "locgpu_batch_deskew_times": (i32, [vp, vp]),
+            "locgpu_motion_from_poses": (i32, [vp, vp, i32, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -813,6 +817,12 @@ class Context:
         self._check(lib().locgpu_records_ingest_times(self._h, out.ctypes.data))
         return float(out[0]), float(out[1])
 
+    def batch_deskew_times(self):
+        """(check kernel ms, move kernel ms) of the most recent Batch.deskew while profile_enable is on (locgpu_batch_deskew_times)."""
+        out = np.zeros(2)
+        self._check(lib().locgpu_batch_deskew_times(self._h, out.ctypes.data))
+        return float(out[0]), float(out[1])
+
     def visit_count_enable(self, on=True):
         self._check(lib().locgpu_visit_count_enable(self._h, int(on)))
 
@@ -1022,6 +1032,22 @@ def sweep_motion(n_scans, knot_times, knot_poses, ref_times):
     if p.shape[1] != 7 * t.shape[1] or len(r) != n_scans:
         raise ValueError("a sweep motion holds K times and K poses of 7 per scan, and one reference time per scan")
     return SweepMotionC(t.shape[1], 0, t.ctypes.data, p.ctypes.data, r.ctypes.data), (t, p, r)
+
+
+def motion_from_poses(poses, stamps):
+    """(knot_times [n, 3], knot_poses [n, 3, 7]) of n consecutive scans from their poses [n, 7] (quaternion xyzw + translation) and
+    strictly increasing stamps [n] (locgpu_motion_from_poses, host only): scan i gets the poses of scans i-1, i, i+1, a missing
+    neighbour extrapolated at constant velocity as the reference's predict_pos. With ref_times they are what Batch.deskew takes."""
+    p = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7)
+    t = np.ascontiguousarray(stamps, dtype=np.float64).reshape(-1)
+    if len(t) != len(p):
+        raise ValueError("one stamp per pose")
+    n = len(p)
+    kt, kp = np.zeros((n, 3), np.float64), np.zeros((n, 3, 7), np.float64)
+    rc = lib().locgpu_motion_from_poses(p.ctypes.data if n else None, t.ctypes.data if n else None, n, kt.ctypes.data if n else None, kp.ctypes.data if n else None)
+    if rc != 0:
+        raise LocGpuError(rc, lib().locgpu_last_error(None).decode())
+    return kt, kp
 
 
 class Sensor:
@@ -1317,6 +1343,43 @@ class Batch:
         if n.value:
             self.ctx._check(lib().locgpu_batch_download_rings(self._h, int(s), out.ctypes.data, int(n.value), ctypes.byref(n)))
         return out
+
+    def keep_times(self, on=True):
+        """Make the plain ingest calls (upload_records, upload_ranges) leave one float64 time key per survivor beside the ring bytes
+        (locgpu_batch_keep_times): what deskew needs. Off by default; off frees the times the batch holds."""
+        self.ctx._check(lib().locgpu_batch_keep_times(self._h, int(bool(on))))
+
+    def download_times(self, s):
+        """The resident time keys of scan ``s`` (float64, one per point); refused when the batch holds none."""
+        self.upload_wait()
+        n = ctypes.c_size_t(0)
+        self.ctx._check(lib().locgpu_batch_download_times(self._h, int(s), None, 0, ctypes.byref(n)))
+        out = np.zeros(int(n.value), np.float64)
+        if n.value:
+            self.ctx._check(lib().locgpu_batch_download_times(self._h, int(s), out.ctypes.data, int(n.value), ctypes.byref(n)))
+        return out
+
+    def deskew(self, dst=None, time_offsets=None, *, knot_times, knot_poses, ref_times):
+        """Motion-compensate the resident scans at their kept point times (locgpu_batch_deskew) into ``dst`` (None: in place): a point's
+        time is its key + time_offsets[s] (None: the key alone); knot_times [n, K], knot_poses [n, K, 7], ref_times [n] as in
+        upload_records_deskew, e.g. from motion_from_poses. The bytes are those of the deskewed ingest of the same scans. Blocking. A
+        refused call raises a LocGpuError that carries ``.status`` (1 for a scan with a refused point time)."""
+        self.upload_wait()
+        dst = self if dst is None else dst
+        dst.upload_wait()
+        offs = None
+        if time_offsets is not None:
+            offs = np.ascontiguousarray(time_offsets, dtype=np.float64).reshape(-1)
+            if len(offs) != self.n_local:
+                raise ValueError("one time offset per scan")
+        motion, keep_m = sweep_motion(self.n_local, knot_times, knot_poses, ref_times)
+        status = np.zeros(self.n_local, np.int32)
+        rc = lib().locgpu_batch_deskew(self._h, dst._h, offs.ctypes.data if offs is not None else None, ctypes.byref(motion), status.ctypes.data)
+        if rc != 0:
+            err = LocGpuError(rc, lib().locgpu_last_error(self.ctx._h).decode())
+            err.status = status
+            raise err
+        return dst
 
     def loam_extract_resident(self, num_scan, edge, surf):
         """loam_extract with the ring bytes upload_ranges left in the batch (locgpu_batch_loam_extract_resident); same returns and errors."""

@@ -479,7 +479,7 @@ int locgpu_batch_preprocess(locgpu_batch* src, float leaf, locgpu_batch* dst, in
         return fail(ctx, LOCGPU_ERR_INVALID, "batch_preprocess: a filtered scan has " + std::to_string(res[n_scans].x) + " points, dst was created for " +
                                                  std::to_string(dst->max_n) + " per scan (dst is unchanged)");
     set_host_counts(dst, counts.data());
-    dst->rings_valid = false;  // centroids have no ring (locgpu_batch_upload_ranges' ring bytes, range_ingest.hip)
+    dst->rings_valid = dst->times_valid = false;  // centroids have no ring and no time (locgpu_batch_upload_ranges' ring bytes, range_ingest.hip)
     return LOCGPU_OK;
 }
 
@@ -520,7 +520,7 @@ int locgpu_batch_upload_clouds(locgpu_batch* b, const locgpu_cloud* const* cloud
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(ctx, e, "batch_upload_clouds"); }
     b->paced_tail = false;
-    b->rings_valid = false;
+    b->rings_valid = b->times_valid = false;
     set_host_counts(b, counts.data());
     return LOCGPU_OK;
 }

@@ -356,7 +356,7 @@ static int batch_loam_extract(locgpu_batch* src, const uint8_t* const* rings, bo
                                                  std::to_string(surf->max_n) + " per scan (both are unchanged)");
     set_host_counts(edge, ne.data());
     set_host_counts(surf, ns.data());
-    edge->rings_valid = surf->rings_valid = false;  // features are written in picking order: whatever rings the destinations held are gone
+    edge->rings_valid = surf->rings_valid = edge->times_valid = surf->times_valid = false;  // features are written in picking order: whatever rings the destinations held are gone
     return LOCGPU_OK;
 }
 

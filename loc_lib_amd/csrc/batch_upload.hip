@@ -224,7 +224,7 @@ int upload_start(locgpu_batch* b, const void* const* srcs, const size_t* counts,
         if (!hip_ok(ctx, hipEventRecord(b->tail_ev, b->stream), "batch upload: hipEventRecord") ||
             !hip_ok(ctx, hipStreamWaitEvent(ctx->copy_stream, b->tail_ev, 0), "batch upload: hipStreamWaitEvent")) return LOCGPU_ERR_NO_DEVICE;
     }
-    b->rings_valid = false;  // the ring bytes of locgpu_batch_upload_ranges belong to the points this upload replaces
+    b->rings_valid = b->times_valid = false;  // the ring bytes and point times of an ingest belong to the points this upload replaces
     const int rc = enqueue(b, b->upl, srcs, counts, stride_bytes, b->n_scans, nullptr, nullptr);
     if (rc == LOCGPU_OK)
         for (int s = 0; s < b->n_scans; ++s) b->counts[s] = (int)counts[s];

@@ -57,6 +57,7 @@ void batch_filters_free(locgpu_ctx* ctx);  // batch_filters.hip: the batch front
 void merge_free(locgpu_ctx* ctx);          // cloud_merge.hip: the global-map pass's workspaces (called by filters_free)
 void range_ingest_free(locgpu_ctx* ctx);   // range_ingest.hip: the ingest's workspaces and the context's remaining sensors (called by locgpu_destroy)
 void record_ingest_free(locgpu_ctx* ctx);  // record_ingest.hip: the point-record ingest's staging and workspaces (called by locgpu_destroy)
+void resident_deskew_free(locgpu_ctx* ctx);  // resident_deskew.hip: locgpu_batch_deskew's motion staging and workspaces (called by locgpu_destroy)
 // batch_filters.hip, for every pass over a batch's points on its context's stream (batch_loam.hip too). order_behind_batch: the stream
 // goes behind everything that may still touch b's points — its pending upload (the host side is waited for) and the idle launches a
 // paced one-scan alignment may have left queued; returns a locgpu_status. set_host_counts: the batch's three copies of its counts

@@ -24,6 +24,7 @@ struct BatchLoamScratch;    // batch_loam.hip
 struct MergeScratch;        // cloud_merge.hip
 struct RangeIngestScratch;  // range_ingest.hip
 struct RecordIngestScratch;  // record_ingest.hip
+struct ResidentDeskewScratch;  // resident_deskew.hip
 }  // namespace locgpu
 struct locgpu_sensor;  // range_ingest.hpp
 
@@ -116,6 +117,7 @@ struct locgpu_ctx {
     locgpu::MergeScratch* merge = nullptr;        // table and joined cloud of the global-map pass (cloud_merge.hip)
     locgpu::RangeIngestScratch* ringest = nullptr;  // staging and workspaces of the range-image ingest (range_ingest.hip)
     locgpu::RecordIngestScratch* recingest = nullptr;  // staging and workspaces of the point-record ingest (record_ingest.hip)
+    locgpu::ResidentDeskewScratch* rdeskew = nullptr;  // motion staging and workspaces of locgpu_batch_deskew (resident_deskew.hip)
     std::vector<locgpu_sensor*> sensors;          // the sensor models created on this context and not destroyed yet (range_ingest.hip)
 
     // reusable one-scan batch for the single-scan entry points
@@ -163,6 +165,12 @@ struct locgpu_batch {
     // locgpu_batch_loam_extract_resident. Allocated on first use; rings_valid is dropped by everything else that writes d_src.
     locgpu::DevBuf<unsigned char> d_rings;
     bool rings_valid = false;
+    // locgpu_batch_keep_times: one float64 time key per point slot, [n_scans][max_n], left beside the ring bytes by the PLAIN ingest
+    // calls (range_ingest.hip, record_ingest.hip) and read by locgpu_batch_deskew (resident_deskew.hip). Allocated on first use;
+    // times_valid is dropped wherever rings_valid is, and by the ingest calls that leave no times.
+    bool keep_times = false;
+    locgpu::DevBuf<double> d_times;
+    bool times_valid = false;
     locgpu::DevBuf<locgpu::PoseState> d_state;
     locgpu::DevBuf<uint32_t> d_nn;  // [5][pitch]
     // [n_scans][ceil(max_n / 64)] run flags of the plane fit, written by the 64-lane walk kernel (SearchArgs::run_flags);

@@ -1,11 +1,13 @@
 // loc_lib_amd/csrc/pose_interp.hpp — math::PoseInterp on the device (LocUtils/include/LocUtils/common/math_utils.h:470-517): the one copy
 // of the slerp and of the matrix made of it, shared by the per-column deskew of the range-image ingest (range_ingest.hip,
-// rd_pose_kernel) and the per-point deskew of the point-record ingest (record_ingest.hip, rec_scatter_kernel).
+// rd_pose_kernel), the per-point deskew of the point-record ingest (record_ingest.hip, rec_scatter_kernel) and the pass over a resident
+// batch (resident_deskew.hip, rsd_move_kernel).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
 
+#include "cloud_filters.hpp"
 #include "device_math.hpp"
 
 namespace locgpu {
@@ -81,6 +83,17 @@ __device__ __forceinline__ void rd_matrix(const double* ref, const double (&pq)[
         m[4 * r + 2] = (a0 * Rq[2] + a1 * Rq[5]) + a2 * Rq[8];
         m[4 * r + 3] = (a0 * d0 + a1 * d1) + a2 * d2;
     }
+}
+
+// One survivor of a scan moved into the reference frame at its OWN time tp: the pose at tp on the knots staged in LDS, its matrix m
+// against the scan's reference pose `ref` (rd_ref_pose), and the point as locgpu_cloud_transform's arithmetic gives it (every
+// survivor is finite). The one copy of the per-point deskew: the store loop of the point-record ingest (record_ingest.hip,
+// rec_scatter_kernel<true>) and the pass over a resident batch (resident_deskew.hip, rsd_move_kernel) both call it.
+__device__ __forceinline__ float4 rd_move_point(const double* t, const double* p, int K, const double* ref, double tp, const float4& pt, double (&m)[12]) {
+    double pq[7];
+    rd_pose_at(t, p, K, tp, pq);
+    rd_matrix(ref, pq, m);
+    return transform_point_f64(pt, m, true);
 }
 
 }  // namespace locgpu

@@ -34,7 +34,9 @@
 //            the column's matrix (transform_point_f64), so only survivors are transformed
 //
 // — so survivors, order, counts and ring bytes are the plain call's. Scratch: 96 B per column and scan for the matrices, 8 B per knot
-// value (+ pinned). The plain entry points launch the four kernels above and nothing else.
+// value (+ pinned). The plain entry points launch the four kernels above and nothing else — with locgpu_batch_keep_times on and a
+// sensor that has column times, ri_scatter_times_kernel in ri_scatter_kernel's place: the same bytes, and col_time[column] of every
+// survivor beside its ring byte, for locgpu_batch_deskew (resident_deskew.hip).
 //
 // Shared with the point-record ingest (record_ingest.hip): Conver's keep rule and block_exclusive (range_ingest.hpp), rd_pose_at and the
 // matrix product (pose_interp.hpp), the offsets and verdict kernels (ingest_launch_*; a second row of sums that this file leaves
@@ -152,14 +154,17 @@ __global__ __launch_bounds__(kRI) void ri_verdict_kernel(int32_t* __restrict__ r
 
 // Tile (blockIdx.x, scan blockIdx.y) → dst + s · dst_max_n + tile offset, {x, y, z, +0}, and the ring bytes beside it: the body of both
 // scatter kernels. kDeskew: the survivor's column is carried through the compaction beside its ring byte and the final store loop
-// applies the column's matrix (mats [n_scans][n_cols][12], rd_pose_kernel), so only survivors are transformed.
-template <bool kDeskew>
+// applies the column's matrix (mats [n_scans][n_cols][12], rd_pose_kernel), so only survivors are transformed. kTimes (plain form only,
+// a batch with locgpu_batch_keep_times on): the column is carried the same way and the store loop leaves col_time[column] in dst_time.
+template <bool kDeskew, bool kTimes = false>
 __device__ __forceinline__ void scatter_tile(const SensorView& v, const uint16_t* __restrict__ img, uint32_t n_tiles, const uint32_t* __restrict__ tile_off,
                                              const int32_t* __restrict__ res, int n_scans, uint32_t dst_max_n, const double* __restrict__ mats, float4* __restrict__ dst,
-                                             unsigned char* __restrict__ dst_ring, int* __restrict__ dst_counts) {
+                                             unsigned char* __restrict__ dst_ring, int* __restrict__ dst_counts, const double* __restrict__ col_time = nullptr,
+                                             double* __restrict__ dst_time = nullptr) {
+    static_assert(!(kDeskew && kTimes), "deskewed points are no longer raw: they leave no times");
     if (res[n_scans] == 0) return;  // the same for every thread of the grid
     __shared__ float4 s_pts[kTile];
-    __shared__ uint16_t s_col[kDeskew ? kTile : 1];  // n_cols <= 12 288
+    __shared__ uint16_t s_col[kDeskew || kTimes ? kTile : 1];  // n_cols <= 12 288
     __shared__ unsigned char s_ring[kTile];
     __shared__ uint32_t s_wave[kRI / 64];
     const uint32_t s = blockIdx.y, tile = blockIdx.x;
@@ -175,7 +180,7 @@ __device__ __forceinline__ void scatter_tile(const SensorView& v, const uint16_t
     for (int j = 0; j < kCellsPerLane; ++j) {
         if (mask & (1u << j)) {
             s_pts[at] = pts[j];
-            if constexpr (kDeskew) s_col[at] = (uint16_t)(base + j - ring[j] * v.n_cols);  // cell = ring · n_cols + column
+            if constexpr (kDeskew || kTimes) s_col[at] = (uint16_t)(base + j - ring[j] * v.n_cols);  // cell = ring · n_cols + column
             s_ring[at] = (unsigned char)ring[j];
             ++at;
         }
@@ -189,6 +194,7 @@ __device__ __forceinline__ void scatter_tile(const SensorView& v, const uint16_t
         else
             dst[out + i] = s_pts[i];
         dst_ring[out + i] = s_ring[i];
+        if constexpr (kTimes) dst_time[out + i] = col_time[s_col[i]];  // s_col < n_cols, the table's length; [n_scans][dst_max_n], the layout of dst
     }
 }
 
@@ -196,6 +202,14 @@ __global__ __launch_bounds__(kRI) void ri_scatter_kernel(SensorView v, const uin
                                                          const int32_t* __restrict__ res, int n_scans, uint32_t dst_max_n, float4* __restrict__ dst,
                                                          unsigned char* __restrict__ dst_ring, int* __restrict__ dst_counts) {
     scatter_tile<false>(v, img, n_tiles, tile_off, res, n_scans, dst_max_n, nullptr, dst, dst_ring, dst_counts);
+}
+
+// ri_scatter_kernel that also leaves every survivor's time key — its column's firing time — in dst_time (locgpu_batch_keep_times).
+__global__ __launch_bounds__(kRI) void ri_scatter_times_kernel(SensorView v, const uint16_t* __restrict__ img, uint32_t n_tiles, const uint32_t* __restrict__ tile_off,
+                                                               const int32_t* __restrict__ res, int n_scans, uint32_t dst_max_n, const double* __restrict__ col_time,
+                                                               float4* __restrict__ dst, unsigned char* __restrict__ dst_ring, int* __restrict__ dst_counts,
+                                                               double* __restrict__ dst_time) {
+    scatter_tile<false, true>(v, img, n_tiles, tile_off, res, n_scans, dst_max_n, nullptr, dst, dst_ring, dst_counts, col_time, dst_time);
 }
 
 // ---- Motion compensation at decode (include/locgpu.h, "Range-image ingest, motion-compensated") ------------------------------------
@@ -349,9 +363,10 @@ hipError_t stage_images(locgpu_ctx* ctx, const uint16_t* const* images, int n_sc
 
 // dk: the checked motion of a deskewed call (check_sweep_motion), or NULL.
 // The pass for n_scans images into dst [n_scans][dst_max_n] (+ ring bytes, + device counts unless dst_counts is NULL), on
-// ctx->stream; the counts and the verdict are on their way to S->h_res when it returns.
+// ctx->stream; the counts and the verdict are on their way to S->h_res when it returns. dst_time (plain form of a sensor with column
+// times only, else NULL): the survivors' time keys, [n_scans][dst_max_n].
 hipError_t ingest_dev(locgpu_ctx* ctx, const locgpu_sensor* sn, const uint16_t* const* images, int n_scans, float4* dst, unsigned char* dst_ring, int* dst_counts,
-                      uint32_t dst_max_n, const locgpu_sweep_motion* dk = nullptr) {
+                      uint32_t dst_max_n, const locgpu_sweep_motion* dk = nullptr, double* dst_time = nullptr) {
     const size_t cells = sn->cells(), cells_pad = (cells + kCellsPerLane - 1) / kCellsPerLane * kCellsPerLane;
     const uint32_t n_tiles = (uint32_t)((cells + kTile - 1) / kTile);
     LOCGPU_TRY(ensure(ctx, (size_t)n_scans, cells_pad, n_tiles));
@@ -406,6 +421,9 @@ hipError_t ingest_dev(locgpu_ctx* ctx, const locgpu_sensor* sn, const uint16_t* 
     if (dk)
         hipLaunchKernelGGL(rd_scatter_kernel, dim3(n_tiles, n_scans), dim3(kRI), 0, s, v, S->d_img.get(), n_tiles, S->tile_off.get(), S->res.get(), n_scans, dst_max_n,
                            S->d_mats.get(), dst, dst_ring, dst_counts);
+    else if (dst_time)
+        hipLaunchKernelGGL(ri_scatter_times_kernel, dim3(n_tiles, n_scans), dim3(kRI), 0, s, v, S->d_img.get(), n_tiles, S->tile_off.get(), S->res.get(), n_scans, dst_max_n,
+                           sn->d_col_time.get(), dst, dst_ring, dst_counts, dst_time);
     else
         hipLaunchKernelGGL(ri_scatter_kernel, dim3(n_tiles, n_scans), dim3(kRI), 0, s, v, S->d_img.get(), n_tiles, S->tile_off.get(), S->res.get(), n_scans, dst_max_n, dst,
                            dst_ring, dst_counts);
@@ -587,7 +605,11 @@ int batch_upload_ranges(locgpu_batch* b, const locgpu_sensor* s, const uint16_t*
     if (rc != LOCGPU_OK) return rc;
     hipError_t e = b->d_rings ? hipSuccess : b->d_rings.alloc(std::max<size_t>(b->pitch, 1));
     if (e != hipSuccess) return hip_fail(ctx, e, (who + ": ring bytes").c_str());
-    e = ingest_dev(ctx, s, images, n_scans, b->d_src, b->d_rings, b->d_counts, (uint32_t)b->max_n, deskew ? motion : nullptr);
+    // locgpu_batch_keep_times: the plain form of a sensor with column times leaves the survivors' time keys; the deskewed form never does
+    const bool times = !deskew && b->keep_times && s->has_col_times;
+    if (e == hipSuccess && times && !b->d_times) e = b->d_times.alloc(std::max<size_t>(b->pitch, 1));
+    if (e != hipSuccess) return hip_fail(ctx, e, (who + ": point times").c_str());
+    e = ingest_dev(ctx, s, images, n_scans, b->d_src, b->d_rings, b->d_counts, (uint32_t)b->max_n, deskew ? motion : nullptr, times ? b->d_times.get() : nullptr);
     // the one read-back: when it is there the whole pass has run, and whatever uses the batch next — on any stream — finds it complete
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) {
@@ -604,6 +626,7 @@ int batch_upload_ranges(locgpu_batch* b, const locgpu_sensor* s, const uint16_t*
                                                  std::to_string(b->max_n) + " per scan (the batch is unchanged)");
     set_host_counts(b, res);
     b->rings_valid = true;
+    b->times_valid = times;
     return LOCGPU_OK;
 }
 

@@ -17,7 +17,9 @@
 //   scatter  block (tile, scan): pick again, compact the tile in LDS in input order (point with the intensity in     rec_scatter_kernel
 //            lane w, ring byte, the time in the deskew form), then a store loop over survivors — deskew form:            <kDeskew>
 //            rd_pose_at at the survivor's time on the scan's knots staged in LDS, the matrix against the scan's
-//            reference pose (computed once per block by thread 0), transform_point_f64 — coalesced float4 stores
+//            reference pose (computed once per block by thread 0), transform_point_f64 — coalesced float4 stores;     <., kTimes>
+//            plain form into a batch with locgpu_batch_keep_times on: the time KEY (double)field * time_scale goes
+//            through the compaction instead and is stored beside the ring byte, for locgpu_batch_deskew (resident_deskew.hip)
 //
 // Scans have different lengths: the grid is (tiles of the longest scan, n_scans) and a tile past its scan's end counts 0. A
 // survivor's position is the number of survivors before it in input order: no atomics, so counts, order and bits do not depend on
@@ -90,8 +92,9 @@ __device__ __forceinline__ bool rec_point(const RecView& v, uint64_t rec, float&
     return conver_keep(x, y, z, v.min_range);
 }
 
-// The point's time: (double)field * time_scale + offset, two IEEE double operations.
-__device__ __forceinline__ double rec_time(const RecView& v, uint64_t rec, double offset) {
+// The point's time key: (double)field * time_scale, the first of the two IEEE double operations of the point's time — what a batch that
+// keeps times (locgpu_batch_keep_times) stores per survivor.
+__device__ __forceinline__ double rec_time_key(const RecView& v, uint64_t rec) {
     double f;
     if (v.time_kind == LOCGPU_TIME_F64) {
         uint32_t q[2];
@@ -102,10 +105,20 @@ __device__ __forceinline__ double rec_time(const RecView& v, uint64_t rec, doubl
         rec_words<1>(v.words, rec + v.time_off, q);
         f = v.time_kind == LOCGPU_TIME_F32 ? (double)__uint_as_float(q[0]) : (double)q[0];
     }
+    double key;
+    {
+#pragma clang fp contract(off)
+        key = f * v.time_scale;
+    }
+    return key;
+}
+
+// The point's time: (double)field * time_scale + offset, two IEEE double operations.
+__device__ __forceinline__ double rec_time(const RecView& v, uint64_t rec, double offset) {
+    const double scaled = rec_time_key(v, rec);
     double tp;
     {
 #pragma clang fp contract(off)
-        const double scaled = f * v.time_scale;
         tp = scaled + offset;
     }
     return tp;
@@ -157,13 +170,16 @@ __global__ __launch_bounds__(kRI) void rec_count_kernel(RecView v, uint32_t n_ti
 
 // Tile (blockIdx.x, scan blockIdx.y) → dst + s · dst_max_n + tile offset, {x, y, z, intensity or +0}, and the ring bytes beside it.
 // kDeskew: each survivor is moved by the matrix of its own time; dbg (NULL unless locgpu_records_deskew_debug is on) receives it.
-template <bool kDeskew>
+// kTimes (plain form only, a batch with locgpu_batch_keep_times on): the survivor's time key rec_time_key goes through the compaction
+// and into dst_time beside the ring byte.
+template <bool kDeskew, bool kTimes = false>
 __global__ __launch_bounds__(kRI) void rec_scatter_kernel(RecView v, uint32_t n_tiles, const uint32_t* __restrict__ tile_off, const int32_t* __restrict__ res, int n_scans,
                                                           uint32_t dst_max_n, const double* __restrict__ motion, int K, double* __restrict__ dbg, float4* __restrict__ dst,
-                                                          unsigned char* __restrict__ dst_ring, int* __restrict__ dst_counts) {
+                                                          unsigned char* __restrict__ dst_ring, int* __restrict__ dst_counts, double* __restrict__ dst_time) {
+    static_assert(!(kDeskew && kTimes), "deskewed points are no longer raw: they leave no times");
     if (res[n_scans] == 0) return;  // the same for every thread of the grid
     __shared__ float4 s_pts[kRecTile];
-    __shared__ double s_tp[kDeskew ? kRecTile : 1];
+    __shared__ double s_tp[kDeskew || kTimes ? kRecTile : 1];
     __shared__ unsigned char s_ring[kRecTile];
     __shared__ uint32_t s_wave[kRI / 64];
     __shared__ double s_t[kDeskew ? kMaxKnots : 1];
@@ -192,23 +208,24 @@ __global__ __launch_bounds__(kRI) void rec_scatter_kernel(RecView v, uint32_t n_
         s_pts[at] = float4{px, py, pz, rec_intensity(v, rec)};
         s_ring[at] = (unsigned char)rec_ring(v, rec);
         if constexpr (kDeskew) s_tp[at] = rec_time(v, rec, motion_time_offset(motion, n_scans, K, s));
+        if constexpr (kTimes) s_tp[at] = rec_time_key(v, rec);
     }
     __syncthreads();
     // tile_off + total <= res[s] <= dst_max_n (the verdict): every store below is inside scan s's rows
     const size_t out = (size_t)s * dst_max_n + tile_off[(size_t)s * n_tiles + tile];
     for (uint32_t j = threadIdx.x; j < total; j += kRI) {
         if constexpr (kDeskew) {
-            double pq[7], m[12];
-            rd_pose_at(s_t, s_p, K, s_tp[j], pq);
-            rd_matrix(s_ref, pq, m);
+            double m[12];
+            const float4 moved = rd_move_point(s_t, s_p, K, s_ref, s_tp[j], s_pts[j], m);
             if (dbg) {  // the same for every thread of the grid; sized n_scans · dst_max_n matrices (ensure_debug)
 #pragma unroll
                 for (int k = 0; k < 12; ++k) dbg[(out + j) * 12 + k] = m[k];
             }
-            dst[out + j] = transform_point_f64(s_pts[j], m, true);  // every survivor is finite
+            dst[out + j] = moved;
         } else {
             dst[out + j] = s_pts[j];
         }
+        if constexpr (kTimes) dst_time[out + j] = s_tp[j];  // [n_scans][dst_max_n], the layout of dst
         if (dst_ring) dst_ring[out + j] = s_ring[j];
     }
 }
@@ -306,8 +323,9 @@ hipError_t stage_records(locgpu_ctx* ctx, const RecCall& c, const std::vector<si
 }
 
 // The pass for c.n_scans blobs into dst [n_scans][dst_max_n] (+ ring bytes unless dst_ring is NULL, + device counts unless dst_counts
-// is NULL) on ctx->stream; counts, verdict and refused-time counts are on their way to S->h_res when it returns.
-hipError_t records_dev(locgpu_ctx* ctx, const RecCall& c, float4* dst, unsigned char* dst_ring, int* dst_counts, uint32_t dst_max_n) {
+// is NULL, + the survivors' time keys [n_scans][dst_max_n] unless dst_time is NULL: plain form of a layout with a time field only) on
+// ctx->stream; counts, verdict and refused-time counts are on their way to S->h_res when it returns.
+hipError_t records_dev(locgpu_ctx* ctx, const RecCall& c, float4* dst, unsigned char* dst_ring, int* dst_counts, uint32_t dst_max_n, double* dst_time = nullptr) {
     RecordIngestScratch* S = scratch(ctx);
     const locgpu_point_layout& L = *c.layout;
     const int n_scans = c.n_scans, K = c.motion ? c.motion->n_knots : 0, rows = c.motion ? 2 : 1;
@@ -370,7 +388,7 @@ hipError_t records_dev(locgpu_ctx* ctx, const RecCall& c, float4* dst, unsigned 
     v.stride = L.stride_bytes;
     v.xyz_off = L.xyz_offset;
     v.time_off = L.time_offset;
-    v.time_kind = c.motion ? L.time_kind : (uint32_t)LOCGPU_TIME_NONE;
+    v.time_kind = c.motion || dst_time ? L.time_kind : (uint32_t)LOCGPU_TIME_NONE;
     v.ring_off = L.ring_offset;
     v.ring_kind = L.ring_kind;
     v.int_off = L.intensity_offset;
@@ -385,9 +403,14 @@ hipError_t records_dev(locgpu_ctx* ctx, const RecCall& c, float4* dst, unsigned 
     ingest_launch_offsets(s, S->tile_cnt.get(), n_tiles, S->tile_off.get(), S->res.get(), n_scans, rows);
     ingest_launch_verdict(s, S->res.get(), n_scans, dst_max_n, rows);
     if (c.motion)
-        hipLaunchKernelGGL(rec_scatter_kernel<true>, grid, dim3(kRI), 0, s, v, n_tiles, S->tile_off.get(), S->res.get(), n_scans, dst_max_n, motion, K, dbg, dst, ring, dst_counts);
+        hipLaunchKernelGGL(rec_scatter_kernel<true>, grid, dim3(kRI), 0, s, v, n_tiles, S->tile_off.get(), S->res.get(), n_scans, dst_max_n, motion, K, dbg, dst, ring, dst_counts,
+                           (double*)nullptr);
+    else if (dst_time)
+        hipLaunchKernelGGL((rec_scatter_kernel<false, true>), grid, dim3(kRI), 0, s, v, n_tiles, S->tile_off.get(), S->res.get(), n_scans, dst_max_n, motion, K, dbg, dst, ring,
+                           dst_counts, dst_time);
     else
-        hipLaunchKernelGGL(rec_scatter_kernel<false>, grid, dim3(kRI), 0, s, v, n_tiles, S->tile_off.get(), S->res.get(), n_scans, dst_max_n, motion, K, dbg, dst, ring, dst_counts);
+        hipLaunchKernelGGL(rec_scatter_kernel<false>, grid, dim3(kRI), 0, s, v, n_tiles, S->tile_off.get(), S->res.get(), n_scans, dst_max_n, motion, K, dbg, dst, ring, dst_counts,
+                           (double*)nullptr);
     LOCGPU_TRY(hipGetLastError());
     if (prof) {
         LOCGPU_TRY(hipEventRecord(S->prof[3], s));
@@ -491,8 +514,12 @@ int batch_upload_records(locgpu_batch* b, const locgpu_point_layout* layout, con
     const bool rings = layout->ring_kind != LOCGPU_RING_NONE;
     hipError_t e = !rings || b->d_rings ? hipSuccess : b->d_rings.alloc(std::max<size_t>(b->pitch, 1));
     if (e != hipSuccess) return hip_fail(ctx, e, (who + ": ring bytes").c_str());
+    // locgpu_batch_keep_times: the plain form of a layout with a time field leaves the survivors' time keys; a deskewed form never does
+    const bool times = !deskew && b->keep_times && layout->time_kind != LOCGPU_TIME_NONE;
+    e = !times || b->d_times ? hipSuccess : b->d_times.alloc(std::max<size_t>(b->pitch, 1));
+    if (e != hipSuccess) return hip_fail(ctx, e, (who + ": point times").c_str());
     const RecCall c{layout, records, n_points, n_scans, time_offsets, deskew ? motion : nullptr, false};
-    e = records_dev(ctx, c, b->d_src, b->d_rings, b->d_counts, (uint32_t)b->max_n);
+    e = records_dev(ctx, c, b->d_src, b->d_rings, b->d_counts, (uint32_t)b->max_n, times ? b->d_times.get() : nullptr);
     // the one read-back: when it is there the whole pass has run, and whatever uses the batch next — on any stream — finds it complete
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) {
@@ -517,6 +544,7 @@ int batch_upload_records(locgpu_batch* b, const locgpu_point_layout* layout, con
     keep_debug(ctx, c);
     set_host_counts(b, res);
     b->rings_valid = rings;
+    b->times_valid = times;
     return LOCGPU_OK;
 }
 
