@@ -97,7 +97,8 @@ typedef struct locgpu_align_stats {
     int32_t status;            /* 0 ok; 1 direct-NDT det(H)==0 ⇒ reference returns before writing result_pose (ndt cpp:435-436);
                                   2 incremental NDT: too few effective residuals ⇒ returns false with the current pose (ndt cpp:349-353);
                                   locgpu_loam_* only: 3 the SURFACE class's evaluation reported false, 4 the EDGE class's did ⇒
-                                  ScanMatch returns false before writing result_pose (loam_registration.cpp:56-70); surface is tested first */
+                                  ScanMatch returns false before writing result_pose (loam_registration.cpp:56-70); surface is tested first;
+                                  locgpu_icp_align_pairs only: 5 (LOCGPU_STATUS_NO_PAIR_TARGET) the scan was given no target and was not aligned */
     int32_t reserved;
     int64_t last_effective_num;
     double last_dx_norm;
@@ -1183,6 +1184,71 @@ LOCGPU_API int locgpu_batch_merge(locgpu_batch* b, const double* poses /* n_scan
  * locgpu_batch_download_scan (scan index out of range, shared-source batch, alignment begun and not ended), a NULL batch or cloud, a
  * cloud on another GPU. */
 LOCGPU_API int locgpu_batch_export_cloud(locgpu_batch* b, int scan, locgpu_cloud* cloud);
+
+/* =====================================================================================================================
+ * ---- Pairwise batch ICP: every scan of a batch against a target of its own.
+ *
+ * The reference's scan-to-scan odometry (slam_demo/src/apps/test_node.cpp:256-315; two PCD files: :437-460) runs, per scan,
+ * SetInputTarget(last_cloud) (icp_registration.cpp:9-29), ScanMatch(current_cloud, SE3(), ...) (icp_registration.cpp:216-244) and
+ * T_w_lc = T_w_lc * T_lc_ln. The initial pose is the identity every time, so the pairs (scan i, scan i-1) of a whole log are
+ * independent of each other. Here n targets are ingested as a FOREST — n KD-trees, each slot for slot what locgpu_icp_set_target
+ * builds for that cloud alone, packed behind one another in one device array — and one call aligns every scan of a batch against
+ * the tree it names. The same call with a score per pair verifies k loop-closure candidates.
+ *
+ * Limits of a forest: 1 <= n_targets; every target is what locgpu_icp_set_target accepts (non-empty, stride >= 12, tree depth <= 64);
+ * all trees together, with a two-slot sentinel leaf behind each and a slot of padding where a tree would start at an odd slot, stay
+ * below 2^29 slots of 8 bytes (4 GiB: what ONE tree may hold), so 3 points' worth of slots per point: about 178 M points in all.
+ * A refused ingest leaves the context exactly as it was and names the target's index in locgpu_last_error.
+ *
+ * A context that holds a forest answers only the calls of this block, and locgpu_icp_set_target* (any form), which replaces the
+ * forest and makes the context ordinary again. Every other entry point that reads the ICP target — locgpu_knn, locgpu_icp_align*,
+ * locgpu_icp_hb*, locgpu_icp_scan_match, locgpu_icp_fitness*, locgpu_icp_init_search, locgpu_pool_*, the map planes, the grid search
+ * mode, locgpu_loam_create_on and the calls of a LOAM handle on such a context — returns LOCGPU_ERR_INVALID with a text that says
+ * so; an ordinary context refuses locgpu_icp_align_pairs / locgpu_icp_fitness_pairs the same way. locgpu_icp_target_info reports the
+ * forest's totals (depth: the largest). locgpu_debug_batch_nn after a pairs call reports point indices of each scan's OWN target.
+ *
+ * Not covered: NDT and LOAM pairs, scan pools, hipGraph replay, sharded and shared-source batches, the C++ facade, bench.py, an
+ * asynchronous (begin / end) form.
+ * ===================================================================================================================== */
+
+/* locgpu_align_stats::status of a scan that locgpu_icp_align_pairs was told not to align (target_of[i] == -1); used for nothing else. */
+#define LOCGPU_STATUS_NO_PAIR_TARGET 5
+
+/* SetInputTarget (icp_registration.cpp:9-29) of n_targets clouds at once, host pointers: pts[j] = n[j] points of stride_bytes each,
+ * deep-copied before the call returns — the last_cloud of every pair of test_node.cpp:256-315. The trees are built on the host in
+ * parallel across trees (each by one thread, in the reference's summation order) and go up in ONE host-to-device copy. Blocking.
+ * LOCGPU_ERR_INVALID for NULL arrays, n_targets < 1, an empty target, stride < 12 and a forest beyond the size limit above;
+ * LOCGPU_ERR_DEPTH for a tree deeper than 64 levels. */
+LOCGPU_API int locgpu_icp_set_target_forest(locgpu_ctx* ctx, const void* const* pts, const size_t* n, int n_targets, size_t stride_bytes);
+/* The same from a resident plain batch of this context: target j = scan j of `batch` (what locgpu_batch_preprocess left there, for
+ * instance — the filtered clouds test_node.cpp:256-315 matches; SetInputTarget, icp_registration.cpp:9-29). The points reach the
+ * host builder the way locgpu_icp_set_target_cloud brings a cloud's there: 16 B a point down, the packed trees up. The batch is not
+ * modified and may be the source batch of the pairs call that follows. Refused (LOCGPU_ERR_INVALID): a NULL batch, a batch of another
+ * context, sharded and shared-source batches, a batch with an alignment begun and not ended, an empty scan (its index is named). */
+LOCGPU_API int locgpu_icp_set_target_forest_batch(locgpu_ctx* ctx, const locgpu_batch* batch);
+/* *n_targets = trees of the forest; leaves[j] = KdTree::size_ of tree j (SetInputTarget, icp_registration.cpp:9-29), depth[j] = its
+ * depth (root = level 1) — what locgpu_icp_target_info reports after locgpu_icp_set_target of that cloud alone. The two arrays have
+ * n_targets entries each and may be NULL (call once with NULL arrays for the count). LOCGPU_ERR_INVALID (*n_targets = 0) when the
+ * context holds an ordinary target, LOCGPU_ERR_NO_TARGET without any. */
+LOCGPU_API int locgpu_icp_forest_info(const locgpu_ctx* ctx, int* n_targets, size_t* leaves, int* depth);
+/* ScanMatch (icp_registration.cpp:216-244) of every scan of `batch` against target target_of[i] of the context's forest — the loop
+ * body of test_node.cpp:256-315 (two clouds: :437-460) for all pairs in one call. init_poses: n_scans x 7, or NULL = the identity for
+ * every scan, the reference's `SE3 init_pos` (test_node.cpp:289). target_of[i] == -1: scan i is not aligned — out_poses[i] is its
+ * initial pose, stats[i].iterations = 0, stats[i].status = LOCGPU_STATUS_NO_PAIR_TARGET. Methods LOCGPU_P2P, LOCGPU_P2LINE,
+ * LOCGPU_P2PLANE; `approximate` / ann_alpha as in locgpu_icp_align_batch; LOCGPU_P2PLANE_MAP and LOCGPU_SEARCH_GRID_EXACT are refused.
+ * Scan i's pose and stats equal, bit for bit, row i of locgpu_icp_align_batch of the SAME batch on an ordinary context that holds
+ * target target_of[i] alone (a batch splits its sums by its shape, so the shape matters). Blocking and eager: it runs eagerly whatever
+ * locgpu_graph_enable was told and never touches the batch's captured graphs. Refused (LOCGPU_ERR_INVALID), with the batch untouched:
+ * NULL arguments, a target_of entry < -1 or >= n_targets, sharded and shared-source batches, a batch of another context, a batch
+ * with an alignment begun and not ended, an ordinary context. */
+LOCGPU_API int locgpu_icp_align_pairs(locgpu_ctx* ctx, locgpu_batch* batch, const int* target_of, const double* init_poses /* n_scans x 7 or NULL */,
+                                      const locgpu_icp_opts* opts, double* out_poses, locgpu_align_stats* stats /* n_scans or NULL */);
+/* locgpu_icp_fitness_batch per pair: the score of scan i under poses[i] against target target_of[i] alone (the GetFitnessScore
+ * definition above: exact nearest neighbour, k = 1), bit for bit what an ordinary context holding that target reports — the check a
+ * caller makes after the ScanMatch of icp_registration.cpp:216-244 on each pair of test_node.cpp:256-315. target_of[i] == -1: {+inf, 0,
+ * 0}. Refusals as locgpu_icp_align_pairs, and a NaN max_range. */
+LOCGPU_API int locgpu_icp_fitness_pairs(locgpu_ctx* ctx, locgpu_batch* batch, const int* target_of, const double* poses, double max_range,
+                                        locgpu_fitness* out);
 
 #ifdef __cplusplus
 }

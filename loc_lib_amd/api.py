@@ -62,7 +62,9 @@ ABI_SYMBOLS = [
     "locgpu_batch_upload_records", "locgpu_batch_upload_records_deskew", "locgpu_cloud_upload_records", "locgpu_cloud_upload_records_deskew",
     "locgpu_records_deskew_debug", "locgpu_records_deskew_matrices", "locgpu_records_ingest_times",
     "locgpu_batch_keep_times", "locgpu_batch_download_times", "locgpu_batch_deskew", "locgpu_batch_deskew_times", "locgpu_motion_from_poses",
+    "locgpu_icp_set_target_forest", "locgpu_icp_set_target_forest_batch", "locgpu_icp_forest_info", "locgpu_icp_align_pairs", "locgpu_icp_fitness_pairs",
 ]
+STATUS_NO_PAIR_TARGET = 5  # LOCGPU_STATUS_NO_PAIR_TARGET
 COMM_ID_BYTES = 128
 NO_INTENSITY = ctypes.c_size_t(-1).value
 
@@ -284,6 +286,9 @@ def lib():
             "locgpu_batch_keep_times": (i32, [vp, i32]), "locgpu_batch_download_times": (i32, [vp, i32, vp, sz, vp]),
             "locgpu_batch_deskew": (i32, [vp, vp, vp, vp, vp]), "locgpu_batch_deskew_times": (i32, [vp, vp]),
             "locgpu_motion_from_poses": (i32, [vp, vp, i32, vp, vp]),
+            "locgpu_icp_set_target_forest": (i32, [vp, vp, vp, i32, sz]), "locgpu_icp_set_target_forest_batch": (i32, [vp, vp]),
+            "locgpu_icp_forest_info": (i32, [vp, vp, vp, vp]), "locgpu_icp_align_pairs": (i32, [vp, vp, vp, vp, vp, vp, vp]),
+            "locgpu_icp_fitness_pairs": (i32, [vp, vp, vp, vp, dbl, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -415,6 +420,51 @@ class Context:
         c = _cloud(cloud)
         fn = lib().locgpu_icp_set_target if wait else lib().locgpu_icp_set_target_async
         self._check(fn(self._h, c.ctypes.data, c.shape[0], c.strides[0]))
+
+    def icp_set_target_forest(self, clouds):
+        """SetInputTarget of several clouds at once (locgpu_icp_set_target_forest): tree j is what icp_set_target(clouds[j]) builds;
+        only icp_align_pairs / icp_fitness_pairs read such a target."""
+        cs = [_cloud(c) for c in clouds]
+        stride = next((c.strides[0] for c in cs if c.shape[0]), 16)
+        if any(c.shape[0] and c.strides[0] != stride for c in cs):
+            raise ValueError("all targets of a forest must share one point stride")
+        ptrs = (ctypes.c_void_p * len(cs))(*[c.ctypes.data if c.shape[0] else None for c in cs])
+        cnts = (ctypes.c_size_t * len(cs))(*[c.shape[0] for c in cs])
+        self._check(lib().locgpu_icp_set_target_forest(self._h, ptrs, cnts, len(cs), stride))
+
+    def icp_set_target_forest_batch(self, batch):
+        """Target j = scan j of the resident plain batch (locgpu_icp_set_target_forest_batch)."""
+        batch.upload_wait()
+        self._check(lib().locgpu_icp_set_target_forest_batch(self._h, batch._h))
+
+    def icp_forest_info(self):
+        """dict(n_targets, leaves [n], depth [n]) of the forest target (locgpu_icp_forest_info)."""
+        n = ctypes.c_int(0)
+        self._check(lib().locgpu_icp_forest_info(self._h, ctypes.byref(n), None, None))
+        leaves = np.zeros(n.value, dtype=np.uint64)
+        depth = np.zeros(n.value, dtype=np.int32)
+        self._check(lib().locgpu_icp_forest_info(self._h, ctypes.byref(n), leaves.ctypes.data, depth.ctypes.data))
+        return dict(n_targets=int(n.value), leaves=[int(v) for v in leaves], depth=[int(v) for v in depth])
+
+    def icp_align_pairs(self, batch, target_of, init_poses, opts):
+        """ScanMatch of scan i of the batch against target target_of[i] of the forest (-1: not aligned; locgpu_icp_align_pairs).
+        init_poses None = the identity for every scan. Returns (poses [n, 7], stats)."""
+        batch.upload_wait()
+        t = np.ascontiguousarray(target_of, dtype=np.int32).reshape(batch.n_scans)
+        ip = None if init_poses is None else _pose(init_poses).reshape(batch.n_scans, 7)
+        out = np.zeros((batch.n_scans, 7))
+        st = (AlignStats * batch.n_scans)()
+        self._check(lib().locgpu_icp_align_pairs(self._h, batch._h, t.ctypes.data, None if ip is None else ip.ctypes.data, ctypes.byref(opts), out.ctypes.data, st))
+        return out, [_stats_dict(s) for s in st]
+
+    def icp_fitness_pairs(self, batch, target_of, poses, max_range=1.0, raw=False):
+        """Score of scan i under poses[i] against target target_of[i] alone (locgpu_icp_fitness_pairs); -1: {+inf, 0, 0}."""
+        batch.upload_wait()
+        t = np.ascontiguousarray(target_of, dtype=np.int32).reshape(batch.n_scans)
+        p = _pose(poses).reshape(batch.n_scans, 7)
+        out = (Fitness * batch.n_scans)()
+        self._check(lib().locgpu_icp_fitness_pairs(self._h, batch._h, t.ctypes.data, p.ctypes.data, max_range, out))
+        return out if raw else [_fitness_dict(f) for f in out]
 
     def icp_target_info(self):
         out = np.zeros(4, dtype=np.int64)

@@ -36,9 +36,10 @@ struct AlignSpec {
     GnParams prm{};
     float alpha = 1.0f;  // pruning factor of the tree walk; 1.0f = exact. Always 1.0f for grid and NDT.
     bool grid = false;   // LOCGPU_SEARCH_GRID_EXACT was asked for
+    bool pairs = false;  // locgpu_icp_align_pairs: scan i is searched in the tree at the batch's pair_base[i] of the context's forest; eager only
     bool ndt() const { return method_is_ndt(prm.method); }
     int k() const { return method_k(prm.method); }
-    bool operator==(const AlignSpec& o) const { return prm == o.prm && alpha == o.alpha && grid == o.grid; }
+    bool operator==(const AlignSpec& o) const { return prm == o.prm && alpha == o.alpha && grid == o.grid && pairs == o.pairs; }
 };
 // locgpu_ndt_opts::method and ::nearby_type (NdtMethod, NdtNearbyType of the reference), and the voxels a nearby type probes per point.
 constexpr int kNdtOptDirect = 1, kNdtOptIncremental = 2;
@@ -87,6 +88,15 @@ struct locgpu_ctx {
     unsigned long long target_epoch = 0;  // bumped by every set_target: captured graphs of older targets are never replayed
 
     locgpu::DevBuf<uint32_t> d_leaf_slots;  // grow-only: slot of every leaf, preorder (what the exact-search grid is built from)
+
+    // Forest target (locgpu_icp_set_target_forest, icp_target.hip): d_tree holds forest_n > 0 trees behind one another, tree j from
+    // slot forest_base[j] on; tree_slots, num_*, depth (the largest) and tree_bounded (the AND) are the whole forest's. Only the pairs
+    // calls read such a target (refuse_forest); every locgpu_icp_set_target* makes the context ordinary again (forest_n = 0).
+    int forest_n = 0;
+    std::vector<uint32_t> forest_base;
+    std::vector<size_t> forest_leaves;
+    std::vector<int> forest_depth;
+    locgpu::DevBuf<uint32_t> d_forest_base;  // grow-only: the device table of the bases
 
     // LOCGPU_P2PLANE_MAP: one plane per leaf, row slot >> 1 = four doubles, NaNs = none (map_planes.hip). Built on first use or by
     // locgpu_icp_build_map_planes, dropped (planes_ready) by every set_target; the buffers are grow-only.
@@ -214,6 +224,11 @@ struct locgpu_batch {
     bool paced_tail = false;       // the last alignment was paced: up to pace_ahead idle launches may still be queued on `stream`
     locgpu::Event tail_ev;         // ... behind which the next upload's copies are ordered (batch_upload.hip)
     locgpu::PinnedBuf<double> h_hb;
+    // locgpu_icp_align_pairs / locgpu_icp_fitness_pairs: per scan the first slot of its target's tree, formed on the host per call
+    // (pair_base[i] = forest_base[target_of[i]]) and uploaded as n_scans words; pair_skip[i]: target_of[i] == -1, the scan is not aligned
+    std::vector<uint32_t> pair_base;
+    std::vector<unsigned char> pair_skip;
+    locgpu::DevBuf<uint32_t> d_pair_base;
     locgpu::PinnedBuf<int> h_active;       // [n_scans]: local indices of the scans still open at the last chunk boundary
     locgpu::DevBuf<int> d_active;          // its device copy (see SearchArgs::active)
     std::vector<int> counts;
@@ -244,6 +259,8 @@ void free_batch(locgpu_batch* b);
 // Validate the matcher's options against the context's target; fill the request of an alignment.
 int check_icp(locgpu_ctx* ctx, const locgpu_icp_opts* o, AlignSpec& spec);
 int check_ndt(locgpu_ctx* ctx, AlignSpec& spec);
+// LOCGPU_ERR_INVALID with a text when the context holds a forest target: the gate of every entry point that reads the ICP target as ONE tree
+int refuse_forest(locgpu_ctx* ctx, const char* who);
 // icp_target.hip
 int target_join(locgpu_ctx* ctx, bool install = true);  // finishes a pending locgpu_icp_set_target_cloud_async (no-op without one)
 void free_target_scratch(locgpu_ctx* ctx);              // the ingest buffers the context keeps between SetInputTarget calls

@@ -118,6 +118,7 @@ int launch_local_stage(locgpu_ctx* ctx, locgpu_batch* b, const LocalStage& w, hi
         sa.visit_totals = w.visits;
         sa.active = w.active; sa.n_active = w.n_active;
         sa.src_of = w.src_of;
+        sa.scan_tree_base = w.scan_tree_base;
         if (sa.visit_totals && !w.capturing) {  // instrumented pass: which tree slots does this launch read at all? (bench.py: compulsory bytes)
             const size_t words = (ctx->tree_slots + 2 + 31) / 32;
             if (words > ctx->touched_words) {
@@ -180,7 +181,7 @@ bool IterLauncher::launch(int do_update) {
     // the order of a scan's additions — hence its bits — must not depend on how many ranks share the batch (found by the eight-rank
     // loopback run of round 6: 32 of 256 scans per rank summed one point per thread where the plain batch sums four)
     const LocalStage w{batch_src(b), b->d_state + b->first, active, n_active, b->d_src_of, b->sharded ? b->n_total : b->split_scans, spec,
-                       ctx->count_visits ? ctx->d_visits : nullptr, b->d_grid_qkey ? &gsc : nullptr, capturing, "search"};
+                       ctx->count_visits ? ctx->d_visits : nullptr, b->d_grid_qkey ? &gsc : nullptr, capturing, "search", spec.pairs ? b->d_pair_base.get() : nullptr};
     const int n_partial_blocks = launch_local_stage(ctx, b, w, s);
     if (n_partial_blocks < 0) return false;
     // The exchange-and-solve tail. Against the pool's (scan_pool.hip): contiguous ranges [first, first + n_scans) instead of two slot
@@ -442,6 +443,17 @@ static void lease_release(locgpu_ctx* ctx, locgpu_batch* b) {
     b->leased = false;
 }
 
+// The per-scan tree bases of a pairs call (b->pair_base, formed by the entry point) → b->d_pair_base, on the batch's stream.
+static int upload_pair_base(locgpu_ctx* ctx, locgpu_batch* b) {
+    if (b->d_pair_base.cap() < (size_t)b->n_scans) {
+        LOCGPU_HIP(ctx, hipStreamSynchronize(b->stream));
+        LOCGPU_HIP(ctx, b->d_pair_base.alloc((size_t)b->n_scans));
+    }
+    // pageable source: the copy has left the host array when the call returns
+    LOCGPU_HIP(ctx, hipMemcpyAsync(b->d_pair_base, b->pair_base.data(), (size_t)b->n_scans * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
+    return LOCGPU_OK;
+}
+
 static int begin_on_stream(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const AlignSpec& spec, bool blocking) {
     const GnParams& prm = spec.prm;
     const bool ndt = spec.ndt();
@@ -450,18 +462,26 @@ static int begin_on_stream(locgpu_ctx* ctx, locgpu_batch* b, const double* init_
     if (!ndt) { const int grc = ensure_grid_lists(ctx, b, spec); if (grc != LOCGPU_OK) return grc; }
     { const int urc = batch_ready(ctx, b); if (urc != LOCGPU_OK) return urc; }
     P.spec = spec;
-    P.graph = ctx->use_graph && !ctx->count_visits && !b->sharded && prm.max_iteration > 0;
+    P.graph = ctx->use_graph && !ctx->count_visits && !b->sharded && prm.max_iteration > 0 && !spec.pairs;  // a pairs alignment is eager whatever locgpu_graph_enable was told
     P.launched = 0;
     b->stage_ev.used = 0;
     P.init_poses.assign(init_poses, init_poses + 7 * (size_t)b->n_total);
     init_states(b, init_poses);
+    if (spec.pairs) {
+        // a scan without a target is done before the first iteration: no kernel touches it, its pose stays its init
+        for (int i = 0; i < b->n_scans; ++i)
+            if (b->pair_skip[i]) { b->h_state[i].done = 1; b->h_state[i].status = LOCGPU_STATUS_NO_PAIR_TARGET; }
+        const int prc = upload_pair_base(ctx, b);
+        if (prc != LOCGPU_OK) return prc;
+    }
     // the search stage's work-list counters: zero once per alignment, whatever an earlier call that failed between a search and
     // its solve kernel left behind (the solve kernel re-zeroes them after every search)
     if (!ndt && !b->counters_clean) LOCGPU_HIP(ctx, hipMemsetAsync(b->d_redo_count, 0, 4 * sizeof(unsigned int), b->stream));
     b->counters_clean = false;  // until this alignment has run to its end
     if (P.graph) { const int rc = ensure_graphs(ctx, b, spec); if (rc != LOCGPU_OK) return rc; }
     // (a blocking call only: between a begin and its end the host is elsewhere, and a chunk keeps the GPU busy meanwhile)
-    P.paced = blocking && !P.graph && b->n_total == 1 && !b->sharded && !ctx->profile && !ctx->count_visits && prm.max_iteration > 0 && pace_ahead() > 0 && !spec.grid;
+    P.paced = blocking && !P.graph && b->n_total == 1 && !b->sharded && !ctx->profile && !ctx->count_visits && prm.max_iteration > 0 && pace_ahead() > 0 && !spec.grid &&
+              !spec.pairs;  // a scan without a target is done from the start: its solve kernel would never post
     if (P.paced) {
         if (!b->h_post) {
             LOCGPU_HIP(ctx, b->h_post.alloc(256 / sizeof(unsigned long long), hipHostMallocCoherent));
@@ -609,14 +629,26 @@ int ensure_map_planes(locgpu_ctx* ctx) {
     return LOCGPU_OK;
 }
 
-// Score of every entry of `b` under its pose: k = 1 exact search stage, then the reduction of fitness.hip.
-int fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, double max_range, locgpu_fitness* out) {
+// Score of every entry of `b` under its pose: k = 1 exact search stage, then the reduction of fitness.hip. pairs: per scan against
+// its own tree of the forest (b->pair_base), a scan without a target (b->pair_skip) is `done` for the search and scores {+inf, 0, 0}.
+static int fitness_on_batch_impl(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, double max_range, locgpu_fitness* out, bool pairs) {
     if (b->sharded) return fail(ctx, LOCGPU_ERR_INVALID, "icp_fitness: sharded batches are not scored");
     if (b->pending.active) return fail(ctx, LOCGPU_ERR_INVALID, "icp_fitness: an alignment of this batch has been begun and not finished");
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
     { const int urc = batch_ready(ctx, b); if (urc != LOCGPU_OK) return urc; }
     init_states(b, poses);
     hipStream_t s = b->stream;
+    if (pairs) {
+        // The search skips a `done` scan; the score kernel does not look at the flag and would follow whatever the scan's list rows
+        // hold: they are set to "no neighbour" (all-ones bytes = kInvalidSlot) first, which makes every point of the scan a non-query.
+        for (int i = 0; i < b->n_scans; ++i)
+            if (b->pair_skip[i]) {
+                b->h_state[i].done = 1;
+                LOCGPU_HIP(ctx, hipMemsetAsync(b->d_nn + (size_t)i * b->max_n, 0xFF, (size_t)b->max_n * sizeof(uint32_t), s));
+            }
+        const int prc = upload_pair_base(ctx, b);
+        if (prc != LOCGPU_OK) return prc;
+    }
     if (!b->counters_clean) LOCGPU_HIP(ctx, hipMemsetAsync(b->d_redo_count, 0, 4 * sizeof(unsigned int), s));
     b->counters_clean = false;
     LOCGPU_HIP(ctx, hipMemcpyAsync(b->d_state, b->h_state, b->n_total * sizeof(PoseState), hipMemcpyHostToDevice, s));
@@ -624,6 +656,7 @@ int fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, doub
     // points pcl::isFinite rejects
     SearchArgs sa = make_search_args(ctx, b, batch_src(b), b->d_state, 1, 1.0f, true);
     sa.src_of = b->d_src_of;
+    if (pairs) sa.scan_tree_base = b->d_pair_base;
     if (!launch_icp_search(sa, s)) return fail(ctx, LOCGPU_ERR_DEPTH, "icp_fitness: unsupported tree depth");
     FitnessArgs fa{ctx->d_tree, batch_src(b), b->d_counts, b->d_state, b->d_nn, b->max_n, b->n_scans, (float)(max_range * max_range), b->d_partials, b->d_hb, b->d_redo_count};
     fa.src_of = b->d_src_of;
@@ -637,8 +670,16 @@ int fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, doub
         out[i].inliers = (int64_t)r[1];
         out[i].finite_points = (int64_t)r[2];
         out[i].score = out[i].inliers > 0 ? r[0] / (double)out[i].inliers : HUGE_VAL;
+        if (pairs && b->pair_skip[i]) out[i] = locgpu_fitness{HUGE_VAL, 0, 0};  // never searched: its list rows are stale
     }
     return LOCGPU_OK;
+}
+
+int fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, double max_range, locgpu_fitness* out) {
+    return fitness_on_batch_impl(ctx, b, poses, max_range, out, false);
+}
+int fitness_pairs_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, double max_range, locgpu_fitness* out) {
+    return fitness_on_batch_impl(ctx, b, poses, max_range, out, true);
 }
 
 // Score of every entry of `b` under its pose against the direct NDT table: the probe-and-reduce kernel of ndt_fitness.hip, then the

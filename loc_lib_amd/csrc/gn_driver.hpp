@@ -33,6 +33,7 @@ struct LocalStage {
     const GridSearchScratch* grid;  // the grid search's work lists when the batch has them
     bool capturing;               // inside hipStreamBeginCapture: nothing may be allocated
     const char* who;              // prefix of the error text
+    const uint32_t* scan_tree_base = nullptr;  // SearchArgs::scan_tree_base: a pairs alignment over a forest target; nullptr = the one tree
 };
 // Enqueues search, then fit + accumulate (ICP), or the direct / incremental NDT accumulate, on `s`, with b->stage_ev's marks around
 // them. Returns the number of partial blocks per scan the solve (or launch_sum_partials) must sum; < 0 on failure (fail() was called).
@@ -63,6 +64,8 @@ int run_align(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const 
 int eval_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, const AlignSpec& spec, double* hb, const char* who);
 // Score of every entry of `b` under its pose: k = 1 exact search stage, then the reduction of fitness.hip.
 int fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, double max_range, locgpu_fitness* out);
+// The same per scan against its own tree of the context's forest (b->pair_base / pair_skip are set): a skipped scan scores {+inf, 0, 0}.
+int fitness_pairs_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, double max_range, locgpu_fitness* out);
 // Score of every entry of `b` under its pose against the context's direct NDT table (ndt_fitness.hip).
 int ndt_fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, locgpu_fitness* out);
 // The plane table of LOCGPU_P2PLANE_MAP for the current target (map_planes.hip); no-op when it is there.

@@ -2,6 +2,7 @@
 #include "env.hpp"
 #include "icp_kernels.hpp"
 #include "launch.hpp"
+#include "search_dispatch.hpp"
 #include "search_walk.hpp"
 
 #include <algorithm>
@@ -337,25 +338,7 @@ __global__ __launch_bounds__(kBlock) void nn_to_index_kernel(const uint2* __rest
 // ---------------------------------------------------------------------------------------------
 // Launchers (declared in launch.hpp).
 
-// depth → the compile-time stack rows D ∈ {32, 40, 64} of the kernels: f(integral_constant<int, D>). False above 64 (no such kernel).
-template <class F>
-static bool with_depth(int depth, F&& f) {
-    if (depth <= 32) f(std::integral_constant<int, 32>{});
-    else if (depth <= 40) f(std::integral_constant<int, 40>{});
-    else if (depth <= 64) f(std::integral_constant<int, 64>{});
-    else return false;
-    return true;
-}
-// k → the compile-time result-set size: f(integral_constant<int, K>), whose verdict is returned. The search stage has kernels for
-// exactly k = 1 and k = 5; launch_knn_query (UP_TO) takes the next of {1, 5, 8}. False when there is none.
-template <bool UP_TO, class F>
-static bool with_k(int k, F&& f) {
-    if (k == 1) return f(std::integral_constant<int, 1>{});
-    if (UP_TO ? k <= 5 : k == 5) return f(std::integral_constant<int, 5>{});
-    if constexpr (UP_TO)
-        if (k <= 8) return f(std::integral_constant<int, 8>{});
-    return false;
-}
+// with_depth / with_k: search_dispatch.hpp
 
 bool stamp_build() {
     static const bool on = env_int("LOCGPU_STAMP", 0) != 0;
@@ -488,6 +471,7 @@ static bool launch_walk(const SearchArgs& a, hipStream_t s) {
 
 bool launch_icp_search(const SearchArgs& a, hipStream_t s, bool* wrote_run_flags) {
     if (wrote_run_flags) *wrote_run_flags = false;
+    if (a.scan_tree_base) return launch_icp_search_pairs(a, s);  // a forest target: every scan walks a tree of its own (icp_search_pairs.hip)
     // Instrumented (visit-counting) runs and trees with non-finite / huge coordinates (no redo list) use the exact one-pass kernel.
     const bool exact_only = a.visit_totals != nullptr || !a.redo_list || !a.redo_list2;
     return with_k<false>(a.k, [&](auto Kc) {

@@ -11,6 +11,7 @@
 #include "context.hpp"
 #include "env.hpp"
 #include "kdtree_build.hpp"
+#include "search_dispatch.hpp"
 
 using namespace locgpu;
 
@@ -22,6 +23,7 @@ void locgpu::free_grid(locgpu_ctx* ctx) {
 // Build the exact-search grid from the packed tree already in HBM (first use of LOCGPU_SEARCH_GRID_EXACT after a set_target).
 int locgpu::ensure_grid(locgpu_ctx* ctx) {
     if (ctx->grid.pts) return LOCGPU_OK;
+    { const int frc = refuse_forest(ctx, "grid search"); if (frc != LOCGPU_OK) return frc; }
     std::string msg;
     const hipError_t e = locgpu::grid_build_device(ctx->d_tree, ctx->d_leaf_slots, ctx->num_leaves, ctx->stream, ctx->grid_buf, ctx->grid, msg);
     if (e != hipSuccess) {
@@ -100,14 +102,15 @@ static int install_tree_meta(locgpu_ctx* ctx, const long long meta[6]) {
     ctx->planes_ready = false;  // the plane table belongs to the previous target (rebuilt on the next use of LOCGPU_P2PLANE_MAP)
     ctx->planes_rows = 0;
     ctx->planes_valid = 0;
+    ctx->forest_n = 0;  // an ordinary target (set_target_forest_packed sets it again behind this call)
+    ctx->forest_base.clear(); ctx->forest_leaves.clear(); ctx->forest_depth.clear();
     return LOCGPU_OK;
 }
 
 // The sentinel leaf behind the packed tree (two slots at index tree_slots): what a lane of the search kernel "visits" when it has
 // no node to visit. Its coordinates are so large that the squared distance overflows to +inf for every sane query.
 static hipError_t write_sentinel_leaf(locgpu_ctx* ctx) {
-    static const uint32_t leaf[4] = {0x7F61B1E6u /* 3.0e38f */, 0xC0000000u, 0x7F61B1E6u, 0x7F61B1E6u};
-    return hipMemcpyAsync(ctx->d_tree + ctx->tree_slots, leaf, sizeof(leaf), hipMemcpyHostToDevice, ctx->stream);
+    return hipMemcpyAsync(ctx->d_tree + ctx->tree_slots, kSentinelLeafSlots, sizeof(kSentinelLeafSlots), hipMemcpyHostToDevice, ctx->stream);
 }
 
 // ---- SetInputTarget with the host build off the caller's thread (locgpu_icp_set_target_cloud_async) ----
@@ -173,7 +176,114 @@ int locgpu::icp_set_target_from_cloud(locgpu_ctx* ctx, const locgpu_cloud* targe
     return LOCGPU_OK;
 }
 
+// ---- a forest target: n trees behind one another in d_tree (kdtree_build.hpp, PackedForest), for the pairs calls ----
+int locgpu::refuse_forest(locgpu_ctx* ctx, const char* who) {
+    if (ctx->forest_n == 0) return LOCGPU_OK;
+    return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": the context holds a forest target (locgpu_icp_set_target_forest), which only locgpu_icp_align_pairs / "
+                                         "locgpu_icp_fitness_pairs read; locgpu_icp_set_target* makes it an ordinary target again");
+}
+
+// xyz[j]: n[j] packed float32 triples (already deep copies). Builds on the host, refuses before the context is touched, then replaces
+// the target: one host-to-device copy for all trees and their sentinel leaves, and the table of bases.
+static int set_target_forest_packed(locgpu_ctx* ctx, const float* const* xyz, const size_t* n, int n_targets, const char* who) {
+    static const bool times = env_flag("LOCGPU_FOREST_TIMES");  // diagnostic: phase times on stderr
+    auto t0 = std::chrono::steady_clock::now();
+    auto lap = [&](const char* what) {
+        if (!times) return;
+        const auto t1 = std::chrono::steady_clock::now();
+        fprintf(stderr, "[locgpu forest ingest] %s %.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
+        t0 = t1;
+    };
+    PackedForest f;
+    std::string err;
+    int bad = -1;
+    if (!build_packed_forest(xyz, n, n_targets, f, err, &bad))
+        return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + (bad >= 0 ? ": target " + std::to_string(bad) + ": " : ": ") + err);
+    for (int j = 0; j < n_targets; ++j)
+        if (f.depth[j] > kMaxSearchDepth)
+            return fail(ctx, LOCGPU_ERR_DEPTH, std::string(who) + ": target " + std::to_string(j) + ": KD-tree depth " + std::to_string(f.depth[j]) + " exceeds the " +
+                                                   std::to_string(kMaxSearchDepth) + "-entry traversal stack");
+    lap("host build");
+    (void)target_join(ctx, false);  // a pending asynchronous ingest is superseded
+    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+    // tree_slots: up to the LAST segment's sentinel leaf, which then stands where an ordinary tree's does
+    const long long meta[6] = {(long long)f.slots.size() - 2, (long long)f.num_leaves, (long long)f.num_nodes, (long long)f.num_points, f.max_depth, f.bounded ? 1 : 0};
+    if ((size_t)n_targets > ctx->d_forest_base.cap()) LOCGPU_HIP(ctx, ctx->d_forest_base.alloc(with_headroom((size_t)n_targets)));
+    const int rc = install_tree_meta(ctx, meta);
+    if (rc != LOCGPU_OK) return rc;
+    LOCGPU_HIP(ctx, hipMemcpyAsync(ctx->d_tree, f.slots.data(), f.slots.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    LOCGPU_HIP(ctx, hipMemcpyAsync(ctx->d_forest_base, f.base.data(), (size_t)n_targets * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    LOCGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    lap("device buffers + H2D");
+    ctx->forest_n = n_targets;
+    ctx->forest_base = std::move(f.base);
+    ctx->forest_leaves = std::move(f.leaves);
+    ctx->forest_depth = std::move(f.depth);
+    return LOCGPU_OK;
+}
+
 extern "C" {
+
+int locgpu_icp_set_target_forest(locgpu_ctx* ctx, const void* const* pts, const size_t* n, int n_targets, size_t stride_bytes) {
+    if (!ctx) return LOCGPU_ERR_INVALID;
+    if (!pts || !n || n_targets < 1) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target_forest: NULL arrays or n_targets < 1");
+    for (int j = 0; j < n_targets; ++j)
+        if (!pts[j] || n[j] == 0 || stride_bytes < 12)
+            return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target_forest: target " + std::to_string(j) + ": empty cloud or stride < 12");
+    // deep copies (icp_registration.cpp:16), packed xyz
+    std::vector<std::vector<float>> xyz((size_t)n_targets);
+    std::vector<const float*> ptr((size_t)n_targets);
+    for (int j = 0; j < n_targets; ++j) {
+        xyz[j].resize(3 * n[j]);
+        const char* base = (const char*)pts[j];
+        for (size_t i = 0; i < n[j]; ++i) std::memcpy(&xyz[j][3 * i], base + i * stride_bytes, 12);
+        ptr[j] = xyz[j].data();
+    }
+    return set_target_forest_packed(ctx, ptr.data(), n, n_targets, "icp_set_target_forest");
+}
+
+int locgpu_icp_set_target_forest_batch(locgpu_ctx* ctx, const locgpu_batch* b) {
+    if (!ctx) return LOCGPU_ERR_INVALID;
+    if (!b || b->ctx != ctx) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target_forest_batch: NULL batch or a batch of another context");
+    if (b->sharded || b->shared_src) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target_forest_batch: sharded and shared-source batches hold no scans of their own");
+    if (b->pending.active) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target_forest_batch: an alignment of this batch has been begun and not finished");
+    if (b->n_scans < 1) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target_forest_batch: the batch holds no scan");
+    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+    { const int orc = order_behind_batch(ctx, const_cast<locgpu_batch*>(b), "icp_set_target_forest_batch: ordering behind the batch"); if (orc != LOCGPU_OK) return orc; }
+    const int n_targets = b->n_scans;
+    std::vector<size_t> n((size_t)n_targets), off((size_t)n_targets);
+    size_t total = 0;
+    for (int j = 0; j < n_targets; ++j) {
+        if (b->counts[j] <= 0) return fail(ctx, LOCGPU_ERR_INVALID, "icp_set_target_forest_batch: target " + std::to_string(j) + ": empty cloud or stride < 12");
+        n[j] = (size_t)b->counts[j];
+        off[j] = total;
+        total += n[j];
+    }
+    // The scans cross PCIe the way a cloud's points do in locgpu_icp_set_target_cloud: 16 B a point into the context's pinned staging
+    // block, all scans behind one another, one wait.
+    float4* stage = nullptr;
+    if (!hip_ok(ctx, cloud_stage(ctx, total, &stage), "pinned staging")) return LOCGPU_ERR_OOM;
+    for (int j = 0; j < n_targets; ++j)
+        LOCGPU_HIP(ctx, hipMemcpyAsync(stage + off[j], b->d_src + (size_t)j * b->max_n, n[j] * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    LOCGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<float> xyz(3 * total);
+    for (size_t i = 0; i < total; ++i) std::memcpy(&xyz[3 * i], &stage[i], 12);
+    std::vector<const float*> ptr((size_t)n_targets);
+    for (int j = 0; j < n_targets; ++j) ptr[j] = xyz.data() + 3 * off[j];
+    return set_target_forest_packed(ctx, ptr.data(), n.data(), n_targets, "icp_set_target_forest_batch");
+}
+
+int locgpu_icp_forest_info(const locgpu_ctx* ctx, int* n_targets, size_t* leaves, int* depth) {
+    if (!ctx) return LOCGPU_ERR_INVALID;
+    { const int jrc = target_join(const_cast<locgpu_ctx*>(ctx)); if (jrc != LOCGPU_OK) return jrc; }
+    if (n_targets) *n_targets = ctx->forest_n;
+    if (ctx->forest_n == 0) return fail(const_cast<locgpu_ctx*>(ctx), ctx->d_tree ? LOCGPU_ERR_INVALID : LOCGPU_ERR_NO_TARGET, "icp_forest_info: the context holds no forest target");
+    for (int j = 0; j < ctx->forest_n; ++j) {
+        if (leaves) leaves[j] = ctx->forest_leaves[j];
+        if (depth) depth[j] = ctx->forest_depth[j];
+    }
+    return LOCGPU_OK;
+}
 
 int locgpu_icp_set_target(locgpu_ctx* ctx, const void* pts, size_t n, size_t stride_bytes) {
     if (!ctx) return LOCGPU_ERR_INVALID;

@@ -406,7 +406,15 @@ bool build_direct(Builder& b, Rec* a, Rec* tmp, size_t n, Pool& pool, unsigned n
     return ok.load();
 }
 
-bool build_packed_kdtree(const float* xyz, size_t n, PackedKdTree& out, std::string& err) {
+// Points per thread worth waking (LOCGPU_BUILD_GRAIN): the rule by which a build sizes its share of the pool.
+static size_t build_grain() {
+    static const size_t grain = [] { const int v = env_int("LOCGPU_BUILD_GRAIN", 0); return v >= 256 ? (size_t)v : (size_t)2048; }();
+    return grain;
+}
+
+// max_threads > 0: at most that many threads (1: the whole build on the caller's thread, no parallel region — what a tree of a forest
+// gets, whose parallel region is the forest's). The tree does not depend on the number of threads.
+static bool build_tree(const float* xyz, size_t n, PackedKdTree& out, std::string& err, unsigned max_threads) {
     out.slots.clear(); out.leaf_slots.clear();  // a PackedKdTree that is reused keeps its capacity (same reason as BuildScratch)
     out.num_leaves = out.num_nodes = out.num_points = 0; out.depth = 0; out.bounded = true;
     if (n == 0) { err = "empty target cloud"; return false; }
@@ -430,8 +438,8 @@ bool build_packed_kdtree(const float* xyz, size_t n, PackedKdTree& out, std::str
     lap(0);
 
     Pool& pool = Pool::get();
-    static const size_t grain = [] { const int v = env_int("LOCGPU_BUILD_GRAIN", 0); return v >= 256 ? (size_t)v : (size_t)2048; }();
-    const unsigned nt = (unsigned)std::min<size_t>(pool.size(), std::max<size_t>(1, n / grain));  // threads worth waking for this map
+    unsigned nt = (unsigned)std::min<size_t>(pool.size(), std::max<size_t>(1, n / build_grain()));  // threads worth waking for this map
+    if (max_threads > 0) nt = std::min(nt, max_threads);
     {
         bool all_bounded = true;
         static const size_t min_task = [] { const int v = env_int("LOCGPU_BUILD_TASK", 0); return v >= 16 ? (size_t)v : (size_t)1024; }();
@@ -621,6 +629,61 @@ bool build_packed_kdtree(const float* xyz, size_t n, PackedKdTree& out, std::str
     // The fast search kernel assumes squared distances cannot overflow or be NaN: true when every float in the tree (leaf
     // coordinates and split thresholds) is finite and small enough. Otherwise searches use the exact kernel only.
     out.bounded = bounded.load();
+    return true;
+}
+
+bool build_packed_kdtree(const float* xyz, size_t n, PackedKdTree& out, std::string& err) { return build_tree(xyz, n, out, err, 0); }
+
+bool build_packed_forest(const float* const* xyz, const size_t* n, int n_trees, PackedForest& out, std::string& err, int* bad, unsigned max_threads) {
+    out = PackedForest();
+    if (bad) *bad = -1;
+    if (!xyz || !n || n_trees < 1) { err = "no target clouds"; return false; }
+    const size_t nt_trees = (size_t)n_trees;
+    size_t points = 0;
+    for (size_t j = 0; j < nt_trees; ++j) {
+        if (!xyz[j] || n[j] == 0) { err = "empty target cloud"; if (bad) *bad = (int)j; return false; }
+        points += n[j];
+    }
+    // 3 slots a point is the most a tree takes; the exact count is checked again below
+    if (points >= kForestMaxSlots) { err = "target clouds too large (the packed forest must stay below 4 GiB)"; return false; }
+    std::vector<PackedKdTree> trees(nt_trees);
+    std::vector<std::string> errs(nt_trees);
+    std::vector<unsigned char> ok(nt_trees, 0);
+    std::vector<size_t> order(nt_trees);  // the largest first: it has the longest way to go
+    for (size_t j = 0; j < nt_trees; ++j) order[j] = j;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t c) { return n[a] > n[c]; });
+    Pool& pool = Pool::get();
+    unsigned nt = (unsigned)std::min<size_t>(pool.size(), std::max<size_t>(1, points / build_grain()));  // build_tree's rule, over all the points
+    if (max_threads > 0) nt = std::min(nt, max_threads);
+    pool.run(nt_trees, nt, [&](size_t i) {
+        const size_t j = order[i];
+        ok[j] = build_tree(xyz[j], n[j], trees[j], errs[j], 1) ? 1 : 0;
+    });
+    size_t at = 0;
+    out.base.resize(nt_trees); out.seg_slots.resize(nt_trees); out.leaves.resize(nt_trees); out.depth.resize(nt_trees);
+    for (size_t j = 0; j < nt_trees; ++j) {
+        if (!ok[j]) { err = errs[j]; if (bad) *bad = (int)j; out = PackedForest(); return false; }
+        at += at & 1;  // a segment starts at an even slot
+        const size_t len = trees[j].slots.size();
+        if (at + len + 2 > kForestMaxSlots) { err = "target clouds too large (the packed forest must stay below 4 GiB)"; out = PackedForest(); return false; }
+        out.base[j] = (uint32_t)at;
+        out.seg_slots[j] = (uint32_t)len;
+        out.leaves[j] = trees[j].num_leaves;
+        out.depth[j] = trees[j].depth;
+        out.num_leaves += trees[j].num_leaves;
+        out.num_nodes += trees[j].num_nodes;
+        out.num_points += trees[j].num_points;
+        out.max_depth = std::max(out.max_depth, trees[j].depth);
+        out.bounded = out.bounded && trees[j].bounded;
+        at += len + 2;
+    }
+    out.slots.assign(at, 0);
+    pool.run(nt_trees, nt, [&](size_t j) {
+        uint64_t* seg = out.slots.data() + out.base[j];
+        std::memcpy(seg, trees[j].slots.data(), trees[j].slots.size() * sizeof(uint64_t));
+        seg[trees[j].slots.size()] = kSentinelLeafSlots[0];
+        seg[trees[j].slots.size() + 1] = kSentinelLeafSlots[1];
+    });
     return true;
 }
 

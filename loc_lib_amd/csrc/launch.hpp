@@ -41,6 +41,9 @@ struct SearchArgs {
     // Optional, k = 5: [n_scans][ceil(max_n / 64)] words, one per 64-lane walk wave — bit `lane` set: the query's neighbour set is not
     // known to be the previous lane's (a leader of the plane fit, AccumArgs::run_flags); nullptr = the walk kernel does nothing new.
     unsigned long long* run_flags = nullptr;
+    // Forest target (locgpu_icp_set_target_forest): [n_scans] first slot of the tree scan s is searched in — the walk runs on
+    // tree + scan_tree_base[s] and every slot written to nn is absolute. nullptr = one tree for all scans, at slot 0.
+    const uint32_t* scan_tree_base = nullptr;
 };
 
 struct AccumArgs {
@@ -69,6 +72,9 @@ struct AccumArgs {
 // wrote_run_flags (optional): whether the route taken wrote a.run_flags — the 64-lane walk kernel does; the 16-lane one-scan kernel,
 // the exact kernel and every other search launcher do not
 bool launch_icp_search(const SearchArgs& a, hipStream_t s, bool* wrote_run_flags = nullptr);
+// icp_search_pairs.hip: the route launch_icp_search takes when a.scan_tree_base is set — the one-thread-per-query exact traversal, once
+// per scan's own tree; no work lists, no run flags, no visit counts
+bool launch_icp_search_pairs(const SearchArgs& a, hipStream_t s);
 // exact tree traversal over a.redo_list only (the list is filled by a preceding fast / grid kernel)
 bool launch_icp_search_redo(const SearchArgs& a, hipStream_t s);
 // the walk traversal with every level stored (a.alpha_eff) over the queries in `list`, then the exact redo kernel for its ties

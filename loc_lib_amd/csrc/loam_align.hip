@@ -340,7 +340,7 @@ int class_target(locgpu_loam* l, int c, const char* who) {
     const int jrc = from_ctx(l, c, target_join(l->ctx[c]));  // an asynchronous ingest ends here at the latest
     if (jrc != LOCGPU_OK) return jrc;
     if (!l->ctx[c]->d_tree) return lfail(l, LOCGPU_ERR_NO_TARGET, std::string(who) + ": the " + (c == kSurf ? "surface" : "edge") + " class has no target");
-    return LOCGPU_OK;
+    return from_ctx(l, c, refuse_forest(l->ctx[c], who));
 }
 
 // Both classes' requests against their current targets (check_icp: the asynchronous ingest ends here, the grid is built on first use).
@@ -660,6 +660,9 @@ int locgpu_loam_create_on(locgpu_ctx* surf_ctx, locgpu_ctx* edge_ctx, const locg
     if (rc != LOCGPU_OK) return rc;
     if (use[kSurf] && use[kEdge] && (surf_ctx == edge_ctx || surf_ctx->device != edge_ctx->device))
         return lfail(nullptr, LOCGPU_ERR_INVALID, "loam_create_on: the two classes need two different contexts on one GPU");
+    for (int c = 0; c < 2; ++c)
+        if (use[c] && ctx[c]->forest_n > 0)
+            return lfail(nullptr, LOCGPU_ERR_INVALID, "loam_create_on: a context holds a forest target (locgpu_icp_set_target_forest), which only the pairs calls read");
     auto* l = new locgpu_loam();
     l->borrowed = true;
     l->opts = *opts;

@@ -160,6 +160,7 @@ int locgpu_knn(locgpu_ctx* ctx, const float* queries, size_t nq, int k, int appr
     if (!ctx) return LOCGPU_ERR_INVALID;
     { const int jrc = target_join(ctx); if (jrc != LOCGPU_OK) return jrc; }
     if (!ctx->d_tree) return fail(ctx, LOCGPU_ERR_NO_TARGET, "knn: no target set");
+    { const int frc = refuse_forest(ctx, "knn"); if (frc != LOCGPU_OK) return frc; }
     if (!queries || !out_idx || k < 1 || k > 8) return fail(ctx, LOCGPU_ERR_INVALID, "knn: bad arguments (1 <= k <= 8)");
     if (search_mode != LOCGPU_SEARCH_TREE_FAITHFUL && search_mode != LOCGPU_SEARCH_GRID_EXACT) return fail(ctx, LOCGPU_ERR_INVALID, "knn: unknown search mode");
     if ((size_t)k > ctx->num_leaves) return fail(ctx, LOCGPU_ERR_K_TOO_LARGE, "knn: k larger than the number of tree leaves");
@@ -360,14 +361,21 @@ static int check_batch(locgpu_ctx* ctx, const locgpu_batch* b, bool args_ok, con
     return LOCGPU_OK;
 }
 
-int check_icp(locgpu_ctx* ctx, const locgpu_icp_opts* o, AlignSpec& spec) {
+// pairs: the request of locgpu_icp_align_pairs, which reads a forest target and nothing else; every other request reads an ordinary one.
+static int check_icp_request(locgpu_ctx* ctx, const locgpu_icp_opts* o, AlignSpec& spec, bool pairs) {
     if (!ctx) return LOCGPU_ERR_INVALID;
     if (!o) return fail(ctx, LOCGPU_ERR_INVALID, "icp: opts is NULL");
     { const int jrc = target_join(ctx); if (jrc != LOCGPU_OK) return jrc; }  // an asynchronous SetInputTarget ends here at the latest
     if (!ctx->d_tree) return fail(ctx, LOCGPU_ERR_NO_TARGET, "icp: SetInputTarget has not been called");
+    if (!pairs) { const int frc = refuse_forest(ctx, "icp"); if (frc != LOCGPU_OK) return frc; }
+    if (pairs && ctx->forest_n == 0)
+        return fail(ctx, LOCGPU_ERR_INVALID, "icp_align_pairs: the context holds an ordinary target; the pairs calls read a forest target (locgpu_icp_set_target_forest)");
     if ((o->method < LOCGPU_P2P || o->method > LOCGPU_P2PLANE) && o->method != LOCGPU_P2PLANE_MAP) return fail(ctx, LOCGPU_ERR_INVALID, "icp: unknown method");
     if (o->search_mode != LOCGPU_SEARCH_TREE_FAITHFUL && o->search_mode != LOCGPU_SEARCH_GRID_EXACT)
         return fail(ctx, LOCGPU_ERR_INVALID, "icp: unknown search mode");
+    if (pairs && (o->method == LOCGPU_P2PLANE_MAP || o->search_mode == LOCGPU_SEARCH_GRID_EXACT))
+        return fail(ctx, LOCGPU_ERR_INVALID, "icp_align_pairs: LOCGPU_P2PLANE_MAP and LOCGPU_SEARCH_GRID_EXACT are not available over a forest target");
+    spec.pairs = pairs;
     if (o->search_mode == LOCGPU_SEARCH_GRID_EXACT) {
         const int rc = ensure_grid(ctx);
         if (rc != LOCGPU_OK) return rc;
@@ -388,6 +396,28 @@ int check_icp(locgpu_ctx* ctx, const locgpu_icp_opts* o, AlignSpec& spec) {
     spec.alpha = (o->approximate && !spec.grid) ? o->ann_alpha : 1.0f;
     // k > size_: GetClosestPoint logs an error and returns nothing (kdtree.cpp:149-153) ⇒ no correspondences at all.
     // The search kernel reproduces that by never filling the k-th slot; nothing to reject here.
+    return LOCGPU_OK;
+}
+
+int check_icp(locgpu_ctx* ctx, const locgpu_icp_opts* o, AlignSpec& spec) { return check_icp_request(ctx, o, spec, false); }
+
+// The batch and the target_of array of pairs call `who`, checked in full before anything of the batch is written; then the per-scan
+// tree bases the driver uploads (b->pair_base, b->pair_skip).
+static int check_pairs(locgpu_ctx* ctx, locgpu_batch* b, const int* target_of, bool args_ok, const char* who) {
+    if (!b || b->ctx != ctx || !target_of || !args_ok) return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": bad arguments (NULL, or a batch of another context)");
+    if (b->sharded || b->shared_src) return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": sharded and shared-source batches are not aligned in pairs");
+    if (b->pending.active) return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": an alignment of this batch has been begun and not finished");
+    if (b->n_scans < 1) return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": the batch holds no scan");
+    for (int i = 0; i < b->n_scans; ++i)
+        if (target_of[i] < -1 || target_of[i] >= ctx->forest_n)
+            return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": target_of[" + std::to_string(i) + "] = " + std::to_string(target_of[i]) + " is neither -1 nor one of the " +
+                                                     std::to_string(ctx->forest_n) + " targets");
+    b->pair_base.assign((size_t)b->n_scans, 0u);
+    b->pair_skip.assign((size_t)b->n_scans, 0);
+    for (int i = 0; i < b->n_scans; ++i) {
+        if (target_of[i] < 0) b->pair_skip[i] = 1;
+        else b->pair_base[i] = ctx->forest_base[(size_t)target_of[i]];
+    }
     return LOCGPU_OK;
 }
 
@@ -472,6 +502,31 @@ int locgpu_icp_align_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* init_
     return rc != LOCGPU_OK ? rc : run_align(ctx, b, init_poses, spec, out_poses, stats);
 }
 
+int locgpu_icp_align_pairs(locgpu_ctx* ctx, locgpu_batch* b, const int* target_of, const double* init_poses, const locgpu_icp_opts* opts, double* out_poses,
+                           locgpu_align_stats* stats) {
+    AlignSpec spec;
+    int rc = check_icp_request(ctx, opts, spec, true);
+    if (rc == LOCGPU_OK) rc = check_pairs(ctx, b, target_of, out_poses != nullptr, "icp_align_pairs");
+    if (rc != LOCGPU_OK) return rc;
+    std::vector<double> identity;
+    if (!init_poses) {  // the reference's `SE3 init_pos` of every scan-to-scan match (test_node.cpp:289)
+        identity.assign(7 * (size_t)b->n_total, 0.0);
+        for (int i = 0; i < b->n_total; ++i) identity[7 * (size_t)i + 3] = 1.0;
+        init_poses = identity.data();
+    }
+    return run_align(ctx, b, init_poses, spec, out_poses, stats);
+}
+
+int locgpu_icp_fitness_pairs(locgpu_ctx* ctx, locgpu_batch* b, const int* target_of, const double* poses, double max_range, locgpu_fitness* out) {
+    if (!ctx) return LOCGPU_ERR_INVALID;
+    { const int jrc = target_join(ctx); if (jrc != LOCGPU_OK) return jrc; }
+    if (!ctx->d_tree) return fail(ctx, LOCGPU_ERR_NO_TARGET, "icp_fitness_pairs: SetInputTarget has not been called");
+    if (ctx->forest_n == 0)
+        return fail(ctx, LOCGPU_ERR_INVALID, "icp_fitness_pairs: the context holds an ordinary target; the pairs calls read a forest target (locgpu_icp_set_target_forest)");
+    const int rc = check_pairs(ctx, b, target_of, poses && out && !std::isnan(max_range), "icp_fitness_pairs");
+    return rc != LOCGPU_OK ? rc : fitness_pairs_on_batch(ctx, b, poses, max_range, out);
+}
+
 int locgpu_icp_align_batch_begin(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, const locgpu_icp_opts* opts) {
     AlignSpec spec;
     int rc = check_icp(ctx, opts, spec);
@@ -550,6 +605,7 @@ int locgpu_icp_build_map_planes(locgpu_ctx* ctx) {
     if (!ctx) return LOCGPU_ERR_INVALID;
     { const int jrc = target_join(ctx); if (jrc != LOCGPU_OK) return jrc; }
     if (!ctx->d_tree) return fail(ctx, LOCGPU_ERR_NO_TARGET, "icp_build_map_planes: SetInputTarget has not been called");
+    { const int frc = refuse_forest(ctx, "icp_build_map_planes"); if (frc != LOCGPU_OK) return frc; }
     return ensure_map_planes(ctx);
 }
 
@@ -802,7 +858,7 @@ int search_batch(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes
 int fitness_target(locgpu_ctx* ctx) {
     { const int jrc = target_join(ctx); if (jrc != LOCGPU_OK) return jrc; }
     if (!ctx->d_tree) return fail(ctx, LOCGPU_ERR_NO_TARGET, "icp_fitness: SetInputTarget has not been called");
-    return LOCGPU_OK;
+    return refuse_forest(ctx, "icp_fitness");
 }
 
 // The NDT score reads the DIRECT table: the incremental voxel set has another table and weights its residuals differently.
