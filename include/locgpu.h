@@ -98,7 +98,7 @@ typedef struct locgpu_align_stats {
                                   2 incremental NDT: too few effective residuals ⇒ returns false with the current pose (ndt cpp:349-353);
                                   locgpu_loam_* only: 3 the SURFACE class's evaluation reported false, 4 the EDGE class's did ⇒
                                   ScanMatch returns false before writing result_pose (loam_registration.cpp:56-70); surface is tested first;
-                                  locgpu_icp_align_pairs only: 5 (LOCGPU_STATUS_NO_PAIR_TARGET) the scan was given no target and was not aligned */
+                                  locgpu_icp_align_pairs / locgpu_ndt_align_pairs only: 5 (LOCGPU_STATUS_NO_PAIR_TARGET) the scan was given no target and was not aligned */
     int32_t reserved;
     int64_t last_effective_num;
     double last_dx_norm;
@@ -1207,8 +1207,8 @@ LOCGPU_API int locgpu_batch_export_cloud(locgpu_batch* b, int scan, locgpu_cloud
  * so; an ordinary context refuses locgpu_icp_align_pairs / locgpu_icp_fitness_pairs the same way. locgpu_icp_target_info reports the
  * forest's totals (depth: the largest). locgpu_debug_batch_nn after a pairs call reports point indices of each scan's OWN target.
  *
- * Not covered: NDT and LOAM pairs, scan pools, hipGraph replay, sharded and shared-source batches, the C++ facade, bench.py, an
- * asynchronous (begin / end) form.
+ * Not covered by this block: NDT and LOAM pairs (NDT pairs have the block behind this one; LOAM pairs are not covered at all),
+ * scan pools, hipGraph replay, sharded and shared-source batches, the C++ facade, bench.py, an asynchronous (begin / end) form.
  * ===================================================================================================================== */
 
 /* locgpu_align_stats::status of a scan that locgpu_icp_align_pairs was told not to align (target_of[i] == -1); used for nothing else. */
@@ -1249,6 +1249,72 @@ LOCGPU_API int locgpu_icp_align_pairs(locgpu_ctx* ctx, locgpu_batch* batch, cons
  * 0}. Refusals as locgpu_icp_align_pairs, and a NaN max_range. */
 LOCGPU_API int locgpu_icp_fitness_pairs(locgpu_ctx* ctx, locgpu_batch* batch, const int* target_of, const double* poses, double max_range,
                                         locgpu_fitness* out);
+
+/* =====================================================================================================================
+ * ---- Pairwise batch NDT: every scan of a batch against a voxel grid of its own.
+ *
+ * The NDT form of the reference's scan-to-scan odometry (TestNdtMatching, slam_demo/src/apps/test_node.cpp:317-374) runs, per scan,
+ * SetInputTarget(last_cloud) (:354; SetDirectNdtTargetCloud, ndt_registration.cpp:65-85, 87-148), ScanMatch(current_cloud, SE3(), ...)
+ * (:356; ndt_registration.cpp:238-261, AlignNdt :374-464) and T_w_lc = T_w_lc * T_lc_ln. The initial pose is the identity every time
+ * (:348), so the pairs of a whole log are independent. Here n targets are ingested as a voxel SET — one table in the layout of an
+ * ordinary direct target whose 64-bit keys carry the target's index above the voxel (target:16 | x:16 | y:16 | z:16) — built ON THE
+ * DEVICE in one pass for all targets, and one call aligns every scan of a batch against the grid it names. From a resident batch no
+ * point crosses PCIe and nothing is built on the host.
+ *
+ * One locgpu_ndt_opts serves the whole set (voxel_size, min_pts_in_voxel, nearby_type, res_outlier_th and the loop's options);
+ * method 1 (direct) only, the incremental method is refused. Every voxel of target j has, bit for bit, the mean and information
+ * matrix locgpu_ndt_set_target of that cloud alone gives it. Limits of a set: 1 <= n_targets <= 65535; every target non-empty;
+ * voxel coordinates strictly inside +-2^15 = 32768 voxels on every axis (an ordinary target: +-2^20) — a target with a point outside
+ * is refused; at most 0x7FFFFF00 points in all. A refused ingest leaves the context exactly as it was and names the target's index
+ * in locgpu_last_error.
+ *
+ * A context that holds a set answers only the calls of this block, and locgpu_ndt_set_target* (any form), which replaces the set
+ * and makes the context ordinary again. Every other reader of the NDT target — locgpu_ndt_align*, locgpu_ndt_hb*,
+ * locgpu_ndt_scan_match, locgpu_ndt_fitness*, locgpu_ndt_init_search, locgpu_ndt_dump, locgpu_pool_create with matcher = 1 and the
+ * pool's re-check at submit — returns LOCGPU_ERR_INVALID with a text that says so; an ordinary context refuses
+ * locgpu_ndt_align_pairs / locgpu_ndt_fitness_pairs the same way. The ICP target of the context is untouched either way.
+ * locgpu_ndt_target_info reports the set's totals. The status of a scan without a target is LOCGPU_STATUS_NO_PAIR_TARGET, above.
+ *
+ * Not covered: LOAM pairs, incremental-NDT sets, scan pools, hipGraph replay, sharded and shared-source batches, the C++ facade,
+ * bench.py, an asynchronous (begin / end) form.
+ * ===================================================================================================================== */
+
+/* SetInputTarget -> SetDirectNdtTargetCloud (ndt_registration.cpp:65-85, 87-148) of n_targets clouds at once, host pointers: pts[j] =
+ * n[j] points of stride_bytes each, deep-copied before the call returns — the last_cloud of every pair of test_node.cpp:317-374. The
+ * points go up in ONE host-to-device copy; keys, one stable sort, per-voxel mean / covariance / SVD run on the device. Blocking.
+ * opts NULL = the defaults. LOCGPU_ERR_INVALID, context unchanged: NULL arrays, n_targets < 1 or > 65535, an empty target (its index
+ * is named), stride < 12, the incremental method, a point outside the set's key range (target index named). */
+LOCGPU_API int locgpu_ndt_set_target_set(locgpu_ctx* ctx, const void* const* pts, const size_t* n, int n_targets, size_t stride_bytes, const locgpu_ndt_opts* opts);
+/* The same from a resident plain batch of this context: target j = scan j of `batch` (what locgpu_batch_preprocess left there, for
+ * instance — the filtered clouds test_node.cpp:317-374 matches; SetDirectNdtTargetCloud, ndt_registration.cpp:65-85, 87-148). Device
+ * only: the scans are read where the batch holds them. The batch is not modified and may be the source batch of the pairs call that
+ * follows. Refused (LOCGPU_ERR_INVALID) in addition: a NULL batch, a batch of another context, sharded and shared-source batches, a
+ * batch with an alignment begun and not ended, an empty scan (its index is named), more than 65535 scans. */
+LOCGPU_API int locgpu_ndt_set_target_set_batch(locgpu_ctx* ctx, const locgpu_batch* batch, const locgpu_ndt_opts* opts);
+/* *n_targets = targets of the set; points[j] = points of target j, voxels[j] = the voxels it keeps (count > min_pts_in_voxel,
+ * SetDirectNdtTargetCloud, ndt_registration.cpp:87-148) — what locgpu_ndt_target_info reports as num_voxels after locgpu_ndt_set_target
+ * of that cloud alone. The arrays have n_targets entries each and may be NULL (call once with NULL arrays for the count).
+ * LOCGPU_ERR_INVALID (*n_targets = 0) when the context holds an ordinary NDT target, LOCGPU_ERR_NO_TARGET without any. */
+LOCGPU_API int locgpu_ndt_set_info(const locgpu_ctx* ctx, int* n_targets, size_t* points /* [n] or NULL */, size_t* voxels /* [n] or NULL */);
+/* locgpu_ndt_dump of ONE target of the set (the grids_ of SetDirectNdtTargetCloud, ndt_registration.cpp:87-148): keys (cap x 3 voxel
+ * coordinates, without the target), mu (cap x 3), info (cap x 9), in ascending (x, y, z) key order — the same bytes in the same order
+ * after every ingest of the same set. *n_out = voxels of the target. Test read-back. */
+LOCGPU_API int locgpu_ndt_set_dump(locgpu_ctx* ctx, int target, int32_t* keys, double* mu, double* info, size_t cap, size_t* n_out);
+/* ScanMatch (ndt_registration.cpp:238-261; AlignNdt, :374-464) of every scan of `batch` against target target_of[i] of the context's
+ * voxel set — the loop body of test_node.cpp:317-374 for all pairs in one call. init_poses: n_scans x 7, or NULL = the identity for
+ * every scan, the reference's `SE3 init_pos` (test_node.cpp:348). target_of[i] == -1: scan i is not aligned — out_poses[i] is its
+ * initial pose, stats[i].iterations = 0, stats[i].status = LOCGPU_STATUS_NO_PAIR_TARGET. Scan i's pose and stats equal, bit for bit,
+ * row i of locgpu_ndt_align_batch of the SAME batch on an ordinary context that holds target target_of[i] alone (locgpu_ndt_set_target,
+ * same options) — status 1 (det(H) == 0, ndt_registration.cpp:435-436: the caller's pose stays) included. Blocking and eager: it runs
+ * eagerly whatever locgpu_graph_enable was told. Refused (LOCGPU_ERR_INVALID), with the batch untouched: NULL arguments, a target_of
+ * entry < -1 or >= n_targets, sharded and shared-source batches, a batch of another context, a batch with an alignment begun and not
+ * ended, an ordinary context. */
+LOCGPU_API int locgpu_ndt_align_pairs(locgpu_ctx* ctx, locgpu_batch* batch, const int* target_of, const double* init_poses /* n_scans x 7 or NULL */,
+                                      double* out_poses, locgpu_align_stats* stats /* n_scans or NULL */);
+/* locgpu_ndt_fitness_batch per pair: the score of scan i under poses[i] against target target_of[i] alone (the residuals of AlignNdt's
+ * gate, ndt_registration.cpp:374-464), bit for bit what an ordinary context holding that target reports — the check a caller makes
+ * after each ScanMatch of test_node.cpp:317-374. target_of[i] == -1: {+inf, 0, 0}. Refusals as locgpu_ndt_align_pairs. */
+LOCGPU_API int locgpu_ndt_fitness_pairs(locgpu_ctx* ctx, locgpu_batch* batch, const int* target_of, const double* poses, locgpu_fitness* out);
 
 #ifdef __cplusplus
 }

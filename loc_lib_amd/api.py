@@ -63,6 +63,7 @@ ABI_SYMBOLS = [
     "locgpu_records_deskew_debug", "locgpu_records_deskew_matrices", "locgpu_records_ingest_times",
     "locgpu_batch_keep_times", "locgpu_batch_download_times", "locgpu_batch_deskew", "locgpu_batch_deskew_times", "locgpu_motion_from_poses",
     "locgpu_icp_set_target_forest", "locgpu_icp_set_target_forest_batch", "locgpu_icp_forest_info", "locgpu_icp_align_pairs", "locgpu_icp_fitness_pairs",
+    "locgpu_ndt_set_target_set", "locgpu_ndt_set_target_set_batch", "locgpu_ndt_set_info", "locgpu_ndt_set_dump", "locgpu_ndt_align_pairs", "locgpu_ndt_fitness_pairs",
 ]
 STATUS_NO_PAIR_TARGET = 5  # LOCGPU_STATUS_NO_PAIR_TARGET
 COMM_ID_BYTES = 128
@@ -289,6 +290,9 @@ def lib():
             "locgpu_icp_set_target_forest": (i32, [vp, vp, vp, i32, sz]), "locgpu_icp_set_target_forest_batch": (i32, [vp, vp]),
             "locgpu_icp_forest_info": (i32, [vp, vp, vp, vp]), "locgpu_icp_align_pairs": (i32, [vp, vp, vp, vp, vp, vp, vp]),
             "locgpu_icp_fitness_pairs": (i32, [vp, vp, vp, vp, dbl, vp]),
+            "locgpu_ndt_set_target_set": (i32, [vp, vp, vp, i32, sz, vp]), "locgpu_ndt_set_target_set_batch": (i32, [vp, vp, vp]),
+            "locgpu_ndt_set_info": (i32, [vp, vp, vp, vp]), "locgpu_ndt_set_dump": (i32, [vp, i32, vp, vp, vp, sz, vp]),
+            "locgpu_ndt_align_pairs": (i32, [vp, vp, vp, vp, vp, vp]), "locgpu_ndt_fitness_pairs": (i32, [vp, vp, vp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -464,6 +468,62 @@ class Context:
         p = _pose(poses).reshape(batch.n_scans, 7)
         out = (Fitness * batch.n_scans)()
         self._check(lib().locgpu_icp_fitness_pairs(self._h, batch._h, t.ctypes.data, p.ctypes.data, max_range, out))
+        return out if raw else [_fitness_dict(f) for f in out]
+
+    def ndt_set_target_set(self, clouds, opts=None):
+        """SetInputTarget of several clouds at once as a voxel set (locgpu_ndt_set_target_set): the grid of target j is what
+        ndt_set_target(clouds[j], opts) builds; only ndt_align_pairs / ndt_fitness_pairs read such a target."""
+        cs = [_cloud(c) for c in clouds]
+        stride = next((c.strides[0] for c in cs if c.shape[0]), 16)
+        if any(c.shape[0] and c.strides[0] != stride for c in cs):
+            raise ValueError("all targets of a voxel set must share one point stride")
+        ptrs = (ctypes.c_void_p * len(cs))(*[c.ctypes.data if c.shape[0] else None for c in cs])
+        cnts = (ctypes.c_size_t * len(cs))(*[c.shape[0] for c in cs])
+        self._check(lib().locgpu_ndt_set_target_set(self._h, ptrs, cnts, len(cs), stride, ctypes.byref(opts) if opts else None))
+
+    def ndt_set_target_set_batch(self, batch, opts=None):
+        """Target j = scan j of the resident plain batch, built on the device (locgpu_ndt_set_target_set_batch)."""
+        batch.upload_wait()
+        self._check(lib().locgpu_ndt_set_target_set_batch(self._h, batch._h, ctypes.byref(opts) if opts else None))
+
+    def ndt_set_info(self):
+        """dict(n_targets, points [n], voxels [n]) of the voxel-set target (locgpu_ndt_set_info)."""
+        n = ctypes.c_int(0)
+        self._check(lib().locgpu_ndt_set_info(self._h, ctypes.byref(n), None, None))
+        points = np.zeros(n.value, dtype=np.uint64)
+        voxels = np.zeros(n.value, dtype=np.uint64)
+        self._check(lib().locgpu_ndt_set_info(self._h, ctypes.byref(n), points.ctypes.data, voxels.ctypes.data))
+        return dict(n_targets=int(n.value), points=[int(v) for v in points], voxels=[int(v) for v in voxels])
+
+    def ndt_set_dump(self, target):
+        """(keys [n, 3], mu [n, 3], info [n, 3, 3]) of one target of the voxel set, in key order (locgpu_ndt_set_dump)."""
+        n_out = ctypes.c_size_t(0)
+        self._check(lib().locgpu_ndt_set_dump(self._h, target, None, None, None, 0, ctypes.byref(n_out)))
+        n = int(n_out.value)
+        keys = np.zeros((max(n, 1), 3), dtype=np.int32)
+        mu = np.zeros((max(n, 1), 3))
+        info = np.zeros((max(n, 1), 9))
+        self._check(lib().locgpu_ndt_set_dump(self._h, target, keys.ctypes.data, mu.ctypes.data, info.ctypes.data, n, ctypes.byref(n_out)))
+        return keys[:n], mu[:n], info[:n].reshape(n, 3, 3)
+
+    def ndt_align_pairs(self, batch, target_of, init_poses=None):
+        """ScanMatch of scan i of the batch against target target_of[i] of the voxel set (-1: not aligned; locgpu_ndt_align_pairs).
+        init_poses None = the identity for every scan. Returns (poses [n, 7], stats)."""
+        batch.upload_wait()
+        t = np.ascontiguousarray(target_of, dtype=np.int32).reshape(batch.n_scans)
+        ip = None if init_poses is None else _pose(init_poses).reshape(batch.n_scans, 7)
+        out = np.zeros((batch.n_scans, 7))
+        st = (AlignStats * batch.n_scans)()
+        self._check(lib().locgpu_ndt_align_pairs(self._h, batch._h, t.ctypes.data, None if ip is None else ip.ctypes.data, out.ctypes.data, st))
+        return out, [_stats_dict(s) for s in st]
+
+    def ndt_fitness_pairs(self, batch, target_of, poses, raw=False):
+        """Score of scan i under poses[i] against target target_of[i] alone (locgpu_ndt_fitness_pairs); -1: {+inf, 0, 0}."""
+        batch.upload_wait()
+        t = np.ascontiguousarray(target_of, dtype=np.int32).reshape(batch.n_scans)
+        p = _pose(poses).reshape(batch.n_scans, 7)
+        out = (Fitness * batch.n_scans)()
+        self._check(lib().locgpu_ndt_fitness_pairs(self._h, batch._h, t.ctypes.data, p.ctypes.data, out))
         return out if raw else [_fitness_dict(f) for f in out]
 
     def icp_target_info(self):

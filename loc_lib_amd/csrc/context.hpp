@@ -36,7 +36,8 @@ struct AlignSpec {
     GnParams prm{};
     float alpha = 1.0f;  // pruning factor of the tree walk; 1.0f = exact. Always 1.0f for grid and NDT.
     bool grid = false;   // LOCGPU_SEARCH_GRID_EXACT was asked for
-    bool pairs = false;  // locgpu_icp_align_pairs: scan i is searched in the tree at the batch's pair_base[i] of the context's forest; eager only
+    bool pairs = false;  // locgpu_icp_align_pairs: scan i is searched in the tree at the batch's pair_base[i] of the context's forest; locgpu_ndt_align_pairs: it is
+                         // looked up under target pair_base[i] of the context's voxel set; eager only
     bool ndt() const { return method_is_ndt(prm.method); }
     int k() const { return method_k(prm.method); }
     bool operator==(const AlignSpec& o) const { return prm == o.prm && alpha == o.alpha && grid == o.grid && pairs == o.pairs; }
@@ -119,6 +120,11 @@ struct locgpu_ctx {
     NdtTable* ndt = nullptr;
     locgpu::IncNdtState* inc = nullptr;  // incremental NDT voxel set (persists across set_target calls)
     locgpu_ndt_opts ndt_opts;
+    // Voxel-set target (locgpu_ndt_set_target_set, ndt_pairs.hip): `ndt` holds the grids of ndt_set_n > 0 targets under keys that carry
+    // the target's index; target j has ndt_set_points[j] points and ndt_set_voxels[j] records from record ndt_set_first[j] on. Only the
+    // pairs calls read such a target (refuse_ndt_set); every locgpu_ndt_set_target* makes the context ordinary again (ndt_set_n = 0).
+    int ndt_set_n = 0;
+    std::vector<size_t> ndt_set_points, ndt_set_voxels, ndt_set_first;
 
     locgpu::FilterScratch* filt = nullptr;  // workspaces of the cloud filters (cloud_filters.hip)
     locgpu::LoamScratch* loam = nullptr;    // workspaces of the LOAM feature picker (loam_features.hip)
@@ -225,7 +231,8 @@ struct locgpu_batch {
     locgpu::Event tail_ev;         // ... behind which the next upload's copies are ordered (batch_upload.hip)
     locgpu::PinnedBuf<double> h_hb;
     // locgpu_icp_align_pairs / locgpu_icp_fitness_pairs: per scan the first slot of its target's tree, formed on the host per call
-    // (pair_base[i] = forest_base[target_of[i]]) and uploaded as n_scans words; pair_skip[i]: target_of[i] == -1, the scan is not aligned
+    // (pair_base[i] = forest_base[target_of[i]]) and uploaded as n_scans words; pair_skip[i]: target_of[i] == -1, the scan is not aligned.
+    // locgpu_ndt_align_pairs / locgpu_ndt_fitness_pairs: pair_base[i] = target_of[i], the word the kernels shift into the voxel key
     std::vector<uint32_t> pair_base;
     std::vector<unsigned char> pair_skip;
     locgpu::DevBuf<uint32_t> d_pair_base;
@@ -258,7 +265,10 @@ int alloc_batch(locgpu_ctx* ctx, int n_scans, size_t max_n, locgpu_batch** out, 
 void free_batch(locgpu_batch* b);
 // Validate the matcher's options against the context's target; fill the request of an alignment.
 int check_icp(locgpu_ctx* ctx, const locgpu_icp_opts* o, AlignSpec& spec);
-int check_ndt(locgpu_ctx* ctx, AlignSpec& spec);
+// pairs: the request of locgpu_ndt_align_pairs, which reads a voxel-set target and nothing else; every other request reads an ordinary one
+int check_ndt(locgpu_ctx* ctx, AlignSpec& spec, bool pairs = false);
+// LOCGPU_ERR_INVALID with a text when the context holds a voxel-set target: the gate of every entry point that reads the NDT target as ONE grid
+int refuse_ndt_set(locgpu_ctx* ctx, const char* who);
 // LOCGPU_ERR_INVALID with a text when the context holds a forest target: the gate of every entry point that reads the ICP target as ONE tree
 int refuse_forest(locgpu_ctx* ctx, const char* who);
 // icp_target.hip

@@ -16,6 +16,7 @@
 #include "gn_driver.hpp"
 #include "ndt_inc.hpp"
 #include "ndt_kernels.hpp"
+#include "ndt_pairs.hpp"
 #include "stream_lease.hpp"
 
 namespace locgpu {
@@ -148,6 +149,9 @@ int launch_local_stage(locgpu_ctx* ctx, locgpu_batch* b, const LocalStage& w, hi
         if (w.spec.prm.method == kMethodNdtInc)
             launch_inc_accum(ctx->inc, ctx->ndt_opts.res_outlier_th, ndt_n_nearby(ctx->ndt_opts.nearby_type), w.src, b->d_counts, w.state, b->max_n, b->n_scans, b->d_partials, s,
                              w.active, w.n_active, w.src_of);
+        else if (w.spec.pairs)
+            n_partial_blocks = launch_ndt_accum_pairs(ctx->ndt, w.scan_tree_base, w.src, b->d_counts, w.state, b->max_n, b->n_scans, b->d_partials, s, w.active, w.n_active,
+                                                      w.split_scans, w.src_of);
         else
             n_partial_blocks = launch_ndt_accum(ctx->ndt, w.src, b->d_counts, w.state, b->max_n, b->n_scans, b->d_partials, s, w.active, w.n_active, w.split_scans, w.src_of);
     }
@@ -443,7 +447,8 @@ static void lease_release(locgpu_ctx* ctx, locgpu_batch* b) {
     b->leased = false;
 }
 
-// The per-scan tree bases of a pairs call (b->pair_base, formed by the entry point) → b->d_pair_base, on the batch's stream.
+// The per-scan words of a pairs call (b->pair_base, formed by the entry point: ICP tree bases, NDT target indices) → b->d_pair_base, on
+// the batch's stream.
 static int upload_pair_base(locgpu_ctx* ctx, locgpu_batch* b) {
     if (b->d_pair_base.cap() < (size_t)b->n_scans) {
         LOCGPU_HIP(ctx, hipStreamSynchronize(b->stream));
@@ -683,8 +688,10 @@ int fitness_pairs_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses
 }
 
 // Score of every entry of `b` under its pose against the direct NDT table: the probe-and-reduce kernel of ndt_fitness.hip, then the
-// ICP score's fixed-order sum. Touches nothing of the search stage (no neighbour lists, no work-list counters).
-int ndt_fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, locgpu_fitness* out) {
+// ICP score's fixed-order sum. Touches nothing of the search stage (no neighbour lists, no work-list counters). pairs: per scan under
+// its own target of the voxel set (b->pair_base); a scan without a target (b->pair_skip) is scored against target 0 and reported as
+// {+inf, 0, 0}.
+static int ndt_fitness_on_batch_impl(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, locgpu_fitness* out, bool pairs) {
     if (b->sharded) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_fitness: sharded batches are not scored");
     if (b->pending.active) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_fitness: an alignment of this batch has been begun and not finished");
     LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
@@ -692,7 +699,13 @@ int ndt_fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, 
     init_states(b, poses);
     hipStream_t s = b->stream;
     LOCGPU_HIP(ctx, hipMemcpyAsync(b->d_state, b->h_state, b->n_total * sizeof(PoseState), hipMemcpyHostToDevice, s));
-    launch_ndt_fitness(ctx->ndt, batch_src(b), b->d_counts, b->d_state, b->max_n, b->n_scans, b->d_partials, b->d_hb, s, b->d_src_of);
+    if (pairs) {
+        const int prc = upload_pair_base(ctx, b);
+        if (prc != LOCGPU_OK) return prc;
+        launch_ndt_fitness_pairs(ctx->ndt, b->d_pair_base, batch_src(b), b->d_counts, b->d_state, b->max_n, b->n_scans, b->d_partials, b->d_hb, s, b->d_src_of);
+    } else {
+        launch_ndt_fitness(ctx->ndt, batch_src(b), b->d_counts, b->d_state, b->max_n, b->n_scans, b->d_partials, b->d_hb, s, b->d_src_of);
+    }
     LOCGPU_HIP(ctx, hipGetLastError());
     LOCGPU_HIP(ctx, hipMemcpyAsync(b->h_hb, b->d_hb, (size_t)b->n_scans * kFitW * sizeof(double), hipMemcpyDeviceToHost, s));
     LOCGPU_HIP(ctx, hipStreamSynchronize(s));
@@ -701,9 +714,13 @@ int ndt_fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, 
         out[i].inliers = (int64_t)r[1];
         out[i].finite_points = (int64_t)r[2];
         out[i].score = out[i].inliers > 0 ? r[0] / (double)out[i].inliers : HUGE_VAL;
+        if (pairs && b->pair_skip[i]) out[i] = locgpu_fitness{HUGE_VAL, 0, 0};
     }
     return LOCGPU_OK;
 }
+
+int ndt_fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, locgpu_fitness* out) { return ndt_fitness_on_batch_impl(ctx, b, poses, out, false); }
+int ndt_fitness_pairs_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, locgpu_fitness* out) { return ndt_fitness_on_batch_impl(ctx, b, poses, out, true); }
 
 int eval_hb_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, const AlignSpec& spec, double* hb, const char* who) {
     const bool ndt = spec.ndt();

@@ -33,7 +33,7 @@ struct LocalStage {
     const GridSearchScratch* grid;  // the grid search's work lists when the batch has them
     bool capturing;               // inside hipStreamBeginCapture: nothing may be allocated
     const char* who;              // prefix of the error text
-    const uint32_t* scan_tree_base = nullptr;  // SearchArgs::scan_tree_base: a pairs alignment over a forest target; nullptr = the one tree
+    const uint32_t* scan_tree_base = nullptr;  // SearchArgs::scan_tree_base: a pairs alignment over a forest target (NDT: the target words over a voxel set); nullptr = the one target
 };
 // Enqueues search, then fit + accumulate (ICP), or the direct / incremental NDT accumulate, on `s`, with b->stage_ev's marks around
 // them. Returns the number of partial blocks per scan the solve (or launch_sum_partials) must sum; < 0 on failure (fail() was called).
@@ -68,6 +68,8 @@ int fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, doub
 int fitness_pairs_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, double max_range, locgpu_fitness* out);
 // Score of every entry of `b` under its pose against the context's direct NDT table (ndt_fitness.hip).
 int ndt_fitness_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, locgpu_fitness* out);
+// The same per scan against its own target of the context's voxel set (b->pair_base / pair_skip are set): a skipped scan scores {+inf, 0, 0}.
+int ndt_fitness_pairs_on_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* poses, locgpu_fitness* out);
 // The plane table of LOCGPU_P2PLANE_MAP for the current target (map_planes.hip); no-op when it is there.
 int ensure_map_planes(locgpu_ctx* ctx);
 

@@ -19,6 +19,7 @@
 #include "launch.hpp"
 #include "ndt_inc.hpp"
 #include "ndt_kernels.hpp"
+#include "ndt_pairs.hpp"
 #include "search_chunks.hpp"
 
 using namespace locgpu;
@@ -402,22 +403,15 @@ static int check_icp_request(locgpu_ctx* ctx, const locgpu_icp_opts* o, AlignSpe
 int check_icp(locgpu_ctx* ctx, const locgpu_icp_opts* o, AlignSpec& spec) { return check_icp_request(ctx, o, spec, false); }
 
 // The batch and the target_of array of pairs call `who`, checked in full before anything of the batch is written; then the per-scan
-// tree bases the driver uploads (b->pair_base, b->pair_skip).
-static int check_pairs(locgpu_ctx* ctx, locgpu_batch* b, const int* target_of, bool args_ok, const char* who) {
+// words the driver uploads (b->pair_base, b->pair_skip; pair_words, ndt_set_key.hpp): of n_targets targets, word i = base[target_of[i]]
+// (ICP: the tree bases of the forest) or, base == nullptr, target_of[i] itself (NDT: the target's index in the voxel set).
+static int check_pairs(locgpu_ctx* ctx, locgpu_batch* b, const int* target_of, bool args_ok, const char* who, int n_targets, const uint32_t* base) {
     if (!b || b->ctx != ctx || !target_of || !args_ok) return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": bad arguments (NULL, or a batch of another context)");
     if (b->sharded || b->shared_src) return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": sharded and shared-source batches are not aligned in pairs");
     if (b->pending.active) return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": an alignment of this batch has been begun and not finished");
     if (b->n_scans < 1) return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": the batch holds no scan");
-    for (int i = 0; i < b->n_scans; ++i)
-        if (target_of[i] < -1 || target_of[i] >= ctx->forest_n)
-            return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": target_of[" + std::to_string(i) + "] = " + std::to_string(target_of[i]) + " is neither -1 nor one of the " +
-                                                     std::to_string(ctx->forest_n) + " targets");
-    b->pair_base.assign((size_t)b->n_scans, 0u);
-    b->pair_skip.assign((size_t)b->n_scans, 0);
-    for (int i = 0; i < b->n_scans; ++i) {
-        if (target_of[i] < 0) b->pair_skip[i] = 1;
-        else b->pair_base[i] = ctx->forest_base[(size_t)target_of[i]];
-    }
+    std::string err;
+    if (!pair_words(target_of, b->n_scans, n_targets, base, b->pair_base, b->pair_skip, err)) return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": " + err);
     return LOCGPU_OK;
 }
 
@@ -506,7 +500,7 @@ int locgpu_icp_align_pairs(locgpu_ctx* ctx, locgpu_batch* b, const int* target_o
                            locgpu_align_stats* stats) {
     AlignSpec spec;
     int rc = check_icp_request(ctx, opts, spec, true);
-    if (rc == LOCGPU_OK) rc = check_pairs(ctx, b, target_of, out_poses != nullptr, "icp_align_pairs");
+    if (rc == LOCGPU_OK) rc = check_pairs(ctx, b, target_of, out_poses != nullptr, "icp_align_pairs", ctx->forest_n, ctx->forest_base.data());
     if (rc != LOCGPU_OK) return rc;
     std::vector<double> identity;
     if (!init_poses) {  // the reference's `SE3 init_pos` of every scan-to-scan match (test_node.cpp:289)
@@ -523,7 +517,7 @@ int locgpu_icp_fitness_pairs(locgpu_ctx* ctx, locgpu_batch* b, const int* target
     if (!ctx->d_tree) return fail(ctx, LOCGPU_ERR_NO_TARGET, "icp_fitness_pairs: SetInputTarget has not been called");
     if (ctx->forest_n == 0)
         return fail(ctx, LOCGPU_ERR_INVALID, "icp_fitness_pairs: the context holds an ordinary target; the pairs calls read a forest target (locgpu_icp_set_target_forest)");
-    const int rc = check_pairs(ctx, b, target_of, poses && out && !std::isnan(max_range), "icp_fitness_pairs");
+    const int rc = check_pairs(ctx, b, target_of, poses && out && !std::isnan(max_range), "icp_fitness_pairs", ctx->forest_n, ctx->forest_base.data());
     return rc != LOCGPU_OK ? rc : fitness_pairs_on_batch(ctx, b, poses, max_range, out);
 }
 
@@ -868,7 +862,7 @@ int ndt_fitness_target(locgpu_ctx* ctx, const char* who) {
         return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": the current NDT target is the incremental one (method 2); the score and the search are defined for the direct target only");
     }
     if (!ctx->ndt) return fail(ctx, LOCGPU_ERR_NO_TARGET, std::string(who) + ": SetInputTarget has not been called");
-    return LOCGPU_OK;
+    return refuse_ndt_set(ctx, who);
 }
 
 // One cloud under n_poses > 1 poses, through the context's shared-source batch in chunks (search_chunks.hpp); score(batch, poses, out)
@@ -1169,16 +1163,31 @@ extern "C" __attribute__((visibility("default"))) size_t locgpu_debug_grid_dump(
 
 // --------------------------------------------------------------------------------------------- NDT
 namespace locgpu {
-void ndt_free(locgpu_ctx* ctx) {
+// the context's direct table, an ordinary target's or a voxel set's, and what it knows about a set
+static void ndt_drop_direct(locgpu_ctx* ctx) {
     delete ctx->ndt;
     ctx->ndt = nullptr;
+    ctx->ndt_set_n = 0;
+    ctx->ndt_set_points.clear(); ctx->ndt_set_voxels.clear(); ctx->ndt_set_first.clear();
+}
+void ndt_free(locgpu_ctx* ctx) {
+    ndt_drop_direct(ctx);
     if (ctx->inc) { inc_ndt_destroy(ctx->inc); ctx->inc = nullptr; }
 }
-int check_ndt(locgpu_ctx* ctx, AlignSpec& spec) {
+int refuse_ndt_set(locgpu_ctx* ctx, const char* who) {
+    if (ctx->ndt_set_n == 0) return LOCGPU_OK;
+    return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": the context holds a voxel-set target (locgpu_ndt_set_target_set), which only locgpu_ndt_align_pairs / "
+                                         "locgpu_ndt_fitness_pairs read; locgpu_ndt_set_target* makes it an ordinary target again");
+}
+int check_ndt(locgpu_ctx* ctx, AlignSpec& spec, bool pairs) {
     if (!ctx) return LOCGPU_ERR_INVALID;
     const bool inc = ctx->ndt_opts.method == kNdtOptIncremental;
     if ((inc && !ctx->inc) || (!inc && !ctx->ndt)) return fail(ctx, LOCGPU_ERR_NO_TARGET, "ndt: SetInputTarget has not been called");
+    if (!pairs) { const int src = refuse_ndt_set(ctx, "ndt"); if (src != LOCGPU_OK) return src; }
+    if (pairs && ctx->ndt_set_n == 0)
+        return fail(ctx, LOCGPU_ERR_INVALID, "ndt_align_pairs: the context holds an ordinary target; the pairs calls read a voxel-set target (locgpu_ndt_set_target_set)");
     spec = AlignSpec{};
+    spec.pairs = pairs;
     GnParams& prm = spec.prm;
     prm.method = inc ? kMethodNdtInc : kMethodNdtDirect;
     prm.max_iteration = ctx->ndt_opts.max_iteration;
@@ -1199,6 +1208,7 @@ static int ndt_set_target_dev(locgpu_ctx* ctx, const float4* d_pts, const float4
     if (!(o.voxel_size > 0.0) || (o.nearby_type != kNearbyCenter && o.nearby_type != kNearby6) || (o.method != kNdtOptDirect && o.method != kNdtOptIncremental) ||
         (o.method == kNdtOptIncremental && o.capacity < 2))
         return fail(ctx, LOCGPU_ERR_INVALID, "ndt_set_target: bad options");
+    if (ctx->ndt_set_n > 0) ndt_drop_direct(ctx);  // a voxel set is replaced: the context is an ordinary one again, whatever becomes of this ingest
     if (o.method == kNdtOptIncremental) {
         // incremental: keep the voxel set unless the grid itself changed
         if (ctx->inc && (ctx->ndt_opts.method != kNdtOptIncremental || ctx->ndt_opts.voxel_size != o.voxel_size || ctx->ndt_opts.capacity != o.capacity)) {
@@ -1269,6 +1279,7 @@ int locgpu_ndt_dump(locgpu_ctx* ctx, int32_t* keys, double* mu, double* info, si
         return LOCGPU_OK;
     }
     if (!ctx->ndt) return fail(ctx, LOCGPU_ERR_NO_TARGET, "ndt_dump: no target");
+    { const int src = refuse_ndt_set(ctx, "ndt_dump"); if (src != LOCGPU_OK) return src; }
     *n_out = ctx->ndt->n_vox;
     const size_t n = std::min(cap, ctx->ndt->n_vox);
     if (n == 0) return LOCGPU_OK;
@@ -1346,6 +1357,144 @@ int locgpu_ndt_align_cloud(locgpu_ctx* ctx, const locgpu_cloud* src, const doubl
     AlignSpec spec;
     const int rc = check_ndt(ctx, spec);
     return rc != LOCGPU_OK ? rc : align_single(ctx, spec, "ndt_align_cloud", src && src->ctx && init_pose && out_pose, nullptr, 0, 0, src, init_pose, out_pose, stats);
+}
+
+// ---- pairwise batch NDT: a voxel-set target and the pairs calls (ndt_pairs.hip) ----
+// The set's options: what locgpu_ndt_set_target accepts, the direct method only.
+static int ndt_set_opts(locgpu_ctx* ctx, const locgpu_ndt_opts* opts, const char* who, locgpu_ndt_opts& o) {
+    if (opts) o = *opts; else locgpu_ndt_opts_default(&o);
+    if (!(o.voxel_size > 0.0) || (o.nearby_type != kNearbyCenter && o.nearby_type != kNearby6) || (o.method != kNdtOptDirect && o.method != kNdtOptIncremental))
+        return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": bad options");
+    if (o.method == kNdtOptIncremental) return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": a voxel set is built by the direct method only (method 1); the incremental method is refused");
+    return LOCGPU_OK;
+}
+
+// Build from points on the device (ndt_set_build's layouts) into a local table; the context is touched only when all of it succeeded.
+static int ndt_install_set(locgpu_ctx* ctx, const float4* d_pts, size_t scan_stride, const std::vector<int>& counts, const locgpu_ndt_opts& o, const char* who) {
+    const int n_targets = (int)counts.size();
+    NdtTable t;
+    std::vector<NdtSetTarget> info;
+    int bad = -1;
+    const hipError_t e = ndt_set_build(t, d_pts, scan_stride, counts.data(), n_targets, o.voxel_size, o.min_pts_in_voxel, ctx->stream, info, &bad);
+    if (e == hipErrorInvalidValue) return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": the set is beyond its size limits (points of all targets, or scans x capacity of the batch)");
+    if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); hip_ok(ctx, e, "ndt_set_build"); return LOCGPU_ERR_NO_DEVICE; }
+    if (bad >= 0)
+        return fail(ctx, LOCGPU_ERR_INVALID, std::string(who) + ": target " + std::to_string(bad) + ": a point lies outside the +-2^15-voxel key range of a voxel set");
+    t.res_outlier_th = o.res_outlier_th;
+    t.n_nearby = ndt_n_nearby(o.nearby_type);
+    if (ctx->inc) { inc_ndt_destroy(ctx->inc); ctx->inc = nullptr; }
+    if (!ctx->ndt) ctx->ndt = new NdtTable();
+    *ctx->ndt = std::move(t);
+    ctx->ndt_set_n = n_targets;
+    ctx->ndt_set_points.assign((size_t)n_targets, 0); ctx->ndt_set_voxels.assign((size_t)n_targets, 0); ctx->ndt_set_first.assign((size_t)n_targets, 0);
+    size_t first = 0;
+    for (int j = 0; j < n_targets; ++j) {
+        ctx->ndt_set_points[j] = (size_t)info[j].points;
+        ctx->ndt_set_voxels[j] = (size_t)info[j].voxels;
+        ctx->ndt_set_first[j] = first;  // records are numbered in (target, key) order
+        first += (size_t)info[j].voxels;
+    }
+    ctx->ndt_opts = o;
+    ctx->target_epoch++;
+    return LOCGPU_OK;
+}
+
+int locgpu_ndt_set_target_set(locgpu_ctx* ctx, const void* const* pts, const size_t* n, int n_targets, size_t stride_bytes, const locgpu_ndt_opts* opts) {
+    if (!ctx) return LOCGPU_ERR_INVALID;
+    std::string err;
+    if (!ndt_set_check_targets(pts, n, n_targets, stride_bytes, err)) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_set_target_set: " + err);
+    locgpu_ndt_opts o;
+    { const int orc = ndt_set_opts(ctx, opts, "ndt_set_target_set", o); if (orc != LOCGPU_OK) return orc; }
+    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<int> counts((size_t)n_targets);
+    size_t total = 0;
+    for (int j = 0; j < n_targets; ++j) { counts[j] = (int)n[j]; total += n[j]; }
+    // the deep copy of SetInputTarget: all targets behind one another in the context's pinned staging block, one copy up
+    float4* stage = nullptr;
+    if (!hip_ok(ctx, cloud_stage(ctx, total, &stage), "pinned staging")) return LOCGPU_ERR_OOM;
+    size_t w = 0;
+    for (int j = 0; j < n_targets; ++j) {
+        const char* base = (const char*)pts[j];
+        for (size_t i = 0; i < n[j]; ++i, ++w) { stage[w] = float4{0.f, 0.f, 0.f, 0.f}; std::memcpy(&stage[w], base + i * stride_bytes, 12); }
+    }
+    DevBuf<float4> d_pts;
+    if (!hip_ok(ctx, d_pts.alloc(total), "hipMalloc voxel-set points")) return LOCGPU_ERR_OOM;
+    LOCGPU_HIP(ctx, hipMemcpyAsync(d_pts, stage, total * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    const int rc = ndt_install_set(ctx, d_pts, 0, counts, o, "ndt_set_target_set");
+    (void)hipStreamSynchronize(ctx->stream);  // the staging block and d_pts are free again
+    return rc;
+}
+
+int locgpu_ndt_set_target_set_batch(locgpu_ctx* ctx, const locgpu_batch* b, const locgpu_ndt_opts* opts) {
+    if (!ctx) return LOCGPU_ERR_INVALID;
+    if (!b || b->ctx != ctx) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_set_target_set_batch: NULL batch or a batch of another context");
+    if (b->sharded || b->shared_src) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_set_target_set_batch: sharded and shared-source batches hold no scans of their own");
+    if (b->pending.active) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_set_target_set_batch: an alignment of this batch has been begun and not finished");
+    if (b->n_scans < 1 || b->n_scans > kNdtSetMaxTargets)
+        return fail(ctx, LOCGPU_ERR_INVALID, "ndt_set_target_set_batch: the batch holds " + std::to_string(b->n_scans) + " scans, a voxel set 1 ... " + std::to_string(kNdtSetMaxTargets) + " targets");
+    locgpu_ndt_opts o;
+    { const int orc = ndt_set_opts(ctx, opts, "ndt_set_target_set_batch", o); if (orc != LOCGPU_OK) return orc; }
+    std::vector<int> counts((size_t)b->n_scans);
+    for (int j = 0; j < b->n_scans; ++j) {
+        if (b->counts[j] <= 0) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_set_target_set_batch: target " + std::to_string(j) + ": empty cloud");
+        counts[j] = b->counts[j];
+    }
+    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+    { const int orc = order_behind_batch(ctx, const_cast<locgpu_batch*>(b), "ndt_set_target_set_batch: ordering behind the batch"); if (orc != LOCGPU_OK) return orc; }
+    // the scans are read where the batch holds them: no point crosses PCIe
+    const int rc = ndt_install_set(ctx, b->d_src, (size_t)b->max_n, counts, o, "ndt_set_target_set_batch");
+    (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+}
+
+int locgpu_ndt_set_info(const locgpu_ctx* ctx, int* n_targets, size_t* points, size_t* voxels) {
+    if (!ctx) return LOCGPU_ERR_INVALID;
+    if (n_targets) *n_targets = ctx->ndt_set_n;
+    locgpu_ctx* c = const_cast<locgpu_ctx*>(ctx);
+    if (ctx->ndt_set_n == 0) {
+        const bool any = ctx->ndt_opts.method == kNdtOptIncremental ? ctx->inc != nullptr : ctx->ndt != nullptr;
+        return any ? fail(c, LOCGPU_ERR_INVALID, "ndt_set_info: the context holds an ordinary NDT target") : fail(c, LOCGPU_ERR_NO_TARGET, "ndt_set_info: SetInputTarget has not been called");
+    }
+    for (int j = 0; j < ctx->ndt_set_n; ++j) {
+        if (points) points[j] = ctx->ndt_set_points[j];
+        if (voxels) voxels[j] = ctx->ndt_set_voxels[j];
+    }
+    return LOCGPU_OK;
+}
+
+int locgpu_ndt_set_dump(locgpu_ctx* ctx, int target, int32_t* keys, double* mu, double* info, size_t cap, size_t* n_out) {
+    if (!ctx || !n_out) return LOCGPU_ERR_INVALID;
+    if (ctx->ndt_set_n == 0 || !ctx->ndt) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_set_dump: the context holds no voxel-set target");
+    if (target < 0 || target >= ctx->ndt_set_n) return fail(ctx, LOCGPU_ERR_INVALID, "ndt_set_dump: target " + std::to_string(target) + " is not one of the " + std::to_string(ctx->ndt_set_n) + " targets");
+    *n_out = ctx->ndt_set_voxels[(size_t)target];
+    const size_t n = std::min(cap, *n_out);
+    if (n == 0) return LOCGPU_OK;
+    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+    LOCGPU_HIP(ctx, ndt_set_dump(*ctx->ndt, ctx->ndt_set_first[(size_t)target], n, keys, mu, info, ctx->stream));
+    return LOCGPU_OK;
+}
+
+int locgpu_ndt_align_pairs(locgpu_ctx* ctx, locgpu_batch* b, const int* target_of, const double* init_poses, double* out_poses, locgpu_align_stats* stats) {
+    AlignSpec spec;
+    int rc = check_ndt(ctx, spec, true);
+    if (rc == LOCGPU_OK) rc = check_pairs(ctx, b, target_of, out_poses != nullptr, "ndt_align_pairs", ctx->ndt_set_n, nullptr);
+    if (rc != LOCGPU_OK) return rc;
+    std::vector<double> identity;
+    if (!init_poses) {  // the reference's `SE3 init_pos` of every scan-to-scan match (test_node.cpp:348)
+        identity.assign(7 * (size_t)b->n_total, 0.0);
+        for (int i = 0; i < b->n_total; ++i) identity[7 * (size_t)i + 3] = 1.0;
+        init_poses = identity.data();
+    }
+    return run_align(ctx, b, init_poses, spec, out_poses, stats);
+}
+
+int locgpu_ndt_fitness_pairs(locgpu_ctx* ctx, locgpu_batch* b, const int* target_of, const double* poses, locgpu_fitness* out) {
+    if (!ctx) return LOCGPU_ERR_INVALID;
+    if (ctx->ndt_opts.method == kNdtOptIncremental ? !ctx->inc : !ctx->ndt) return fail(ctx, LOCGPU_ERR_NO_TARGET, "ndt_fitness_pairs: SetInputTarget has not been called");
+    if (ctx->ndt_set_n == 0)
+        return fail(ctx, LOCGPU_ERR_INVALID, "ndt_fitness_pairs: the context holds an ordinary target; the pairs calls read a voxel-set target (locgpu_ndt_set_target_set)");
+    const int rc = check_pairs(ctx, b, target_of, poses && out, "ndt_fitness_pairs", ctx->ndt_set_n, nullptr);
+    return rc != LOCGPU_OK ? rc : ndt_fitness_pairs_on_batch(ctx, b, poses, out);
 }
 
 }  // extern "C"

@@ -60,6 +60,60 @@ __device__ __forceinline__ void ndt_mean_scatter(const float4* __restrict__ psor
     c[0] = c00; c[1] = c01; c[2] = c02; c[3] = c11; c[4] = c12; c[5] = c22;
 }
 
+// One kept voxel of a DIRECT table, the run psorted[b, e) under `key`: math::ComputeMeanAndCov's sums (ndt_mean_scatter), Σ/(n−1),
+// one-sided Jacobi SVD, λ1,λ2 clamped to ≥ 1e-3·λ0, info = V diag(1/λ) Uᵀ (ndt cpp:111-130) — then claim() takes the voxel's table
+// slot and returns the index of its record, which is written. The single-target build (ndt_kernels.hip) and the voxel-set build
+// (ndt_pairs.hip) differ in claim() alone, so a voxel has the same bits in both.
+template <class Claim>
+__device__ __forceinline__ void ndt_voxel_record(unsigned long long key, const float4* psorted, uint32_t b, uint32_t e, NdtRecord* rec, Claim claim) {
+    const uint32_t len = e - b;
+    double mu[3], c[6];
+    ndt_mean_scatter(psorted, b, e, mu, c);
+    const double mx = mu[0], my = mu[1], mz = mu[2];
+    const double len1 = (double)(len - 1);
+    const double sxx = c[0] / len1, sxy = c[1] / len1, sxz = c[2] / len1, syy = c[3] / len1, syz = c[4] / len1, szz = c[5] / len1;
+    double a[3][3] = {{sxx, sxy, sxz}, {sxy, syy, syz}, {sxz, syz, szz}};  // columns of the symmetric Σ
+    double vv[3][3];
+    jacobi_svd_onesided<3, 3>(a, vv);
+    double sv[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) sv[k] = sqrt(a[k][0] * a[k][0] + a[k][1] * a[k][1] + a[k][2] * a[k][2]);
+    // order by descending singular value (stable, like std::sort on three keys with > comparator)
+    int o0 = 0, o1 = 1, o2 = 2;
+    if (sv[o1] > sv[o0]) { const int t = o0; o0 = o1; o1 = t; }
+    if (sv[o2] > sv[o1]) { const int t = o1; o1 = o2; o2 = t; }
+    if (sv[o1] > sv[o0]) { const int t = o0; o0 = o1; o1 = t; }
+    const int ord[3] = {o0, o1, o2};
+    double lam[3], U[3][3], V[3][3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int cidx = ord[k];
+        lam[k] = cidx == 0 ? sv[0] : (cidx == 1 ? sv[1] : sv[2]);
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const double vr = cidx == 0 ? vv[0][r] : (cidx == 1 ? vv[1][r] : vv[2][r]);
+            const double ar = cidx == 0 ? a[0][r] : (cidx == 1 ? a[1][r] : a[2][r]);
+            V[k][r] = vr;
+            U[k][r] = lam[k] > 0.0 ? ar / lam[k] : vr;
+        }
+    }
+    if (lam[1] < lam[0] * 1e-3) lam[1] = lam[0] * 1e-3;
+    if (lam[2] < lam[0] * 1e-3) lam[2] = lam[0] * 1e-3;
+    const unsigned int vid = claim();
+    NdtRecord& R = rec[vid];
+    R.key = key;
+    R.mu[0] = mx; R.mu[1] = my; R.mu[2] = mz;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int cc = 0; cc < 3; ++cc) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s += V[k][r] * (1.0 / lam[k]) * U[k][cc];
+            R.info[3 * r + cc] = s;
+        }
+}
+
 // every slot of a table to its empty value
 template <class T>
 __global__ void ndt_fill_kernel(T* p, size_t n, T v) {

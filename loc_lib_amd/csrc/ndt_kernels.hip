@@ -22,7 +22,8 @@
 namespace locgpu {
 
 // One thread per voxel (run of the sorted keys) with more than min_pts points: math::ComputeMeanAndCov's sums (ndt_mean_scatter),
-// Σ/(n−1), one-sided Jacobi SVD, clamp, info = V diag(1/λ) Uᵀ (ndt cpp:111-130) — then the record goes into the table.
+// Σ/(n−1), one-sided Jacobi SVD, clamp, info = V diag(1/λ) Uᵀ (ndt cpp:111-130; ndt_voxel_record, ndt_ingest.hpp) — then the record goes
+// into the table.
 __global__ __launch_bounds__(kBlock) void ndt_voxel_kernel(const unsigned long long* __restrict__ skey, const float4* __restrict__ psorted, const uint32_t* __restrict__ ustart,
                                                            const int* __restrict__ n_runs, int min_pts, NdtSlot* __restrict__ slots, NdtRecord* __restrict__ rec, size_t cap_mask,
                                                            int* __restrict__ n_vox) {
@@ -32,59 +33,18 @@ __global__ __launch_bounds__(kBlock) void ndt_voxel_kernel(const unsigned long l
     const uint32_t len = e - b;
     const unsigned long long key = skey[b];
     if (key == kNdtEmpty || (int)len <= min_pts) return;  // count > min_pts_in_voxel_ (ndt cpp:111,137)
-    double mu[3], c[6];
-    ndt_mean_scatter(psorted, b, e, mu, c);
-    const double mx = mu[0], my = mu[1], mz = mu[2];
-    const double len1 = (double)(len - 1);
-    const double sxx = c[0] / len1, sxy = c[1] / len1, sxz = c[2] / len1, syy = c[3] / len1, syz = c[4] / len1, szz = c[5] / len1;
-    double a[3][3] = {{sxx, sxy, sxz}, {sxy, syy, syz}, {sxz, syz, szz}};  // columns of the symmetric Σ
-    double vv[3][3];
-    jacobi_svd_onesided<3, 3>(a, vv);
-    double sv[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) sv[k] = sqrt(a[k][0] * a[k][0] + a[k][1] * a[k][1] + a[k][2] * a[k][2]);
-    // order by descending singular value (stable, like std::sort on three keys with > comparator)
-    int o0 = 0, o1 = 1, o2 = 2;
-    if (sv[o1] > sv[o0]) { const int t = o0; o0 = o1; o1 = t; }
-    if (sv[o2] > sv[o1]) { const int t = o1; o1 = o2; o2 = t; }
-    if (sv[o1] > sv[o0]) { const int t = o0; o0 = o1; o1 = t; }
-    const int ord[3] = {o0, o1, o2};
-    double lam[3], U[3][3], V[3][3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int cidx = ord[k];
-        lam[k] = cidx == 0 ? sv[0] : (cidx == 1 ? sv[1] : sv[2]);
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const double vr = cidx == 0 ? vv[0][r] : (cidx == 1 ? vv[1][r] : vv[2][r]);
-            const double ar = cidx == 0 ? a[0][r] : (cidx == 1 ? a[1][r] : a[2][r]);
-            V[k][r] = vr;
-            U[k][r] = lam[k] > 0.0 ? ar / lam[k] : vr;
+    ndt_voxel_record(key, psorted, b, e, rec, [&]() -> unsigned int {
+        // claim a table slot (keys are distinct: a first probe that finds the slot taken walks on)
+        size_t h = ndt_hash32(key, cap_mask);
+        for (;;) {
+            const unsigned long long prev = atomicCAS(&slots[h].key, kNdtEmpty, key);
+            if (prev == kNdtEmpty) break;
+            h = (h + 1) & cap_mask;
         }
-    }
-    if (lam[1] < lam[0] * 1e-3) lam[1] = lam[0] * 1e-3;
-    if (lam[2] < lam[0] * 1e-3) lam[2] = lam[0] * 1e-3;
-    // claim a table slot (keys are distinct: a first probe that finds the slot taken walks on)
-    size_t h = ndt_hash32(key, cap_mask);
-    for (;;) {
-        const unsigned long long prev = atomicCAS(&slots[h].key, kNdtEmpty, key);
-        if (prev == kNdtEmpty) break;
-        h = (h + 1) & cap_mask;
-    }
-    const unsigned int vid = (unsigned int)atomicAdd(n_vox, 1);  // which record a voxel gets varies from run to run; what is in it does not
-    slots[h].vid = vid;
-    NdtRecord& R = rec[vid];
-    R.key = key;
-    R.mu[0] = mx; R.mu[1] = my; R.mu[2] = mz;
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int cc = 0; cc < 3; ++cc) {
-            double s = 0.0;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) s += V[k][r] * (1.0 / lam[k]) * U[k][cc];
-            R.info[3 * r + cc] = s;
-        }
+        const unsigned int vid = (unsigned int)atomicAdd(n_vox, 1);  // which record a voxel gets varies from run to run; what is in it does not
+        slots[h].vid = vid;
+        return vid;
+    });
 }
 
 // Read-back for tests: the records as dense arrays.
