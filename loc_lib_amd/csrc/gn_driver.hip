@@ -16,7 +16,6 @@
 #include "gn_driver.hpp"
 #include "ndt_inc.hpp"
 #include "ndt_kernels.hpp"
-#include "ndt_pairs.hpp"
 #include "stream_lease.hpp"
 
 namespace locgpu {
@@ -149,11 +148,9 @@ int launch_local_stage(locgpu_ctx* ctx, locgpu_batch* b, const LocalStage& w, hi
         if (w.spec.prm.method == kMethodNdtInc)
             launch_inc_accum(ctx->inc, ctx->ndt_opts.res_outlier_th, ndt_n_nearby(ctx->ndt_opts.nearby_type), w.src, b->d_counts, w.state, b->max_n, b->n_scans, b->d_partials, s,
                              w.active, w.n_active, w.src_of);
-        else if (w.spec.pairs)
-            n_partial_blocks = launch_ndt_accum_pairs(ctx->ndt, w.scan_tree_base, w.src, b->d_counts, w.state, b->max_n, b->n_scans, b->d_partials, s, w.active, w.n_active,
-                                                      w.split_scans, w.src_of);
         else
-            n_partial_blocks = launch_ndt_accum(ctx->ndt, w.src, b->d_counts, w.state, b->max_n, b->n_scans, b->d_partials, s, w.active, w.n_active, w.split_scans, w.src_of);
+            n_partial_blocks = launch_ndt_accum(ctx->ndt, w.src, b->d_counts, w.state, b->max_n, b->n_scans, b->d_partials, s, w.active, w.n_active, w.split_scans, w.src_of,
+                                                w.spec.pairs ? w.scan_tree_base : nullptr);
     }
     ev.mark(s);
     return n_partial_blocks;
@@ -702,10 +699,8 @@ static int ndt_fitness_on_batch_impl(locgpu_ctx* ctx, locgpu_batch* b, const dou
     if (pairs) {
         const int prc = upload_pair_base(ctx, b);
         if (prc != LOCGPU_OK) return prc;
-        launch_ndt_fitness_pairs(ctx->ndt, b->d_pair_base, batch_src(b), b->d_counts, b->d_state, b->max_n, b->n_scans, b->d_partials, b->d_hb, s, b->d_src_of);
-    } else {
-        launch_ndt_fitness(ctx->ndt, batch_src(b), b->d_counts, b->d_state, b->max_n, b->n_scans, b->d_partials, b->d_hb, s, b->d_src_of);
     }
+    launch_ndt_fitness(ctx->ndt, batch_src(b), b->d_counts, b->d_state, b->max_n, b->n_scans, b->d_partials, b->d_hb, s, b->d_src_of, pairs ? b->d_pair_base.get() : nullptr);
     LOCGPU_HIP(ctx, hipGetLastError());
     LOCGPU_HIP(ctx, hipMemcpyAsync(b->h_hb, b->d_hb, (size_t)b->n_scans * kFitW * sizeof(double), hipMemcpyDeviceToHost, s));
     LOCGPU_HIP(ctx, hipStreamSynchronize(s));

@@ -2,7 +2,8 @@
 // locgpu_ndt_fitness): the mean over the inlier points of the smallest accepted χ² residual eᵀ·info·e among the voxels AlignNdt probes
 // for the point (ndt_registration.cpp:399-433). AlignNdt forms that residual for its gate (:416-421) and drops it; here it is kept.
 //
-// Shape: one kernel probes the voxel table with ndt_accum_kernel's look-up (ndt_kernels.hip, where it says why this is a copy) and
+// Shape: one kernel probes the voxel table with ndt_accum_kernel's look-up (ndt_kernels.hip, where it says why this is a copy and not a
+// shared function; like that kernel it is a template over the key rule, so a voxel set is scored by the same text) and
 // reduces {Σ min res, inliers, finite points} in FP64 per block — the accumulators' scheme, spelled out in the kernel (it says
 // why); the row format is the ICP score's (fitness.hip), so its last small kernel adds the block rows of a scan in its
 // fixed order. No atomics on the sums.
@@ -17,13 +18,17 @@ namespace locgpu {
 
 constexpr int kNdtFitPts = 4;  // = kFitPts of fitness.hip: launch_fitness_sum sums icp_fitness_rows(max_n) rows per scan
 
+// A template over the key rule, as ndt_accum_kernel is: one target's table, or a voxel set with the scan's look-ups under its own target.
+template <class Rule>
 __global__ __launch_bounds__(kBlock) void ndt_fitness_accum_kernel(const NdtSlot* __restrict__ slots, const NdtRecord* __restrict__ rec, size_t cap_mask,
                                                                    double inv_voxel, double res_th, int n_nearby, const float4* __restrict__ src,
                                                                    const int* __restrict__ counts, const PoseState* __restrict__ st, int max_n,
-                                                                   double* __restrict__ partials, const int* __restrict__ src_of) {
+                                                                   double* __restrict__ partials, const int* __restrict__ src_of, Rule rule) {
     __shared__ double s_part[kBlock / 64][kFitW];
     const int scan = blockIdx.y;
     const int n = counts[scan];
+    unsigned long long tbits = 0;  // the set's rule: the key bits of this scan's target
+    if constexpr (std::is_same_v<Rule, NdtVoxelSet>) tbits = ndt_set_target_bits(rule.pair_target[scan]);
     double sum = 0.0, inl = 0.0, fin = 0.0;
     // one point at a time (as the accumulate kernel): its seven look-ups are what is in flight together
 #pragma unroll 1
@@ -42,17 +47,31 @@ __global__ __launch_bounds__(kBlock) void ndt_fitness_accum_kernel(const NdtSlot
         unsigned int vx[7];
         size_t hs[7];
         bool found[7];
-        // the packed key is linear in the coordinates (ndt_pack): a face neighbour's key is the centre's ± one constant, and it is in
-        // range when the centre is and the one coordinate that moved still is
-        const bool centre_ok = ndt_key_in_range(kx, ky, kz);
-        const unsigned long long key0 = ndt_pack(centre_ok ? kx : 0, centre_ok ? ky : 0, centre_ok ? kz : 0);
+        // keys and probe validity per rule, as in ndt_accum_kernel (ndt_kernels.hip, where each rule is explained)
+        if constexpr (std::is_same_v<Rule, NdtOneTarget>) {
+            const bool centre_ok = ndt_key_in_range(kx, ky, kz);
+            const unsigned long long key0 = ndt_pack(centre_ok ? kx : 0, centre_ok ? ky : 0, centre_ok ? kz : 0);
 #pragma unroll
-        for (int j = 0; j < 7; ++j) {
-            const int moved = ox[j] != 0 ? kx + ox[j] : (oy[j] != 0 ? ky + oy[j] : kz + oz[j]);  // j = 0: kz, in range with the centre
-            found[j] = j < n_nearby && centre_ok && moved > -kNdtBias && moved < kNdtBias;
-            const long long delta = (long long)ox[j] * (1ll << 42) + (long long)oy[j] * (1ll << 21) + (long long)oz[j];  // a constant after unrolling
-            key[j] = found[j] ? key0 + (unsigned long long)delta : key0;
-            hs[j] = ndt_hash32(key[j], cap_mask);
+            for (int j = 0; j < 7; ++j) {
+                const int moved = ox[j] != 0 ? kx + ox[j] : (oy[j] != 0 ? ky + oy[j] : kz + oz[j]);  // j = 0: kz, in range with the centre
+                found[j] = j < n_nearby && centre_ok && moved > -kNdtBias && moved < kNdtBias;
+                const long long delta = (long long)ox[j] * (1ll << 42) + (long long)oy[j] * (1ll << 21) + (long long)oz[j];  // a constant after unrolling
+                key[j] = found[j] ? key0 + (unsigned long long)delta : key0;
+                hs[j] = ndt_hash32(key[j], cap_mask);
+            }
+        } else {
+            const bool centre_ok = ndt_key_in_range(kx, ky, kz);
+            const bool okx = ndt_set_coord_ok(kx), oky = ndt_set_coord_ok(ky), okz = ndt_set_coord_ok(kz);
+            const unsigned long long key0 = ndt_set_pack(tbits, centre_ok ? kx : 0, centre_ok ? ky : 0, centre_ok ? kz : 0);
+#pragma unroll
+            for (int j = 0; j < 7; ++j) {
+                const int moved = ox[j] != 0 ? kx + ox[j] : (oy[j] != 0 ? ky + oy[j] : kz + oz[j]);  // j = 0: kz
+                const bool rest_ok = ox[j] != 0 ? (oky && okz) : (oy[j] != 0 ? (okx && okz) : (okx && oky));
+                found[j] = j < n_nearby && centre_ok && rest_ok && ndt_set_coord_ok(moved);
+                const unsigned long long delta = ndt_set_delta(ox[j], oy[j], oz[j]);  // a constant after unrolling
+                key[j] = found[j] ? key0 + delta : key0;
+                hs[j] = ndt_hash32(key[j], cap_mask);
+            }
         }
 #pragma unroll
         for (int j = 0; j < 7; ++j) { const NdtSlot sl = slots[hs[j]]; kk[j] = sl.key; vx[j] = sl.vid; }
@@ -105,11 +124,15 @@ __global__ __launch_bounds__(kBlock) void ndt_fitness_accum_kernel(const NdtSlot
 }
 
 void launch_ndt_fitness(const NdtTable* t, const float4* src, const int* counts, const PoseState* st, int max_n, int n_scans, double* partials,
-                        double* out, hipStream_t s, const int* src_of) {
+                        double* out, hipStream_t s, const int* src_of, const uint32_t* pair_target) {
     static_assert(kNdtFitPts * kBlock == 1024, "the rows launch_fitness_sum adds");
     const int rows = icp_fitness_rows(max_n);
-    hipLaunchKernelGGL(ndt_fitness_accum_kernel, dim3(rows, n_scans), dim3(kBlock), 0, s, t->d_slots, t->d_rec, t->cap - 1, t->inv_voxel, t->res_outlier_th,
-                       t->n_nearby, src, counts, st, max_n, partials, src_of);
+    if (pair_target)
+        hipLaunchKernelGGL(ndt_fitness_accum_kernel<NdtVoxelSet>, dim3(rows, n_scans), dim3(kBlock), 0, s, t->d_slots, t->d_rec, t->cap - 1, t->inv_voxel, t->res_outlier_th,
+                           t->n_nearby, src, counts, st, max_n, partials, src_of, NdtVoxelSet{pair_target});
+    else
+        hipLaunchKernelGGL(ndt_fitness_accum_kernel<NdtOneTarget>, dim3(rows, n_scans), dim3(kBlock), 0, s, t->d_slots, t->d_rec, t->cap - 1, t->inv_voxel, t->res_outlier_th,
+                           t->n_nearby, src, counts, st, max_n, partials, src_of, NdtOneTarget{});
     launch_fitness_sum(partials, rows, n_scans, out, nullptr, s);
 }
 

@@ -75,6 +75,12 @@ hipError_t NdtIngest::run(const float4* d_pts, size_t n, double inv_voxel, bool 
     const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
     LOCGPU_TRY(hipMemsetAsync(ctr, 0, kIngCtrs * sizeof(int), s));
     hipLaunchKernelGGL(ndt_key_kernel, dim3(grid), dim3(kBlock), 0, s, d_pts, n, inv_voxel, masked ? keep.get() : nullptr, pkey, pidx, ctr);
+    return group(d_pts, n, s);
+}
+
+hipError_t NdtIngest::group(const float4* d_pts, size_t n, hipStream_t s) {
+    if (n + 1 > cap_) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
     size_t tb = temp.cap();
     LOCGPU_TRY(prim::sort_pairs(temp, tb, pkey.get(), skey.get(), pidx.get(), sidx.get(), n, 0, 64, s));  // stable: a voxel's points keep their input order
     hipLaunchKernelGGL(ndt_head_kernel, dim3(grid), dim3(kBlock), 0, s, skey, n, head);

@@ -1,4 +1,5 @@
-// loc_lib_amd/csrc/ndt_ingest.hpp — the ingest front both NDT tables are built from (ndt_kernels.hip: direct, ndt_inc.hip: incremental).
+// loc_lib_amd/csrc/ndt_ingest.hpp — the ingest front every NDT table is built from (ndt_kernels.hip: direct, ndt_pairs.hip: the
+// voxel set, with a key of its own in front of the grouping half, ndt_inc.hip: incremental).
 //
 // point → key → stable radix sort → run heads → exclusive sum → run starts and the points in voxel order → per-voxel mean and scatter
 // summed sequentially in input order. That sequence is why both tables carry the reference's bits (its per-voxel index list holds a
@@ -35,9 +36,12 @@ struct NdtIngest {
     // room for clouds of up to cap − 1 points; with_masks: ukey and keep too
     hipError_t reserve(size_t cap, bool with_masks);
     hipError_t ensure_temp(size_t bytes) { return bytes <= temp.cap() ? hipSuccess : temp.alloc(bytes + 256); }
-    // keys → sort → heads → scan → runs, enqueued on `s` (no synchronisation, no read-back). A point outside the ±2^20-voxel key
+    // keys → group(), enqueued on `s` (no synchronisation, no read-back). A point outside the ±2^20-voxel key
     // range raises ctr[kIngBadKey]; it, and with `masked` a point whose keep[i] == 0, gets kNdtEmpty and sorts into the last run.
     hipError_t run(const float4* d_pts, size_t n, double inv_voxel, bool masked, hipStream_t s);
+    // The grouping half: sort → heads → scan → runs over the n keys in pkey, pidx[i] = the index in d_pts of the point behind key i.
+    // Writes ctr[kIngRuns] and ctr[kIngLastEmpty] and no other counter. For a caller with a key of its own (the voxel set, ndt_pairs.hip).
+    hipError_t group(const float4* d_pts, size_t n, hipStream_t s);
 
   private:
     size_t cap_ = 0;
@@ -58,6 +62,17 @@ __device__ __forceinline__ void ndt_mean_scatter(const float4* __restrict__ psor
         c00 += dx * dx; c01 += dx * dy; c02 += dx * dz; c11 += dy * dy; c12 += dy * dz; c22 += dz * dz;
     }
     c[0] = c00; c[1] = c01; c[2] = c02; c[3] = c11; c[4] = c12; c[5] = c22;
+}
+
+// Claims the table slot of `key` and returns it (keys are distinct: a first probe that finds the slot taken walks on). The caller
+// writes the slot's record index.
+__device__ __forceinline__ size_t ndt_claim_slot(NdtSlot* slots, unsigned long long key, size_t cap_mask) {
+    size_t h = ndt_hash32(key, cap_mask);
+    for (;;) {
+        const unsigned long long prev = atomicCAS(&slots[h].key, kNdtEmpty, key);
+        if (prev == kNdtEmpty) return h;
+        h = (h + 1) & cap_mask;
+    }
 }
 
 // One kept voxel of a DIRECT table, the run psorted[b, e) under `key`: math::ComputeMeanAndCov's sums (ndt_mean_scatter), Σ/(n−1),

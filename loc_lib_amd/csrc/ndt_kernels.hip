@@ -34,29 +34,44 @@ __global__ __launch_bounds__(kBlock) void ndt_voxel_kernel(const unsigned long l
     const unsigned long long key = skey[b];
     if (key == kNdtEmpty || (int)len <= min_pts) return;  // count > min_pts_in_voxel_ (ndt cpp:111,137)
     ndt_voxel_record(key, psorted, b, e, rec, [&]() -> unsigned int {
-        // claim a table slot (keys are distinct: a first probe that finds the slot taken walks on)
-        size_t h = ndt_hash32(key, cap_mask);
-        for (;;) {
-            const unsigned long long prev = atomicCAS(&slots[h].key, kNdtEmpty, key);
-            if (prev == kNdtEmpty) break;
-            h = (h + 1) & cap_mask;
-        }
+        const size_t h = ndt_claim_slot(slots, key, cap_mask);
         const unsigned int vid = (unsigned int)atomicAdd(n_vox, 1);  // which record a voxel gets varies from run to run; what is in it does not
         slots[h].vid = vid;
         return vid;
     });
 }
 
-// Read-back for tests: the records as dense arrays.
+// Read-back for tests: the records as dense arrays, the key unpacked by the table's rule (a set's key without its target).
+template <class Rule>
 __global__ __launch_bounds__(kBlock) void ndt_dump_kernel(const NdtRecord* __restrict__ rec, size_t n, int* __restrict__ keys, double* __restrict__ mu, double* __restrict__ info) {
     const size_t o = (size_t)blockIdx.x * kBlock + threadIdx.x;
     if (o >= n) return;
     const NdtRecord& R = rec[o];
-    keys[3 * o + 0] = (int)((R.key >> 42) & 0x1FFFFF) - kNdtBias;
-    keys[3 * o + 1] = (int)((R.key >> 21) & 0x1FFFFF) - kNdtBias;
-    keys[3 * o + 2] = (int)(R.key & 0x1FFFFF) - kNdtBias;
+    if constexpr (std::is_same_v<Rule, NdtVoxelSet>) {
+        int t, x, y, z;
+        ndt_set_unpack(R.key, t, x, y, z);
+        keys[3 * o + 0] = x; keys[3 * o + 1] = y; keys[3 * o + 2] = z;
+    } else {
+        keys[3 * o + 0] = (int)((R.key >> 42) & 0x1FFFFF) - kNdtBias;
+        keys[3 * o + 1] = (int)((R.key >> 21) & 0x1FFFFF) - kNdtBias;
+        keys[3 * o + 2] = (int)(R.key & 0x1FFFFF) - kNdtBias;
+    }
     for (int k = 0; k < 3; ++k) mu[3 * o + k] = R.mu[k];
     for (int k = 0; k < 9; ++k) info[9 * o + k] = R.info[k];
+}
+
+hipError_t ndt_table_alloc(NdtTable& t, size_t runs, size_t n_rec, hipStream_t s) {
+    // A SPARSE table: at load 0.03 nearly every look-up — hit or miss — ends at its first probe, and a collision walk is what costs
+    // (a wave walks as long as its unluckiest lane, seven times per point); the lines a launch touches are as many as the voxels it
+    // looks up, whatever the table's size (measured: load <= 0.5, 15.7 ms per 256-scan step; load <= 0.03, see profiles/experiments.md).
+    size_t cap = 1024;
+    while (cap < 32 * runs && cap < ((size_t)1 << 26)) cap <<= 1;  // at most 1 GB of slots ...
+    while (cap < 2 * runs) cap <<= 1;                              // ... but never above load 0.5
+    LOCGPU_TRY(t.d_slots.alloc(cap));
+    LOCGPU_TRY(t.d_rec.alloc(n_rec));
+    t.cap = cap;
+    hipLaunchKernelGGL(ndt_fill_kernel<NdtSlot>, dim3((unsigned)((cap + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, t.d_slots.get(), cap, NdtSlot{kNdtEmpty, 0u, 0u});
+    return hipMemsetAsync(t.d_rec, 0, n_rec * sizeof(NdtRecord), s);  // record 0 is read for voxels that are not there: finite numbers, never accepted
 }
 
 hipError_t ndt_build(NdtTable& t, const float4* d_pts, size_t n, double voxel_size, int min_pts_in_voxel, hipStream_t s, bool* bad_key) {
@@ -73,20 +88,10 @@ hipError_t ndt_build(NdtTable& t, const float4* d_pts, size_t n, double voxel_si
     LOCGPU_TRY(hipStreamSynchronize(s));
     *bad_key = h_ctr[kIngBadKey] != 0;
     const size_t runs = (size_t)h_ctr[kIngRuns];
-    // A SPARSE table: at load 0.03 nearly every look-up — hit or miss — ends at its first probe, and a collision walk is what costs
-    // (a wave walks as long as its unluckiest lane, seven times per point); the lines a launch touches are as many as the voxels it
-    // looks up, whatever the table's size (measured: load <= 0.5, 15.7 ms per 256-scan step; load <= 0.03, see profiles/experiments.md).
-    size_t cap = 1024;
-    while (cap < 32 * runs && cap < ((size_t)1 << 26)) cap <<= 1;  // at most 1 GB of slots ...
-    while (cap < 2 * runs) cap <<= 1;                              // ... but never above load 0.5
-    LOCGPU_TRY(t.d_slots.alloc(cap));
-    LOCGPU_TRY(t.d_rec.alloc(std::max<size_t>(runs, 1)));  // room for every run; the kept voxels fill a prefix
-    t.cap = cap;
-    hipLaunchKernelGGL(ndt_fill_kernel<NdtSlot>, dim3((unsigned)((cap + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, t.d_slots.get(), cap, NdtSlot{kNdtEmpty, 0u, 0u});
-    LOCGPU_TRY(hipMemsetAsync(t.d_rec, 0, std::max<size_t>(runs, 1) * sizeof(NdtRecord), s));  // record 0 is read for voxels that are not there: finite numbers, never accepted
+    LOCGPU_TRY(ndt_table_alloc(t, runs, std::max<size_t>(runs, 1), s));  // room for every run; the kept voxels fill a prefix
     if (runs > 0 && !*bad_key)
         hipLaunchKernelGGL(ndt_voxel_kernel, dim3((unsigned)((runs + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, ing.skey, ing.psorted, ing.ustart, ing.ctr, min_pts_in_voxel,
-                           t.d_slots, t.d_rec, cap - 1, d_n_vox);
+                           t.d_slots, t.d_rec, t.cap - 1, d_n_vox);
     LOCGPU_TRY(hipGetLastError());
     LOCGPU_TRY(hipMemcpyAsync(h_ctr, ing.ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, s));
     LOCGPU_TRY(hipStreamSynchronize(s));
@@ -94,15 +99,17 @@ hipError_t ndt_build(NdtTable& t, const float4* d_pts, size_t n, double voxel_si
     return hipSuccess;
 }
 
-hipError_t ndt_dump(const NdtTable& t, int* keys, double* mu, double* info, size_t out_cap, hipStream_t s) {
-    const size_t n = std::min(out_cap, t.n_vox);
+hipError_t ndt_dump_range(const NdtTable& t, size_t first, size_t n, bool set_keys, int* keys, double* mu, double* info, hipStream_t s) {
     if (!t.d_rec || n == 0) return hipSuccess;
+    if (first + n > t.n_vox) return hipErrorInvalidValue;
     DevBuf<int> d_keys;
     DevBuf<double> d_mu, d_info;
     LOCGPU_TRY(d_keys.alloc(n * 3));
     LOCGPU_TRY(d_mu.alloc(n * 3));
     LOCGPU_TRY(d_info.alloc(n * 9));
-    hipLaunchKernelGGL(ndt_dump_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, t.d_rec, n, d_keys, d_mu, d_info);
+    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+    if (set_keys) hipLaunchKernelGGL(ndt_dump_kernel<NdtVoxelSet>, grid, dim3(kBlock), 0, s, t.d_rec.get() + first, n, d_keys, d_mu, d_info);
+    else hipLaunchKernelGGL(ndt_dump_kernel<NdtOneTarget>, grid, dim3(kBlock), 0, s, t.d_rec.get() + first, n, d_keys, d_mu, d_info);
     if (keys) LOCGPU_TRY(hipMemcpyAsync(keys, d_keys, n * 3 * sizeof(int), hipMemcpyDeviceToHost, s));
     if (mu) LOCGPU_TRY(hipMemcpyAsync(mu, d_mu, n * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
     if (info) LOCGPU_TRY(hipMemcpyAsync(info, d_info, n * 9 * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -110,21 +117,33 @@ hipError_t ndt_dump(const NdtTable& t, int* keys, double* mu, double* info, size
     return hipSuccess;
 }
 
+hipError_t ndt_dump(const NdtTable& t, int* keys, double* mu, double* info, size_t out_cap, hipStream_t s) {
+    return ndt_dump_range(t, 0, std::min(out_cap, t.n_vox), false, keys, mu, info, s);
+}
+
 // ---------------------------------------------------------------------------------------------
 // K5. Grid (ceil(max_n/256), n_scans).
 // The seven-voxel look-up below is written out in the kernel, and again in ndt_fitness_accum_kernel (ndt_fitness.hip: the same table
-// and hash) and in inc_accum_kernel (ndt_inc.hip: another table and hash). It is not a shared function on purpose: this kernel sits
-// at 126 VGPRs under the 128 that amdgpu_waves_per_eu(4,4) allows, with no scratch, and every shape of a shared __forceinline__
-// look-up that was tried (arrays by reference, a returned struct, a visitor, the slot look-up alone without the residual, an
-// always_inline lambda around the unchanged text) put 240-440 bytes per lane of scratch into it. Sharing the fitness kernel's copy
-// alone would leave two of three, so it stays too.
+// and hash). It is not a shared FUNCTION on purpose: this kernel sits at 126 VGPRs under the 128 that amdgpu_waves_per_eu(4,4)
+// allows, with no scratch, and every shape of a shared __forceinline__ look-up that was tried (arrays by reference, a returned
+// struct, a visitor, the slot look-up alone without the residual, an always_inline lambda around the unchanged text) put 240-440
+// bytes per lane of scratch into it. What IS shared is the kernel's text: the single-target look-up and the voxel set's (pairwise batch
+// NDT) are this one template over the key rule (ndt_kernels.hpp), and they differ in the block that forms the seven keys and nowhere
+// else — probe order, collision walk, record 0 for absent voxels, gate, sums and partial layout are written once, and each
+// instantiation compiles to the registers and instructions of a kernel written out for its rule (profiles/ndt_one_kernel_text.md).
+// A scan of a set reads the word of its target (pair_target[scan], uniform over the block) and forms its keys under that target's
+// bits; its range rule is given at the block.
+// inc_accum_kernel (ndt_inc.hip) stays a kernel of its own: another table layout, another hash, contracted arithmetic.
+template <class Rule>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LOCGPU_NDT_WAVES, LOCGPU_NDT_WAVES))) void ndt_accum_kernel(const NdtSlot* __restrict__ slots, const NdtRecord* __restrict__ rec, size_t cap_mask,
                                                            double inv_voxel, double res_th, int n_nearby, const float4* __restrict__ src,
                                                            const int* __restrict__ counts, const PoseState* __restrict__ st, int max_n,
                                                            double* __restrict__ partials, int pts, const int* __restrict__ active,
-                                                           const int* __restrict__ src_of) {
+                                                           const int* __restrict__ src_of, Rule rule) {
     const int scan = active ? active[blockIdx.y] : (int)blockIdx.y;
     if (st[scan].done) return;
+    unsigned long long tbits = 0;  // the set's rule: the key bits of this scan's target
+    if constexpr (std::is_same_v<Rule, NdtVoxelSet>) tbits = ndt_set_target_bits(rule.pair_target[scan]);
     double acc[28];
 #pragma unroll
     for (int v = 0; v < 28; ++v) acc[v] = 0.0;
@@ -150,17 +169,37 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LOCGPU_N
         unsigned int vx[7];
         size_t hs[7];
         bool found[7];
-        // the packed key is linear in the coordinates (ndt_pack): a face neighbour's key is the centre's ± one constant, and it is in
-        // range when the centre is and the one coordinate that moved still is
-        const bool centre_ok = ndt_key_in_range(kx, ky, kz);
-        const unsigned long long key0 = ndt_pack(centre_ok ? kx : 0, centre_ok ? ky : 0, centre_ok ? kz : 0);
+        if constexpr (std::is_same_v<Rule, NdtOneTarget>) {
+            // the packed key is linear in the coordinates (ndt_pack): a face neighbour's key is the centre's ± one constant, and it is in
+            // range when the centre is and the one coordinate that moved still is
+            const bool centre_ok = ndt_key_in_range(kx, ky, kz);
+            const unsigned long long key0 = ndt_pack(centre_ok ? kx : 0, centre_ok ? ky : 0, centre_ok ? kz : 0);
 #pragma unroll
-        for (int j = 0; j < 7; ++j) {
-            const int moved = ox[j] != 0 ? kx + ox[j] : (oy[j] != 0 ? ky + oy[j] : kz + oz[j]);  // j = 0: kz, in range with the centre
-            found[j] = j < n_nearby && centre_ok && moved > -kNdtBias && moved < kNdtBias;
-            const long long delta = (long long)ox[j] * (1ll << 42) + (long long)oy[j] * (1ll << 21) + (long long)oz[j];  // a constant after unrolling
-            key[j] = found[j] ? key0 + (unsigned long long)delta : key0;
-            hs[j] = ndt_hash32(key[j], cap_mask);
+            for (int j = 0; j < 7; ++j) {
+                const int moved = ox[j] != 0 ? kx + ox[j] : (oy[j] != 0 ? ky + oy[j] : kz + oz[j]);  // j = 0: kz, in range with the centre
+                found[j] = j < n_nearby && centre_ok && moved > -kNdtBias && moved < kNdtBias;
+                const long long delta = (long long)ox[j] * (1ll << 42) + (long long)oy[j] * (1ll << 21) + (long long)oz[j];  // a constant after unrolling
+                key[j] = found[j] ? key0 + (unsigned long long)delta : key0;
+                hs[j] = ndt_hash32(key[j], cap_mask);
+            }
+        } else {
+            // the set's key is linear in the coordinates and formed in signed arithmetic (ndt_set_pack): key0 + delta is the probed voxel's
+            // key whenever THAT voxel is in the set's range, wherever the centre lies within the ordinary range. So a probe is valid iff
+            // its OWN three coordinates are in the set's ±2^15 range and the centre is within the ordinary ±2^20 (the rule above). A
+            // voxel outside the set's range is in no target of the set, so a table of that target alone does not hold it either — but a
+            // query just outside whose face neighbour is inside must still probe that neighbour, as it does there.
+            const bool centre_ok = ndt_key_in_range(kx, ky, kz);
+            const bool okx = ndt_set_coord_ok(kx), oky = ndt_set_coord_ok(ky), okz = ndt_set_coord_ok(kz);
+            const unsigned long long key0 = ndt_set_pack(tbits, centre_ok ? kx : 0, centre_ok ? ky : 0, centre_ok ? kz : 0);
+#pragma unroll
+            for (int j = 0; j < 7; ++j) {
+                const int moved = ox[j] != 0 ? kx + ox[j] : (oy[j] != 0 ? ky + oy[j] : kz + oz[j]);  // j = 0: kz
+                const bool rest_ok = ox[j] != 0 ? (oky && okz) : (oy[j] != 0 ? (okx && okz) : (okx && oky));
+                found[j] = j < n_nearby && centre_ok && rest_ok && ndt_set_coord_ok(moved);
+                const unsigned long long delta = ndt_set_delta(ox[j], oy[j], oz[j]);  // a constant after unrolling
+                key[j] = found[j] ? key0 + delta : key0;
+                hs[j] = ndt_hash32(key[j], cap_mask);
+            }
         }
 #pragma unroll
         for (int j = 0; j < 7; ++j) { const NdtSlot sl = slots[hs[j]]; kk[j] = sl.key; vx[j] = sl.vid; }
@@ -248,13 +287,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LOCGPU_N
 }
 
 int launch_ndt_accum(const NdtTable* t, const float4* src, const int* counts, const PoseState* st, int max_n, int n_scans, double* partials,
-                     hipStream_t s, const int* active, int n_active, int split_scans, const int* src_of) {
+                     hipStream_t s, const int* active, int n_active, int split_scans, const int* src_of, const uint32_t* pair_target) {
     const int blocks = (max_n + kBlock - 1) / kBlock;
     const long total_blocks = (long)blocks * (split_scans > 0 ? split_scans : n_scans);  // the split — the order of the sums — never depends on `active`
     const int pts = total_blocks >= 8192 ? 8 : (total_blocks >= 4096 ? 4 : (total_blocks >= 2048 ? 2 : 1));
     dim3 grid((blocks + pts - 1) / pts, active ? n_active : n_scans);
-    hipLaunchKernelGGL(ndt_accum_kernel, grid, dim3(kBlock), 0, s, t->d_slots, t->d_rec, t->cap - 1, t->inv_voxel, t->res_outlier_th,
-                       t->n_nearby, src, counts, st, max_n, partials, pts, active, src_of);
+    if (pair_target)
+        hipLaunchKernelGGL(ndt_accum_kernel<NdtVoxelSet>, grid, dim3(kBlock), 0, s, t->d_slots, t->d_rec, t->cap - 1, t->inv_voxel, t->res_outlier_th,
+                           t->n_nearby, src, counts, st, max_n, partials, pts, active, src_of, NdtVoxelSet{pair_target});
+    else
+        hipLaunchKernelGGL(ndt_accum_kernel<NdtOneTarget>, grid, dim3(kBlock), 0, s, t->d_slots, t->d_rec, t->cap - 1, t->inv_voxel, t->res_outlier_th,
+                           t->n_nearby, src, counts, st, max_n, partials, pts, active, src_of, NdtOneTarget{});
     return (int)grid.x;  // partial blocks per scan
 }
 

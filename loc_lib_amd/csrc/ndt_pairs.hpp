@@ -1,5 +1,6 @@
-// loc_lib_amd/csrc/ndt_pairs.hpp — pairwise batch NDT: a voxel SET target and the kernels that look a scan up in its own grid of it
-// (include/locgpu.h, "Pairwise batch NDT").
+// loc_lib_amd/csrc/ndt_pairs.hpp — pairwise batch NDT: the build of a voxel SET target (include/locgpu.h, "Pairwise batch NDT";
+// DESIGN.md §23). A scan is looked up in its own grid of the set by launch_ndt_accum / launch_ndt_fitness with pair_target
+// (ndt_kernels.hpp).
 //
 // A set of n targets is ONE NdtTable in the layout of ndt_kernels.hpp — 16-byte slots, open addressing, dense 128-byte records — whose
 // 64-bit keys carry the target's index above the voxel (ndt_set_key.hpp: target:16 | x:16 | y:16 | z:16), so a scan's look-up in its
@@ -29,12 +30,5 @@ hipError_t ndt_set_build(NdtTable& t, const float4* d_pts, size_t scan_stride, c
                          std::vector<NdtSetTarget>& info, int* bad_target);
 // Test read-back: records [first, first + n) as dense arrays (keys n×3 int32 without the target, mu n×3, info n×9), in key order.
 hipError_t ndt_set_dump(const NdtTable& t, size_t first, size_t n, int* keys, double* mu, double* info, hipStream_t s);
-
-// launch_ndt_accum / launch_ndt_fitness (ndt_kernels.hpp) with scan i looked up under target pair_target[i] of the set (a device
-// array of n_scans words, locgpu_batch::d_pair_base). Same grids, same split of the sums, same partial layout.
-int launch_ndt_accum_pairs(const NdtTable* t, const uint32_t* pair_target, const float4* src, const int* counts, const PoseState* st, int max_n, int n_scans,
-                           double* partials, hipStream_t s, const int* active = nullptr, int n_active = 0, int split_scans = 0, const int* src_of = nullptr);
-void launch_ndt_fitness_pairs(const NdtTable* t, const uint32_t* pair_target, const float4* src, const int* counts, const PoseState* st, int max_n, int n_scans,
-                              double* partials, double* out, hipStream_t s, const int* src_of = nullptr);
 
 }  // namespace locgpu
