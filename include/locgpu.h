@@ -594,6 +594,35 @@ LOCGPU_API int locgpu_debug_batch_run_flags(locgpu_ctx* ctx, locgpu_batch* batch
  * over four batches) still has every alignment in flight on a stream of its own. Before the first alignment: the stream the batch was
  * dealt when it was created. -1 for NULL. */
 LOCGPU_API int locgpu_debug_batch_slot(const locgpu_batch* batch);
+/* Test hooks: the SOLVE stage that ends every Gauss-Newton iteration, on normal equations the caller chooses — the production
+ * launchers of gn_solve_kernel, sum_partials_kernel and loam_solve_kernel (csrc/icp_fit.hip), not copies: the fixed-order sum of the
+ * block partials, the 6×6 pivoted LU, the accept / abort rules (ICP: icp_registration.cpp:204-211, 362-375, "/16" for P2P :287; direct
+ * NDT tests det(H) == 0 first and ends the alignment, ndt_registration.cpp:435-459; incremental NDT tests effective_num alone,
+ * ndt_registration.cpp:349-353; LOAM: each class by its own count and det, surface first, then the sum, loam_registration.cpp:47-90),
+ * the SE3 update with the refresh of R, and the stop tests. Both calls block, own their device memory for the call and touch neither
+ * the context's targets nor any batch.
+ *   partials   host, the kernels' own layout [n_scans][blocks_per_scan][32] doubles: 21 H (upper triangle, row by row), 6 B,
+ *              effective_num, 4 spare (never read)
+ *   method     a locgpu_icp_method, or 3 = direct NDT, 4 = incremental NDT (the values the library uses inside)
+ *   state_in / state_out   n_scans rows of 160 bytes, the whole per-scan state: double q[4] (x y z w) at byte 0, double t[3] at 32,
+ *              double R[9] (row-major) at 56, double last_dx_norm at 128, int64 last_eff at 136, then int32 iterations (144),
+ *              converged (148), done (152), status (156; 0 ok, 1 direct NDT det(H) == 0, 2 incremental NDT too few, 3 / 4 LOAM surface /
+ *              edge class false). state_in seeds every row; state_out receives every row as the kernels left it.
+ *   do_update  0: H/B evaluation only (hb and last_eff are written)
+ *   two_stage  1: the route of a sharded batch — launch_sum_partials (first = 0, n_local = n_scans) into one row per scan, then the
+ *              solve on those rows with blocks_per_scan = 1
+ *   scans / n_launch   optional (NULL: every scan): the scan pool's indirection — n_launch blocks, block i solves scan scans[i]
+ *   hb_out     n_scans × 44 doubles = H36, B6, effective_num, ok (LOAM: n_scans × 46 = H36 and B6 of the SUM, effective_num[2], ok[2]);
+ *              read first: rows no block writes (finished or unlisted scans) come back as they went in
+ * locgpu_debug_loam_solve: NULL partials = the class is switched off (not both). LOCGPU_ERR_INVALID, and nothing is launched, for a
+ * NULL argument, n_scans outside [1, 1024], blocks_per_scan outside [1, 4096], an unknown method, a scans entry out of range or listed
+ * twice. (The rules restated: icp_registration.cpp:204-211, 362-375; ndt_registration.cpp:349-353, 435-459; loam_registration.cpp:47-90.) */
+LOCGPU_API int locgpu_debug_gn_solve(locgpu_ctx* ctx, const double* partials, int n_scans, int blocks_per_scan, int method, int min_effective_pts,
+                                     double eps, int max_iteration, int do_update, int two_stage, const int* scans, int n_launch,
+                                     const void* state_in, void* state_out, double* hb_out);
+LOCGPU_API int locgpu_debug_loam_solve(locgpu_ctx* ctx, const double* partials_surf, int blocks_surf, const double* partials_edge, int blocks_edge,
+                                       int n_scans, const int min_effective_pts[2], double eps, int max_iteration, int do_update,
+                                       const void* state_in, void* state_out, double* hb_out);
 
 /* =====================================================================================================================
  * Clouds resident in HBM and the filters either side of the matcher.

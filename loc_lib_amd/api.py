@@ -21,6 +21,14 @@ P2PLANE_MAP = 5  # labelled fast mode: planes fitted once per map point at inges
 SEARCH_TREE_FAITHFUL, SEARCH_GRID_EXACT = 0, 1
 CENTER, NEARBY6 = 0, 1
 DIRECT_NDT, INCREMENTAL_NDT = 1, 2
+# The `method` of the Gauss–Newton solve stage for the two NDT variants (csrc/icp_kernels.hpp: kMethodNdtDirect, kMethodNdtInc — the
+# values locgpu_icp_method leaves free); Context.debug_gn_solve takes them beside P2P, P2LINE, P2PLANE and P2PLANE_MAP.
+SOLVE_NDT_DIRECT, SOLVE_NDT_INC = 3, 4
+ACC_W, HB_W, LOAM_HB_W = 32, 44, 46  # doubles per block partial (21 H, 6 B, effective_num, 4 spare) / per hb row of the solve / of the LOAM solve
+# One row of state_in / state_out of the solve-stage test hooks: the library's per-scan state, 160 bytes (include/locgpu.h).
+SOLVE_STATE = np.dtype([("q", "<f8", (4,)), ("t", "<f8", (3,)), ("R", "<f8", (9,)), ("last_dx_norm", "<f8"), ("last_eff", "<i8"),
+                        ("iterations", "<i4"), ("converged", "<i4"), ("done", "<i4"), ("status", "<i4")])
+assert SOLVE_STATE.itemsize == 160
 
 # every symbol include/locgpu.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -30,6 +38,7 @@ ABI_SYMBOLS = [
     "locgpu_icp_hb_batch", "locgpu_gn_update", "locgpu_ndt_set_target", "locgpu_ndt_target_info", "locgpu_ndt_dump",
     "locgpu_ndt_align", "locgpu_profile_enable", "locgpu_profile_read", "locgpu_visit_count_enable", "locgpu_visit_count_read",
     "locgpu_search_stats_read", "locgpu_debug_batch_nn", "locgpu_debug_batch_run_flags", "locgpu_debug_batch_slot", "locgpu_graph_enable",
+    "locgpu_debug_gn_solve", "locgpu_debug_loam_solve",
     "locgpu_cloud_create", "locgpu_cloud_destroy", "locgpu_cloud_upload", "locgpu_cloud_info", "locgpu_cloud_download", "locgpu_cloud_copy",
     "locgpu_cloud_remove_nan", "locgpu_cloud_voxel_filter", "locgpu_cloud_crop_box", "locgpu_cloud_transform", "locgpu_cloud_append",
     "locgpu_icp_set_target_cloud", "locgpu_icp_set_target_cloud_async", "locgpu_ndt_set_target_cloud", "locgpu_icp_align_cloud", "locgpu_ndt_align_cloud",
@@ -213,6 +222,8 @@ def lib():
             "locgpu_profile_enable": (i32, [vp, i32]), "locgpu_profile_read": (i32, [vp, vp, i32]),
             "locgpu_visit_count_enable": (i32, [vp, i32]), "locgpu_visit_count_read": (i32, [vp, vp, i32]),
             "locgpu_search_stats_read": (i32, [vp, vp, i32]), "locgpu_debug_batch_nn": (i32, [vp, vp, i32, vp]), "locgpu_debug_batch_run_flags": (i32, [vp, vp, vp, vp]), "locgpu_debug_batch_slot": (i32, [vp]), "locgpu_graph_enable": (i32, [vp, i32]),
+            "locgpu_debug_gn_solve": (i32, [vp, vp, i32, i32, i32, i32, dbl, i32, i32, i32, vp, i32, vp, vp, vp]),
+            "locgpu_debug_loam_solve": (i32, [vp, vp, i32, vp, i32, i32, vp, dbl, i32, i32, vp, vp, vp]),
             "locgpu_cloud_create": (i32, [vp, vp]), "locgpu_cloud_destroy": (None, [vp]),
             "locgpu_cloud_upload": (i32, [vp, vp, sz, sz, sz, i32]), "locgpu_cloud_info": (i32, [vp, vp, vp]),
             "locgpu_cloud_download": (i32, [vp, vp, sz, sz, sz]), "locgpu_cloud_copy": (i32, [vp, vp]),
@@ -956,6 +967,44 @@ class Context:
         written = ctypes.c_int(0)
         self._check(lib().locgpu_debug_batch_run_flags(self._h, batch._h, out.ctypes.data, ctypes.byref(written)))
         return out, bool(written.value)
+
+    def debug_gn_solve(self, partials, state, method, min_effective_pts=10, eps=1e-2, max_iteration=20, do_update=True, two_stage=False,
+                       scans=None, hb=None):
+        """The production solve stage on chosen block partials (locgpu_debug_gn_solve). partials [n_scans, blocks_per_scan, ACC_W] float64,
+        state [n_scans] SOLVE_STATE, scans: optional list — block i solves scan scans[i]; hb: optional [n_scans, HB_W] start contents (rows
+        no block writes come back unchanged; default NaN). Returns (state_out [n_scans] SOLVE_STATE, hb [n_scans, HB_W])."""
+        p = np.ascontiguousarray(partials, dtype=np.float64)
+        if p.ndim != 3 or p.shape[2] != ACC_W:
+            raise ValueError("partials must be [n_scans, blocks_per_scan, %d]" % ACC_W)
+        n, blocks = p.shape[0], p.shape[1]
+        st_in = np.ascontiguousarray(state, dtype=SOLVE_STATE).reshape(n)
+        st_out = np.zeros(n, dtype=SOLVE_STATE)
+        hb_out = np.full((n, HB_W), np.nan) if hb is None else np.array(hb, dtype=np.float64, copy=True).reshape(n, HB_W)
+        sc = None if scans is None else np.ascontiguousarray(scans, dtype=np.int32)
+        self._check(lib().locgpu_debug_gn_solve(self._h, p.ctypes.data, n, blocks, int(method), int(min_effective_pts), float(eps), int(max_iteration),
+                                                int(bool(do_update)), int(bool(two_stage)), None if sc is None else sc.ctypes.data,
+                                                0 if sc is None else len(sc), st_in.ctypes.data, st_out.ctypes.data, hb_out.ctypes.data))
+        return st_out, hb_out
+
+    def debug_loam_solve(self, partials_surf, partials_edge, state, min_effective_pts=(10, 10), eps=1e-3, max_iteration=20, do_update=True, hb=None):
+        """The production LOAM solve on chosen block partials of the two classes (locgpu_debug_loam_solve); None switches a class off.
+        Returns (state_out [n_scans] SOLVE_STATE, hb [n_scans, LOAM_HB_W])."""
+        parts = [None if p is None else np.ascontiguousarray(p, dtype=np.float64) for p in (partials_surf, partials_edge)]
+        for p in parts:
+            if p is not None and (p.ndim != 3 or p.shape[2] != ACC_W):
+                raise ValueError("partials must be [n_scans, blocks_per_scan, %d]" % ACC_W)
+        n = len(state)
+        if any(p is not None and p.shape[0] != n for p in parts):
+            raise ValueError("every class needs a row set per scan")
+        st_in = np.ascontiguousarray(state, dtype=SOLVE_STATE).reshape(n)
+        st_out = np.zeros(n, dtype=SOLVE_STATE)
+        hb_out = np.full((n, LOAM_HB_W), np.nan) if hb is None else np.array(hb, dtype=np.float64, copy=True).reshape(n, LOAM_HB_W)
+        mins = np.ascontiguousarray(min_effective_pts, dtype=np.int32).reshape(2)
+        self._check(lib().locgpu_debug_loam_solve(self._h, None if parts[0] is None else parts[0].ctypes.data, 0 if parts[0] is None else parts[0].shape[1],
+                                                  None if parts[1] is None else parts[1].ctypes.data, 0 if parts[1] is None else parts[1].shape[1], n,
+                                                  mins.ctypes.data, float(eps), int(max_iteration), int(bool(do_update)), st_in.ctypes.data,
+                                                  st_out.ctypes.data, hb_out.ctypes.data))
+        return st_out, hb_out
 
     def search_stats_read(self, reset=True):
         out = np.zeros(4, dtype=np.uint64)

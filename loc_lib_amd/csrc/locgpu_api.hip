@@ -56,6 +56,43 @@ void locgpu::free_batch(locgpu_batch* b) {
     delete b;
 }
 
+// The two solve-stage test hooks: caller-chosen block partials through the production launchers (launch_gn_solve, launch_sum_partials,
+// launch_loam_solve) on buffers that live for the call. A state row is a PoseState, byte for byte (the header documents the offsets).
+static_assert(sizeof(PoseState) == 160 && offsetof(PoseState, t) == 32 && offsetof(PoseState, R) == 56 && offsetof(PoseState, last_dx_norm) == 128 &&
+                  offsetof(PoseState, last_eff) == 136 && offsetof(PoseState, iterations) == 144 && offsetof(PoseState, converged) == 148 &&
+                  offsetof(PoseState, done) == 152 && offsetof(PoseState, status) == 156,
+              "the state row of locgpu_debug_gn_solve / locgpu_debug_loam_solve (include/locgpu.h) is PoseState");
+constexpr int kDebugMaxScans = 1024, kDebugMaxBlocks = 4096;
+
+// upload → `launch` on the context's stream → state and hb back; the stream is synchronised before the buffers die, whatever failed
+template <typename Launch>
+static int debug_solve_run(locgpu_ctx* ctx, const double* const partials[2], const int blocks[2], int n_scans, const int* scans, int n_launch, bool want_acc,
+                           const void* state_in, void* state_out, double* hb_out, int hb_w, Launch launch) {
+    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    DevBuf<double> d_part[2], d_acc, d_hb;
+    DevBuf<PoseState> d_st;
+    DevBuf<int> d_scans;
+    const size_t st_bytes = (size_t)n_scans * sizeof(PoseState), hb_bytes = (size_t)n_scans * hb_w * sizeof(double);
+    bool ok = hip_ok(ctx, d_st.alloc(n_scans), "hipMalloc state") && hip_ok(ctx, d_hb.alloc((size_t)n_scans * hb_w), "hipMalloc hb") &&
+              (!want_acc || hip_ok(ctx, d_acc.alloc((size_t)n_scans * kAccW), "hipMalloc acc")) && (!scans || hip_ok(ctx, d_scans.alloc(n_launch), "hipMalloc scans"));
+    for (int c = 0; ok && c < 2; ++c)
+        if (partials[c]) ok = hip_ok(ctx, d_part[c].alloc((size_t)n_scans * blocks[c] * kAccW), "hipMalloc partials");
+    if (!ok) return LOCGPU_ERR_OOM;
+    for (int c = 0; ok && c < 2; ++c)
+        if (partials[c]) ok = hip_ok(ctx, hipMemcpyAsync(d_part[c], partials[c], (size_t)n_scans * blocks[c] * kAccW * sizeof(double), hipMemcpyHostToDevice, s), "H2D partials");
+    ok = ok && hip_ok(ctx, hipMemcpyAsync(d_st, state_in, st_bytes, hipMemcpyHostToDevice, s), "H2D state") &&
+         hip_ok(ctx, hipMemcpyAsync(d_hb, hb_out, hb_bytes, hipMemcpyHostToDevice, s), "H2D hb") &&  // rows no block writes come back as they went in
+         (!scans || hip_ok(ctx, hipMemcpyAsync(d_scans, scans, (size_t)n_launch * sizeof(int), hipMemcpyHostToDevice, s), "H2D scans"));
+    if (ok) {
+        launch(d_part[0].get(), d_part[1].get(), d_st.get(), d_acc.get(), d_hb.get(), scans ? d_scans.get() : nullptr, s);
+        ok = hip_ok(ctx, hipGetLastError(), "debug solve launch") && hip_ok(ctx, hipMemcpyAsync(state_out, d_st, st_bytes, hipMemcpyDeviceToHost, s), "D2H state") &&
+             hip_ok(ctx, hipMemcpyAsync(hb_out, d_hb, hb_bytes, hipMemcpyDeviceToHost, s), "D2H hb");
+    }
+    if (!hip_ok(ctx, hipStreamSynchronize(s), "debug solve sync")) ok = false;
+    return ok ? LOCGPU_OK : LOCGPU_ERR_NO_DEVICE;
+}
+
 extern "C" {
 
 void locgpu_icp_opts_default(locgpu_icp_opts* o) {
@@ -576,6 +613,65 @@ int locgpu_debug_batch_run_flags(locgpu_ctx* ctx, locgpu_batch* b, uint64_t* out
     return LOCGPU_OK;
 }
 
+int locgpu_debug_gn_solve(locgpu_ctx* ctx, const double* partials, int n_scans, int blocks_per_scan, int method, int min_effective_pts, double eps,
+                          int max_iteration, int do_update, int two_stage, const int* scans, int n_launch, const void* state_in, void* state_out, double* hb_out) {
+    if (!ctx) return LOCGPU_ERR_INVALID;
+    if (!partials || !state_in || !state_out || !hb_out) return fail(ctx, LOCGPU_ERR_INVALID, "debug_gn_solve: NULL argument");
+    if (n_scans < 1 || n_scans > kDebugMaxScans || blocks_per_scan < 1 || blocks_per_scan > kDebugMaxBlocks)
+        return fail(ctx, LOCGPU_ERR_INVALID, "debug_gn_solve: n_scans outside [1, 1024] or blocks_per_scan outside [1, 4096]");
+    if (!(method == LOCGPU_P2P || method == LOCGPU_P2LINE || method == LOCGPU_P2PLANE || method == LOCGPU_P2PLANE_MAP || method_is_ndt(method)))
+        return fail(ctx, LOCGPU_ERR_INVALID, "debug_gn_solve: unknown method");
+    if (scans) {
+        if (n_launch < 1 || n_launch > n_scans) return fail(ctx, LOCGPU_ERR_INVALID, "debug_gn_solve: n_launch outside [1, n_scans]");
+        std::vector<char> seen(n_scans, 0);
+        for (int i = 0; i < n_launch; ++i) {  // two blocks on one scan would race on its state
+            if (scans[i] < 0 || scans[i] >= n_scans || seen[scans[i]]) return fail(ctx, LOCGPU_ERR_INVALID, "debug_gn_solve: a scans entry is out of range or listed twice");
+            seen[scans[i]] = 1;
+        }
+    }
+    GnParams prm{};
+    prm.method = method;
+    prm.max_iteration = max_iteration;
+    prm.min_effective_pts = min_effective_pts;
+    prm.eps = eps;
+    const double* const parts[2] = {partials, nullptr};
+    const int blocks[2] = {blocks_per_scan, 0};
+    const int n_solve = scans ? n_launch : n_scans;
+    return debug_solve_run(ctx, parts, blocks, n_scans, scans, n_solve, two_stage != 0, state_in, state_out, hb_out, 44,
+                           [&](const double* d_part, const double*, PoseState* d_st, double* d_acc, double* d_hb, const int* d_scans, hipStream_t s) {
+                               if (two_stage) {  // the sharded route: every scan's sum as a one-row partial, then the solve on those rows
+                                   launch_sum_partials(d_part, blocks_per_scan, d_st, 0, n_scans, n_scans, d_acc, s);
+                                   launch_gn_solve(d_acc, 1, d_st, n_solve, prm, do_update, d_hb, nullptr, s, d_scans);
+                               } else {
+                                   launch_gn_solve(d_part, blocks_per_scan, d_st, n_solve, prm, do_update, d_hb, nullptr, s, d_scans);
+                               }
+                           });
+}
+
+int locgpu_debug_loam_solve(locgpu_ctx* ctx, const double* partials_surf, int blocks_surf, const double* partials_edge, int blocks_edge, int n_scans,
+                            const int min_effective_pts[2], double eps, int max_iteration, int do_update, const void* state_in, void* state_out, double* hb_out) {
+    if (!ctx) return LOCGPU_ERR_INVALID;
+    if ((!partials_surf && !partials_edge) || !min_effective_pts || !state_in || !state_out || !hb_out) return fail(ctx, LOCGPU_ERR_INVALID, "debug_loam_solve: NULL argument");
+    if (n_scans < 1 || n_scans > kDebugMaxScans || (partials_surf && (blocks_surf < 1 || blocks_surf > kDebugMaxBlocks)) ||
+        (partials_edge && (blocks_edge < 1 || blocks_edge > kDebugMaxBlocks)))
+        return fail(ctx, LOCGPU_ERR_INVALID, "debug_loam_solve: n_scans outside [1, 1024] or a class's blocks outside [1, 4096]");
+    const double* const parts[2] = {partials_surf, partials_edge};
+    const int blocks[2] = {partials_surf ? blocks_surf : 0, partials_edge ? blocks_edge : 0};
+    return debug_solve_run(ctx, parts, blocks, n_scans, nullptr, n_scans, false, state_in, state_out, hb_out, kLoamHbW,
+                           [&](const double* d_surf, const double* d_edge, PoseState* d_st, double*, double* d_hb, const int*, hipStream_t s) {
+                               LoamSolveArgs a{};
+                               a.partials[0] = d_surf; a.partials[1] = d_edge;
+                               for (int c = 0; c < 2; ++c) { a.blocks_per_scan[c] = blocks[c]; a.min_effective_pts[c] = min_effective_pts[c]; a.list_counts[c] = nullptr; }
+                               a.max_iteration = max_iteration;
+                               a.eps = eps;
+                               a.st = d_st;
+                               a.do_update = do_update;
+                               a.hb_out = d_hb;
+                               a.scans = nullptr;
+                               launch_loam_solve(a, n_scans, s);
+                           });
+}
+
 int locgpu_icp_hb(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double pose[7], const locgpu_icp_opts* opts, double H[36],
                   double B[6], int64_t* effective_num, int* ok) {
     AlignSpec spec;
@@ -647,8 +743,9 @@ int locgpu_gn_update(const double hb[44], int method, int min_effective_pts, dou
     if (method == LOCGPU_P2P)
         for (int i = 0; i < 6; ++i) dx[i] = dx[i] / 16;
     se3_apply_update(pose, pose + 4, dx);
-    double n2 = 0.0;
-    for (int i = 0; i < 6; ++i) n2 += dx[i] * dx[i];
+    // dx.norm() in the association of gn_solve_kernel and of the reference's binary (icp_fit.hip, gn_update): summed left to
+    // right the square can differ in its last bit, and with it a stop decision that falls on eps
+    const double n2 = (dx[0] * dx[0] + (dx[2] * dx[2] + dx[4] * dx[4])) + (dx[1] * dx[1] + (dx[3] * dx[3] + dx[5] * dx[5]));
     if (applied) *applied = 1;
     if (stop) *stop = std::sqrt(n2) < eps;
     return LOCGPU_OK;
