@@ -1345,6 +1345,45 @@ LOCGPU_API int locgpu_ndt_align_pairs(locgpu_ctx* ctx, locgpu_batch* batch, cons
  * after each ScanMatch of test_node.cpp:317-374. target_of[i] == -1: {+inf, 0, 0}. Refusals as locgpu_ndt_align_pairs. */
 LOCGPU_API int locgpu_ndt_fitness_pairs(locgpu_ctx* ctx, locgpu_batch* batch, const int* target_of, const double* poses, locgpu_fitness* out);
 
+/* =====================================================================================================================
+ * ---- The ICP target's KD-trees built on the device (csrc/forest_build.hip, csrc/forest_plan.hpp).
+ *
+ * SetInputTarget (icp_registration.cpp:9-29) builds the mean-split tree of kdtree.cpp:10-31 / :58-94 / :96-123, whose thresholds are
+ * float32 sums in index order (math_utils.h:35-47). The calls above build it on the host, so a resident target crosses PCIe twice.
+ * The calls of this block build the SAME trees — slot for slot, and for a forest the same array byte for byte, pads and sentinel
+ * leaves included — in HBM: one workgroup per tree, level by level, every node's sum a serial chain in the reference's order, nodes,
+ * trees and coordinates side by side. Nothing crosses PCIe but a table per tree down and the per-tree depths and flags up.
+ *
+ * A tree with a degenerate split (every point of a node on one side: duplicate points, NaNs; kdtree.cpp:66-70) cannot be placed
+ * top-down. The kernel only finds that out; the WHOLE call then takes the host path of the matching call above (same result by
+ * construction), and locgpu_icp_device_build_info says so. A refused call — LOCGPU_ERR_DEPTH included — leaves the context exactly as
+ * it was: the trees are built beside the context's target and swapped in on success.
+ *
+ * Opt-in: no other entry point builds on the device. Not covered: LOAM handles, the C++ facade, asynchronous and broadcast forms,
+ * scan pools, sharded and shared-source batches, bench.py.
+ * ===================================================================================================================== */
+
+/* locgpu_icp_set_target_forest_batch (SetInputTarget of every scan of a resident plain batch, icp_registration.cpp:9-29; the last_cloud of
+ * test_node.cpp:256-315) with the trees built on the device. Accepts and refuses exactly what that call does and leaves the same context
+ * state: the forest's bytes, locgpu_icp_forest_info, locgpu_icp_target_info, the search kernels' `bounded` choice. Blocking. */
+LOCGPU_API int locgpu_icp_set_target_forest_device(locgpu_ctx* ctx, const locgpu_batch* batch);
+/* locgpu_icp_set_target_cloud (SetInputTarget, icp_registration.cpp:9-29; the keyframe local map of lio.cpp:296-305) with the tree built on
+ * the device: a forest of one tree installed as an ORDINARY target, its leaf-slot list and sentinel leaf included. Blocking. Refused: a
+ * NULL cloud, a cloud of another context, an empty cloud; LOCGPU_ERR_DEPTH for a tree deeper than 64 levels. */
+LOCGPU_API int locgpu_icp_set_target_cloud_device(locgpu_ctx* ctx, const locgpu_cloud* target);
+/* What the last of the two calls above did on this context (kdtree.cpp:58-94 is what both paths build). out[0]: 0 no such call yet, 1 the
+ * device build, 2 the host path after a degenerate split; out[1]: index of the first degenerate tree of the last device build, or -1;
+ * out[2]: levels the kernel split (the deepest tree's depth - 1); out[3]: points per tile of the cooperative path; out[4]: the node
+ * length up to which one lane splits a node (longer nodes take the cooperative path); out[5]: threads per workgroup (one workgroup a
+ * tree); out[6]: 1 a forest, 2 a single cloud; out[7]: 1 when the context's CURRENT target, however it was built, lets the fast
+ * search kernel run (every float finite and below 1e18). */
+LOCGPU_API int locgpu_icp_device_build_info(const locgpu_ctx* ctx, int64_t out[8]);
+/* Test read-back of the packed tree or forest as it stands in HBM after ANY locgpu_icp_set_target* call (kdtree.cpp:10-31's tree in the
+ * layout of csrc/kdtree_build.cpp): slots[0 .. min(cap, S + 2)) with S = locgpu_icp_target_info's bytes / 8, i.e. every segment, pad
+ * and sentinel leaf up to the last sentinel leaf; for an ORDINARY target also leaf_slots[0 .. min(leaf_cap, leaves)), the slot of every
+ * leaf in preorder (a forest keeps none: the array is left alone). Either array may be NULL. */
+LOCGPU_API int locgpu_debug_tree_read(locgpu_ctx* ctx, uint64_t* slots, size_t cap, uint32_t* leaf_slots, size_t leaf_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,7 +73,9 @@ ABI_SYMBOLS = [
     "locgpu_batch_keep_times", "locgpu_batch_download_times", "locgpu_batch_deskew", "locgpu_batch_deskew_times", "locgpu_motion_from_poses",
     "locgpu_icp_set_target_forest", "locgpu_icp_set_target_forest_batch", "locgpu_icp_forest_info", "locgpu_icp_align_pairs", "locgpu_icp_fitness_pairs",
     "locgpu_ndt_set_target_set", "locgpu_ndt_set_target_set_batch", "locgpu_ndt_set_info", "locgpu_ndt_set_dump", "locgpu_ndt_align_pairs", "locgpu_ndt_fitness_pairs",
+    "locgpu_icp_set_target_forest_device", "locgpu_icp_set_target_cloud_device", "locgpu_icp_device_build_info", "locgpu_debug_tree_read",
 ]
+BUILD_PATH_NONE, BUILD_PATH_DEVICE, BUILD_PATH_HOST = 0, 1, 2  # locgpu_icp_device_build_info: out[0]
 STATUS_NO_PAIR_TARGET = 5  # LOCGPU_STATUS_NO_PAIR_TARGET
 COMM_ID_BYTES = 128
 NO_INTENSITY = ctypes.c_size_t(-1).value
@@ -304,6 +306,8 @@ def lib():
             "locgpu_ndt_set_target_set": (i32, [vp, vp, vp, i32, sz, vp]), "locgpu_ndt_set_target_set_batch": (i32, [vp, vp, vp]),
             "locgpu_ndt_set_info": (i32, [vp, vp, vp, vp]), "locgpu_ndt_set_dump": (i32, [vp, i32, vp, vp, vp, sz, vp]),
             "locgpu_ndt_align_pairs": (i32, [vp, vp, vp, vp, vp, vp]), "locgpu_ndt_fitness_pairs": (i32, [vp, vp, vp, vp, vp]),
+            "locgpu_icp_set_target_forest_device": (i32, [vp, vp]), "locgpu_icp_set_target_cloud_device": (i32, [vp, vp]),
+            "locgpu_icp_device_build_info": (i32, [vp, vp]), "locgpu_debug_tree_read": (i32, [vp, vp, sz, vp, sz]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -451,6 +455,34 @@ class Context:
         """Target j = scan j of the resident plain batch (locgpu_icp_set_target_forest_batch)."""
         batch.upload_wait()
         self._check(lib().locgpu_icp_set_target_forest_batch(self._h, batch._h))
+
+    def icp_set_target_forest_device(self, batch):
+        """icp_set_target_forest_batch with the trees built on the device (locgpu_icp_set_target_forest_device)."""
+        batch.upload_wait()
+        self._check(lib().locgpu_icp_set_target_forest_device(self._h, batch._h))
+
+    def icp_set_target_cloud_device(self, cloud):
+        """icp_set_target_cloud with the tree built on the device (locgpu_icp_set_target_cloud_device)."""
+        self._check(lib().locgpu_icp_set_target_cloud_device(self._h, cloud._h))
+
+    def icp_device_build_info(self):
+        """dict(path, first_degenerate, levels, tile, lane_len, threads, kind, bounded) — locgpu_icp_device_build_info."""
+        out = np.zeros(8, dtype=np.int64)
+        self._check(lib().locgpu_icp_device_build_info(self._h, out.ctypes.data))
+        return dict(path=int(out[0]), first_degenerate=int(out[1]), levels=int(out[2]), tile=int(out[3]), lane_len=int(out[4]), threads=int(out[5]),
+                    kind=int(out[6]), bounded=bool(out[7]))
+
+    def debug_tree_read(self):
+        """(slots uint64 [S + 2], leaf_slots uint32 [leaves] or None for a forest): the packed target as it stands in HBM, sentinel
+        leaves and pads included (locgpu_debug_tree_read)."""
+        info = np.zeros(4, dtype=np.int64)
+        self._check(lib().locgpu_icp_target_info(self._h, info.ctypes.data))
+        slots = np.zeros(int(info[3]) // 8 + 2, dtype=np.uint64)
+        n = ctypes.c_int(0)
+        forest = lib().locgpu_icp_forest_info(self._h, ctypes.byref(n), None, None) == 0
+        leaves = None if forest else np.zeros(int(info[0]), dtype=np.uint32)
+        self._check(lib().locgpu_debug_tree_read(self._h, slots.ctypes.data, slots.size, None if forest else leaves.ctypes.data, 0 if forest else leaves.size))
+        return slots, leaves
 
     def icp_forest_info(self):
         """dict(n_targets, leaves [n], depth [n]) of the forest target (locgpu_icp_forest_info)."""

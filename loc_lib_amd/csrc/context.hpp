@@ -25,6 +25,7 @@ struct MergeScratch;        // cloud_merge.hip
 struct RangeIngestScratch;  // range_ingest.hip
 struct RecordIngestScratch;  // record_ingest.hip
 struct ResidentDeskewScratch;  // resident_deskew.hip
+struct ForestBuildScratch;  // forest_build.hpp
 }  // namespace locgpu
 struct locgpu_sensor;  // range_ingest.hpp
 
@@ -98,6 +99,7 @@ struct locgpu_ctx {
     std::vector<size_t> forest_leaves;
     std::vector<int> forest_depth;
     locgpu::DevBuf<uint32_t> d_forest_base;  // grow-only: the device table of the bases
+    locgpu::ForestBuildScratch* fbuild = nullptr;  // the device tree build's scratch, the tree it builds beside d_tree, and its report (forest_build.hip)
 
     // LOCGPU_P2PLANE_MAP: one plane per leaf, row slot >> 1 = four doubles, NaNs = none (map_planes.hip). Built on first use or by
     // locgpu_icp_build_map_planes, dropped (planes_ready) by every set_target; the buffers are grow-only.
@@ -274,6 +276,10 @@ int refuse_forest(locgpu_ctx* ctx, const char* who);
 // icp_target.hip
 int target_join(locgpu_ctx* ctx, bool install = true);  // finishes a pending locgpu_icp_set_target_cloud_async (no-op without one)
 void free_target_scratch(locgpu_ctx* ctx);              // the ingest buffers the context keeps between SetInputTarget calls
+// meta = {slots, leaves, nodes, points, depth, bounded}: waits for the readers of the old target, makes room in d_tree / d_leaf_slots
+// and sets the context's description of an ORDINARY target (forest_n = 0); the caller fills the arrays
+int install_tree_meta(locgpu_ctx* ctx, const long long meta[6]);
+void forest_build_free(locgpu_ctx* ctx);                // forest_build.hip: the device tree build's scratch (called by locgpu_destroy)
 // SetInputTarget from a resident cloud of any context on ctx's GPU; async: the host tree build runs on a worker thread
 int icp_set_target_from_cloud(locgpu_ctx* ctx, const locgpu_cloud* target, bool async);
 int ensure_grid(locgpu_ctx* ctx);                       // the exact-search grid of the current target (built on first use)

@@ -86,7 +86,7 @@ static int build_host_tree(locgpu_ctx* ctx, const void* pts, size_t n, size_t st
 
 // meta = {slots, leaves, nodes, points, depth, bounded}. The device buffers only ever grow: a streaming front-end re-ingests its
 // local map every keyframe (lio.cpp:296-305) and must not pay a hipMalloc/hipFree pair (≈100 µs each) per ingest.
-static int install_tree_meta(locgpu_ctx* ctx, const long long meta[6]) {
+int locgpu::install_tree_meta(locgpu_ctx* ctx, const long long meta[6]) {
     for (hipStream_t st : ctx->slot_stream) LOCGPU_HIP(ctx, hipStreamSynchronize(st));  // nobody reads the old tree any more (a begun alignment must be finished first)
     free_grid(ctx);
     const size_t slots = (size_t)meta[0], leaves = (size_t)meta[1];

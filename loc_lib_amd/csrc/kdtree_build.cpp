@@ -8,7 +8,8 @@
 // Why on the host: split thresholds are float32 means accumulated SEQUENTIALLY in index order; any
 // reassociation changes a threshold by an ulp and with it the tree. Sub-trees are independent, so
 // the build is parallel across sub-trees while every node keeps the reference's summation order.
-// This runs once per SetInputTarget (map change), never per scan.
+// This runs once per SetInputTarget (map change), never per scan. (forest_build.hip builds the same trees in HBM for points that are
+// resident there: one node's sum stays a serial chain, nodes, trees and coordinates run side by side. Opt-in)
 //
 // Packed layout (8-byte slots, preorder):
 //   internal node  : 1 slot  { float thresh ; u32 (axis<<30) | right_child_slot }   left child = slot+1

@@ -186,6 +186,7 @@ void locgpu_destroy(locgpu_ctx* ctx) {
     range_ingest_free(ctx);
     record_ingest_free(ctx);
     resident_deskew_free(ctx);
+    forest_build_free(ctx);
     for (hipStream_t st : ctx->slot_stream) if (st) (void)hipStreamDestroy(st);
     delete ctx;
 }
