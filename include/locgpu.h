@@ -489,6 +489,13 @@ LOCGPU_API int locgpu_ndt_set_target(locgpu_ctx* ctx, const void* pts, size_t n,
 LOCGPU_API int locgpu_ndt_target_info(const locgpu_ctx* ctx, int64_t out[3]);
 /* Read the voxel table back (tests): keys n×3 int32, mu n×3 f64, info n×9 f64 row-major; returns count through *n_out. */
 LOCGPU_API int locgpu_ndt_dump(locgpu_ctx* ctx, int32_t* keys, double* mu, double* info, size_t cap, size_t* n_out);
+/* Debug / test read-back (like locgpu_debug_batch_nn) of the open-addressing SLOT array of whichever NDT target the context holds —
+ * the direct table (the grids_ map of SetDirectNdtTargetCloud, ndt_registration.cpp:87-148), a voxel set (locgpu_ndt_set_target_set) or
+ * the incremental key -> voxel table of the last call (SetIncNdtTargetCloud, :150-183): *n_slots = slots of the table (a power of two);
+ * keys[i] = the raw 64-bit key in slot i, all ones = free; vid[i] = the index of that voxel's record (direct and set: the row of
+ * locgpu_ndt_dump / of the set's records in (target, key) order; incremental: the voxel's storage slot), -1 for a free slot. The first
+ * min(cap, *n_slots) entries are written; NULL arrays: the count only. Copies, nothing else: no alignment depends on it. */
+LOCGPU_API int locgpu_debug_ndt_slots(locgpu_ctx* ctx, uint64_t* keys, int32_t* vid, size_t cap, size_t* n_slots);
 /* ---- NdtRegistration::ScanMatch minus the output cloud (ndt_registration.cpp:238-257 → AlignNdt :374-464).
  * When stats->status == 1 the reference leaves result_pose unassigned; out_pose then holds init_pose. */
 LOCGPU_API int locgpu_ndt_align(locgpu_ctx* ctx, const void* src, size_t n, size_t stride_bytes, const double init_pose[7],

@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "locgpu_icp_opts_default", "locgpu_ndt_opts_default", "locgpu_create", "locgpu_destroy", "locgpu_last_error",
     "locgpu_device_count", "locgpu_icp_set_target", "locgpu_icp_set_target_async", "locgpu_icp_target_info", "locgpu_knn", "locgpu_icp_hb", "locgpu_icp_align",
     "locgpu_transform_cloud", "locgpu_batch_create", "locgpu_batch_destroy", "locgpu_icp_align_batch", "locgpu_ndt_align_batch",
-    "locgpu_icp_hb_batch", "locgpu_gn_update", "locgpu_ndt_set_target", "locgpu_ndt_target_info", "locgpu_ndt_dump",
+    "locgpu_icp_hb_batch", "locgpu_gn_update", "locgpu_ndt_set_target", "locgpu_ndt_target_info", "locgpu_ndt_dump", "locgpu_debug_ndt_slots",
     "locgpu_ndt_align", "locgpu_profile_enable", "locgpu_profile_read", "locgpu_visit_count_enable", "locgpu_visit_count_read",
     "locgpu_search_stats_read", "locgpu_debug_batch_nn", "locgpu_debug_batch_run_flags", "locgpu_debug_batch_slot", "locgpu_graph_enable",
     "locgpu_debug_gn_solve", "locgpu_debug_loam_solve",
@@ -220,7 +220,7 @@ def lib():
             "locgpu_icp_hb_batch": (i32, [vp, vp, vp, vp, vp]),
             "locgpu_gn_update": (i32, [vp, i32, i32, dbl, vp, vp, vp, vp]),
             "locgpu_ndt_set_target": (i32, [vp, vp, sz, sz, vp]), "locgpu_ndt_target_info": (i32, [vp, vp]),
-            "locgpu_ndt_dump": (i32, [vp, vp, vp, vp, sz, vp]), "locgpu_ndt_align": (i32, [vp, vp, sz, sz, vp, vp, vp]),
+            "locgpu_ndt_dump": (i32, [vp, vp, vp, vp, sz, vp]), "locgpu_debug_ndt_slots": (i32, [vp, vp, vp, sz, vp]), "locgpu_ndt_align": (i32, [vp, vp, sz, sz, vp, vp, vp]),
             "locgpu_profile_enable": (i32, [vp, i32]), "locgpu_profile_read": (i32, [vp, vp, i32]),
             "locgpu_visit_count_enable": (i32, [vp, i32]), "locgpu_visit_count_read": (i32, [vp, vp, i32]),
             "locgpu_search_stats_read": (i32, [vp, vp, i32]), "locgpu_debug_batch_nn": (i32, [vp, vp, i32, vp]), "locgpu_debug_batch_run_flags": (i32, [vp, vp, vp, vp]), "locgpu_debug_batch_slot": (i32, [vp]), "locgpu_graph_enable": (i32, [vp, i32]),
@@ -853,6 +853,18 @@ class Context:
         n_out = ctypes.c_size_t(0)
         self._check(lib().locgpu_ndt_dump(self._h, keys.ctypes.data, mu.ctypes.data, info.ctypes.data, n, ctypes.byref(n_out)))
         return keys[:n], mu[:n], info[:n].reshape(n, 3, 3)
+
+    def debug_ndt_slots(self):
+        """(keys [cap] uint64, vid [cap] int32) of the slot array of the NDT target the context holds — direct, voxel set or incremental
+        (locgpu_debug_ndt_slots): the raw key of every slot (all ones: free) and its record index (-1: free)."""
+        n = ctypes.c_size_t(0)
+        self._check(lib().locgpu_debug_ndt_slots(self._h, None, None, 0, ctypes.byref(n)))
+        cap = int(n.value)
+        keys = np.zeros(max(cap, 1), dtype=np.uint64)
+        vid = np.zeros(max(cap, 1), dtype=np.int32)
+        self._check(lib().locgpu_debug_ndt_slots(self._h, keys.ctypes.data, vid.ctypes.data, cap, ctypes.byref(n)))
+        assert int(n.value) == cap
+        return keys[:cap], vid[:cap]
 
     def ndt_align(self, src, init_pose):
         s = _cloud(src)

@@ -1386,6 +1386,23 @@ int locgpu_ndt_dump(locgpu_ctx* ctx, int32_t* keys, double* mu, double* info, si
     return LOCGPU_OK;
 }
 
+int locgpu_debug_ndt_slots(locgpu_ctx* ctx, uint64_t* keys, int32_t* vid, size_t cap, size_t* n_slots) {
+    if (!ctx || !n_slots) return LOCGPU_ERR_INVALID;
+    if (ctx->ndt_opts.method == kNdtOptIncremental && ctx->inc) {
+        *n_slots = inc_ndt_table_size(ctx->inc);
+        if ((!keys && !vid) || cap == 0 || *n_slots == 0) return LOCGPU_OK;
+        LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+        LOCGPU_HIP(ctx, inc_ndt_slots_read(ctx->inc, keys, vid, cap, ctx->stream));
+        return LOCGPU_OK;
+    }
+    if (!ctx->ndt) return fail(ctx, LOCGPU_ERR_NO_TARGET, "debug_ndt_slots: no NDT target");
+    *n_slots = ctx->ndt->cap;
+    if ((!keys && !vid) || cap == 0) return LOCGPU_OK;
+    LOCGPU_HIP(ctx, hipSetDevice(ctx->device));
+    LOCGPU_HIP(ctx, ndt_slots_read(*ctx->ndt, keys, vid, cap, ctx->stream));
+    return LOCGPU_OK;
+}
+
 int locgpu_ndt_align_batch(locgpu_ctx* ctx, locgpu_batch* b, const double* init_poses, double* out_poses, locgpu_align_stats* stats) {
     AlignSpec spec;
     int rc = check_ndt(ctx, spec);

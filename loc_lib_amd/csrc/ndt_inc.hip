@@ -524,6 +524,17 @@ size_t inc_ndt_dump(const IncNdtState* st, int32_t* keys, double* mu, double* in
     return n;
 }
 
+size_t inc_ndt_table_size(const IncNdtState* st) { return st ? st->table_cap : 0; }
+
+hipError_t inc_ndt_slots_read(const IncNdtState* st, uint64_t* keys, int32_t* vid, size_t cap, hipStream_t s) {
+    const size_t n = std::min(cap, st->table_cap);
+    if (n == 0) return hipSuccess;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t) && sizeof(int) == sizeof(int32_t), "the table's words are the read-back's");
+    if (keys) LOCGPU_TRY(hipMemcpyAsync(keys, st->d_keys, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    if (vid) LOCGPU_TRY(hipMemcpyAsync(vid, st->d_vid, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    return hipStreamSynchronize(s);
+}
+
 const void* inc_ndt_table_ptr(const IncNdtState* st) { return st ? (const void*)st->d_keys : nullptr; }
 
 }  // namespace locgpu

@@ -11,6 +11,7 @@
 // K5 follows AlignNdt's inner loop (:399-433): 7 probes in the reference's offset order (:57-58), χ² gate with info,
 // sums NOT weighted by info, effective_num once per source point.
 #include <algorithm>
+#include <vector>
 
 #include "icp_kernels.hpp"
 #include "ndt_ingest.hpp"
@@ -119,6 +120,19 @@ hipError_t ndt_dump_range(const NdtTable& t, size_t first, size_t n, bool set_ke
 
 hipError_t ndt_dump(const NdtTable& t, int* keys, double* mu, double* info, size_t out_cap, hipStream_t s) {
     return ndt_dump_range(t, 0, std::min(out_cap, t.n_vox), false, keys, mu, info, s);
+}
+
+hipError_t ndt_slots_read(const NdtTable& t, uint64_t* keys, int32_t* vid, size_t out_cap, hipStream_t s) {
+    const size_t n = std::min(out_cap, t.cap);
+    if (!t.d_slots || n == 0 || (!keys && !vid)) return hipSuccess;
+    std::vector<NdtSlot> h(n);
+    LOCGPU_TRY(hipMemcpyAsync(h.data(), t.d_slots, n * sizeof(NdtSlot), hipMemcpyDeviceToHost, s));
+    LOCGPU_TRY(hipStreamSynchronize(s));
+    for (size_t i = 0; i < n; ++i) {
+        if (keys) keys[i] = (uint64_t)h[i].key;
+        if (vid) vid[i] = h[i].key == kNdtEmpty ? -1 : (int32_t)h[i].vid;
+    }
+    return hipSuccess;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -14,6 +14,7 @@
 
 #include "device_buffer.hpp"
 #include "device_math.hpp"
+#include "ndt_key.hpp"
 #include "ndt_set_key.hpp"
 
 struct alignas(128) NdtRecord {
@@ -40,32 +41,6 @@ struct NdtTable {
 
 namespace locgpu {
 
-constexpr unsigned long long kNdtEmpty = ~0ull;
-constexpr int kNdtBias = 1 << 20;
-
-__host__ __device__ inline bool ndt_key_in_range(int x, int y, int z) {
-    return x > -kNdtBias && x < kNdtBias && y > -kNdtBias && y < kNdtBias && z > -kNdtBias && z < kNdtBias;
-}
-__host__ __device__ inline unsigned long long ndt_pack(int x, int y, int z) {
-    return ((unsigned long long)(unsigned)(x + kNdtBias) << 42) | ((unsigned long long)(unsigned)(y + kNdtBias) << 21) |
-           (unsigned long long)(unsigned)(z + kNdtBias);
-}
-__host__ __device__ inline size_t ndt_hash(unsigned long long k, size_t cap_mask) {
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-    return (size_t)k & cap_mask;
-}
-
-// Slot of a voxel in the DIRECT table (the incremental one keeps ndt_hash): the two halves of the packed key folded with one
-// multiply, then the 32-bit murmur finaliser — the accumulate kernel hashes seven voxels per point, and the 64-bit finaliser seven
-// times over was a good part of its integer instructions. On the bench map's 614 k voxels it collides no more often than the 64-bit
-// one (11 k keys share a first slot at load 0.02; x·A ^ y·B ^ z·C, the classic spatial hash, ten times as many: walls and ground are
-// lattices of keys, and its products cancel on them).
-__host__ __device__ inline size_t ndt_hash32(unsigned long long key, size_t cap_mask) {
-    uint32_t h = (uint32_t)key + (uint32_t)(key >> 32) * 0x9E3779B1u;
-    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-    return (size_t)h & cap_mask;
-}
-
 // Voxel of a point: `(pt * inv_voxel_size_).cast<int>()` (ndt cpp:100,404).
 __device__ __forceinline__ void ndt_key_of(const D3& p, double inv, int& kx, int& ky, int& kz) {
     kx = (int)(p.x * inv); ky = (int)(p.y * inv); kz = (int)(p.z * inv);  // C++ double→int: truncation toward zero
@@ -89,6 +64,9 @@ hipError_t ndt_build(NdtTable& t, const float4* d_pts, size_t n, double voxel_si
 hipError_t ndt_dump_range(const NdtTable& t, size_t first, size_t n, bool set_keys, int* keys, double* mu, double* info, hipStream_t s);
 // ... up to out_cap voxels of a single-target table, from the first.
 hipError_t ndt_dump(const NdtTable& t, int* keys, double* mu, double* info, size_t out_cap, hipStream_t s);
+// Test read-back of the slot array itself: the first min(out_cap, t.cap) slots' raw keys (kNdtEmpty: free) and record indices (-1 for a
+// free slot), in slot order. Copies only; NULL arrays are skipped.
+hipError_t ndt_slots_read(const NdtTable& t, uint64_t* keys, int32_t* vid, size_t out_cap, hipStream_t s);
 
 // K5: per-point 7-voxel probe + χ² gate + un-weighted JᵀJ / Jᵀe sums (AlignNdt inner loop, ndt cpp:399-433).
 // active / n_active (optional): the scans to launch (SearchArgs::active); split_scans > 0: split the partial sums as a plain batch of

@@ -27,7 +27,7 @@ def test_library_exports_every_declared_symbol(api):
 def test_header_cites_reference_for_every_entry_point():
     text = open(os.path.join(ROOT, "include", "locgpu.h")).read()
     for fn in ("locgpu_icp_set_target", "locgpu_knn", "locgpu_icp_hb", "locgpu_icp_align", "locgpu_transform_cloud",
-               "locgpu_ndt_set_target", "locgpu_ndt_align", "locgpu_ndt_hb", "locgpu_debug_gn_solve", "locgpu_debug_loam_solve"):
+               "locgpu_ndt_set_target", "locgpu_ndt_align", "locgpu_ndt_hb", "locgpu_debug_gn_solve", "locgpu_debug_loam_solve", "locgpu_debug_ndt_slots"):
         pos = text.index(fn + "(")
         block = text[max(0, pos - 900):pos]
         assert re.search(r"\.(cpp|h|hpp):\d+", block), fn
