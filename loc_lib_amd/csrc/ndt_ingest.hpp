@@ -75,6 +75,10 @@ __device__ __forceinline__ size_t ndt_claim_slot(NdtSlot* slots, unsigned long l
     }
 }
 
+// The numerical rank of a voxel's covariance: 1e-14 ≈ 90·2^-53 is above the rounding of a few dozen points' sums and a decade below
+// the smallest λ2/λ0 the voxel tests treat as full rank (1e-13). The CPU checker's ClampedInfo carries the same constant.
+constexpr double kNdtNoiseRatio = 1e-14;
+
 // One kept voxel of a DIRECT table, the run psorted[b, e) under `key`: math::ComputeMeanAndCov's sums (ndt_mean_scatter), Σ/(n−1),
 // one-sided Jacobi SVD, λ1,λ2 clamped to ≥ 1e-3·λ0, info = V diag(1/λ) Uᵀ (ndt cpp:111-130) — then claim() takes the voxel's table
 // slot and returns the index of its record, which is written. The single-target build (ndt_kernels.hip) and the voxel-set build
@@ -99,6 +103,10 @@ __device__ __forceinline__ void ndt_voxel_record(unsigned long long key, const f
     if (sv[o2] > sv[o1]) { const int t = o1; o1 = o2; o2 = t; }
     if (sv[o1] > sv[o0]) { const int t = o0; o0 = o1; o1 = t; }
     const int ord[3] = {o0, o1, o2};
+    // A singular value at or below kNdtNoiseRatio·λ0 is rounding noise of the sums and so is its column of a: it carries no
+    // direction, and two such columns need not even be orthogonal to each other. There U takes V's column, which is exact to
+    // rounding (Σ is symmetric PSD: U = V), as it always did for a column of exact zeros. Voxels with λ2 ≥ 1e-13·λ0 never get here.
+    const double noise = kNdtNoiseRatio * sv[o0];
     double lam[3], U[3][3], V[3][3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -109,7 +117,7 @@ __device__ __forceinline__ void ndt_voxel_record(unsigned long long key, const f
             const double vr = cidx == 0 ? vv[0][r] : (cidx == 1 ? vv[1][r] : vv[2][r]);
             const double ar = cidx == 0 ? a[0][r] : (cidx == 1 ? a[1][r] : a[2][r]);
             V[k][r] = vr;
-            U[k][r] = lam[k] > 0.0 ? ar / lam[k] : vr;
+            U[k][r] = lam[k] > noise ? ar / lam[k] : vr;
         }
     }
     if (lam[1] < lam[0] * 1e-3) lam[1] = lam[0] * 1e-3;

@@ -448,8 +448,9 @@ static void ClampedInfo(const double sigma[9], double info[9]) {
         const int c = order[k];
         for (int r = 0; r < 3; ++r) {
             V[k][r] = v[c][r];
-            // Σ symmetric PSD ⇒ U = V; use the computed left vector when it is well defined.
-            U[k][r] = (sv[c] > 0) ? a[c][r] / sv[c] : v[c][r];
+            // Σ symmetric PSD ⇒ U = V; use the computed left vector when it is well defined: a singular value at or below 1e-14·λ0
+            // is rounding noise of the sums and its column has no direction (kNdtNoiseRatio of csrc/ndt_ingest.hpp, the same rule).
+            U[k][r] = (sv[c] > 1e-14 * lam[0]) ? a[c][r] / sv[c] : v[c][r];
         }
     }
     if (lam[1] < lam[0] * 1e-3) lam[1] = lam[0] * 1e-3;
